@@ -109,7 +109,46 @@ def parse():
     ap.add_argument("--no-occupancy-timing", action="store_true", help="skip timing the every-16-steps occupancy-grid update (reported separately, SURVEY 8(d))")
     ap.add_argument("--allreduce-chunks", type=int, default=1, help="N > 1: exchange the table gradient as this many level-group chunks, each started as soon "
                     "as the backward has produced its rows (default 1 = one all-reduce after the backward)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the headline loop computed as DIR/<name>.npy "
+                    "(float32 / float64): the loss of its last step (the fresh-ray loop returns it; the baked-pool loop keeps none), the samples marched by "
+                    "its last trained steps, the trained parameters (fp32 masters; a parameter of more than DUMP_SAMPLE entries as a fixed, seeded sample).  "
+                    "The warm-up then runs DUMP_WARM_RINGS x 16 steps instead of --warm-seconds of wall time: the dumped state is that of a fixed number "
+                    "of training steps (priming, warm-up, --steps), the same for a fast build and a slow one")
     return ap.parse_args()
+
+
+# ----------------------------------------------------------------------------------------------------- --dump-outputs
+DUMP_SAMPLE = 1 << 20  # entries written of a larger parameter (the 12.6 M-entry hash table: 48 MB of fp32 in full)
+DUMP_MAX_BYTES = 64 << 20
+DUMP_WARM_RINGS = 64  # --dump-outputs: warm-up rings of 16 steps (~0.5 s at 0.51 ms per step, the default --warm-seconds)
+
+
+def collect_outputs(field, renderer, loss=None, ahead=()):
+    """What a caller of the timed loop holds after its last step, as host arrays: the step's loss (a device scalar the loop returns), the samples
+    marched by each of its last trained steps (oldest first), and every parameter of the field.  Called right after the timed region, with the
+    fp32 module parameters current (HalfLeafAdam.sync / AcceleratedTrainer.sync).  ahead: the step-counter ring slots that already hold the
+    marches of steps after the timed region (issued one call early); they are left out.  The sample positions depend on the parameter's size only."""
+    out = {}
+    if loss is not None:
+        out["loss"] = loss.detach().float().reshape(1).cpu().numpy()
+    first = renderer.local_step % 16  # the slot of the oldest step in the ring
+    slots = [s for s in ((first + i) % 16 for i in range(16)) if s not in ahead]
+    out["step_samples"] = renderer.step_counter[slots, 0].cpu().numpy().astype(np.float64)
+    for name, p in field.named_parameters():
+        v = p.detach().float().reshape(-1)
+        if v.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).choice(v.numel(), DUMP_SAMPLE, replace=False))
+            v, name = v[torch.from_numpy(idx).to(v.device)], name + ".sample"
+        out["param." + name] = v.cpu().numpy()
+    return out
+
+
+def dump_outputs(outputs, path):
+    assert sum(a.nbytes for a in outputs.values()) <= DUMP_MAX_BYTES, "--dump-outputs: more than 64 MB"
+    os.makedirs(path, exist_ok=True)
+    for name, a in outputs.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 # ----------------------------------------------------------------------------------------------------- CPU baseline
@@ -194,11 +233,13 @@ def cpu_baseline(args, bits, n_rays):
 
 
 # ----------------------------------------------------------------------------------------------------- training leg
-def measure_training(args, mlp, rays, steps, warmup, dev, rank, world, sc, grid, bits, time_grid_kernels, graph=False, dtype=None, dropin_only=False):
+def measure_training(args, mlp, rays, steps, warmup, dev, rank, world, sc, grid, bits, time_grid_kernels, graph=False, dtype=None, dropin_only=False,
+                     outputs=False):
     """K timed training steps of one configuration. Returns (result dict, field, renderer).
     dtype: "fp16" | "bf16" | "fp32" (default args.dtype).  bf16 = bf16 autocast with the FFMLPs on their bf16 kernels (the hash table is
     narrowed to fp16 under any autocast, gridencoder/grid.py:41), GradScaler (the table gradient is fp16), torch's fused Adam.
-    dropin_only: the reference's callers unchanged -- eager launches, no field glue / render tail kernels, torch.optim.Adam + GradScaler."""
+    dropin_only: the reference's callers unchanged -- eager launches, no field glue / render tail kernels, torch.optim.Adam + GradScaler.
+    outputs: a fixed warm-up (DUMP_WARM_RINGS) on every rank, and on rank 0 collect_outputs() of the last timed step in the result ("outputs")."""
     dtype = dtype or args.dtype
     no_ext = dropin_only
     import nerftex_hip
@@ -580,7 +621,7 @@ def measure_training(args, mlp, rays, steps, warmup, dev, rank, world, sc, grid,
     # Untimed steps until --warm-seconds of wall time have passed (whole rings, so the ring bookkeeping below is unchanged)
     t_w = time.perf_counter()
     k_w = 0
-    while time.perf_counter() - t_w < args.warm_seconds:
+    while k_w < DUMP_WARM_RINGS * RING if outputs else time.perf_counter() - t_w < args.warm_seconds:
         for _ in range(RING):
             graph_step(k_w) if use_graph else train_step(k_w, count=False)
             k_w += 1
@@ -609,6 +650,14 @@ def measure_training(args, mlp, rays, steps, warmup, dev, rank, world, sc, grid,
         spread = {"min": q[0], "median": q[len(q) // 2], "max": q[-1], "rings": len(q),
                   "note": "ms per step over each 16-step ring of the timed region (device events on the main stream)"}
     samples_timed = torch.tensor(counted["rings"] + partial_ring(), dtype=torch.int64, device=dev)
+    last_outputs = None
+    if outputs and rank == 0:  # (before the untimed steps below)
+        if fused_opt:
+            opt.sync()
+        ahead = ()  # slots marched already for the steps after the region: L .. marched (march-ahead: one slot, or a group of them)
+        if use_graph and gstate.get("marched", -1) >= 0 and 0 <= gstate["marched"] - renderer.local_step < group:
+            ahead = range(renderer.local_step, gstate["marched"] + 1)
+        last_outputs = collect_outputs(field, renderer, ahead=ahead)
     replay_us = {}  # (filled by main(): the rocprofv3 child runs after every timed loop of this process -- the device idles ~30 s meanwhile)
     kernel_us, all_kernel_us = {}, {}
     if time_grid_kernels:
@@ -688,7 +737,7 @@ def measure_training(args, mlp, rays, steps, warmup, dev, rank, world, sc, grid,
                mean_count=renderer.mean_count, kernel_us=kernel_us, all_kernel_us=all_kernel_us, use_amp=use_amp, fused_opt=fused_opt, dtype=dtype,
                graph=("three replayed HIP graphs per step (march | shade + backward | optimizer); the gradient all-reduce, launched eagerly after the backward, overlaps the next step's march" if split_graph else
                       (f"replayed HIP graphs: shade + backward + optimizer of {group} consecutive steps per graph, and on a second stream the marches of the next {group} steps (a march needs the rays and the occupancy grid, not the weights)") if march_ahead else
-                      "one replayed HIP graph per step") if use_graph else "", dt_gamma=dt_gamma, n_global=n_global)
+                      "one replayed HIP graph per step") if use_graph else "", dt_gamma=dt_gamma, n_global=n_global, outputs=last_outputs)
     return res, field, renderer
 
 
@@ -857,12 +906,13 @@ def measure_occupancy_update(renderer, use_amp, amp_dtype, ms_per_step, samples_
     return out
 
 
-def measure_accelerated(args, mlp, rays, steps, dev, grid, group=1, dtype="fp16", randint_rays=False, fused_table_update=None, n_views=4):
+def measure_accelerated(args, mlp, rays, steps, dev, grid, group=1, dtype="fp16", randint_rays=False, fused_table_update=None, n_views=4, outputs=False):
     """A training loop that feeds FRESH rays every step through ngp_harness.accelerate (the one call a trainer adds to the drop-in
     packages: graph replay + fused field + HalfLeafAdam / FusedAmp, or torch's capturable Adam + GradScaler for nn.Linear MLPs).
     group = k > 1: `step_group` -- the loop has the batches of k consecutive steps at a time ([k, N, 3] tensors, copied into the graphs'
     static buffers every call) and hands the NEXT k batches over one call early: one replayed graph per k steps, their marches ahead on the
-    second stream -- the structure of the baked-pool loop of measure_training, with rays the graphs have never seen."""
+    second stream -- the structure of the baked-pool loop of measure_training, with rays the graphs have never seen.
+    outputs: a fixed warm-up (DUMP_WARM_RINGS), and collect_outputs() of the last timed step in the result ("outputs")."""
     from ngp_harness import scene
     from ngp_harness.accelerate import accelerate
     from ngp_harness.model import NGPField, Renderer
@@ -934,8 +984,9 @@ def measure_accelerated(args, mlp, rays, steps, dev, grid, group=1, dtype="fp16"
     per_call = max(group, 1)
     for c in range((16 + 16 + 48) // per_call):  # priming (full-size buffers, mean count), warm steps, capture, past the first mean_count read-backs
         call(c)
-    t_w = time.perf_counter()
-    while time.perf_counter() - t_w < args.warm_seconds or renderer.local_step != 0:  # clocks (see measure_training); then on to a ring boundary
+    t_w, c_w = time.perf_counter(), c
+    while ((c - c_w) * per_call < DUMP_WARM_RINGS * 16 if outputs else time.perf_counter() - t_w < args.warm_seconds) or renderer.local_step != 0:  # clocks (see
+                                                                                   # measure_training); then on to a ring boundary
         call(c := c + 1)                                                               # (the sample count is read from whole rings)
         if renderer.local_step == 0:
             torch.cuda.synchronize()
@@ -960,8 +1011,13 @@ def measure_accelerated(args, mlp, rays, steps, dev, grid, group=1, dtype="fp16"
         samples = int(sum(rings)) + int(renderer.step_counter[:renderer.local_step, 0].sum().item())
     per_ring_ms = sorted(marks[i].elapsed_time(marks[i + 1]) / 16 for i in range(steps // 16))
     spread = {"min": per_ring_ms[0], "median": per_ring_ms[len(per_ring_ms) // 2], "max": per_ring_ms[-1], "rings": len(per_ring_ms)} if len(per_ring_ms) >= 3 else None
+    last_outputs = None
+    if outputs:
+        trainer.sync()
+        ahead = range(trainer._ahead[0], trainer._ahead[0] + per_call) if trainer._ahead is not None else ()  # (next_rays of the last call)
+        last_outputs = collect_outputs(field, renderer, trainer.loss, ahead=ahead)
     return {"value": samples / (t1 - t0), "ms_per_step": (t1 - t0) / steps * 1e3, "loss": float(trainer.loss), "spread": spread, "samples": samples, "steps": steps,
-            "steps_per_call": per_call}
+            "steps_per_call": per_call, "outputs": last_outputs}
 
 
 def measure_trained_state(args, dev, sc, grid, rays=8192, train_steps=1008, timed_steps=208):
@@ -1206,8 +1262,10 @@ def main():
     sc = scene.Scene(bound=args.bound, seed=0)
     grid, thresh, bits = sc.bitfield()
     res, field, renderer = measure_training(args, args.mlp, args.rays, args.steps, args.warmup, dev, rank, world, sc, grid, bits,
-                                            not args.no_kernel_timing, graph=not args.no_graph)
+                                            not args.no_kernel_timing, graph=not args.no_graph, outputs=bool(args.dump_outputs))
     use_amp, dt_gamma = res["use_amp"], res["dt_gamma"]
+    # (--dump-outputs: the loop above collects its outputs even when the fresh-ray loop below becomes the headline: that loop may still fail at
+    # run time, and the baked-pool loop is the headline then)
     # ---- the headline at N = 1: the same step fed with FRESH rays through the one call a trainer makes (ngp_harness.accelerate, step_group): the
     # loop above bakes its pool of ray batches into the graphs -- a trainer cannot -- so it is reported under other_config and the number a
     # training loop gets is `value`.  Same kernels, same graphs-per-steps structure; the rays are copied into static buffers every call.
@@ -1218,7 +1276,7 @@ def main():
         try:
             # (what accelerate() gives a trainer, nothing else: until round 5 this loop ran with the march_lean knob set; on round 6's step the default march is
             # the better neighbour by a hair -- 0.508 vs 0.511 - 0.516 ms per step over two pairs of runs on one box -- and it is what a caller gets)
-            fresh = measure_accelerated(args, "ffmlp", args.rays, args.steps, dev, grid, group=args.steps_per_graph)
+            fresh = measure_accelerated(args, "ffmlp", args.rays, args.steps, dev, grid, group=args.steps_per_graph, outputs=bool(args.dump_outputs))
         except Exception as e:  # noqa: BLE001 -- fall back to the baked-pool loop as the headline, and say so
             print(f"[bench] fresh-ray loop failed ({type(e).__name__}: {e}); headline = the baked-pool loop", file=sys.stderr)
             fresh = None
@@ -1494,6 +1552,8 @@ def main():
             occ = dict(occ)
             occ["ms_per_step_including_update"] = fresh["ms_per_step"] + occ["ms_partial"] / 16
             occ["value_including_occupancy_update_per_gpu"] = fresh["samples"] / fresh["steps"] / (occ["ms_per_step_including_update"] * 1e-3)
+        if args.dump_outputs:
+            dump_outputs(head["outputs"], args.dump_outputs)
         out = {
             "metric": "ray-samples/s (train)",
             "value": head["value"],
