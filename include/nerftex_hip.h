@@ -143,6 +143,36 @@ int nerftex_grid_register_offsets(const int32_t* offsets_dev, uint32_t L, const 
  * [extension]                                                                                                             */
 int nerftex_deferred_error(void);
 
+/* The hash table's clustering regulariser (gridencoder/grid_clustering.py:93-217, tools/map.py:747-774 of the reference): per level
+ * l, rows x = table[offsets[l] : offsets[l+1]] against centres[l] [K, C],
+ *   q = normalise_rows((1 + |x - c|^2 / alpha)^(-(alpha + 1) / 2)),  p = normalise_rows(q^2 / colsum(q)) (detached),
+ *   loss = weight * sum over the levels of mean_{i,k} p (log p - log q)   (KLDivLoss(reduction='mean')).
+ * *level (device int32): 0..L-1 = that level, -1 = every level summed (the reference's pick_level=False); anything else writes a
+ * NaN loss and no gradient.  grad_table / grad_centres (optional): grad_scale * d loss / d x is ADDED into the level's rows of
+ * grad_table [rows, C], grad_scale * d loss / d centres into grad_centres [L, K, C]; grad_scale is a device float (NULL = 1).
+ * Nothing is read back, allocated or synchronised: capturable.  No float atomics: the same bits on every run.  C in {1, 2, 4, 8},
+ * 1 <= K <= 16, alpha > 0; max_level_rows (host) is the largest level's row count -- it sizes the launch, the kernels take each
+ * level's count from offsets.  scratch: caller-owned, 16-byte aligned, nerftex_grid_cluster_scratch_bytes(desc) bytes (it depends
+ * on C, K, L and max_level_rows only).  [extension: the reference evaluates the loss with ~30 framework ops on the host's level pick] */
+typedef struct nerftex_grid_cluster_desc {
+    const float* table;      /* [offsets[L], C] fp32 */
+    const int32_t* offsets;  /* device [L + 1] */
+    uint32_t C, L, K;
+    uint32_t max_level_rows;
+    const float* centres;    /* [L, K, C] fp32 */
+    float alpha;
+    float weight;
+    const int32_t* level;    /* device int32 */
+    const float* grad_scale; /* device, may be NULL */
+    float* loss;             /* device fp32 scalar, written */
+    float* grad_table;       /* may be NULL */
+    float* grad_centres;     /* may be NULL */
+    void* scratch;
+    size_t scratch_bytes;
+} nerftex_grid_cluster_desc;
+int nerftex_grid_cluster_scratch_bytes(const nerftex_grid_cluster_desc* desc, size_t* bytes);
+int nerftex_grid_cluster_loss(const nerftex_grid_cluster_desc* desc, void* stream);
+
 /* The same two calls with the caller's coordinate normalisation folded in: every kernel reads x = (inputs + in_add) * in_mul
  * (two fp32 roundings, as the framework's add and multiply before the call: gridencoder/grid.py:141 with in_add = bound,
  * in_mul = 1 / (2 bound)).  dy_dx / grad_inputs stay derivatives with respect to the NORMALISED x; in_mul > 0.             */

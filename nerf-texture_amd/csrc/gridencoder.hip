@@ -1214,3 +1214,6 @@ extern "C" int nerftex_grid_encode_backward(const void* grad, const float* input
     return grid_backward_entry(grad, inputs, offsets, grad_embeddings, B, D, C, L, S, H, calc_grad_inputs, dy_dx, grad_inputs, gridtype,
                                align_corners, dtype, layout, false, 0.0f, 1.0f, stream);
 }
+
+// the clustering regulariser over the same tables (nerftex_grid_cluster_loss)
+#include "grid_cluster.inc"

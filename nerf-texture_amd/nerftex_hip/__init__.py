@@ -86,6 +86,8 @@ _SIGNATURES = {
     "nerftex_grid_encode_backward": [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _f32, _u32, _i, _vp, _vp, _u32, _i, _i, _i, _vp],
     "nerftex_grid_register_offsets": [_vp, _u32, _vp],
     "nerftex_deferred_error": [],
+    "nerftex_grid_cluster_scratch_bytes": [_vp, C.POINTER(_sz)],
+    "nerftex_grid_cluster_loss": [_vp, _vp],
     "nerftex_grid_encode_forward_affine": [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _f32, _u32, _i, _vp, _u32, _i, _i, _i, _f32, _f32, _vp],
     "nerftex_grid_encode_backward_affine": [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _f32, _u32, _i, _vp, _vp, _u32, _i, _i, _i, _f32, _f32, _vp],
     "nerftex_sh_encode_forward": [_vp, _vp, _u32, _u32, _u32, _i, _vp, _vp],
@@ -138,6 +140,13 @@ class TableAdam(C.Structure):
 class StepTrailer(C.Structure):
     """nerftex_step_trailer of include/nerftex_hip.h: opaque, filled by nerftex_field_backward_live_deferred."""
     _fields_ = [("opaque", C.c_uint64 * 16)]
+
+
+class GridClusterDesc(C.Structure):
+    """nerftex_grid_cluster_desc of include/nerftex_hip.h, field for field."""
+    _fields_ = [("table", _vp), ("offsets", _vp), ("C", _u32), ("L", _u32), ("K", _u32), ("max_level_rows", _u32), ("centres", _vp), ("alpha", _f32),
+                ("weight", _f32), ("level", _vp), ("grad_scale", _vp), ("loss", _vp), ("grad_table", _vp), ("grad_centres", _vp), ("scratch", _vp),
+                ("scratch_bytes", _sz)]
 
 
 class StepLoss(C.Structure):

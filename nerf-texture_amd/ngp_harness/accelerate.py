@@ -397,7 +397,124 @@ class AcceleratedTrainer:
             self._graphs, self._groups, self._warm = None, None, 0
 
 
+def draw_ring_levels(num_levels, count=RING):
+    """The hash-grid levels the reference's clustering_loss picks in `count` consecutive training steps: its own call,
+    np.random.choice(np.arange(L), [1]) once per step, in step order (gridencoder/grid_clustering.py:204-207) -- after the same
+    np.random.seed, the same levels as the reference trainer.  Host only; int32 [count]."""
+    import numpy as np
+
+    return np.array([int(np.random.choice(np.arange(num_levels), [1])[0]) for _ in range(count)], dtype=np.int32)
+
+
+class CurvedTrainer(AcceleratedTrainer):
+    """accelerate() of a Renderer over `curved.CurvedField`: the NeRF-Texture training step (main.py:85-190, nerf/utils.py:637-666) --
+    image loss + regular_weight * clustering loss, torch's fused capturable Adam over field.get_params(lr) (cluster centres included) under
+    GradScaler -- with the structure of the ngp field's trainer: a march graph and a shade graph per ring slot, `steps_per_call` groups,
+    `next_rays` march-ahead.  The regulariser is the step form of nerftex_grid_cluster_loss, run inside the shade graph after the backward
+    and before the optimizer: it ADDS scale * d reg / d x into the fp32 table gradient and the centres' gradient (never through an fp16
+    gradient: at 1e-8 / (2^19 * 4) it would flush to zero).  The level of each step of a ring is drawn at the ring's start with the
+    reference's own np.random call (draw_ring_levels) into a device int32[16] the slot graphs index.  trainer.loss = image loss + regulariser,
+    trainer.reg_loss = the regulariser: device scalars, nothing is read back.  The fp32 parameters are current after every step (no sync()).
+    Not here: prob_model (the log-variance table), world size > 1, and the ngp field's fused AMP options (HalfLeafAdam, fused table update,
+    dead-sample skipping, the one-launch composite step), which are refused if asked for."""
+
+    def __init__(self, renderer, regular_weight=1e-8, rays_per_batch=None, lr=1e-2, betas=(0.9, 0.99), eps=1e-15, dt_gamma=1 / 128, bg_color=1,
+                 perturb=True, max_steps=1024, amp_dtype=torch.float16, graph=True, steps_per_call=1, march_across_ring_end=False, pipeline_adam=0,
+                 skip_dead_samples=None, fused_table_update=None, fused_composite_step=None):
+        from .curved import CurvedField
+
+        field = renderer.field
+        assert isinstance(field, CurvedField), "CurvedTrainer trains a curved.CurvedField"
+        assert field.encoder_var is None, "accelerate(): prob_model=True (the log-variance table) is not on the graphed path (main.py:86 trains without it)"
+        dist = torch.distributed
+        assert not (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1), "accelerate() of the curved field: world size 1"
+        for name, v in (("pipeline_adam", pipeline_adam), ("skip_dead_samples", skip_dead_samples), ("fused_table_update", fused_table_update),
+                        ("fused_composite_step", fused_composite_step)):
+            assert not v, f"{name}: an option of the ngp field's fused AMP step; the curved field trains with torch's fused Adam + GradScaler"
+        self.renderer, self.field = renderer, field
+        self.dev = next(field.parameters()).device
+        self.n_rays = rays_per_batch
+        self.dt_gamma, self.bg_color, self.perturb, self.max_steps = dt_gamma, bg_color, perturb, max_steps
+        self.amp_dtype = amp_dtype
+        self.use_graph = bool(graph)
+        self.fused, self.amp, self.pipeline_adam = False, None, 0
+        self.skip_dead_samples = self.fused_table_update = self.fused_composite_step = False
+        renderer.skip_dead_samples, renderer.root_one, renderer.defer_step_loss = False, None, False
+        # (capturable either way: graph=False runs the very optimizer arithmetic the graphs replay)
+        self.opt = torch.optim.Adam(field.get_params(lr), betas=betas, eps=eps, fused=True, capturable=True)
+        self.scaler = torch.amp.GradScaler("cuda", enabled=amp_dtype in (torch.float16, torch.bfloat16))
+        self._one = torch.ones((), dtype=torch.float32, device=self.dev)
+        self._graphs, self._M = None, 0
+        self.march_across_ring_end = bool(march_across_ring_end)
+        self.group = int(steps_per_call)
+        assert self.group in (1, 2, 4, 8, 16), "steps_per_call must divide the 16-entry step-counter ring"
+        self._groups = None
+        self._rays, self._targets = None, None
+        self._primed, self._warm = 0, 0
+        self._ahead = None
+        self._side = None
+        if self.dev.type == "cuda":
+            from .streams import ensure_pool
+
+            ensure_pool(self.dev)
+        self.loss = torch.zeros((), dtype=torch.float32, device=self.dev)
+        # the regulariser: static level picks of the ring's 16 steps, the centres' gradient as one [L, K, C] buffer the per-level parameters'
+        # .grad are views of (zeroed every step, never set to None: the kernel adds into it), its loss
+        enc = field.encoder
+        self.regular_weight = float(regular_weight)
+        self._layers = list(enc.cluster_layers)
+        self._alpha = float(self._layers[0].alpha)
+        assert all(float(l.alpha) == self._alpha for l in self._layers)
+        self._levels = torch.zeros(RING, dtype=torch.int32, device=self.dev)
+        self.ring_levels = None  # (the host copy of the current ring's picks)
+        centres = [l.cluster_centers for l in self._layers]
+        self._centres_grad = torch.zeros((len(centres),) + tuple(centres[0].shape), dtype=torch.float32, device=self.dev)
+        for i, c in enumerate(centres):
+            c.grad = self._centres_grad[i]
+        keep = {id(c) for c in centres}
+        self._other_params = [p for p in field.parameters() if id(p) not in keep]
+        self.reg_loss = torch.zeros((), dtype=torch.float32, device=self.dev)
+
+    def _draw_levels(self):
+        self.ring_levels = draw_ring_levels(self.field.encoder.num_levels)
+        self._levels.copy_(torch.from_numpy(self.ring_levels))  # (stream-ordered behind the previous ring's steps)
+
+    def _shade(self, marched, tgt):
+        r, enc = self.renderer, self.field.encoder
+        slot = tgt.storage_offset() // tgt.numel()  # (the targets are the rows of the static [RING, N, 3] buffer: row = ring slot)
+        for p in self._other_params:
+            p.grad = None
+        self._centres_grad.zero_()
+        with torch.autocast("cuda", dtype=self.amp_dtype):
+            image, depth, loss, scaled = r.shade_train(marched, self.bg_color, target=tgt, scale=None)
+        self.scaler.scale(scaled).backward()
+        from gridencoder.grid_clustering import grid_cluster_step
+
+        grid_cluster_step(enc.embeddings.detach(), enc.offsets, torch.stack([l.cluster_centers.detach() for l in self._layers]), self._levels[slot],
+                          self._alpha, self.regular_weight, loss=self.reg_loss, grad_table=enc.embeddings.grad, grad_centres=self._centres_grad,
+                          grad_scale=self.scaler.scale(self._one))
+        self.scaler.step(self.opt)
+        self.scaler.update()
+        self.loss.copy_(loss.detach().reshape(()) + self.reg_loss)
+
+    def step(self, rays_o, rays_d, target, next_rays=None, _eager=False):
+        if self.renderer.local_step % RING == 0:
+            self._draw_levels()
+        return super().step(rays_o, rays_d, target, next_rays=next_rays, _eager=_eager)
+
+    def step_group(self, rays_o, rays_d, target, next_rays=None):
+        eager = not self.use_graph or self._primed < RING or self._warm < max(2, self.group)  # (that path draws in `step`)
+        if not eager and self.renderer.local_step % RING == 0:
+            self._draw_levels()
+        return super().step_group(rays_o, rays_d, target, next_rays=next_rays)
+
+
 def accelerate(renderer, **kw):
     """See the module docstring.  Keyword arguments: rays_per_batch, lr, betas, eps, dt_gamma, bg_color, perturb, max_steps, amp_dtype, graph,
-    steps_per_call (k > 1: `step_group` takes the batches of k consecutive steps and replays one graph for them), march_across_ring_end."""
+    steps_per_call (k > 1: `step_group` takes the batches of k consecutive steps and replays one graph for them), march_across_ring_end.
+    A renderer over a curved.CurvedField gets a CurvedTrainer (its docstring; regular_weight, default 1e-8)."""
+    from .curved import CurvedField
+
+    if isinstance(renderer.field, CurvedField):
+        return CurvedTrainer(renderer, **kw)
     return AcceleratedTrainer(renderer, **kw)
