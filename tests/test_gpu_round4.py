@@ -216,7 +216,7 @@ def test_bench_launches_its_own_ranks():
 
     env = dict(os.environ, NERFTEX_DP_SHARE_GPU="1")
     env.pop("WORLD_SIZE", None), env.pop("RANK", None), env.pop("LOCAL_RANK", None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "16", "--warmup", "4", "--rays", "2048", "--no-cpu-baseline", "--no-other",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--steps", "16", "--warmup", "4", "--rays", "2048", "--no-cpu-baseline", "--no-other",
            "--no-infer", "--no-kernel-timing", "--allreduce-chunks", "2"]
     out = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
@@ -630,7 +630,7 @@ def test_chunked_gradient_exchange_keeps_replicas_identical(extra):
     for chunks in (1, 3):
         env = dict(os.environ, NERFTEX_DP_SHARE_GPU="1")
         env.pop("WORLD_SIZE", None), env.pop("RANK", None), env.pop("LOCAL_RANK", None)
-        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "16", "--warmup", "4", "--rays", "8192", "--no-cpu-baseline", "--no-other",
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--steps", "16", "--warmup", "4", "--rays", "8192", "--no-cpu-baseline", "--no-other",
                "--no-infer", "--no-kernel-timing", "--warm-seconds", "0", "--allreduce-chunks", str(chunks)] + extra
         out = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
         assert out.returncode == 0, out.stderr[-3000:]

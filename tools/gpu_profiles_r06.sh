@@ -9,7 +9,7 @@ export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 timeout 1200 python -m pytest tests -m gpu -q -p no:cacheprovider > $out/pytest.log 2>&1; echo "pytest rc=$?" >> $out/pytest.log
 tail -4 $out/pytest.log
-NERFTEX_KEEP_PMC=$out/pmc_bench.txt NERFTEX_KEEP_STATS=$out/kernel_stats.csv timeout 1200 python bench.py > $out/bench.json 2> $out/bench.err
+NERFTEX_KEEP_PMC=$out/pmc_bench.txt NERFTEX_KEEP_STATS=$out/kernel_stats.csv timeout 1200 python bench.py --full > $out/bench.json 2> $out/bench.err
 tail -2 $out/bench.err
 bash tools/gpu_timeline.sh $tag/timeline > /dev/null 2>&1
 LINES_OUT=10 bash tools/gpu_pmc_any.sh $tag/sq_ffmlp "field_forward|ffmlp_backward|wgrad_reduce" -- $R/bench.py --no-graph --steps 16 --warmup 4 --warm-seconds 0 --no-kernel-timing --no-cpu-baseline --no-other --no-infer --baked-pool > /dev/null 2>&1

@@ -8,7 +8,7 @@
 #   comp        tools/composite_step_ab.py (the step's compositing as one launch against the three launches, per composite_keep)
 #   comp-prof   the same under rocprofv3 --kernel-trace --stats (KEEPS=1,2,4)
 #   probe / dead   tools/tile_adam_probe.py / tools/dead_skip_probe.py
-#   bench       python bench.py (default run)
+#   bench       python bench.py --full
 mode=${1:-tests-new}
 tag=${2:-r06_$mode}
 out=$PWD/gpurun_out/$tag
@@ -56,5 +56,5 @@ for r in d["rows"]:
 PY
     ;;
   bench)
-    timeout 1200 python bench.py > $out/bench.json 2> $out/bench.err; tail -5 $out/bench.err; cat $out/bench.json | head -c 3000 ;;
+    timeout 1200 python bench.py --full > $out/bench.json 2> $out/bench.err; tail -5 $out/bench.err; cat $out/bench.json | head -c 3000 ;;
 esac

@@ -6,7 +6,7 @@ out=$PWD/gpurun_out/$tag
 mkdir -p $out
 export TMPDIR=/tmp
 timeout 1500 python -m pytest tests -m gpu -q > $out/pytest.log 2>&1; echo "pytest rc=$?" >> $out/pytest.log
-timeout 900 python bench.py > $out/bench.json 2> $out/bench.err
+timeout 900 python bench.py --full > $out/bench.json 2> $out/bench.err
 ( cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -- python $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-other --no-infer > $out/prof_bench.json 2> $out/prof.err )
 for c in FETCH_SIZE WRITE_SIZE; do
   ( cd /tmp && timeout 300 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $out/pmc_$c -- python $GRAFT_REPO_ROOT/tools/bench_kernels.py --ops grid_fwd,grid_bwd --rays 8192 --dtypes f16 > $out/pmc_$c.log 2>&1 )

@@ -51,7 +51,7 @@ class LoggedStream(_Stream):
 
 
 torch.cuda.Stream = LoggedStream
-sys.argv = [sys.argv[0], "--no-other", "--no-cpu-baseline", "--no-replay-profile", "--no-traffic-profile", "--no-occupancy-timing", "--trained-steps", "0"] + sys.argv[1:]
+sys.argv = [sys.argv[0], "--full", "--no-other", "--no-cpu-baseline", "--no-replay-profile", "--no-traffic-profile", "--no-occupancy-timing", "--trained-steps", "0"] + sys.argv[1:]
 mark("main begins")
 bench.main()
 mark("main ends")
