@@ -453,6 +453,18 @@ int nerftex_grid_encode_backward_phase_amp(const void* grad, const float* inputs
  * updates what is left (rows [0, first_updated_row) and its other tensors) the same way, flips *live iff the step is applied and, on a skipped
  * step, re-derives the fp16 copy this call rewrote in place (param_half) from the live fp32 set.
  * fp16 tables, C = 2, NERFTEX_LAYOUT_GRAD_OVERWRITE, a registered level table whose levels are multiples of 4 rows; everything else is refused. */
+/* Extension: a learning-rate schedule on the device -- torch.optim.lr_scheduler.LambdaLR as the reference trains with it (main_nerf.py:131-133:
+ * lr = base_lr * 0.1 ** min(iter / iters, 1), stepped after every optimizer step, skipped ones included, nerf/utils.py:1020-1025).  Training step
+ * number t (*iter) uses base_lr * factor[min(t, n - 1)], the product in double as LambdaLR forms it in Python; the launch that ends a step (the
+ * loss scaler's tail of the _sched Adam entries, or nerftex_lr_schedule_publish) advances *iter by one, whether the step is applied or skipped.
+ * A replayed graph reads the step's rate from here instead of holding the rate of its capture.  factor: device double [n], n >= 1; iter: device
+ * word.  The descriptor itself is a host struct, read when the call is made.                                                               */
+typedef struct nerftex_lr_schedule {
+    const double* factor;
+    uint32_t n;
+    uint32_t* iter;
+} nerftex_lr_schedule;
+
 typedef struct nerftex_table_adam {
     float* param[2];       /* fp32 table, state sets 0 and 1, [rows, 2] each */
     float* exp_avg[2];
@@ -463,6 +475,8 @@ typedef struct nerftex_table_adam {
     const float* grad_scale; /* device, may be NULL: gradients are divided by it */
     float* found_inf;      /* device: raised on inf / nan */
     double lr, beta1, beta2, eps;
+    const nerftex_lr_schedule* sched; /* may be NULL: train at lr.  Else lr is the base rate and the step's rate is read from the schedule, before
+                                         the step's last launch advances it (the counter this step will end with)                              */
 } nerftex_table_adam;
 int nerftex_grid_encode_backward_adam(const void* grad, const float* inputs, const int32_t* offsets, void* grad_embeddings, uint32_t B,
                                       uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H, uint32_t gridtype, int align_corners, int dtype,
@@ -827,6 +841,26 @@ int nerftex_adam_mixed_step_amp_db(int count, float* const* params, float* const
                                    float* scale, int32_t* growth_tracker, float* found_inf, uint32_t* ticket, double growth_factor,
                                    double backoff_factor, int growth_interval, uint32_t* live, void* repair_half, const float* repair_param0,
                                    const float* repair_param1, uint64_t repair_n, void* stream);
+/* Extension: nerftex_adam_mixed_step_amp and nerftex_adam_mixed_step_amp_db with the learning rate of the step taken from a schedule
+ * (nerftex_lr_schedule, above): base_lr * factor[min(*iter, n - 1)] in place of lr, and the loss scaler's tail also advances *iter -- on a
+ * skipped step as well (*step, Adam's bias-correction count, still advances on applied steps only).  Same bits as the unscheduled calls fed that
+ * product as lr.                                                                                                                              */
+int nerftex_adam_mixed_step_amp_sched(int count, float* const* params, float* const* exp_avgs, float* const* exp_avg_sqs,
+                                      const void* const* grads16, void* const* params16, const uint64_t* n, uint32_t bf16_mask, float* step,
+                                      double base_lr, const nerftex_lr_schedule* sched, double beta1, double beta2, double eps, float* scale,
+                                      int32_t* growth_tracker, float* found_inf, uint32_t* ticket, double growth_factor, double backoff_factor,
+                                      int growth_interval, void* stream);
+int nerftex_adam_mixed_step_amp_db_sched(int count, float* const* params, float* const* exp_avgs, float* const* exp_avg_sqs, float* const* params1,
+                                         float* const* exp_avgs1, float* const* exp_avg_sqs1, const void* const* grads16, void* const* params16,
+                                         const uint64_t* n, uint32_t bf16_mask, float* step, double base_lr, const nerftex_lr_schedule* sched,
+                                         double beta1, double beta2, double eps, float* scale, int32_t* growth_tracker, float* found_inf,
+                                         uint32_t* ticket, double growth_factor, double backoff_factor, int growth_interval, uint32_t* live,
+                                         void* repair_half, const float* repair_param0, const float* repair_param1, uint64_t repair_n, void* stream);
+/* Extension: the schedule for an optimizer that reads its learning rate from a device tensor (torch.optim.Adam(fused=True) with tensor lr: a
+ * float32 it reads at each step).  One thread: lr_out[g][0] = (float)(base_lrs[g] * factor[min(*iter, n - 1)]) for g < groups -- the rounding
+ * of LRScheduler's group["lr"].fill_(value) -- then *iter += 1.  Launched in front of the optimizer in every step, skipped ones included.
+ * base_lrs / lr_out: host arrays of 1..8 entries (lr_out: device fp32 scalars).                                                            */
+int nerftex_lr_schedule_publish(const nerftex_lr_schedule* sched, const double* base_lrs, float* const* lr_out, uint32_t groups, void* stream);
 int nerftex_amp_check_mixed(int count, const void* const* grads16, const uint64_t* n, uint32_t bf16_mask, float* found_inf, void* stream);
 int nerftex_amp_update(float* scale, int32_t* growth_tracker, float* found_inf, float* step, double growth_factor,
                        double backoff_factor, int growth_interval, void* stream);

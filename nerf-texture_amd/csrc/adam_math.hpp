@@ -13,6 +13,19 @@ struct AdamConsts {
     double lr, beta1, beta2, eps;
 };
 
+// nerftex_lr_schedule (include/nerftex_hip.h) on the device: where AdamConsts::lr comes from when the rate changes every step
+struct LrSched {
+    const double* factor;  // [n]
+    uint32_t n;
+    uint32_t* iter;  // training step number, advanced by the step's last launch
+};
+struct NoSched {};
+
+// torch's LambdaLR: base_lr * lr_lambda(t), the product in double; past the table's end its last entry
+__device__ __forceinline__ double scheduled_lr(const double base_lr, const LrSched& s, const uint32_t t) {
+    return base_lr * s.factor[t < s.n ? t : s.n - 1u];
+}
+
 // what every parameter of one step shares
 struct AdamStep {
     float step_size, bc2_sqrt;

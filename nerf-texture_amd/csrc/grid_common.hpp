@@ -50,6 +50,9 @@ struct TableAdamArgs {
     const float* step;
     const float* grad_scale;
     double lr, beta1, beta2, eps;
+    const double* lr_factor;  // nerftex_lr_schedule; NULL: no schedule
+    uint32_t lr_n;
+    uint32_t* lr_iter;
 };
 
 // coordinate d of point b as the kernels see it (identity unless the caller folded its normalisation in)

@@ -1138,6 +1138,16 @@ static int backward_adam_entry(const void* grad, const float* inputs, const int3
     ta.beta1 = adam->beta1;
     ta.beta2 = adam->beta2;
     ta.eps = adam->eps;
+    if (adam->sched) {
+        const nerftex_lr_schedule* ls = adam->sched;
+        if (!ls->factor || !ls->iter || ls->n == 0) {
+            set_error("grid_encode_backward_adam: the learning-rate schedule needs its factor table (n >= 1) and its step counter");
+            return NERFTEX_ERR_INVALID;
+        }
+        ta.lr_factor = ls->factor;
+        ta.lr_n = ls->n;
+        ta.lr_iter = ls->iter;
+    }
     return grid_backward_entry(grad, inputs, offsets, grad_embeddings, B, D, C, L, S, H, 0, nullptr, nullptr, gridtype, align_corners, dtype, layout, true,
                                in_add, in_mul, stream, adam->found_inf, 0, 0, 0, &ta, first_updated_row);
 }

@@ -195,6 +195,7 @@ struct TileAdam {
     const float* step;     // completed optimizer steps; this update is number *step + 1
     const float* grad_scale;
     AdamConsts k;
+    LrSched sched;  // factor == nullptr: k.lr as given; else k.lr is the base rate of a device schedule (nerftex_lr_schedule)
     AdamStep* step_consts;  // library scratch: the step's constants, written by the summing launch for the combine launch behind it
 };
 
@@ -591,7 +592,9 @@ __global__ __launch_bounds__(kSumThreads) __attribute__((amdgpu_waves_per_eu(8, 
         fx = fixed_f32_scale(level_maximum(tab.chunk_max, it.level, nchunks, reinterpret_cast<float*>(smem + kTileBytes)));
     if constexpr (ADAM) {  // the step's constants (two double pows): one lane, once, while the others clear the tile
         if (threadIdx.x == 0 && (it.slices == 1 || blockIdx.x + item_offset == 0)) {
-            s_step = adam_step_consts(adam.k, (double)(*adam.step + 1.0f), adam.grad_scale);
+            AdamConsts k = adam.k;
+            if (adam.sched.factor) k.lr = scheduled_lr(adam.k.lr, adam.sched, *adam.sched.iter);  // (this step's: its last launch advances the counter)
+            s_step = adam_step_consts(k, (double)(*adam.step + 1.0f), adam.grad_scale);
             if (blockIdx.x + item_offset == 0) *adam.step_consts = s_step;  // for combine_tiles_kernel<true>, the launch behind this one
         }
     }
@@ -936,6 +939,7 @@ int grid_backward_binned(const T* grad, bool blc, const float* inputs, const int
         ad.step = ta->step;
         ad.grad_scale = ta->grad_scale;
         ad.k = AdamConsts{ta->lr, ta->beta1, ta->beta2, ta->eps};
+        ad.sched = LrSched{ta->lr_factor, ta->lr_n, ta->lr_iter};
     }
     dt.stale_flag = stale_flag();
     dt.found_inf = sizeof(T) == 2 ? lc.found_inf : nullptr;  // (fp32 tables: the caller scans, launch_backward)

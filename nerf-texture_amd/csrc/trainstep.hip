@@ -12,6 +12,7 @@
 //                updates in double (double betas times float state), the parameter update in float, the bias corrections from
 //                double pow rounded to float -- tests/test_gpu_trainstep.py compares with torch.optim.Adam(fused=True).
 #include <algorithm>
+#include <type_traits>
 
 #include "adam_math.hpp"  // AdamConsts, AdamStep, adam_one: shared with the hash-grid backward that applies the update from its tiles
 #include "common.hpp"
@@ -249,11 +250,20 @@ __device__ __forceinline__ void adam_tensor(const AdamState src, const AdamState
     }
 }
 
-// up to 8 tensors per launch (the table and the MLP weight vectors): a block finds its tensor, then grid-strides inside it
+// up to 8 tensors per launch (the table and the MLP weight vectors): a block finds its tensor, then grid-strides inside it.
+// SCHED: the learning rate is base (k.lr) * the schedule's factor of this step, and the loss scaler's tail advances the schedule's step counter
+template <bool SCHED>
 __global__ __launch_bounds__(kAdamThreads) void adam_half_kernel(const AdamTensors tens, const float* step, const float step_offset,
-                                                                 const AdamConsts k, const float* grad_scale, const float* found_inf,
-                                                                 const AmpTail tail, const AdamRepair repair) {
+                                                                 const AdamConsts k_in, const float* grad_scale, const float* found_inf,
+                                                                 const AmpTail tail, const AdamRepair repair,
+                                                                 const std::conditional_t<SCHED, LrSched, NoSched> sched) {
     // every device word the launch depends on, read up front in one round trip
+    uint32_t iter_v = 0u;
+    AdamConsts k = k_in;
+    if constexpr (SCHED) {
+        iter_v = *sched.iter;
+        k.lr = scheduled_lr(k_in.lr, sched, iter_v);
+    }
     const float found_v = found_inf ? *found_inf : 0.0f;
     const uint32_t live_v = tens.live ? *tens.live : 0u;
     const float step_v = *step;
@@ -294,6 +304,7 @@ __global__ __launch_bounds__(kAdamThreads) void adam_half_kernel(const AdamTenso
                 // (tail.scale / found_inf / step are the words read above: grad_scale == tail.scale, found_inf == tail.found_inf in the _amp entries)
                 amp_update_loaded(tail.scale, tail.growth_tracker, tail.found_inf, tail.step, tail.growth_factor, tail.backoff_factor, tail.growth_interval, tail.live,
                                   found_v, scale_v, tracker_v, step_v, live_v);
+                if constexpr (SCHED) *sched.iter = iter_v + 1u;  // every training step, applied or skipped (LambdaLR steps after both)
                 *tail.ticket = 0u;
             }
         }
@@ -333,8 +344,21 @@ __global__ __launch_bounds__(256) void amp_check_half_kernel(const CheckTensors 
 }
 
 __global__ void amp_update_kernel(float* scale, int32_t* growth_tracker, float* found_inf, float* step, const double growth_factor,
-                                  const double backoff_factor, const int growth_interval, uint32_t* live) {
+                                  const double backoff_factor, const int growth_interval, uint32_t* live, uint32_t* lr_iter) {
     amp_update(scale, growth_tracker, found_inf, step, growth_factor, backoff_factor, growth_interval, live);
+    if (lr_iter) *lr_iter += 1u;  // (a scheduled step with nothing to update still counts)
+}
+
+// nerftex_lr_schedule_publish: the step's rate into the fp32 lr tensors of torch's fused Adam, then the counter advances
+struct LrPublish {
+    double base[kMaxTensors];
+    float* out[kMaxTensors];
+    uint32_t groups;
+};
+__global__ void lr_publish_kernel(const LrSched sched, const LrPublish pub) {
+    const uint32_t t = *sched.iter;
+    for (uint32_t g = 0; g < pub.groups; g++) *pub.out[g] = (float)scheduled_lr(pub.base[g], sched, t);
+    *sched.iter = t + 1u;
 }
 
 }  // namespace
@@ -402,7 +426,16 @@ struct AdamSecondSet {
 int adam_half_launch(int count, float* const* params, float* const* exp_avgs, float* const* exp_avg_sqs, const void* const* grads_half,
                      void* const* params_half, const uint64_t* n, const float* step, float step_offset, double lr, double beta1, double beta2,
                      double eps, const float* grad_scale, const float* found_inf, const AmpTail& tail, void* stream, uint32_t bf16_mask = 0,
-                     const struct AdamSecondSet* second = nullptr);
+                     const struct AdamSecondSet* second = nullptr, const LrSched* sched = nullptr);
+// a nerftex_lr_schedule as the kernels take it; false (error set): unusable
+bool take_schedule(const nerftex_lr_schedule* s, LrSched& out, const char* who) {
+    if (!s || !s->factor || !s->iter || s->n == 0) {
+        set_error("%s: the learning-rate schedule needs its factor table (n >= 1) and its step counter", who);
+        return false;
+    }
+    out = LrSched{s->factor, s->n, s->iter};
+    return true;
+}
 }  // namespace
 
 extern "C" int nerftex_adam_half_step(int count, float* const* params, float* const* exp_avgs, float* const* exp_avg_sqs,
@@ -481,11 +514,78 @@ extern "C" int nerftex_adam_mixed_step_amp_db(int count, float* const* params, f
                             bf16_mask, &second);
 }
 
+// the two _amp entries above with the step's learning rate read from a device schedule, the scaler's tail advancing its counter
+extern "C" int nerftex_adam_mixed_step_amp_sched(int count, float* const* params, float* const* exp_avgs, float* const* exp_avg_sqs,
+                                                 const void* const* grads16, void* const* params16, const uint64_t* n, uint32_t bf16_mask, float* step,
+                                                 double base_lr, const nerftex_lr_schedule* sched, double beta1, double beta2, double eps, float* scale,
+                                                 int32_t* growth_tracker, float* found_inf, uint32_t* ticket, double growth_factor, double backoff_factor,
+                                                 int growth_interval, void* stream) {
+    clear_error();
+    LrSched ls{};
+    if (!take_schedule(sched, ls, "adam_mixed_step_amp_sched")) return NERFTEX_ERR_INVALID;
+    if (!scale || !growth_tracker || !found_inf || !step || !ticket) {
+        set_error("adam_mixed_step_amp_sched: scale, growth_tracker, found_inf, step and ticket must not be NULL");
+        return NERFTEX_ERR_INVALID;
+    }
+    const AmpTail tail{scale, growth_tracker, found_inf, step, ticket, growth_factor, backoff_factor, growth_interval, nullptr};
+    return adam_half_launch(count, params, exp_avgs, exp_avg_sqs, grads16, params16, n, step, 1.0f, base_lr, beta1, beta2, eps, scale, found_inf, tail,
+                            stream, bf16_mask, nullptr, &ls);
+}
+extern "C" int nerftex_adam_mixed_step_amp_db_sched(int count, float* const* params, float* const* exp_avgs, float* const* exp_avg_sqs, float* const* params1,
+                                                    float* const* exp_avgs1, float* const* exp_avg_sqs1, const void* const* grads16, void* const* params16,
+                                                    const uint64_t* n, uint32_t bf16_mask, float* step, double base_lr, const nerftex_lr_schedule* sched,
+                                                    double beta1, double beta2, double eps, float* scale, int32_t* growth_tracker, float* found_inf,
+                                                    uint32_t* ticket, double growth_factor, double backoff_factor, int growth_interval, uint32_t* live,
+                                                    void* repair_half, const float* repair_param0, const float* repair_param1, uint64_t repair_n, void* stream) {
+    clear_error();
+    LrSched ls{};
+    if (!take_schedule(sched, ls, "adam_mixed_step_amp_db_sched")) return NERFTEX_ERR_INVALID;
+    if (!scale || !growth_tracker || !found_inf || !step || !ticket || !live || !params1 || !exp_avgs1 || !exp_avg_sqs1) {
+        set_error("adam_mixed_step_amp_db_sched: scale, growth_tracker, found_inf, step, ticket, live and the second state set must not be NULL");
+        return NERFTEX_ERR_INVALID;
+    }
+    if (repair_n && (!repair_half || !repair_param0 || !repair_param1 || repair_n % 8 || misaligned(repair_half) || misaligned(repair_param0) ||
+                     misaligned(repair_param1))) {
+        set_error("adam_mixed_step_amp_db_sched: the repair range needs its three buffers, 16-byte aligned, and a multiple of 8 elements");
+        return NERFTEX_ERR_INVALID;
+    }
+    const AmpTail tail{scale, growth_tracker, found_inf, step, ticket, growth_factor, backoff_factor, growth_interval, live};
+    const AdamSecondSet second{params1, exp_avgs1, exp_avg_sqs1, live, AdamRepair{static_cast<half_t*>(repair_half), {repair_param0, repair_param1}, repair_n}};
+    return adam_half_launch(count, params, exp_avgs, exp_avg_sqs, grads16, params16, n, step, 1.0f, base_lr, beta1, beta2, eps, scale, found_inf, tail, stream,
+                            bf16_mask, &second, &ls);
+}
+
+extern "C" int nerftex_lr_schedule_publish(const nerftex_lr_schedule* sched, const double* base_lrs, float* const* lr_out, uint32_t groups, void* stream) {
+    clear_error();
+    LrSched ls{};
+    if (!take_schedule(sched, ls, "lr_schedule_publish")) return NERFTEX_ERR_INVALID;
+    if (groups == 0 || groups > (uint32_t)kMaxTensors || !base_lrs || !lr_out) {
+        set_error("lr_schedule_publish: 1 to %d parameter groups, with their base rates and lr tensors", kMaxTensors);
+        return NERFTEX_ERR_INVALID;
+    }
+    LrPublish pub{};
+    for (uint32_t g = 0; g < groups; g++) {
+        if (!lr_out[g]) {
+            set_error("lr_schedule_publish: group %u has no lr tensor", g);
+            return NERFTEX_ERR_INVALID;
+        }
+        pub.base[g] = base_lrs[g];
+        pub.out[g] = lr_out[g];
+    }
+    pub.groups = groups;
+    hipStream_t st = as_stream(stream);
+    {
+        KernelTimer kt("lr_publish_kernel", st);
+        hipLaunchKernelGGL(lr_publish_kernel, dim3(1), dim3(1), 0, st, ls, pub);
+    }
+    return check_launch("lr_schedule_publish");
+}
+
 namespace {
 int adam_half_launch(int count, float* const* params, float* const* exp_avgs, float* const* exp_avg_sqs, const void* const* grads_half,
                      void* const* params_half, const uint64_t* n, const float* step, float step_offset, double lr, double beta1, double beta2,
                      double eps, const float* grad_scale, const float* found_inf, const AmpTail& tail, void* stream, uint32_t bf16_mask,
-                     const AdamSecondSet* second) {
+                     const AdamSecondSet* second, const LrSched* sched) {
     clear_error();
     if (count < 0 || count > kMaxTensors) {
         set_error("adam_half_step: at most 8 tensors per call");
@@ -528,7 +628,7 @@ int adam_half_launch(int count, float* const* params, float* const* exp_avgs, fl
     if (tens.count == 0 && !repair.n) {  // nothing to update: the scaler's bookkeeping still happens
         if (tail.scale) {
             hipLaunchKernelGGL(amp_update_kernel, dim3(1), dim3(1), 0, st, tail.scale, tail.growth_tracker, tail.found_inf, tail.step, tail.growth_factor,
-                               tail.backoff_factor, tail.growth_interval, tail.live);
+                               tail.backoff_factor, tail.growth_interval, tail.live, sched ? sched->iter : nullptr);
             return check_launch("adam_half_step(amp)");
         }
         return NERFTEX_OK;
@@ -536,7 +636,12 @@ int adam_half_launch(int count, float* const* params, float* const* exp_avgs, fl
     const AdamConsts k{lr, beta1, beta2, eps};
     {
         KernelTimer kt("adam_half_kernel", st);
-        hipLaunchKernelGGL(adam_half_kernel, dim3(blocks), dim3(kAdamThreads), 0, st, tens, step, step_offset, k, grad_scale, found_inf, tail, repair);
+        if (sched)
+            hipLaunchKernelGGL(adam_half_kernel<true>, dim3(blocks), dim3(kAdamThreads), 0, st, tens, step, step_offset, k, grad_scale, found_inf, tail, repair,
+                               *sched);
+        else
+            hipLaunchKernelGGL(adam_half_kernel<false>, dim3(blocks), dim3(kAdamThreads), 0, st, tens, step, step_offset, k, grad_scale, found_inf, tail, repair,
+                               NoSched{});
     }
     return check_launch("adam_half_step");
 }
@@ -590,7 +695,7 @@ extern "C" int nerftex_amp_update(float* scale, int32_t* growth_tracker, float* 
     {
         KernelTimer kt("amp_update_kernel", st);
         hipLaunchKernelGGL(amp_update_kernel, dim3(1), dim3(1), 0, st, scale, growth_tracker, found_inf, step, growth_factor, backoff_factor,
-                           growth_interval, (uint32_t*)nullptr);
+                           growth_interval, (uint32_t*)nullptr, (uint32_t*)nullptr);
     }
     return check_launch("amp_update");
 }

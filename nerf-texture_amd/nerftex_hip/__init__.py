@@ -61,6 +61,11 @@ _SIGNATURES = {
     "nerftex_amp_check_mixed": [_i, _vp, _vp, _u32, _vp, _vp],
     "nerftex_adam_mixed_step_amp_db": [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _f64, _f64, _f64, _f64, _vp, _vp, _vp, _vp, _f64, _f64, _i,
                                        _vp, _vp, _vp, _vp, _u64, _vp],
+    "nerftex_adam_mixed_step_amp_sched": [_i, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _f64, _vp, _f64, _f64, _f64, _vp, _vp, _vp, _vp, _f64, _f64, _i,
+                                          _vp],
+    "nerftex_adam_mixed_step_amp_db_sched": [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _f64, _vp, _f64, _f64, _f64, _vp, _vp, _vp, _vp,
+                                             _f64, _f64, _i, _vp, _vp, _vp, _vp, _u64, _vp],
+    "nerftex_lr_schedule_publish": [_vp, _vp, _vp, _u32, _vp],
     "nerftex_field_backward_live": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "nerftex_field_backward_live_bf16": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "nerftex_field_backward_live_consume": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
@@ -131,10 +136,15 @@ _SIGNATURES = {
     "nerftex_debug_workspace": [C.c_int, _vp, C.POINTER(_vp), C.POINTER(C.c_size_t)],
     "nerftex_raytracer_trace": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp],
 }
+class LrSchedule(C.Structure):
+    """nerftex_lr_schedule of include/nerftex_hip.h, field for field."""
+    _fields_ = [("factor", _vp), ("n", _u32), ("iter", _vp)]
+
+
 class TableAdam(C.Structure):
-    """nerftex_table_adam of include/nerftex_hip.h, field for field."""
+    """nerftex_table_adam of include/nerftex_hip.h, field for field (sched: address of a LrSchedule, or None)."""
     _fields_ = [("param", _vp * 2), ("exp_avg", _vp * 2), ("exp_avg_sq", _vp * 2), ("param_half", _vp), ("live", _vp), ("step", _vp),
-                ("grad_scale", _vp), ("found_inf", _vp), ("lr", _f64), ("beta1", _f64), ("beta2", _f64), ("eps", _f64)]
+                ("grad_scale", _vp), ("found_inf", _vp), ("lr", _f64), ("beta1", _f64), ("beta2", _f64), ("eps", _f64), ("sched", _vp)]
 
 
 class StepTrailer(C.Structure):

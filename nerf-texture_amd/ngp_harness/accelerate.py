@@ -42,9 +42,10 @@ RING = 16
 class AcceleratedTrainer:
     def __init__(self, renderer, rays_per_batch=None, lr=1e-2, betas=(0.9, 0.99), eps=1e-15, dt_gamma=1 / 128, bg_color=1, perturb=True, max_steps=1024,
                  amp_dtype=torch.float16, graph=True, steps_per_call=1, march_across_ring_end=False, pipeline_adam=0, skip_dead_samples=None,
-                 fused_table_update=None, fused_composite_step=None):
+                 fused_table_update=None, fused_composite_step=None, lr_scheduler=None, total_steps=None):
         from .model import NGPField
 
+        _refuse_unschedulable(lr_scheduler, pipeline_adam)
         field = renderer.field
         assert isinstance(field, NGPField), "accelerate() knows the ngp field (hash grid + two MLPs)"
         self.renderer, self.field = renderer, field
@@ -137,6 +138,35 @@ class AcceleratedTrainer:
 
             ensure_pool(self.dev)  # (every stream of the package exists BEFORE this trainer's captures: streams.py)
         self.loss = torch.zeros((), dtype=torch.float32, device=self.dev)
+        self._attach_schedule(lr_scheduler, total_steps)
+
+    def _attach_schedule(self, factory, total_steps):
+        """lr_scheduler = factory (the reference Trainer's shape: `lambda optimizer: LambdaLR(optimizer, ...)`), called on this trainer's optimizer:
+        its lambda's factors go into a device table every optimizer launch reads (lr_schedule.py).  trainer.lr_scheduler is the LambdaLR, kept
+        current on the host after every call.  Without a schedule the graphs hold the rate of their capture: a changed param_groups[g]["lr"]
+        makes the next replay raise (_lr_guard)."""
+        self.lr_scheduler, self._lr_sched, self._captured_lr = None, None, None
+        if factory is None:
+            return
+        from torch.optim.lr_scheduler import LRScheduler
+
+        from .lr_schedule import DeviceLRSchedule
+
+        if isinstance(factory, LRScheduler) or not callable(factory):
+            raise TypeError("lr_scheduler: pass a factory, `lambda optimizer: LambdaLR(optimizer, ...)` (it is called on the trainer's own optimizer)")
+        sched = factory(self.opt)
+        self._lr_sched = DeviceLRSchedule(sched, total_steps, self.dev)
+        if self.fused:
+            self.opt.lr_schedule = self._lr_sched  # HalfLeafAdam: the _sched launches (and the table update's descriptor)
+        else:
+            self._lr_sched.use_tensor_lr(self.opt)  # torch's fused Adam reads an fp32 tensor written by nerftex_lr_schedule_publish
+        self.lr_scheduler = sched
+
+    def _lr_guard(self):
+        """Without a schedule the replayed launches train at the rate they were captured with: refuse to replay after it changed."""
+        if self._lr_sched is None and self._captured_lr is not None and self._captured_lr != _host_lrs(self.opt):
+            raise RuntimeError(f"param_groups lr changed from {self._captured_lr} to {_host_lrs(self.opt)} after the training graphs were captured; "
+                               "they would keep training at the old rate.  Attach the schedule with accelerate(..., lr_scheduler=, total_steps=)")
 
     @staticmethod
     def _split_k_layers(field):
@@ -182,6 +212,8 @@ class AcceleratedTrainer:
             self.amp.step()
         else:
             self.scaler.scale(scaled).backward()  # (scale None: `scaled` is the loss itself, with its graph)
+            if self._lr_sched is not None:
+                self._lr_sched.publish()  # this step's rate into the optimizer's lr tensors; counts skipped steps too
             self.scaler.step(self.opt)
             self.scaler.update()
         self.loss.copy_(loss.detach().reshape(()))
@@ -220,6 +252,7 @@ class AcceleratedTrainer:
                     self._groups.append(gg)
             self._graphs = graphs
             r.local_step = keep_step % RING
+            self._captured_lr = _host_lrs(self.opt)
 
     def _ensure_buffers(self, n_rays):
         if self._rays is None:
@@ -251,6 +284,8 @@ class AcceleratedTrainer:
         `step`: the same kernels in the same order on the same data (tests/test_gpu_round4.py).  Returns the last step's loss (device scalar)."""
         r, k = self.renderer, self.group
         assert k > 1 and rays_o.shape[0] == k and rays_o.dim() == 3, "step_group: [steps_per_call, N, 3] rays (steps_per_call > 1)"
+        if self._lr_sched is not None:
+            self._lr_sched.check(k)
         assert rays_o.is_contiguous() and rays_d.is_contiguous(), "step_group: rays_o / rays_d must be contiguous [k, N, 3] tensors"
         self._ensure_buffers(rays_o.shape[1])
         if not self.use_graph or self._primed < RING or self._warm < max(2, k):
@@ -263,6 +298,7 @@ class AcceleratedTrainer:
         assert r.local_step % k == 0, "step_group and step must not be mixed once the graphs run (the ring slot must stay a multiple of steps_per_call)"
         if self._graphs is None:
             self._capture()
+        self._lr_guard()
         g0 = r.local_step
         main = torch.cuda.current_stream()
         if self._ahead is not None and self._ahead == (g0, rays_o.data_ptr(), rays_d.data_ptr()):
@@ -284,6 +320,8 @@ class AcceleratedTrainer:
             ready.record(main)  # everything enqueued so far (the production of the next rays, an occupancy update) -- NOT this group's kernels
         self._groups[g0 // k].replay()
         r.local_step = g0 + k
+        if self._lr_sched is not None:
+            self._lr_sched.advance(k)
         def march_ahead(slot0):
             no, nd = next_rays
             assert no.shape == rays_o.shape and no.is_contiguous() and nd.is_contiguous(), "next_rays: contiguous [k, N, 3] tensors"
@@ -313,6 +351,8 @@ class AcceleratedTrainer:
         rays_o, rays_d, target = rays_o.reshape(-1, 3), rays_d.reshape(-1, 3), target.reshape(-1, 3)
         assert rays_o.is_contiguous() and rays_d.is_contiguous(), "accelerate().step: rays_o / rays_d must be contiguous [N,3] tensors"
         self._ensure_buffers(rays_o.shape[0])
+        if self._lr_sched is not None:
+            self._lr_sched.check(1)
         main = torch.cuda.current_stream()
         if _eager or not self.use_graph or self._primed < RING or self._warm < 2:
             # the reference's first steps: full-size sample buffers until the ring holds a mean count (its update_extra_state cadence);
@@ -323,6 +363,8 @@ class AcceleratedTrainer:
             ro.copy_(rays_o, non_blocking=True), rd.copy_(rays_d, non_blocking=True), tg.copy_(target, non_blocking=True)
             marched, _ = self._march(ro, rd, mean_count=self._M if sized else None)
             self._shade(marched, tg)
+            if self._lr_sched is not None:
+                self._lr_sched.advance(1)
             self._primed += 1
             self._warm += 1 if sized else 0
             if r.local_step == RING:
@@ -332,6 +374,7 @@ class AcceleratedTrainer:
         assert self.group == 1, "this trainer was built with steps_per_call > 1: call step_group"
         if self._graphs is None:
             self._capture()
+        self._lr_guard()
         g = r.local_step
         gm, ga, _ = self._graphs[g]
         if self._ahead is not None and self._ahead == (g, rays_o.data_ptr(), rays_d.data_ptr()):
@@ -352,6 +395,8 @@ class AcceleratedTrainer:
             ready.record(main)  # everything enqueued so far (the production of the next rays, an occupancy update, this batch's march) -- NOT the rest of this step
         ga.replay()
         r.local_step = g + 1
+        if self._lr_sched is not None:
+            self._lr_sched.advance(1)
         if not last:
             if ready is not None:
                 self._march_ahead(g + 1, next_rays, ready)
@@ -397,6 +442,22 @@ class AcceleratedTrainer:
             self._graphs, self._groups, self._warm = None, None, 0
 
 
+def _host_lrs(opt):
+    return [None if isinstance(g["lr"], torch.Tensor) else float(g["lr"]) for g in opt.param_groups]
+
+
+def _refuse_unschedulable(lr_scheduler, pipeline_adam):
+    """Paths that cannot read the rate from the device schedule are refused at construction, never run at a constant rate."""
+    if lr_scheduler is None:
+        return
+    if int(pipeline_adam) > 1:
+        raise ValueError("lr_scheduler: pipeline_adam updates the table row range by row range (HalfLeafAdam.launch_rows), which cannot follow a "
+                         "learning-rate schedule; build the trainer without pipeline_adam")
+    dist = torch.distributed
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        raise ValueError("lr_scheduler: the device learning-rate schedule is single-process (world size 1)")
+
+
 def draw_ring_levels(num_levels, count=RING):
     """The hash-grid levels the reference's clustering_loss picks in `count` consecutive training steps: its own call,
     np.random.choice(np.arange(L), [1]) once per step, in step order (gridencoder/grid_clustering.py:204-207) -- after the same
@@ -420,8 +481,10 @@ class CurvedTrainer(AcceleratedTrainer):
 
     def __init__(self, renderer, regular_weight=1e-8, rays_per_batch=None, lr=1e-2, betas=(0.9, 0.99), eps=1e-15, dt_gamma=1 / 128, bg_color=1,
                  perturb=True, max_steps=1024, amp_dtype=torch.float16, graph=True, steps_per_call=1, march_across_ring_end=False, pipeline_adam=0,
-                 skip_dead_samples=None, fused_table_update=None, fused_composite_step=None):
+                 skip_dead_samples=None, fused_table_update=None, fused_composite_step=None, lr_scheduler=None, total_steps=None):
         from .curved import CurvedField
+
+        _refuse_unschedulable(lr_scheduler, pipeline_adam)
 
         field = renderer.field
         assert isinstance(field, CurvedField), "CurvedTrainer trains a curved.CurvedField"
@@ -474,6 +537,7 @@ class CurvedTrainer(AcceleratedTrainer):
         keep = {id(c) for c in centres}
         self._other_params = [p for p in field.parameters() if id(p) not in keep]
         self.reg_loss = torch.zeros((), dtype=torch.float32, device=self.dev)
+        self._attach_schedule(lr_scheduler, total_steps)  # (the optimizer's learning rates become fp32 tensors the schedule writes)
 
     def _draw_levels(self):
         self.ring_levels = draw_ring_levels(self.field.encoder.num_levels)
@@ -493,6 +557,8 @@ class CurvedTrainer(AcceleratedTrainer):
         grid_cluster_step(enc.embeddings.detach(), enc.offsets, torch.stack([l.cluster_centers.detach() for l in self._layers]), self._levels[slot],
                           self._alpha, self.regular_weight, loss=self.reg_loss, grad_table=enc.embeddings.grad, grad_centres=self._centres_grad,
                           grad_scale=self.scaler.scale(self._one))
+        if self._lr_sched is not None:
+            self._lr_sched.publish()
         self.scaler.step(self.opt)
         self.scaler.update()
         self.loss.copy_(loss.detach().reshape(()) + self.reg_loss)
@@ -511,7 +577,9 @@ class CurvedTrainer(AcceleratedTrainer):
 
 def accelerate(renderer, **kw):
     """See the module docstring.  Keyword arguments: rays_per_batch, lr, betas, eps, dt_gamma, bg_color, perturb, max_steps, amp_dtype, graph,
-    steps_per_call (k > 1: `step_group` takes the batches of k consecutive steps and replays one graph for them), march_across_ring_end.
+    steps_per_call (k > 1: `step_group` takes the batches of k consecutive steps and replays one graph for them), march_across_ring_end,
+    lr_scheduler + total_steps (a factory `lambda optimizer: LambdaLR(optimizer, lr_lambda)`, as the reference's Trainer takes it, and the number
+    of training steps its device table covers: every step, replayed or eager, trains at the rate LambdaLR gives it; `trainer.lr_scheduler`).
     A renderer over a curved.CurvedField gets a CurvedTrainer (its docstring; regular_weight, default 1e-8)."""
     from .curved import CurvedField
 

@@ -18,8 +18,9 @@ def model_state(renderer):
     return out
 
 
-def save_checkpoint(path, renderer, epoch=0, global_step=0, stats=None, optimizer=None, scaler=None):
-    """Write what Trainer.save_checkpoint(full=optimizer is not None) writes (nerf/utils.py:1485-1523)."""
+def save_checkpoint(path, renderer, epoch=0, global_step=0, stats=None, optimizer=None, scaler=None, lr_scheduler=None):
+    """Write what Trainer.save_checkpoint(full=optimizer is not None) writes (nerf/utils.py:1485-1523).  lr_scheduler: the reference's
+    'lr_scheduler' entry, LambdaLR.state_dict() (a trainer's `trainer.lr_scheduler` is kept current on the host: nothing is read back)."""
     state = {"epoch": epoch, "global_step": global_step, "stats": stats or {"loss": [], "valid_loss": [], "results": [], "checkpoints": [], "best_result": None},
              # plain Python numbers, as nerf/utils.py:1496-1497 stores them (the device-side occupancy update keeps mean_density as a view of
              # a buffer every later update overwrites: never pickle that)
@@ -28,6 +29,8 @@ def save_checkpoint(path, renderer, epoch=0, global_step=0, stats=None, optimize
         state["optimizer"] = optimizer.state_dict()
     if scaler is not None:
         state["scaler"] = scaler.state_dict()
+    if lr_scheduler is not None:
+        state["lr_scheduler"] = lr_scheduler.state_dict()
     torch.save(state, path)
     return state
 
@@ -54,9 +57,12 @@ def load_model_state(renderer, model_sd, strict=True):
     return missing, unexpected
 
 
-def load_checkpoint(path, renderer, optimizer=None, scaler=None, model_only=False, map_location=None):
+def load_checkpoint(path, renderer, optimizer=None, scaler=None, model_only=False, map_location=None, lr_scheduler=None):
     """Trainer.load_checkpoint (nerf/utils.py:1537-1602): model (non-strict, like the reference), mean_count / mean_density, then -- unless
-    model_only -- optimizer and scaler state.  Returns the checkpoint dict (epoch, global_step, stats are the caller's)."""
+    model_only -- optimizer, scaler and lr_scheduler state.  The scheduler of an accelerate(..., lr_scheduler=) trainer gets its last_epoch
+    into the device step counter and the host mirror (a reference checkpoint is accepted when its base_lrs, one per reference param group,
+    all equal this optimizer's); any other scheduler its own load_state_dict.  Returns the checkpoint dict (epoch, global_step, stats are
+    the caller's)."""
     ckpt = torch.load(path, map_location=map_location, weights_only=False)
     if "model" not in ckpt:
         load_model_state(renderer, ckpt, strict=True)
@@ -76,4 +82,9 @@ def load_checkpoint(path, renderer, optimizer=None, scaler=None, model_only=Fals
         optimizer.load_state_dict(ckpt["optimizer"])
     if scaler is not None and "scaler" in ckpt:
         scaler.load_state_dict(ckpt["scaler"])
+    if lr_scheduler is not None and "lr_scheduler" in ckpt:  # (after the optimizer: its state load rewrote the groups' lr)
+        from .lr_schedule import device_schedule_of
+
+        dev = device_schedule_of(lr_scheduler)
+        (dev or lr_scheduler).load_state_dict(ckpt["lr_scheduler"])
     return ckpt

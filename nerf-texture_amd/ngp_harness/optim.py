@@ -65,6 +65,7 @@ class HalfLeafAdam(torch.optim.Optimizer):
         self.step_count = torch.zeros((), dtype=torch.float32, device=self.masters[0].device)  # completed steps; device-side for graph replay
         self.live = None  # double-buffered form (enable_double_buffer): device word, which of the two state sets holds the current state
         self.fused_table = None  # (leaf index, first row) of a table whose rows from there on this step's backward has updated already
+        self.lr_schedule = None  # lr_schedule.DeviceLRSchedule: every launch reads the step's rate from the device (FusedAmp launches only)
 
     # ---- double-buffered state (round 6): what lets the hash-grid backward apply the update of the hashed levels from its LDS tiles -----------
     def enable_double_buffer(self):
@@ -110,6 +111,8 @@ class HalfLeafAdam(torch.optim.Optimizer):
         t.param_half, t.live, t.step = self.leaves[i].data_ptr(), self.live.data_ptr(), self.step_count.data_ptr()
         t.grad_scale, t.found_inf = amp.scale.data_ptr(), amp.found_inf.data_ptr()
         t.lr, t.beta1, t.beta2, t.eps = float(grp["lr"]), grp["betas"][0], grp["betas"][1], grp["eps"]
+        if self.lr_schedule is not None:  # lr = the base rate; the kernel reads this step's factor (the step's last launch advances it after)
+            t.lr, t.sched = self.lr_schedule.base_lrs[0], self.lr_schedule.desc_ptr
         return t
 
     def trainable(self):
@@ -166,6 +169,7 @@ class HalfLeafAdam(torch.optim.Optimizer):
     def launch_rows(self, i, a, b, step_offset, grad_scale, found_inf):
         """Adam over rows [a, b) of leaf i alone (current stream): the table updated level group by level group, each group as soon as its rows
         of the gradient are final (accelerate(pipeline_adam=True)).  The step number is *step_count + step_offset; step_count is not advanced."""
+        assert self.lr_schedule is None, "launch_rows cannot follow a learning-rate schedule"
         g = self.leaves[i].grad
         assert g is not None and g.dtype == self.leaves[i].dtype and g.is_contiguous()
         if b <= a:
@@ -194,7 +198,13 @@ class HalfLeafAdam(torch.optim.Optimizer):
         arrays = (_ptr_array([self.masters[i] for i in idx]), _ptr_array([self.exp_avg[i] for i in idx]),
                   _ptr_array([self.exp_avg_sq[i] for i in idx]), _ptr_array(grads), _ptr_array([self.leaves[i] for i in idx]), n)
         hyper = (float(grp["lr"]), grp["betas"][0], grp["betas"][1], grp["eps"])
-        if amp is None:
+        sched = self.lr_schedule
+        assert sched is None or amp is not None, "a learning-rate schedule is advanced by the loss scaler's launch (FusedAmp)"
+        if sched is not None:
+            scale, tracker, found, ticket, growth, backoff, interval = amp
+            check(lib.nerftex_adam_mixed_step_amp_sched(len(idx), *arrays, mask, ptr(self.step_count), sched.base_lrs[0], sched.desc_ptr, *hyper[1:],
+                                                        ptr(scale), ptr(tracker), ptr(found), ptr(ticket), growth, backoff, interval, stream()))
+        elif amp is None:
             check(lib.nerftex_adam_mixed_step(len(idx), *arrays, mask, ptr(self.step_count), float(step_offset), *hyper, ptr(grad_scale), ptr(found_inf),
                                               stream()))
         else:
@@ -228,10 +238,17 @@ class HalfLeafAdam(torch.optim.Optimizer):
         n = (ctypes.c_uint64 * max(len(idx), 1))(*[g.numel() for g in grads])
         sets = [_ptr_array([view(s[k][i], i) for i in idx]) for k in range(2) for s in (self._p, self._m, self._v)]  # p0 m0 v0 p1 m1 v1
         scale, tracker, found, ticket, growth, backoff, interval = amp
-        check(lib.nerftex_adam_mixed_step_amp_db(len(idx), *sets, _ptr_array(grads), _ptr_array([view(self.leaves[i].data, i) for i in idx]), n, mask,
-                                                 ptr(self.step_count), float(grp["lr"]), grp["betas"][0], grp["betas"][1], grp["eps"], ptr(scale), ptr(tracker),
-                                                 ptr(found), ptr(ticket), growth, backoff, interval, ptr(self.live), ptr(repair[0]), ptr(repair[1]), ptr(repair[2]),
-                                                 int(repair[3]), stream()))
+        sched = self.lr_schedule
+        if sched is not None:
+            check(lib.nerftex_adam_mixed_step_amp_db_sched(len(idx), *sets, _ptr_array(grads), _ptr_array([view(self.leaves[i].data, i) for i in idx]), n,
+                                                           mask, ptr(self.step_count), sched.base_lrs[0], sched.desc_ptr, grp["betas"][0], grp["betas"][1],
+                                                           grp["eps"], ptr(scale), ptr(tracker), ptr(found), ptr(ticket), growth, backoff, interval,
+                                                           ptr(self.live), ptr(repair[0]), ptr(repair[1]), ptr(repair[2]), int(repair[3]), stream()))
+        else:
+            check(lib.nerftex_adam_mixed_step_amp_db(len(idx), *sets, _ptr_array(grads), _ptr_array([view(self.leaves[i].data, i) for i in idx]), n, mask,
+                                                     ptr(self.step_count), float(grp["lr"]), grp["betas"][0], grp["betas"][1], grp["eps"], ptr(scale),
+                                                     ptr(tracker), ptr(found), ptr(ticket), growth, backoff, interval, ptr(self.live), ptr(repair[0]),
+                                                     ptr(repair[1]), ptr(repair[2]), int(repair[3]), stream()))
         for i in idx:
             torch.autograd.graph.increment_version(self.masters[i])
 
@@ -240,6 +257,7 @@ class HalfLeafAdam(torch.optim.Optimizer):
         """torch.optim protocol (plain, or driven by torch.amp.GradScaler through grad_scale / found_inf)."""
         assert closure is None
         assert self.live is None, "the double-buffered optimizer is driven by FusedAmp.step()"
+        assert self.lr_schedule is None, "a learning-rate schedule is advanced by the loss scaler's launch: drive this optimizer with FusedAmp"
         _poll_deferred_error()
         grad_scale = getattr(self, "grad_scale", None)
         found_inf = getattr(self, "found_inf", None)
