@@ -14,9 +14,10 @@ into the graphs; a trainer cannot):
     trainer = accelerate(renderer, steps_per_call=4)     # the benchmarked structure for a loop that has 4 batches at a time:
     loss = trainer.step_group(o4, d4, t4, next_rays=(o4n, d4n))           # [4, N, 3] tensors: one graph for 4 steps, 4 marches ahead
 
-  * the step replayed as HIP graphs, one set per slot of the renderer's 16-entry step-counter ring (renderer.py:656-660): the march of a
-    batch (near / far, DDA, sample expansion: it needs the rays and the occupancy grid, NOT the weights) and the rest of the step (field,
-    compositing + loss, backward, loss scaler, optimizer) are separate graphs, reading rays / targets from static buffers the call copies into;
+  * the step replayed as HIP graphs over the renderer's 16-entry step-counter ring (renderer.py:656-660): the march of a batch (near / far,
+    DDA, sample expansion: it needs the rays and the occupancy grid, NOT the weights) is one graph per ring slot, the rest (field, compositing
+    + loss, backward, loss scaler, optimizer) of the `steps_per_call` steps of a call is one graph per call of the ring; both read rays /
+    targets from static buffers the call copies into.  `step` is `step_group` with one batch: one body (`_steps`) enqueues either;
   * `next_rays`: a trainer that has its next batch's rays when it calls `step` (one `get_rays` ahead: software pipelining) hands them over
     and their march runs on a second, high-priority stream UNDER this step's kernels -- latency-bound work on issue slots the step leaves
     idle -- instead of in front of the next step; the next call must then pass the same rays (checked).  It is ordered behind the
@@ -31,8 +32,9 @@ into the graphs; a trainer cannot):
 The occupancy update stays the caller's (`renderer.update_extra_state_device()` every 16 steps writes grid and bitfield in place: the
 graphs keep reading the same tensors).  A march started by `next_rays` reads the grid as it is at that moment: hand the next rays over
 AFTER the update when one is due (the ring's end, where nothing is marched ahead anyway: the read-back comes first there).
-Values: the same kernels in the same order as the eager step -- tests/test_gpu_round3.py holds the replayed step to the eager loss
-trajectory, with and without `next_rays`.
+Values: the same kernels in the same order as the eager step -- tests/test_gpu_round3.py::test_accelerate_replays_the_eager_step holds the
+replayed step to the eager loss trajectory (bit for bit with and without `next_rays` on the FFMLP field), tests/test_gpu_round4.py::
+test_step_group_trains_like_single_steps holds `step_group` to `step`, parameters bit for bit.
 """
 import torch
 
@@ -48,12 +50,7 @@ class AcceleratedTrainer:
         _refuse_unschedulable(lr_scheduler, pipeline_adam)
         field = renderer.field
         assert isinstance(field, NGPField), "accelerate() knows the ngp field (hash grid + two MLPs)"
-        self.renderer, self.field = renderer, field
-        self.dev = next(field.parameters()).device
-        self.n_rays = rays_per_batch
-        self.dt_gamma, self.bg_color, self.perturb, self.max_steps = dt_gamma, bg_color, perturb, max_steps
-        self.amp_dtype = amp_dtype
-        self.use_graph = bool(graph)
+        self._init_loop(renderer, field, rays_per_batch, dt_gamma, bg_color, perturb, max_steps, amp_dtype, graph, steps_per_call, march_across_ring_end)
         bf16 = amp_dtype == torch.bfloat16 and getattr(field, "fused_field_bf16", False)  # bf16 networks over the fp16 table (round 5)
         self.fused = field.mlp == "ffmlp" and ((field.fused_glue and amp_dtype == torch.float16) or bf16)
         if self.fused:
@@ -109,7 +106,6 @@ class AcceleratedTrainer:
         assert not self.fused_table_update or can_fuse, "fused_table_update needs the fused FFMLP field under FusedAmp (and no pipeline_adam)"
         if self.fused_table_update:
             self.amp.fuse_table_update(field.encoder)
-        self._one = torch.ones((), dtype=torch.float32, device=self.dev)
         # fused_composite_step (round 6; None = on under the fused AMP step): compositing forward, render tail and their backward -- three adjacent,
         # latency-bound launches -- as ONE (fused.composite_tail's `one`: the step's root gradient is the tensor `_one`, so the forward's launch can
         # form the loss gradient itself).  Same outputs and gradients bit for bit (tests/test_gpu_round6.py).
@@ -118,27 +114,37 @@ class AcceleratedTrainer:
         assert not self.fused_composite_step or can_step, "fused_composite_step needs the fused AMP step (the root gradient must be known to be one)"
         renderer.root_one = self._one if self.fused_composite_step else None
         renderer.defer_step_loss = bool(self.fused_composite_step)  # (`_shade` reads the loss after the backward: the field's backward may finish it)
-        self._graphs, self._M = None, 0
+        self._attach_schedule(lr_scheduler, total_steps)
+
+    def _init_loop(self, renderer, field, rays_per_batch, dt_gamma, bg_color, perturb, max_steps, amp_dtype, graph, steps_per_call, march_across_ring_end):
+        """What the step loop keeps, whatever the field and its optimizer (both constructors start here)."""
+        self.renderer, self.field = renderer, field
+        self.dev = next(field.parameters()).device
+        self.n_rays = rays_per_batch
+        self.dt_gamma, self.bg_color, self.perturb, self.max_steps = dt_gamma, bg_color, perturb, max_steps
+        self.amp_dtype = amp_dtype
+        self.use_graph = bool(graph)
+        self._one = torch.ones((), dtype=torch.float32, device=self.dev)
         # steps_per_call = k > 1: `step_group` takes the batches of k consecutive steps at once and replays ONE graph for their shade + backward +
         # optimizer (the hand-over between two graph launches idles the device ~10 us: bench.py's --steps-per-graph), their k marches being
         # graphs of their own that run ahead on the second stream when the caller hands the NEXT group's rays over
+        self.group = int(steps_per_call)
+        assert self.group in (1, 2, 4, 8, 16), "steps_per_call must divide the 16-entry step-counter ring"
         # march_across_ring_end: at the ring's last call, `next_rays` are marched ahead as well (right behind the mean_count read-back) instead
         # of inline at the start of the next ring.  That march reads the occupancy grid while this call's steps still run: a trainer that
         # updates the grid every 16 steps (nerf/utils.py:1011) must then do so BEFORE the ring's last call, not after it.  Off by default.
-        self.march_across_ring_end = bool(march_across_ring_end)
-        self.group = int(steps_per_call)
-        assert self.group in (1, 2, 4, 8, 16), "steps_per_call must divide the 16-entry step-counter ring"
-        self._groups = None
+        # It acts for steps_per_call > 1 only: single steps never march across the ring's end.
+        self.march_across_ring_end = bool(march_across_ring_end) and self.group > 1
+        self._graphs, self._groups, self._M = None, None, 0  # per ring slot (march graph, marched tensors); per call of the ring its shade graph; the buffer size
         self._rays, self._targets = None, None  # static inputs per ring slot: rays (the march of slot g + 1 may run while slot g's is still read), targets
         self._primed, self._warm = 0, 0
-        self._ahead = None  # (slot, data_ptr of rays_o, data_ptr of rays_d) of a march started by `next_rays`
+        self._ahead = None  # (first slot, data_ptr of rays_o, data_ptr of rays_d) of the marches started by `next_rays`
         self._side = None
         if self.dev.type == "cuda":
             from .streams import ensure_pool
 
             ensure_pool(self.dev)  # (every stream of the package exists BEFORE this trainer's captures: streams.py)
         self.loss = torch.zeros((), dtype=torch.float32, device=self.dev)
-        self._attach_schedule(lr_scheduler, total_steps)
 
     def _attach_schedule(self, factory, total_steps):
         """lr_scheduler = factory (the reference Trainer's shape: `lambda optimizer: LambdaLR(optimizer, ...)`), called on this trainer's optimizer:
@@ -181,8 +187,8 @@ class AcceleratedTrainer:
         with torch.autocast("cuda", dtype=self.amp_dtype):
             return self.renderer.march_train(ro, rd, dt_gamma=self.dt_gamma, perturb=self.perturb, max_steps=self.max_steps, mean_count=mean_count)
 
-    def _shade(self, marched, tgt):
-        r = self.renderer
+    def _shade(self, marched, slot):
+        r, tgt = self.renderer, self._targets[slot]
         if self.fused:
             for leaf in self.opt.leaves:
                 leaf.grad = None
@@ -219,38 +225,38 @@ class AcceleratedTrainer:
         self.loss.copy_(loss.detach().reshape(()))
 
     def _capture(self):
-        """Record the graphs.  Nothing is executed here: the two eager steps at this buffer size that `step` ran just before (real
-        training steps) have sized the library's workspaces and done every lazy initialisation outside the capture."""
+        """Record the graphs: a march graph per ring slot into `_graphs`, a shade graph (shade + backward + optimizer of its `group` steps) per
+        call of the ring into `_groups`.  Nothing is executed here: the eager steps at this buffer size that ran just before (real training
+        steps) have sized the library's workspaces and done every lazy initialisation outside the capture."""
         from .streams import capture_section
 
-        r = self.renderer
+        r, k = self.renderer, self.group
         with capture_section():
             keep_step = r.local_step
-            graphs, pool, pool_m = [], None, None
+            graphs, pool, pool_m = [], None, None  # (the march graphs share one memory pool, the shade graphs another: a march may run beside a shade)
+
+            def shade_graph(g0):
+                nonlocal pool
+                gg = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(gg, pool=pool, capture_error_mode="thread_local"):
+                    for g in range(g0, g0 + k):
+                        self._shade(graphs[g][1], g)
+                pool = gg.pool()
+                return gg
+
+            groups = []
             for g in range(RING):  # per ring slot: the step's counter is slot g, as in the eager loop
                 r.local_step = g
                 gm = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(gm, pool=pool_m, capture_error_mode="thread_local"):  # (own memory pool: it may run beside the other graph)
+                with torch.cuda.graph(gm, pool=pool_m, capture_error_mode="thread_local"):
                     marched, _ = self._march(*self._rays[g], mean_count=self._M)
                 pool_m = gm.pool()
-                ga = None
-                if self.group == 1:
-                    ga = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(ga, pool=pool, capture_error_mode="thread_local"):
-                        self._shade(marched, self._targets[g])
-                    pool = ga.pool()
-                graphs.append((gm, ga, marched))  # (the sample tensors stay alive: the second graph reads them)
-            self._groups = None
-            if self.group > 1:  # shade + backward + optimizer of `group` consecutive steps per graph
-                self._groups = []
-                for g0 in range(0, RING, self.group):
-                    gg = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(gg, pool=pool, capture_error_mode="thread_local"):
-                        for g in range(g0, g0 + self.group):
-                            self._shade(graphs[g][2], self._targets[g])
-                    pool = gg.pool()
-                    self._groups.append(gg)
-            self._graphs = graphs
+                graphs.append((gm, marched))  # (the sample tensors stay alive: the shade graph reads them)
+                if k == 1:  # a single step's shade graph is recorded right behind its march, a group's behind all sixteen (the order lays out the two pools)
+                    groups.append(shade_graph(g))
+            if k > 1:
+                groups = [shade_graph(g0) for g0 in range(0, RING, k)]
+            self._graphs, self._groups = graphs, groups
             r.local_step = keep_step % RING
             self._captured_lr = _host_lrs(self.opt)
 
@@ -281,128 +287,91 @@ class AcceleratedTrainer:
         """steps_per_call = k consecutive training steps in one call: rays_o / rays_d / target [k, N, 3] -- batch i is step i's (FRESH rays every
         call: they are copied into the graphs' static buffers).  next_rays = (rays_o, rays_d) [k, N, 3] of the NEXT call: their k marches start
         now, on the second stream, beside this group's kernels; the next call must pass those very tensors.  Same arithmetic as k calls of
-        `step`: the same kernels in the same order on the same data (tests/test_gpu_round4.py).  Returns the last step's loss (device scalar)."""
-        r, k = self.renderer, self.group
-        assert k > 1 and rays_o.shape[0] == k and rays_o.dim() == 3, "step_group: [steps_per_call, N, 3] rays (steps_per_call > 1)"
+        `step`: the same kernels in the same order on the same data (tests/test_gpu_round4.py::test_step_group_trains_like_single_steps).
+        Returns the last step's loss (device scalar)."""
+        assert self.group > 1 and rays_o.dim() == 3 and rays_o.shape[0] == self.group, "step_group: [steps_per_call, N, 3] rays (steps_per_call > 1)"
+        return self._steps(rays_o, rays_d, target, next_rays)
+
+    def step(self, rays_o, rays_d, target, next_rays=None):
+        """One training step on a batch of rays [N,3], [N,3] and their target colours [N,3] (device tensors; N fixed after the first call).
+        next_rays = (rays_o, rays_d) of the batch the NEXT call will pass: its march starts now, beside this step (module docstring).
+        Returns the loss as a device scalar that the NEXT call overwrites.  It is `step_group` with one batch."""
+        # views, for contiguous rays: the hand-over of `next_rays` is recognised by the address of these tensors (a reshape of a non-contiguous
+        # tensor would be a fresh copy with a fresh address every call)
+        return self._steps(rays_o.reshape(1, -1, 3), rays_d.reshape(1, -1, 3), target.reshape(1, -1, 3), next_rays)
+
+    def _steps(self, rays_o, rays_d, target, next_rays):
+        """The k steps of one call, on ring slots g0 .. g0 + k: `step_group`, and `step` as its k = 1.  rays_o / rays_d / target: [k, N, 3]."""
+        r, k = self.renderer, rays_o.shape[0]
+        assert rays_o.is_contiguous() and rays_d.is_contiguous(), "rays_o / rays_d must be contiguous tensors (next_rays are recognised by their address)"
+        self._ensure_buffers(rays_o.shape[1])
         if self._lr_sched is not None:
             self._lr_sched.check(k)
-        assert rays_o.is_contiguous() and rays_d.is_contiguous(), "step_group: rays_o / rays_d must be contiguous [k, N, 3] tensors"
-        self._ensure_buffers(rays_o.shape[1])
-        if not self.use_graph or self._primed < RING or self._warm < max(2, k):
-            # the reference's first steps (full-size buffers until the ring holds a mean count), then `k` eager steps at the size the graphs
-            # will be recorded with -- one by one, on the eager path; k of them so that the ring slot is a multiple of k when the graphs start
+        if not self.use_graph or self._primed < RING or self._warm < max(2, self.group):
+            # the reference's first steps: full-size sample buffers until the ring holds a mean count (its update_extra_state cadence); then -- and
+            # after every change of the buffer size -- eager steps at the size the graphs will be recorded with: two, or `group` of them, so that
+            # the ring slot is a multiple of `group` when the graphs start
             assert self._ahead is None
             for i in range(k):
-                self.step(rays_o[i], rays_d[i], target[i], _eager=True)
+                self._eager_step(rays_o[i], rays_d[i], target[i])
             return self.loss
-        assert r.local_step % k == 0, "step_group and step must not be mixed once the graphs run (the ring slot must stay a multiple of steps_per_call)"
+        g0 = r.local_step
+        assert k == self.group, "this trainer was built with steps_per_call > 1: call step_group"
+        assert g0 % k == 0, "step_group and step must not be mixed once the graphs run (the ring slot must stay a multiple of steps_per_call)"
+        if g0 == 0:
+            self._ring_start()
         if self._graphs is None:
             self._capture()
         self._lr_guard()
-        g0 = r.local_step
         main = torch.cuda.current_stream()
-        if self._ahead is not None and self._ahead == (g0, rays_o.data_ptr(), rays_d.data_ptr()):
-            main.wait_stream(self._side)  # marched beside the previous group
-        else:
-            if self._ahead is not None:
-                self._ahead = None
-                main.wait_stream(self._side)
+        ahead, self._ahead = self._ahead, None
+        if ahead is not None:
+            main.wait_stream(self._side)  # marched beside the previous call
+            if ahead != (g0, rays_o.data_ptr(), rays_d.data_ptr()):  # ... but other tensors: it is forgotten (the next call starts clean), this call refused
                 raise AssertionError("next_rays of the previous call must be the rays of this call (same tensors)")
+        else:
             self._ray_o[g0:g0 + k].copy_(rays_o, non_blocking=True), self._ray_d[g0:g0 + k].copy_(rays_d, non_blocking=True)
             for g in range(g0, g0 + k):
                 self._graphs[g][0].replay()
-        self._ahead = None
         self._targets[g0:g0 + k].copy_(target, non_blocking=True)
-        last = g0 + k == RING
         ready = None
         if next_rays is not None:
             ready = torch.cuda.Event()
-            ready.record(main)  # everything enqueued so far (the production of the next rays, an occupancy update) -- NOT this group's kernels
+            ready.record(main)  # everything enqueued so far (the production of the next rays, an occupancy update, this call's marches) -- NOT the rest of this call
         self._groups[g0 // k].replay()
         r.local_step = g0 + k
         if self._lr_sched is not None:
             self._lr_sched.advance(k)
-        def march_ahead(slot0):
-            no, nd = next_rays
-            assert no.shape == rays_o.shape and no.is_contiguous() and nd.is_contiguous(), "next_rays: contiguous [k, N, 3] tensors"
-            with torch.cuda.stream(self._side_stream()):
-                self._side.wait_event(ready)
-                self._ray_o[slot0:slot0 + k].copy_(no, non_blocking=True), self._ray_d[slot0:slot0 + k].copy_(nd, non_blocking=True)
-                for g in range(slot0, slot0 + k):
-                    self._graphs[g][0].replay()
-            self._ahead = (slot0, no.data_ptr(), nd.data_ptr())
-
-        if not last:
+        if g0 + k < RING:
             if ready is not None:
-                march_ahead(g0 + k)
+                self._march_ahead(g0 + k, k, next_rays, ready)
         else:
             self._ring_end(ready)
             if ready is not None and self.march_across_ring_end and self._graphs is not None:  # (graphs dropped: the buffer size changed)
-                march_ahead(0)
+                self._march_ahead(0, k, next_rays, ready)
         return self.loss
 
-    def step(self, rays_o, rays_d, target, next_rays=None, _eager=False):
-        """One training step on a batch of rays [N,3], [N,3] and their target colours [N,3] (device tensors; N fixed after the first call).
-        next_rays = (rays_o, rays_d) of the batch the NEXT call will pass: its march starts now, beside this step (module docstring).
-        Returns the loss as a device scalar that the NEXT call overwrites."""
+    def _eager_step(self, rays_o, rays_d, target):
+        """One step launched kernel by kernel, through the static buffers of its ring slot (graph=False keeps the same buffer-size policy)."""
         r = self.renderer
-        # contiguous views: the hand-over of `next_rays` is recognised by the address of these tensors (a reshape of a non-contiguous
-        # tensor would be a fresh copy with a fresh address every call)
-        rays_o, rays_d, target = rays_o.reshape(-1, 3), rays_d.reshape(-1, 3), target.reshape(-1, 3)
-        assert rays_o.is_contiguous() and rays_d.is_contiguous(), "accelerate().step: rays_o / rays_d must be contiguous [N,3] tensors"
-        self._ensure_buffers(rays_o.shape[0])
-        if self._lr_sched is not None:
-            self._lr_sched.check(1)
-        main = torch.cuda.current_stream()
-        if _eager or not self.use_graph or self._primed < RING or self._warm < 2:
-            # the reference's first steps: full-size sample buffers until the ring holds a mean count (its update_extra_state cadence);
-            # then -- and after every change of the buffer size -- two eager steps at the size the graphs will be recorded with
-            sized = self._primed >= RING  # (graph=False keeps the same buffer-size policy, launched eagerly)
-            ro, rd = self._rays[r.local_step % RING]
-            tg = self._targets[r.local_step % RING]
-            ro.copy_(rays_o, non_blocking=True), rd.copy_(rays_d, non_blocking=True), tg.copy_(target, non_blocking=True)
-            marched, _ = self._march(ro, rd, mean_count=self._M if sized else None)
-            self._shade(marched, tg)
-            if self._lr_sched is not None:
-                self._lr_sched.advance(1)
-            self._primed += 1
-            self._warm += 1 if sized else 0
-            if r.local_step == RING:
-                r.update_mean_count()
-                self._resize()
-            return self.loss
-        assert self.group == 1, "this trainer was built with steps_per_call > 1: call step_group"
-        if self._graphs is None:
-            self._capture()
-        self._lr_guard()
-        g = r.local_step
-        gm, ga, _ = self._graphs[g]
-        if self._ahead is not None and self._ahead == (g, rays_o.data_ptr(), rays_d.data_ptr()):
-            main.wait_stream(self._side)  # marched beside the previous step
-        else:
-            if self._ahead is not None:  # the march that ran ahead was of other tensors: forget it (the next call starts clean), then refuse
-                self._ahead = None
-                main.wait_stream(self._side)
-                raise AssertionError("next_rays of the previous call must be the rays of this call (same tensors)")
-            self._rays[g][0].copy_(rays_o, non_blocking=True), self._rays[g][1].copy_(rays_d, non_blocking=True)
-            gm.replay()
-        self._ahead = None
-        self._targets[g].copy_(target, non_blocking=True)
-        last = g + 1 == RING
-        ready = None
-        if next_rays is not None:
-            ready = torch.cuda.Event()
-            ready.record(main)  # everything enqueued so far (the production of the next rays, an occupancy update, this batch's march) -- NOT the rest of this step
-        ga.replay()
-        r.local_step = g + 1
+        g = r.local_step % RING
+        if g == 0:
+            self._ring_start()
+        sized = self._primed >= RING
+        (ro, rd), tg = self._rays[g], self._targets[g]
+        ro.copy_(rays_o, non_blocking=True), rd.copy_(rays_d, non_blocking=True), tg.copy_(target, non_blocking=True)
+        marched, _ = self._march(ro, rd, mean_count=self._M if sized else None)
+        self._shade(marched, g)
         if self._lr_sched is not None:
             self._lr_sched.advance(1)
-        if not last:
-            if ready is not None:
-                self._march_ahead(g + 1, next_rays, ready)
-        else:
-            self._ring_end(ready)
-        return self.loss
+        self._primed += 1
+        self._warm += 1 if sized else 0
+        if r.local_step == RING:
+            r.update_mean_count()
+            self._resize()
+
+    def _ring_start(self):
+        """Called before a step is issued at ring slot 0, eager or replayed (CurvedTrainer draws the ring's levels here)."""
 
     def sync(self):
         """Make the fp32 module parameters and the optimizer's moment tensors current (double-buffered optimizer state, `fused_table_update`): one
@@ -417,18 +386,20 @@ class AcceleratedTrainer:
             self._side = side_stream(self.dev)  # the process-wide high-priority stream (streams.py: why it is shared)
         return self._side
 
-    def _march_ahead(self, slot, next_rays, ready):
-        no, nd = next_rays[0].reshape(-1, 3), next_rays[1].reshape(-1, 3)
-        assert no.shape[0] == self.n_rays
-        assert next_rays[0].is_contiguous() and next_rays[1].is_contiguous(), "next_rays must be contiguous (they are recognised by address in the next call)"
+    def _march_ahead(self, slot0, k, next_rays, ready):
+        """The marches of the next call's k batches, into slots slot0 .. slot0 + k, on the side stream: behind `ready`, beside this call's kernels."""
+        no, nd = next_rays
+        assert no.is_contiguous() and nd.is_contiguous() and no.numel() == nd.numel() == k * self.n_rays * 3, \
+            "next_rays: the contiguous rays of the next call (they are recognised by address there)"
         with torch.cuda.stream(self._side_stream()):
             self._side.wait_event(ready)
-            self._rays[slot][0].copy_(no, non_blocking=True), self._rays[slot][1].copy_(nd, non_blocking=True)
-            self._graphs[slot][0].replay()
-        self._ahead = (slot, no.data_ptr(), nd.data_ptr())
+            self._ray_o[slot0:slot0 + k].copy_(no.view(k, -1, 3), non_blocking=True), self._ray_d[slot0:slot0 + k].copy_(nd.view(k, -1, 3), non_blocking=True)
+            for g in range(slot0, slot0 + k):
+                self._graphs[g][0].replay()
+        self._ahead = (slot0, no.data_ptr(), nd.data_ptr())
 
     def _resize(self):
-        """After a mean_count read-back: (re)choose the sample-buffer size; a change drops the graphs (two eager steps, then a new capture)."""
+        """After a mean_count read-back: (re)choose the sample-buffer size; a change drops the graphs (eager steps at the new size, then a new capture)."""
         r = self.renderer
         if self._M == 0 or r.mean_count + 128 > self._M or r.mean_count < 0.8 * self._M:
             if self._M == 0:
@@ -494,33 +465,13 @@ class CurvedTrainer(AcceleratedTrainer):
         for name, v in (("pipeline_adam", pipeline_adam), ("skip_dead_samples", skip_dead_samples), ("fused_table_update", fused_table_update),
                         ("fused_composite_step", fused_composite_step)):
             assert not v, f"{name}: an option of the ngp field's fused AMP step; the curved field trains with torch's fused Adam + GradScaler"
-        self.renderer, self.field = renderer, field
-        self.dev = next(field.parameters()).device
-        self.n_rays = rays_per_batch
-        self.dt_gamma, self.bg_color, self.perturb, self.max_steps = dt_gamma, bg_color, perturb, max_steps
-        self.amp_dtype = amp_dtype
-        self.use_graph = bool(graph)
+        self._init_loop(renderer, field, rays_per_batch, dt_gamma, bg_color, perturb, max_steps, amp_dtype, graph, steps_per_call, march_across_ring_end)
         self.fused, self.amp, self.pipeline_adam = False, None, 0
         self.skip_dead_samples = self.fused_table_update = self.fused_composite_step = False
         renderer.skip_dead_samples, renderer.root_one, renderer.defer_step_loss = False, None, False
         # (capturable either way: graph=False runs the very optimizer arithmetic the graphs replay)
         self.opt = torch.optim.Adam(field.get_params(lr), betas=betas, eps=eps, fused=True, capturable=True)
         self.scaler = torch.amp.GradScaler("cuda", enabled=amp_dtype in (torch.float16, torch.bfloat16))
-        self._one = torch.ones((), dtype=torch.float32, device=self.dev)
-        self._graphs, self._M = None, 0
-        self.march_across_ring_end = bool(march_across_ring_end)
-        self.group = int(steps_per_call)
-        assert self.group in (1, 2, 4, 8, 16), "steps_per_call must divide the 16-entry step-counter ring"
-        self._groups = None
-        self._rays, self._targets = None, None
-        self._primed, self._warm = 0, 0
-        self._ahead = None
-        self._side = None
-        if self.dev.type == "cuda":
-            from .streams import ensure_pool
-
-            ensure_pool(self.dev)
-        self.loss = torch.zeros((), dtype=torch.float32, device=self.dev)
         # the regulariser: static level picks of the ring's 16 steps, the centres' gradient as one [L, K, C] buffer the per-level parameters'
         # .grad are views of (zeroed every step, never set to None: the kernel adds into it), its loss
         enc = field.encoder
@@ -539,18 +490,17 @@ class CurvedTrainer(AcceleratedTrainer):
         self.reg_loss = torch.zeros((), dtype=torch.float32, device=self.dev)
         self._attach_schedule(lr_scheduler, total_steps)  # (the optimizer's learning rates become fp32 tensors the schedule writes)
 
-    def _draw_levels(self):
+    def _ring_start(self):
         self.ring_levels = draw_ring_levels(self.field.encoder.num_levels)
         self._levels.copy_(torch.from_numpy(self.ring_levels))  # (stream-ordered behind the previous ring's steps)
 
-    def _shade(self, marched, tgt):
+    def _shade(self, marched, slot):
         r, enc = self.renderer, self.field.encoder
-        slot = tgt.storage_offset() // tgt.numel()  # (the targets are the rows of the static [RING, N, 3] buffer: row = ring slot)
         for p in self._other_params:
             p.grad = None
         self._centres_grad.zero_()
         with torch.autocast("cuda", dtype=self.amp_dtype):
-            image, depth, loss, scaled = r.shade_train(marched, self.bg_color, target=tgt, scale=None)
+            image, depth, loss, scaled = r.shade_train(marched, self.bg_color, target=self._targets[slot], scale=None)
         self.scaler.scale(scaled).backward()
         from gridencoder.grid_clustering import grid_cluster_step
 
@@ -562,17 +512,6 @@ class CurvedTrainer(AcceleratedTrainer):
         self.scaler.step(self.opt)
         self.scaler.update()
         self.loss.copy_(loss.detach().reshape(()) + self.reg_loss)
-
-    def step(self, rays_o, rays_d, target, next_rays=None, _eager=False):
-        if self.renderer.local_step % RING == 0:
-            self._draw_levels()
-        return super().step(rays_o, rays_d, target, next_rays=next_rays, _eager=_eager)
-
-    def step_group(self, rays_o, rays_d, target, next_rays=None):
-        eager = not self.use_graph or self._primed < RING or self._warm < max(2, self.group)  # (that path draws in `step`)
-        if not eager and self.renderer.local_step % RING == 0:
-            self._draw_levels()
-        return super().step_group(rays_o, rays_d, target, next_rays=next_rays)
 
 
 def accelerate(renderer, **kw):
