@@ -47,7 +47,7 @@ class AcceleratedTrainer:
                  fused_table_update=None, fused_composite_step=None, lr_scheduler=None, total_steps=None):
         from .model import NGPField
 
-        _refuse_unschedulable(lr_scheduler, pipeline_adam)
+        _refuse_options(lr_scheduler, pipeline_adam)
         field = renderer.field
         assert isinstance(field, NGPField), "accelerate() knows the ngp field (hash grid + two MLPs)"
         self._init_loop(renderer, field, rays_per_batch, dt_gamma, bg_color, perturb, max_steps, amp_dtype, graph, steps_per_call, march_across_ring_end)
@@ -75,35 +75,22 @@ class AcceleratedTrainer:
         else:
             self.opt = torch.optim.Adam(field.get_params(lr), betas=betas, eps=eps, fused=True, capturable=self.use_graph)
             self.amp, self.scaler = None, torch.amp.GradScaler("cuda", enabled=amp_dtype in (torch.float16, torch.bfloat16))  # (the table gradient is fp16 either way)
-        # pipeline_adam = k > 1 (fused path; round 5, an A/B -- OFF by default): the table gradient is summed in k level groups and the Adam update of
-        # group g runs on a second stream while group g + 1 is being summed (VALU-bound sums beside an HBM-bound update).  CAVEAT, the reason it is
-        # not the default: GradScaler skips the WHOLE step when any gradient element is non-finite; here group g's update has started before the
-        # groups behind it have been scanned.  Non-finite incoming gradients are caught before (the MLP backward's scan, which every overflow of
-        # dL/dfeatures passes through); what is not is a row of a LATER level group overflowing fp16 as a sum of finite contributions -- then the
-        # earlier groups are already updated and the step is skipped for the rest.
-        self.pipeline_adam = int(pipeline_adam) if (self.fused and int(pipeline_adam) > 1 and self.amp is not None and field.fused_field) else 0
-        if self.pipeline_adam:
-            from .dp import TableGradChunks
-
-            self._chunks = TableGradChunks(field.encoder, self.pipeline_adam)
-            self._chunks.with_amp = True
-            self._adam_stream = torch.cuda.Stream(device=self.dev)
         # skip_dead_samples (round 6; None = on wherever it exists -- the fused FFMLP field): the compositing backward flags the 32-sample steps that
         # carry a gradient and both MLP backward kernels and the hash-grid backward's record builder walk the flagged steps only.  In a trained scene
         # most samples sit behind the point where their ray's transmittance has underflowed and get EXACTLY zero gradients (raymarching.cu:843-870:
         # 42 % of the samples after 100 steps of the bench's scene, 99.6 % after 1000): the backward then costs what the live samples cost.  Exact: the
         # same parameters bit for bit (tests/test_gpu_round6.py); a young field, where every sample carries a gradient, pays one ballot per 64 steps.
-        can_skip = bool(self.fused and field.mlp == "ffmlp" and not self.pipeline_adam)
+        can_skip = bool(self.fused and field.mlp == "ffmlp")
         self.skip_dead_samples = can_skip if skip_dead_samples is None else bool(skip_dead_samples)
-        assert not self.skip_dead_samples or can_skip, "skip_dead_samples needs the fused FFMLP field (and no pipeline_adam)"
+        assert not self.skip_dead_samples or can_skip, "skip_dead_samples needs the fused FFMLP field"
         renderer.skip_dead_samples = self.skip_dead_samples
         # fused_table_update (round 6; None = on wherever it exists): the hash-grid backward's summing kernel applies Adam to the hashed levels' rows
         # from its LDS tiles -- the record walk of some workgroups beside the parameter stream of others -- instead of writing their gradient for
         # the optimizer launch to read back (optim.FusedAmp.fuse_table_update).  Same parameters bit for bit, skipped overflow steps included; the
         # optimizer state is double-buffered: the fp32 module parameters are current after `trainer.sync()` (state_dict() calls it).
-        can_fuse = bool(self.fused and self.amp is not None and hasattr(self.amp, "covered") and not self.pipeline_adam and field.mlp == "ffmlp")
+        can_fuse = bool(self.fused and self.amp is not None and hasattr(self.amp, "covered") and field.mlp == "ffmlp")
         self.fused_table_update = can_fuse if fused_table_update is None else bool(fused_table_update)
-        assert not self.fused_table_update or can_fuse, "fused_table_update needs the fused FFMLP field under FusedAmp (and no pipeline_adam)"
+        assert not self.fused_table_update or can_fuse, "fused_table_update needs the fused FFMLP field under FusedAmp"
         if self.fused_table_update:
             self.amp.fuse_table_update(field.encoder)
         # fused_composite_step (round 6; None = on under the fused AMP step): compositing forward, render tail and their backward -- three adjacent,
@@ -196,24 +183,7 @@ class AcceleratedTrainer:
             self.opt.zero_grad(set_to_none=True)
         with torch.autocast("cuda", dtype=self.amp_dtype):
             image, depth, loss, scaled = r.shade_train(marched, self.bg_color, target=tgt, scale=self.amp.scale if self.amp else None)
-        if self.amp and self.pipeline_adam:
-            scaled.backward(self._one)  # (the table gradient is only BINNED: TableGradChunks is attached)
-            chunks, main, side = self._chunks, torch.cuda.current_stream(), self._adam_stream
-            state = chunks.take()
-            if state[1] is None:  # a batch the phased backward does not take (small): the gradient is complete, one update
-                self.amp.step()
-            else:
-                for i in range(len(chunks)):
-                    chunks.sum_chunk(i, state)
-                    ev = torch.cuda.Event()
-                    ev.record(main)
-                    with torch.cuda.stream(side):
-                        side.wait_event(ev)
-                        a, b = chunks.rows[i]
-                        self.opt.launch_rows(0, a, b, 1.0, self.amp.scale, self.amp.found_inf)
-                main.wait_stream(side)
-                self.amp.step(exclude=(0,))  # the two MLP weight vectors + the scale / step-counter update
-        elif self.amp:
+        if self.amp:
             scaled.backward(self._one)
             self.amp.step()
         else:
@@ -417,13 +387,15 @@ def _host_lrs(opt):
     return [None if isinstance(g["lr"], torch.Tensor) else float(g["lr"]) for g in opt.param_groups]
 
 
-def _refuse_unschedulable(lr_scheduler, pipeline_adam):
-    """Paths that cannot read the rate from the device schedule are refused at construction, never run at a constant rate."""
+def _refuse_options(lr_scheduler, pipeline_adam):
+    """What neither trainer does is refused at construction, before the renderer is looked at: the removed pipeline_adam (the keyword stays so
+    that callers passing 0 keep working), and a learning-rate schedule where the rate cannot be read from the device schedule -- never run at
+    a constant rate instead."""
+    if pipeline_adam:
+        raise ValueError(f"pipeline_adam={pipeline_adam!r}: pipelined Adam was removed (built, bit-identical, measured slower, and GradScaler could no "
+                         "longer skip a whole step: DESIGN_HISTORY.md, VERDICT r4 item 2 row; profiles/r05_pipeline_adam.json); pass 0 or leave it out")
     if lr_scheduler is None:
         return
-    if int(pipeline_adam) > 1:
-        raise ValueError("lr_scheduler: pipeline_adam updates the table row range by row range (HalfLeafAdam.launch_rows), which cannot follow a "
-                         "learning-rate schedule; build the trainer without pipeline_adam")
     dist = torch.distributed
     if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
         raise ValueError("lr_scheduler: the device learning-rate schedule is single-process (world size 1)")
@@ -455,18 +427,17 @@ class CurvedTrainer(AcceleratedTrainer):
                  skip_dead_samples=None, fused_table_update=None, fused_composite_step=None, lr_scheduler=None, total_steps=None):
         from .curved import CurvedField
 
-        _refuse_unschedulable(lr_scheduler, pipeline_adam)
+        _refuse_options(lr_scheduler, pipeline_adam)
 
         field = renderer.field
         assert isinstance(field, CurvedField), "CurvedTrainer trains a curved.CurvedField"
         assert field.encoder_var is None, "accelerate(): prob_model=True (the log-variance table) is not on the graphed path (main.py:86 trains without it)"
         dist = torch.distributed
         assert not (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1), "accelerate() of the curved field: world size 1"
-        for name, v in (("pipeline_adam", pipeline_adam), ("skip_dead_samples", skip_dead_samples), ("fused_table_update", fused_table_update),
-                        ("fused_composite_step", fused_composite_step)):
+        for name, v in (("skip_dead_samples", skip_dead_samples), ("fused_table_update", fused_table_update), ("fused_composite_step", fused_composite_step)):
             assert not v, f"{name}: an option of the ngp field's fused AMP step; the curved field trains with torch's fused Adam + GradScaler"
         self._init_loop(renderer, field, rays_per_batch, dt_gamma, bg_color, perturb, max_steps, amp_dtype, graph, steps_per_call, march_across_ring_end)
-        self.fused, self.amp, self.pipeline_adam = False, None, 0
+        self.fused, self.amp = False, None
         self.skip_dead_samples = self.fused_table_update = self.fused_composite_step = False
         renderer.skip_dead_samples, renderer.root_one, renderer.defer_step_loss = False, None, False
         # (capturable either way: graph=False runs the very optimizer arithmetic the graphs replay)

@@ -5,6 +5,8 @@ density logit, the SH(4) direction encoding, its narrowing to fp16, the zero pad
 net's 32 inputs; `color_out(hc)` replaces the slice / sigmoid / cast to fp32 after the colour net.  Same arithmetic and
 roundings as the framework ops (tests/test_gpu_field_glue.py compares against them).
 """
+import ctypes
+
 import torch
 from torch.autograd import Function
 
@@ -61,12 +63,7 @@ sigma_geo_dir = _sigma_geo_dir.apply
 color_out = _color_out.apply
 
 
-import os
-
-# False (NERFTEX_FIELD_BACKWARD=split): the six launches (glue, MLP + reduce, glue, MLP + reduce) nerftex_field_backward's three replace --
-# same gradients, for A/B
 STEP_TRAILER = True  # the field backward's reduction launch rides on the hash-grid backward's fill launch (round 6; False: its own launch)
-FIELD_BACKWARD_FUSED = os.environ.get("NERFTEX_FIELD_BACKWARD", "fused") != "split"
 DEBUG_TAP = None  # debugging aid (tools/determinism_probe.py): a callable that is shown the field backward's intermediate gradients
 
 
@@ -128,7 +125,7 @@ class _ngp_field(Function):
             ctx.grad_chunker = getattr(enc, "grad_chunker", None)  # dp.TableGradChunks: the table gradient is finished level group by level group
             ctx.table_adam = getattr(enc, "table_adam", None)  # optim.FusedAmp.fuse_table_update: the summing kernel applies Adam to the tiles it owns
             ctx.live_holder = getattr(enc, "step_live_holder", None)  # Renderer.shade_train(skip_dead_samples): where composite_tail's backward leaves its step flags
-            if ctx.live_holder is not None and (FIELD_BACKWARD_FUSED or mlp_dtype == torch.bfloat16) and ws_h.dtype == wc_h.dtype == mlp_dtype:
+            if ctx.live_holder is not None:
                 ctx.live_holder["field_consumes"] = True  # this node's backward is nerftex_field_backward_live_consume: it also finishes the step's loss
         else:
             check(field_forward(ptr(feats), ptr(dirs), ptr(ws_h), ptr(wc_h), B, ptr(sigma), ptr(rgbs), None, None, None, None, stream()))
@@ -137,142 +134,141 @@ class _ngp_field(Function):
 
     @staticmethod
     def backward(ctx, grad_sigma, grad_rgbs):
-        from nerftex_hip import F16, LAYOUT_BLC, LAYOUT_GRAD_OVERWRITE
-
         x, table_h, offsets, ws_h, wc_h, x_rows, h, cin, rgbs = ctx.saved_tensors
         S, H, gridtype, align, affine, t_dtype, ws_dtype, wc_dtype = ctx.meta
         B, dev = x.shape[0], x.device
-        half = dict(dtype=torch.float16, device=dev)
         mlp_dtype = ctx.mlp_dtype
-        bf16 = mlp_dtype == torch.bfloat16
+        # ---- prepare: the gradient buffers, and what the step around this node has attached to it
+        # the one precondition of everything this backward shares with the step around it (the loss scaler's sink, the step flags, the loss it
+        # finishes): the table is an fp16 leaf and both weight leaves are in the networks' 16-bit type -- the gradients it writes are `.grad` as is
+        leaves_16bit = t_dtype == torch.float16 and ws_dtype == wc_dtype == mlp_dtype
         grad_sigma = torch.zeros(B, dtype=torch.float32, device=dev) if grad_sigma is None else grad_sigma.contiguous().float()
         grad_rgbs = torch.zeros(B, 3, dtype=torch.float32, device=dev) if grad_rgbs is None else grad_rgbs.contiguous().float()
         grad_cin, grad_wc = torch.empty(B, 32, dtype=mlp_dtype, device=dev), torch.empty_like(wc_h)
-        grad_x, grad_ws = torch.empty(B, 32, **half), torch.empty_like(ws_h)  # (grad_x feeds the hash-grid backward: the TABLE's type, fp16)
-        sink = ctx.amp_sink if ((FIELD_BACKWARD_FUSED or bf16) and t_dtype == torch.float16 and ws_dtype == wc_dtype == mlp_dtype) else None
+        grad_x, grad_ws = torch.empty(B, 32, dtype=torch.float16, device=dev), torch.empty_like(ws_h)  # (grad_x feeds the hash-grid backward: the TABLE's type, fp16)
+        grad_table = torch.empty_like(table_h)
+        sink = ctx.amp_sink if leaves_16bit else None
         found = ptr(sink.found_inf) if sink is not None else None
+        # (the chunked form hands autograd a gradient that is FINISHED LATER, in place: only valid when `.grad` becomes this very tensor --
+        # an fp16 leaf, so that `.to(t_dtype)` below is the identity, and no earlier `.grad` to accumulate into: TableGradChunks.begin checks --
+        # and when no loss scaler waits for its scan: data parallelism scans the SUMMED gradient)
+        chunker = ctx.grad_chunker if (sink is None and t_dtype == torch.float16) else None
+        fuse = ctx.table_adam.table_adam_for(table_h) if (ctx.table_adam is not None and ctx.table_adam is sink) else None
         # round 6, dead-sample skip: one word per 32 samples, 0 = the compositing backward gave all 32 exactly zero gradients (composite_tail's
         # backward, which has run just before this one, left them in the holder).  Both MLP backward kernels walk the live steps only: dead steps
         # issue no loads and no MFMAs; their rows of grad_x are written as zeros (what the plain kernels compute: the hash-grid backward drops them).
-        holder = ctx.live_holder
-        flags = holder.pop("flags", None) if holder is not None else None
+        holder = ctx.live_holder if ctx.live_holder is not None else {}  # (no holder: nothing was left, as from an empty one)
+        flags = holder.pop("flags", None)
         # consume (composite_tail's one-launch form set the flags in the FORWARD, in a buffer that lives across steps): this call leaves them zero again
-        consume = holder.pop("consume", False) if holder is not None else False
-        loss_job = holder.pop("loss_job", None) if holder is not None else None  # (composite_tail's one-launch form left the loss for this call to finish)
-        if flags is not None and not (flags.numel() * 32 >= B and (FIELD_BACKWARD_FUSED or bf16) and ws_dtype == wc_dtype == mlp_dtype):
+        consume = holder.pop("consume", False)
+        loss_job = holder.pop("loss_job", None)  # (composite_tail's one-launch form left the loss for this call to finish)
+        if flags is not None and not (flags.numel() * 32 >= B and leaves_16bit):
             if consume:
                 flags.zero_()
             flags = None
-        trailer = None
-        if consume or loss_job is not None:
-            assert (FIELD_BACKWARD_FUSED or bf16) and ws_dtype == wc_dtype == mlp_dtype, "announced in the forward (field_consumes)"
-            import ctypes
-
-            job = None
-            if loss_job is not None:
-                from nerftex_hip import StepLoss
-
-                err, n_rays, loss_mul, scale, losses = loss_job
-                job = ctypes.byref(StepLoss(ptr(err), n_rays, loss_mul, ptr(scale), ptr(losses), losses.data_ptr() + 4))
-            args = (ptr(grad_sigma), ptr(grad_rgbs), ptr(rgbs), ptr(h), ptr(cin), ptr(x_rows), ptr(ws_h), ptr(wc_h), B, ptr(grad_cin), ptr(grad_x), ptr(grad_ws),
-                    ptr(grad_wc), ptr(flags), job, found)
-            # the reduction launch of this call (weight gradients + found_inf, the flags' clearing, the loss) is small, latency-bound and feeds nothing before
-            # the optimizer: when the hash-grid backward below is the tile-owner form, its fill launch runs it on its first workgroups (STEP_TRAILER)
-            if STEP_TRAILER and B > 0 and ctx.table_adam is not None and ctx.table_adam is sink and ctx.grad_chunker is None and t_dtype == torch.float16:
-                from nerftex_hip import StepTrailer
-
-                trailer = StepTrailer()
-                check((lib.nerftex_field_backward_live_deferred_bf16 if bf16 else lib.nerftex_field_backward_live_deferred)(*args, ctypes.byref(trailer), stream()))
-            else:
-                check((lib.nerftex_field_backward_live_consume_bf16 if bf16 else lib.nerftex_field_backward_live_consume)(*args, stream()))
-        elif flags is not None:
-            field_backward = lib.nerftex_field_backward_live_bf16 if bf16 else lib.nerftex_field_backward_live
-            check(field_backward(ptr(grad_sigma), ptr(grad_rgbs), ptr(rgbs), ptr(h), ptr(cin), ptr(x_rows), ptr(ws_h), ptr(wc_h), B, ptr(grad_cin), ptr(grad_x),
-                                 ptr(grad_ws), ptr(grad_wc), ptr(flags), found, stream()))
-        elif bf16:  # one entry point, found_inf optional (no split / unfused form of the bf16 field backward exists)
-            check(lib.nerftex_field_backward_bf16(ptr(grad_sigma), ptr(grad_rgbs), ptr(rgbs), ptr(h), ptr(cin), ptr(x_rows), ptr(ws_h), ptr(wc_h), B,
-                                                  ptr(grad_cin), ptr(grad_x), ptr(grad_ws), ptr(grad_wc), found, stream()))
-        elif sink is not None:  # GradScaler's non-finite scan rides on the stores of the three gradients (no amp_check launch this step)
-            check(lib.nerftex_field_backward_amp(ptr(grad_sigma), ptr(grad_rgbs), ptr(rgbs), ptr(h), ptr(cin), ptr(x_rows), ptr(ws_h), ptr(wc_h), B,
-                                                 ptr(grad_cin), ptr(grad_x), ptr(grad_ws), ptr(grad_wc), found, stream()))
-        elif FIELD_BACKWARD_FUSED:  # the two glue kernels ride on the MLP backward kernels' load stage, one reduction for both networks
-            check(lib.nerftex_field_backward(ptr(grad_sigma), ptr(grad_rgbs), ptr(rgbs), ptr(h), ptr(cin), ptr(x_rows), ptr(ws_h), ptr(wc_h), B, ptr(grad_cin),
-                                             ptr(grad_x), ptr(grad_ws), ptr(grad_wc), stream()))
-        else:
-            grad_hc = torch.empty(B, 16, **half)
-            check(lib.nerftex_field_out_backward(ptr(grad_rgbs), ptr(rgbs), B, ptr(grad_hc), stream()))
-            check(lib.nerftex_ffmlp_backward(ptr(grad_hc), ptr(cin), ptr(wc_h), None, B, 32, 16, 64, 3, 0, 6, 1, None, ptr(grad_cin), ptr(grad_wc), stream()))
-            grad_h = torch.empty(B, 16, **half)
-            check(lib.nerftex_field_mid_backward(ptr(grad_sigma), ptr(grad_cin), ptr(h), B, ptr(grad_h), stream()))
-            check(lib.nerftex_ffmlp_backward(ptr(grad_h), ptr(x_rows), ptr(ws_h), None, B, 32, 16, 64, 2, 0, 6, 1, None, ptr(grad_x), ptr(grad_ws), stream()))
+        assert leaves_16bit or not (consume or loss_job is not None), "announced in the forward (field_consumes)"
+        # ---- the field backward: both MLPs and the glue between them (an attached chunker keeps the reduction a launch of this call, as it always has)
+        defer = STEP_TRAILER and B > 0 and fuse is not None and ctx.grad_chunker is None
+        trailer = _field_backward(mlp_dtype == torch.bfloat16,
+                                  (ptr(grad_sigma), ptr(grad_rgbs), ptr(rgbs), ptr(h), ptr(cin), ptr(x_rows), ptr(ws_h), ptr(wc_h), B, ptr(grad_cin), ptr(grad_x),
+                                   ptr(grad_ws), ptr(grad_wc)), found, flags, consume, loss_job, defer)
         if DEBUG_TAP is not None:
             DEBUG_TAP(grad_x=grad_x, x=x, grad_sigma=grad_sigma, grad_rgbs=grad_rgbs, grad_cin=grad_cin, meta=(S, H, gridtype, align, affine))
-        grad_table = torch.empty_like(table_h)
-        dummy = torch.empty(1, **half)
-        # (the chunked form hands autograd a gradient that is FINISHED LATER, in place: only valid when `.grad` becomes this very tensor --
-        # an fp16 leaf, so that `.to(t_dtype)` below is the identity, and no earlier `.grad` to accumulate into: TableGradChunks.begin checks)
-        chunker = ctx.grad_chunker if ((sink is None or getattr(ctx.grad_chunker, "with_amp", False)) and t_dtype == torch.float16) else None
-        if chunker is not None:
-            # only BIN the contributions here; the caller sums the level groups one by one (chunker.sum_chunk) -- data parallelism: each group's
-            # all-reduce starts while the next group is being summed; single GPU (round 5, with_amp): each group's Adam runs on a second stream
-            # while the next group is being summed (the non-finite scan rides on each group's stores).  grad_table is complete once every group
-            # has been summed.
-            L = offsets.shape[0] - 1
-            args = (ptr(grad_x), ptr(x), ptr(table_h), ptr(offsets), ptr(grad_table), B, 3, 2, L, S, H, gridtype, align, F16, LAYOUT_BLC | LAYOUT_GRAD_OVERWRITE,
-                    affine[0], affine[1])
-            if sink is not None:
-                phase = lambda ph, lo, hi: lib.nerftex_grid_encode_backward_phase_amp(*args, ph, lo, hi, found, stream())  # noqa: E731
-            else:
-                phase = lambda ph, lo, hi: lib.nerftex_grid_encode_backward_phase(*args, ph, lo, hi, stream())  # noqa: E731
-            if phase(1, 0, L) == 0:
-                chunker.begin(grad_table, lambda lo, hi: check(phase(2, lo, hi)), keep=(grad_x, x, table_h, offsets, dummy))
-                if sink is not None:
-                    sink.covered = (grad_table.data_ptr(), grad_ws.data_ptr(), grad_wc.data_ptr())
-                return None, None, grad_table.to(t_dtype), None, grad_ws.to(ws_dtype), grad_wc.to(wc_dtype), None, None, None, None
-            chunker.begin(grad_table, None, keep=None)  # (small batch / unknown table: the one-call backward below; the groups are complete already)
-        fuse = ctx.table_adam.table_adam_for(table_h) if (ctx.table_adam is not None and ctx.table_adam is sink and chunker is None) else None
-        if trailer is not None and fuse is not None:
-            import ctypes
-
-            first = ctypes.c_uint32(0)
-            rc = lib.nerftex_grid_encode_backward_adam_trailer(ptr(grad_x), ptr(x), ptr(offsets), ptr(grad_table), B, 3, 2, offsets.shape[0] - 1, S, H, gridtype, align,
-                                                               F16, LAYOUT_BLC | LAYOUT_GRAD_OVERWRITE, affine[0], affine[1], ctypes.byref(fuse), ctypes.byref(first),
-                                                               ctypes.byref(trailer), stream())
-            if rc != 0:  # (refused: nothing was launched -- the trailer as a launch of its own, then the error)
-                lib.nerftex_step_trailer_run(ctypes.byref(trailer), stream())
-            check(rc)
-            trailer = None
-            sink.opt.fused_table = (sink.table_index, int(first.value))
-            sink.covered = (grad_table.data_ptr(), grad_ws.data_ptr(), grad_wc.data_ptr())
-            return None, None, grad_table.to(t_dtype), None, grad_ws.to(ws_dtype), grad_wc.to(wc_dtype), None, None, None, None
-        if trailer is not None:  # (the hash-grid backward is not the tile-owner form after all)
-            import ctypes
-
-            check(lib.nerftex_step_trailer_run(ctypes.byref(trailer), stream()))
-            trailer = None
-        if fuse is not None:
-            # round 6: the hashed levels' tiles never leave LDS as a gradient -- their owners run Adam on the rows (double-buffered state, so that a
-            # step GradScaler skips leaves no trace); grad_table receives the coarse levels' rows [0, first) only, the rest stays uninitialised
-            import ctypes
-
-            first = ctypes.c_uint32(0)
-            check(lib.nerftex_grid_encode_backward_adam(ptr(grad_x), ptr(x), ptr(offsets), ptr(grad_table), B, 3, 2, offsets.shape[0] - 1, S, H, gridtype, align,
-                                                        F16, LAYOUT_BLC | LAYOUT_GRAD_OVERWRITE, affine[0], affine[1], ctypes.byref(fuse), ctypes.byref(first),
-                                                        stream()))
-            sink.opt.fused_table = (sink.table_index, int(first.value))
-            sink.covered = (grad_table.data_ptr(), grad_ws.data_ptr(), grad_wc.data_ptr())
-        elif sink is not None:
-            check(lib.nerftex_grid_encode_backward_amp(ptr(grad_x), ptr(x), ptr(table_h), ptr(offsets), ptr(grad_table), B, 3, 2, offsets.shape[0] - 1, S, H,
-                                                       0, ptr(dummy), ptr(dummy), gridtype, align, F16, LAYOUT_BLC | LAYOUT_GRAD_OVERWRITE, affine[0],
-                                                       affine[1], found, stream()))
+        # ---- the table backward
+        first = _table_backward(grad_x, x, table_h, offsets, grad_table, (S, H, gridtype, align, affine), chunker, fuse, trailer, found)
+        if sink is not None:
             # the buffers whose scan is done (addresses, not references: a second reference would make autograd copy the gradient instead
             # of handing the tensor itself to `.grad`); FusedAmp.step checks `.grad` off against them
             sink.covered = (grad_table.data_ptr(), grad_ws.data_ptr(), grad_wc.data_ptr())
-        else:
-            check(lib.nerftex_grid_encode_backward_affine(ptr(grad_x), ptr(x), ptr(table_h), ptr(offsets), ptr(grad_table), B, 3, 2, offsets.shape[0] - 1, S,
-                                                          H, 0, ptr(dummy), ptr(dummy), gridtype, align, F16, LAYOUT_BLC | LAYOUT_GRAD_OVERWRITE, affine[0],
-                                                          affine[1], stream()))
+            if first is not None:
+                sink.opt.fused_table = (sink.table_index, first)
         return None, None, grad_table.to(t_dtype), None, grad_ws.to(ws_dtype), grad_wc.to(wc_dtype), None, None, None, None
+
+
+# the field backward's entry points, form -> (fp16, bf16).  One call each: the glue rides on the MLP backward kernels' load stage, one reduction
+# serves both networks.  The bf16 field has no twin without found_inf: its "amp" form takes NULL.
+_BACKWARD_ENTRY = {
+    "plain": ("nerftex_field_backward", None),
+    "amp": ("nerftex_field_backward_amp", "nerftex_field_backward_bf16"),
+    "live": ("nerftex_field_backward_live", "nerftex_field_backward_live_bf16"),
+    "live_consume": ("nerftex_field_backward_live_consume", "nerftex_field_backward_live_consume_bf16"),
+    "live_deferred": ("nerftex_field_backward_live_deferred", "nerftex_field_backward_live_deferred_bf16"),
+}
+
+
+def _field_backward(bf16, core, found, flags, consume, loss_job, defer):
+    """Run the field backward that fits what the step has attached.  core: the thirteen arguments every form starts with; found: the loss
+    scaler's found_inf (GradScaler's non-finite scan rides on the stores of the three gradients) or None; flags: the live-step words or None;
+    consume / loss_job: composite_tail's one-launch form wants the flags cleared / the step's loss finished by this call's reduction launch.
+    defer: that reduction launch -- small, latency-bound, feeding nothing before the optimizer -- is left to the hash-grid backward's fill
+    launch (STEP_TRAILER).  -> the nerftex_step_trailer it then left for `_table_backward`, else None."""
+    def run(form, *more):
+        entry = _BACKWARD_ENTRY[form][bool(bf16)]
+        assert entry is not None, f"the bf16 field has no {form!r} backward"
+        check(getattr(lib, entry)(*core, *more, stream()))
+
+    if consume or loss_job is not None:
+        job = None
+        if loss_job is not None:
+            from nerftex_hip import StepLoss
+
+            err, n_rays, loss_mul, scale, losses = loss_job
+            job = ctypes.byref(StepLoss(ptr(err), n_rays, loss_mul, ptr(scale), ptr(losses), losses.data_ptr() + 4))
+        if not defer:
+            run("live_consume", ptr(flags), job, found)
+            return None
+        from nerftex_hip import StepTrailer
+
+        trailer = StepTrailer()
+        run("live_deferred", ptr(flags), job, found, ctypes.byref(trailer))
+        return trailer
+    if flags is not None:
+        run("live", ptr(flags), found)
+    elif found is not None or bf16:
+        run("amp", found)
+    else:
+        run("plain")
+    return None
+
+
+def _table_backward(grad_x, x, table_h, offsets, grad_table, meta, chunker, fuse, trailer, found):
+    """Run the hash-grid backward that fits: phased for a `chunker` (dp.TableGradChunks: only the binning runs here), the tile-owner Adam form for
+    `fuse` (a nerftex_table_adam) with or without the field backward's `trailer` on its fill launch, the form that raises `found` (found_inf),
+    or the plain one.  -> the first table row the launch has UPDATED instead of writing its gradient (the tile-owner forms), else None."""
+    from nerftex_hip import F16, LAYOUT_BLC, LAYOUT_GRAD_OVERWRITE
+
+    S, H, gridtype, align, affine = meta
+    B, L = x.shape[0], offsets.shape[0] - 1
+    shape, how = (B, 3, 2, L, S, H), (gridtype, align, F16, LAYOUT_BLC | LAYOUT_GRAD_OVERWRITE, affine[0], affine[1])
+    if chunker is not None:
+        # only BIN the contributions here; the caller sums the level groups one by one (chunker.sum_chunk) -- data parallelism: each group's
+        # all-reduce starts while the next group is being summed.  grad_table is complete once every group has been summed.
+        args = (ptr(grad_x), ptr(x), ptr(table_h), ptr(offsets), ptr(grad_table), *shape, *how)
+        if lib.nerftex_grid_encode_backward_phase(*args, 1, 0, L, stream()) == 0:
+            chunker.begin(grad_table, lambda lo, hi: check(lib.nerftex_grid_encode_backward_phase(*args, 2, lo, hi, stream())), keep=(grad_x, x, table_h, offsets))
+            return None
+        chunker.begin(grad_table, None, keep=None)  # (small batch / unknown table: the one-call backward below; the groups are complete already)
+    if fuse is not None:
+        # round 6: the hashed levels' tiles never leave LDS as a gradient -- their owners run Adam on the rows (double-buffered state, so that a
+        # step GradScaler skips leaves no trace); grad_table receives the coarse levels' rows [0, first) only, the rest stays uninitialised
+        first = ctypes.c_uint32(0)
+        args = (ptr(grad_x), ptr(x), ptr(offsets), ptr(grad_table), *shape, *how, ctypes.byref(fuse), ctypes.byref(first))
+        if trailer is None:
+            check(lib.nerftex_grid_encode_backward_adam(*args, stream()))
+        else:
+            rc = lib.nerftex_grid_encode_backward_adam_trailer(*args, ctypes.byref(trailer), stream())
+            if rc != 0:  # (refused: nothing was launched -- the trailer as a launch of its own, then the error)
+                lib.nerftex_step_trailer_run(ctypes.byref(trailer), stream())
+            check(rc)
+        return int(first.value)
+    assert trailer is None, "the field backward defers its reduction to the tile-owner form only"
+    dummy = torch.empty(1, dtype=torch.float16, device=x.device)
+    args = (ptr(grad_x), ptr(x), ptr(table_h), ptr(offsets), ptr(grad_table), *shape, 0, ptr(dummy), ptr(dummy), *how)
+    if found is not None:
+        check(lib.nerftex_grid_encode_backward_amp(*args, found, stream()))
+    else:
+        check(lib.nerftex_grid_encode_backward_affine(*args, stream()))
+    return None
 
 
 _INFER_CACHE = {}

@@ -239,6 +239,14 @@ class Renderer(nn.Module):
         self.iter_density = 0
         self.mean_count = 0
         self.local_step = 0
+        # per-step switches that whoever drives the step sets (accelerate(), bench.py, tools/): shade_train's skip_dead_samples / root_one /
+        # defer_step_loss / keep_step_live (explained there), render_infer's count_real_samples; last_step_live: the last step's holder, left for them
+        self.skip_dead_samples = False
+        self.root_one = None
+        self.defer_step_loss = False
+        self.keep_step_live = False
+        self.count_real_samples = False
+        self.last_step_live = None
 
     def set_occupancy(self, density_grid):
         """Install an analytic density grid (the synthetic scene) and pack it, as update_extra_state :648-654 would."""
@@ -416,7 +424,7 @@ class Renderer(nn.Module):
             counter = self.step_counter[self.local_step % 16]
             self.local_step += 1
         m = self.mean_count if mean_count is None else mean_count
-        if getattr(self, "fused_march", True) and not force_all_rays and m > 0:
+        if not force_all_rays and m > 0:
             # a fixed sample budget (the graph-replayed step): near / far, the counter reset and the buffers' zero fill ride on the march's two
             # launches (raymarching.march_rays_train_fresh: same bits as the sequence below, tests/test_gpu_round3.py)
             with torch.no_grad():
@@ -435,7 +443,7 @@ class Renderer(nn.Module):
         """Second half (:389-425): field evaluation, compositing, background.
 
         target [N,3] (with a scalar bg_color): the blend, the depth normalisation and the MSE against the target pixels run as one
-        kernel (ngp_harness/fused.py render_tail); returns (image, depth, loss * loss_mul, that times the loss scaler's `scale`)
+        kernel (ngp_harness/fused.py composite_tail); returns (image, depth, loss * loss_mul, that times the loss scaler's `scale`)
         instead of (image, depth); backward goes through the last one."""
         nears, fars, xyzs, dirs, deltas, rays = marched
         # skip_dead_samples (round 6; accelerate sets it): the compositing backward flags the 32-sample steps that carry a gradient -- in a trained
@@ -443,17 +451,16 @@ class Renderer(nn.Module):
         # and the fused field's backward (both MLPs, the hash-grid record builder) walks the flagged steps only.  The two autograd nodes share a dict.
         holder = None
         enc = getattr(self.field, "encoder", None)
-        if (target is not None and getattr(self, "skip_dead_samples", False) and getattr(self, "fused_composite_tail", True) and enc is not None
-                and torch.is_grad_enabled()):
+        if target is not None and self.skip_dead_samples and enc is not None and torch.is_grad_enabled():
             holder = {}
-            if getattr(self, "root_one", None) is not None:  # composite_tail's one-launch form sets the flags in a buffer that lives across steps
+            if self.root_one is not None:  # composite_tail's one-launch form sets the flags in a buffer that lives across steps
                 words = (xyzs.shape[0] + 31) // 32
                 buf = getattr(self, "_live_words", None)
                 if buf is None or buf.numel() < words or buf.device != xyzs.device:
                     buf = self._live_words = torch.zeros(words, dtype=torch.int32, device=xyzs.device)
                 holder["buffer"] = buf
-                holder["defer_loss"] = getattr(self, "defer_step_loss", False)  # (accelerate: the loss is read after the backward -- the field's backward finishes it)
-                holder["keep_last"] = getattr(self, "keep_step_live", False)  # (a copy of the flags for whoever counts them: bench.py's dead-step fraction)
+                holder["defer_loss"] = self.defer_step_loss  # (accelerate: the loss is read after the backward -- the field's backward finishes it)
+                holder["keep_last"] = self.keep_step_live  # (a copy of the flags for whoever counts them: bench.py's dead-step fraction)
             enc.step_live_holder = holder
             self.last_step_live = holder  # (after the backward: holder["last"] = the step's flags)
         try:
@@ -466,12 +473,9 @@ class Renderer(nn.Module):
         if target is not None:
             from . import fused
 
-            if getattr(self, "fused_composite_tail", True):  # compositing + blend + depth + MSE: one launch per direction
-                # root_one (accelerate, fused AMP step): the tensor `scaled.backward(one)` will be called with -- forward + backward in one launch
-                return fused.composite_tail(sigmas, rgbs, deltas, rays, nears, fars, target, float(bg_color), loss_mul, scale, holder,
-                                            getattr(self, "root_one", None))
-            weights_sum, depth, image = raymarching.composite_rays_train(sigmas, rgbs, deltas, rays)
-            return fused.render_tail(weights_sum, depth, image, nears, fars, target, float(bg_color), loss_mul, scale)
+            # compositing + blend + depth + MSE: one launch per direction; root_one (accelerate, fused AMP step): the tensor
+            # `scaled.backward(one)` will be called with -- forward + backward in one launch
+            return fused.composite_tail(sigmas, rgbs, deltas, rays, nears, fars, target, float(bg_color), loss_mul, scale, holder, self.root_one)
         weights_sum, depth, image = raymarching.composite_rays_train(sigmas, rgbs, deltas, rays)
         image = image + (1 - weights_sum).unsqueeze(-1) * bg_color
         depth = torch.clamp(depth - nears, min=0) / (fars - nears)
@@ -513,7 +517,7 @@ class Renderer(nn.Module):
             if self.density_scale != 1:
                 sigmas = self.density_scale * sigmas
             raymarching.composite_rays(n_alive, n_step, rays_alive[i % 2], rays_t[i % 2], sigmas, rgbs, deltas, weights_sum, depth, image)
-            if getattr(self, "count_real_samples", False):  # (bench.py: how many of the slots an iteration shades hold a sample -- delta > 0 -- at all)
+            if self.count_real_samples:  # (bench.py: how many of the slots an iteration shades hold a sample -- delta > 0 -- at all)
                 self.real_samples = getattr(self, "real_samples", 0) + (deltas[:n_alive * n_step, 0] > 0).sum()
             n_samples += xyzs.shape[0]
             step += n_step

@@ -166,27 +166,12 @@ class HalfLeafAdam(torch.optim.Optimizer):
                 self.param_groups[0][k] = v
         self.resync()
 
-    def launch_rows(self, i, a, b, step_offset, grad_scale, found_inf):
-        """Adam over rows [a, b) of leaf i alone (current stream): the table updated level group by level group, each group as soon as its rows
-        of the gradient are final (accelerate(pipeline_adam=True)).  The step number is *step_count + step_offset; step_count is not advanced."""
-        assert self.lr_schedule is None, "launch_rows cannot follow a learning-rate schedule"
-        g = self.leaves[i].grad
-        assert g is not None and g.dtype == self.leaves[i].dtype and g.is_contiguous()
-        if b <= a:
-            return
-        parts = [t[a:b] for t in (self.masters[i].data, self.exp_avg[i], self.exp_avg_sq[i], g, self.leaves[i].data)]
-        grp = self.param_groups[0]
-        n = (ctypes.c_uint64 * 1)(parts[0].numel())
-        check(lib.nerftex_adam_mixed_step(1, *[_ptr_array([t]) for t in parts], n, (self.bf16_mask >> i) & 1, ptr(self.step_count), float(step_offset),
-                                          float(grp["lr"]), grp["betas"][0], grp["betas"][1], grp["eps"], ptr(grad_scale), ptr(found_inf), stream()))
-
-    def _launch(self, step_offset, grad_scale, found_inf, amp=None, exclude=()):
-        """One launch over every leaf that has a gradient (but `exclude`: leaves already updated by launch_rows).  amp = (scale, growth_tracker,
-        found_inf, ticket, growth, backoff, interval): the loss scaler's update rides along (step number *step_count + 1; the launch advances
-        step_count itself)."""
-        idx = [i for i, leaf in enumerate(self.leaves) if leaf.grad is not None and i not in exclude]
+    def _launch(self, step_offset, grad_scale, found_inf, amp=None):
+        """One launch over every leaf that has a gradient.  amp = (scale, growth_tracker, found_inf, ticket, growth, backoff, interval): the loss
+        scaler's update rides along (step number *step_count + 1; the launch advances step_count itself)."""
+        idx = [i for i, leaf in enumerate(self.leaves) if leaf.grad is not None]
         if self.live is not None:
-            return self._launch_double_buffered(idx, amp, exclude)
+            return self._launch_double_buffered(idx, amp)
         if not idx and amp is None:
             return
         grads = [self.leaves[i].grad for i in idx]
@@ -211,14 +196,14 @@ class HalfLeafAdam(torch.optim.Optimizer):
             scale, tracker, found, ticket, growth, backoff, interval = amp
             check(lib.nerftex_adam_mixed_step_amp(len(idx), *arrays, mask, ptr(self.step_count), *hyper, ptr(scale), ptr(tracker), ptr(found), ptr(ticket),
                                                   growth, backoff, interval, stream()))
-        for i in list(idx) + list(exclude):
+        for i in idx:
             torch.autograd.graph.increment_version(self.masters[i])
 
-    def _launch_double_buffered(self, idx, amp, exclude):
+    def _launch_double_buffered(self, idx, amp):
         """The step's last launch over double-buffered state (nerftex_adam_mixed_step_amp_db): reads the live set, writes the other one, flips
         `live` iff the step is applied.  A table whose hashed rows the backward has updated already (`fused_table`) is passed from row 0 to the
         first updated row only; the rows behind are the launch's REPAIR range (their fp16 copy is re-derived from the live set on a skipped step)."""
-        assert amp is not None and not exclude, "the double-buffered optimizer runs under FusedAmp, every leaf in one launch"
+        assert amp is not None, "the double-buffered optimizer runs under FusedAmp"
         assert idx == list(range(len(self.leaves))), "double-buffered state: every parameter must be written every step (a leaf without a gradient would go stale when the sets flip)"
         fused, self.fused_table = self.fused_table, None
         cut = {}
@@ -340,11 +325,9 @@ class FusedAmp:
         check(lib.nerftex_amp_check_mixed(len(grads), _ptr_array(grads), n, mask, ptr(self.found_inf), stream()))
 
     @torch.no_grad()
-    def step(self, exclude=()):
-        """exclude: indices of leaves whose Adam update has been launched already (HalfLeafAdam.launch_rows, reading this object's scale and
-        found_inf): they are neither scanned nor updated here; the scale / step-counter update still is."""
+    def step(self):
         _poll_deferred_error()
-        grads = [leaf.grad for i, leaf in enumerate(self.opt.leaves) if leaf.grad is not None and i not in exclude]
+        grads = [leaf.grad for leaf in self.opt.leaves if leaf.grad is not None]
         covered = getattr(self, "covered", None)
         if covered:  # gradients whose producing kernels already raised found_inf (attach): the very tensors, untouched since
             grads = [g for g in grads if g.data_ptr() not in covered]
@@ -355,4 +338,4 @@ class FusedAmp:
         if grads:
             self._check(grads)
         # Adam (skipped on overflow) and the scale / step-counter update in one launch
-        self.opt._launch(1.0, self.scale, self.found_inf, (self.scale, self.growth_tracker, self.found_inf, self.ticket, *self.consts), exclude=exclude)
+        self.opt._launch(1.0, self.scale, self.found_inf, (self.scale, self.growth_tracker, self.found_inf, self.ticket, *self.consts))

@@ -11,10 +11,10 @@ from ngp_harness.optim import FusedAmp, HalfLeafAdam
 class CpuHalfLeafAdam(HalfLeafAdam):
     _needs_device = False
 
-    def _launch(self, step_offset, grad_scale, found_inf, amp=None, exclude=()):
-        idx = [i for i, leaf in enumerate(self.leaves) if leaf.grad is not None and i not in exclude]
+    def _launch(self, step_offset, grad_scale, found_inf, amp=None):
+        idx = [i for i, leaf in enumerate(self.leaves) if leaf.grad is not None]
         if self.live is not None:
-            return self._launch_double_buffered(idx, amp, exclude)
+            return self._launch_double_buffered(idx, amp)
         grp = self.param_groups[0]
         lr, (b1, b2), eps = float(grp["lr"]), grp["betas"], grp["eps"]
         if amp is not None:
@@ -53,8 +53,8 @@ class CpuHalfLeafAdam(HalfLeafAdam):
     # ---- double-buffered form (round 6): the stand-in of nerftex_adam_mixed_step_amp_db -- reads the live set, writes the other one, flips `live` iff the
     # step is applied; a table whose rows from `first_row` on an earlier kernel of the step has updated already is passed up to that row only, and on a
     # skipped step the 16-bit copy of the rows behind it is re-derived from the live set (the repair)
-    def _launch_double_buffered(self, idx, amp, exclude):
-        assert amp is not None and not exclude and idx == list(range(len(self.leaves)))
+    def _launch_double_buffered(self, idx, amp):
+        assert amp is not None and idx == list(range(len(self.leaves)))
         fused, self.fused_table = self.fused_table, None
         grp = self.param_groups[0]
         lr, (b1, b2), eps = float(grp["lr"]), grp["betas"], grp["eps"]
