@@ -785,6 +785,50 @@ int nerftex_composite_step(const float* sigmas, const float* rgbs, const float* 
                            float* weights_sum, float* depth, float* image, float* image_out, float* depth_out, float* err, float* loss,
                            float* scaled_loss, float* grad_sigmas, float* grad_rgbs, uint32_t* step_live, void* stream);
 
+/* The criterion of a training step, its per-ray loss and the error map (nerf/utils.py:617-632, --error_map): the three train-step ends above
+ * trained one objective, the mean squared error.  The reference's NeRF-Texture trainer uses torch.nn.L1Loss (main.py:187), its ngp trainer
+ * MSELoss with a Huber loss beside it (main_nerf.py:104-106).  With a nerftex_step_loss_desc the same launches form
+ *   element e(d), d = image_out - target:  MSE d^2;  L1 |d|;  HUBER 0.5 d^2 where |d| <= delta, else delta (|d| - 0.5 delta)   (torch's)
+ *   *loss = sum(e) / 3N * loss_mul;   grad_image = (de/dd) * g / 3N  (L1: sign(d), 0 at d == 0;  HUBER: d where |d| <= delta, else delta sign(d))
+ *   ray_loss[n] = (sum over the ray's three channels of e) / 3: the reference's criterion(pred, gt).mean(-1), before loss_mul and scale;
+ *   error_map[i] = keep * error_map[i] + take * ray_loss[n] for i = error_inds[n] when 0 <= i < error_cells; any other index -- negative
+ *   ones included -- touches nothing.  A plain read-modify-write by the thread that holds the ray's error, no extra launch: the indices of one
+ *   call are distinct (torch.multinomial without replacement); with duplicates ONE of the candidates lands, as with torch's scatter_.  The map
+ *   is written by the forward, whether or not a loss scaler later skips the step (the reference writes it before backward() too).
+ * An unknown kind, a Huber delta that is not finite and > 0, or a map without indices (or indices without a map): NERFTEX_ERR_INVALID,
+ * nothing is launched.  desc NULL: the call is the entry it extends.                                                                     */
+#define NERFTEX_LOSS_MSE 0
+#define NERFTEX_LOSS_L1 1
+#define NERFTEX_LOSS_HUBER 2
+typedef struct nerftex_step_loss_desc {
+    uint32_t kind;             /* NERFTEX_LOSS_MSE / _L1 / _HUBER */
+    float param;               /* Huber delta (> 0); ignored otherwise */
+    float* ray_loss;           /* [N] or NULL */
+    float* error_map;          /* [error_cells] or NULL */
+    const int64_t* error_inds; /* [N]; required iff error_map */
+    uint64_t error_cells;
+    float keep, take;          /* the reference's 0.1f, 0.9f */
+} nerftex_step_loss_desc;
+/* nerftex_render_tail_forward_live / nerftex_render_tail_backward / nerftex_composite_tail_backward_live / nerftex_composite_step with a
+ * descriptor: the criterion's loss instead of the squared error, everything else as documented there (err [N] of nerftex_composite_step_ex: the
+ * rays' summed elements -- nerftex_step_loss finishes the loss of any criterion).  The two backward entries read kind and param only.       */
+int nerftex_render_tail_forward_ex(const float* weights_sum, const float* depth, const float* image, const float* nears, const float* fars,
+                                   const float* target, float bg, float loss_mul, uint32_t N, float* image_out, float* depth_out, float* partial,
+                                   uint32_t* ticket, float* loss, const float* scale, float* scaled_loss, uint32_t* step_live, uint32_t n_steps,
+                                   const nerftex_step_loss_desc* desc, void* stream);
+int nerftex_render_tail_backward_ex(const float* grad_loss, const float* scale, float loss_mul, const float* image_out, const float* target,
+                                    float bg, uint32_t N, float* grad_image, float* grad_weights_sum, const nerftex_step_loss_desc* desc,
+                                    void* stream);
+int nerftex_composite_tail_backward_ex(const float* grad_loss, const float* scale, float loss_mul, const float* image_out, const float* target,
+                                       float bg, const float* sigmas, const float* rgbs, const float* deltas, const int32_t* rays,
+                                       const float* weights_sum, const float* image, uint32_t M, uint32_t N, float* grad_sigmas, float* grad_rgbs,
+                                       uint32_t* step_live, const nerftex_step_loss_desc* desc, void* stream);
+int nerftex_composite_step_ex(const float* sigmas, const float* rgbs, const float* deltas, const int32_t* rays, uint32_t M, uint32_t N,
+                              const float* nears, const float* fars, const float* target, float bg, float loss_mul, const float* scale,
+                              float* weights_sum, float* depth, float* image, float* image_out, float* depth_out, float* err, float* loss,
+                              float* scaled_loss, float* grad_sigmas, float* grad_rgbs, uint32_t* step_live, const nerftex_step_loss_desc* desc,
+                              void* stream);
+
 /* One Adam step (main_nerf.py:128: betas (0.9, 0.99), eps 1e-15, no weight decay) of an fp32 master table from the
  * fp16 gradient the encoder backward produced, writing the fp16 copy the next forward reads: param, exp_avg,
  * exp_avg_sq [n] fp32 in place, grad_half [n] fp16 in, param_half [n] fp16 out.  step: device float, already

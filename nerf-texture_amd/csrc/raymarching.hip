@@ -20,6 +20,7 @@
 #include "workspace.hpp"
 
 #include <cstdlib>
+#include <type_traits>
 
 #pragma clang fp contract(off)
 
@@ -922,6 +923,11 @@ struct TailBackward {
     // (raymarching.cu:843-870 computes the same zeros): the MLP backward and the hash-grid backward skip the steps whose word stays 0.
     uint32_t* step_live;
 };
+// ... of the one general instantiation (nerftex_composite_tail_backward_ex): the criterion as wave-uniform fields
+struct TailBackwardEx : TailBackward {
+    uint32_t kind;
+    float param;
+};
 
 __global__ __launch_bounds__(kCompBlock) void composite_train_fwd_kernel(const float* __restrict__ sigmas, const float* __restrict__ rgbs,
                                                                         const float* __restrict__ deltas, const int* __restrict__ rays,
@@ -979,6 +985,21 @@ __device__ __forceinline__ RayGrad ray_loss_gradient(float norm, float gl, float
     return q;
 }
 
+// ... of the criterion `kind` (step_loss.hpp): the MSE by the expressions above, L1 / Huber as grad_image = (de/dd) * gl / 3N
+__device__ __forceinline__ RayGrad ray_criterion_gradient(uint32_t kind, float delta, float norm, float count, float gl, float bg, const float* out,
+                                                          const float* tgt) {
+#pragma clang fp contract(off)
+    if (kind == NERFTEX_LOSS_MSE) return ray_loss_gradient(norm, gl, bg, out, tgt);
+    RayGrad q;
+    q.gi0 = criterion_grad(kind, delta, out[0] - tgt[0], gl, count);
+    q.gi1 = criterion_grad(kind, delta, out[1] - tgt[1], gl, count);
+    q.gi2 = criterion_grad(kind, delta, out[2] - tgt[2], gl, count);
+    float sum = 0.0f;
+    sum += q.gi0; sum += q.gi1; sum += q.gi2;
+    q.gws = -(sum * bg);
+    return q;
+}
+
 // one sample's gradients (raymarching.cu:855-870) + its step flag: the first live lane of a 32-sample step (the lanes of one step are consecutive
 // inside the 64-sample window that starts at row `window0`) sets the step's word
 __device__ __forceinline__ void sample_backward(bool on, size_t i, uint32_t window0, uint32_t lane, float d0, const ChunkOut& o, float c0r, float c1g, float c2b,
@@ -1008,14 +1029,16 @@ __device__ __forceinline__ void sample_backward(bool on, size_t i, uint32_t wind
     }
 }
 
-template <bool TAIL>
+template <bool TAIL, bool EX = false>
 __global__ __launch_bounds__(kCompBlock) void composite_train_bwd_kernel(const float* __restrict__ grad_weights_sum,
                                                                         const float* __restrict__ grad_image,
                                                                         const float* __restrict__ sigmas, const float* __restrict__ rgbs,
                                                                         const float* __restrict__ deltas, const int* __restrict__ rays,
                                                                         const float* __restrict__ weights_sum, const float* __restrict__ image,
                                                                         uint32_t M, uint32_t N, float* __restrict__ grad_sigmas,
-                                                                        float* __restrict__ grad_rgbs, const TailBackward tail) {
+                                                                        float* __restrict__ grad_rgbs,
+                                                                        const std::conditional_t<EX, TailBackwardEx, TailBackward> tail) {
+    static_assert(TAIL || !EX, "the criterion belongs to the tail");
     const uint32_t n = blockIdx.x * (kCompBlock / kWave) + threadIdx.x / kWave;
     const uint32_t lane = threadIdx.x & (kWave - 1);
     if (n >= N) return;
@@ -1030,7 +1053,8 @@ __global__ __launch_bounds__(kCompBlock) void composite_train_bwd_kernel(const f
         const float norm = (float)(2.0 / (double)((size_t)N * 3));
         const float out[3] = {tail.image_out[(size_t)index * 3], tail.image_out[(size_t)index * 3 + 1], tail.image_out[(size_t)index * 3 + 2]};
         const float tgt[3] = {tail.target[(size_t)index * 3], tail.target[(size_t)index * 3 + 1], tail.target[(size_t)index * 3 + 2]};
-        q = ray_loss_gradient(norm, gl, tail.bg, out, tgt);
+        if constexpr (EX) q = ray_criterion_gradient(tail.kind, tail.param, norm, (float)((size_t)N * 3), gl, tail.bg, out, tgt);
+        else q = ray_loss_gradient(norm, gl, tail.bg, out, tgt);
     } else {
         q.gws = grad_weights_sum[index];
         q.gi0 = grad_image[3 * (size_t)index]; q.gi1 = grad_image[3 * (size_t)index + 1]; q.gi2 = grad_image[3 * (size_t)index + 2];
@@ -1070,8 +1094,18 @@ struct StepTail {
     uint32_t* step_live;  // optional; ZERO on entry (nerftex_field_backward_live_consume leaves it so); set as TailBackward::step_live is
 };
 
+// ... of the one general instantiation (nerftex_composite_step_ex): criterion, per-ray loss and error map, and the kept chunks as a RUNTIME
+// count (the composite_keep knob), all wave-uniform
+struct StepTailEx : StepTail {
+    StepCriterion crit;
+    float count;    // (float)(3N)
+    uint32_t keep;  // 1 .. the instantiation's KEEP
+};
+
 struct RayTail { float out[3], depth_out, err; };
-__device__ __forceinline__ RayTail ray_tail_forward(float ws, float d, float i0, float i1, float i2, float near, float far, const float* tgt, float bg) {
+template <bool EX = false>
+__device__ __forceinline__ RayTail ray_tail_forward(float ws, float d, float i0, float i1, float i2, float near, float far, const float* tgt, float bg,
+                                                    uint32_t kind = NERFTEX_LOSS_MSE, float delta = 0.0f) {
 #pragma clang fp contract(off)  // (render_tail_forward_kernel: the framework's blend is a multiply, then an add)
     RayTail t;
     const float back = (1.0f - ws) * bg;
@@ -1082,19 +1116,23 @@ __device__ __forceinline__ RayTail ray_tail_forward(float ws, float d, float i0,
         const float v = img[c] + back;
         t.out[c] = v;
         const float e = v - tgt[c];
-        err += e * e;
+        if constexpr (EX) err += criterion_element(kind, delta, e);
+        else err += e * e;
     }
     t.err = err;
     t.depth_out = fmaxf(d - near, 0.0f) / (far - near);
     return t;
 }
 
-template <int KEEP>
+template <int KEEP, bool EX = false>
 __global__ __launch_bounds__(kCompBlock) void composite_step_kernel(const float* __restrict__ sigmas, const float* __restrict__ rgbs,
                                                                     const float* __restrict__ deltas, const int* __restrict__ rays, uint32_t M,
                                                                     uint32_t N, float* __restrict__ weights_sum, float* __restrict__ depth,
                                                                     float* __restrict__ image, float* __restrict__ grad_sigmas,
-                                                                    float* __restrict__ grad_rgbs, const StepTail tail) {
+                                                                    float* __restrict__ grad_rgbs,
+                                                                    const std::conditional_t<EX, StepTailEx, StepTail> tail) {
+    uint32_t keep = (uint32_t)KEEP;  // chunks kept in registers: the instantiation's, or fewer at the general one's word
+    if constexpr (EX) keep = tail.keep;
     const uint32_t n = blockIdx.x * (kCompBlock / kWave) + threadIdx.x / kWave;
     const uint32_t lane = threadIdx.x & (kWave - 1);
     if (n >= N) return;
@@ -1111,7 +1149,7 @@ __global__ __launch_bounds__(kCompBlock) void composite_step_kernel(const float*
 #pragma unroll
     for (int c = 0; c < KEEP; c++) {
         const uint32_t k = (uint32_t)c * kWave + lane;
-        in[c] = load_chunk(sigmas, rgbs, deltas, (size_t)offset + k, k < steps);
+        in[c] = load_chunk(sigmas, rgbs, deltas, (size_t)offset + k, k < steps && (uint32_t)c < keep);
     }
     asm volatile("" ::"v"(scale_now), "v"(near), "v"(far), "v"(tgt[0]), "v"(tgt[1]), "v"(tgt[2]));  // (issued here, not where they are used)
     zero_uncovered_rows(rays, n, lane, offset, num_steps, M, N, grad_sigmas, grad_rgbs);
@@ -1120,14 +1158,16 @@ __global__ __launch_bounds__(kCompBlock) void composite_step_kernel(const float*
     ChunkOut kept[KEEP];
 #pragma unroll
     for (int j = 0; j < KEEP; j++)
-        if ((uint32_t)j * kWave < steps) kept[j] = chunk_walk<true>(in[j], c);  // (wave-uniform)
+        if ((uint32_t)j < keep && (uint32_t)j * kWave < steps) kept[j] = chunk_walk<true>(in[j], c);  // (wave-uniform)
     const RayCarry at_keep = c;
-    for (uint32_t c0 = (uint32_t)KEEP * kWave; c0 < steps; c0 += kWave) {  // chunks past the kept ones: the totals now, their gradients by a second walk below
+    for (uint32_t c0 = keep * kWave; c0 < steps; c0 += kWave) {  // chunks past the kept ones: the totals now, their gradients by a second walk below
         const uint32_t k = c0 + lane;
         chunk_walk<true>(load_chunk(sigmas, rgbs, deltas, (size_t)offset + k, k < steps), c);
     }
     const RayCarry fin = c;
-    const RayTail rt = ray_tail_forward(fin.ws, fin.d, fin.r, fin.g, fin.b, near, far, tgt, tail.bg);
+    RayTail rt;
+    if constexpr (EX) rt = ray_tail_forward<true>(fin.ws, fin.d, fin.r, fin.g, fin.b, near, far, tgt, tail.bg, tail.crit.kind, tail.crit.param);
+    else rt = ray_tail_forward(fin.ws, fin.d, fin.r, fin.g, fin.b, near, far, tgt, tail.bg);
     if (lane == 0) {
         weights_sum[index] = fin.ws;
         depth[index] = fin.d;
@@ -1135,18 +1175,21 @@ __global__ __launch_bounds__(kCompBlock) void composite_step_kernel(const float*
         tail.image_out[3 * (size_t)index] = rt.out[0]; tail.image_out[3 * (size_t)index + 1] = rt.out[1]; tail.image_out[3 * (size_t)index + 2] = rt.out[2];
         tail.depth_out[index] = rt.depth_out;
         tail.err[index] = rt.err;
+        if constexpr (EX) record_ray_loss(tail.crit, index, rt.err);  // (the lane that holds the ray's error: no launch, no atomics)
     }
     if (dead) return;
-    const RayGrad q = ray_loss_gradient(tail.norm, scale_now * tail.loss_mul, tail.bg, rt.out, tgt);  // (TailBackward with grad_loss = 1: 1.0f * scale is scale)
+    RayGrad q;  // (TailBackward with grad_loss = 1: 1.0f * scale is scale)
+    if constexpr (EX) q = ray_criterion_gradient(tail.crit.kind, tail.crit.param, tail.norm, tail.count, scale_now * tail.loss_mul, tail.bg, rt.out, tgt);
+    else q = ray_loss_gradient(tail.norm, scale_now * tail.loss_mul, tail.bg, rt.out, tgt);
 #pragma unroll
     for (int j = 0; j < KEEP; j++)
-        if ((uint32_t)j * kWave < steps) {
+        if ((uint32_t)j < keep && (uint32_t)j * kWave < steps) {
             const uint32_t k = (uint32_t)j * kWave + lane;
             sample_backward(k < steps, (size_t)offset + k, offset + (uint32_t)j * kWave, lane, in[j].d0, kept[j], in[j].c0, in[j].c1, in[j].c2, q, fin, grad_sigmas,
                             grad_rgbs, tail.step_live);
         }
     c = at_keep;
-    for (uint32_t c0 = (uint32_t)KEEP * kWave; c0 < steps; c0 += kWave) {
+    for (uint32_t c0 = keep * kWave; c0 < steps; c0 += kWave) {
         const uint32_t k = c0 + lane;
         const bool on = k < steps;
         const size_t i = (size_t)offset + k;
@@ -1550,13 +1593,29 @@ extern "C" int nerftex_composite_tail_backward_live(const float* grad_loss, cons
                                                     float bg, const float* sigmas, const float* rgbs, const float* deltas, const int32_t* rays,
                                                     const float* weights_sum, const float* image, uint32_t M, uint32_t N, float* grad_sigmas,
                                                     float* grad_rgbs, uint32_t* step_live, void* stream) {
+    return nerftex_composite_tail_backward_ex(grad_loss, scale, loss_mul, image_out, target, bg, sigmas, rgbs, deltas, rays, weights_sum, image, M, N, grad_sigmas,
+                                              grad_rgbs, step_live, nullptr, stream);
+}
+
+// ... for the criterion of the step's nerftex_step_loss_desc (only kind and param are read; NULL: the MSE launch, as it always was)
+extern "C" int nerftex_composite_tail_backward_ex(const float* grad_loss, const float* scale, float loss_mul, const float* image_out, const float* target,
+                                                  float bg, const float* sigmas, const float* rgbs, const float* deltas, const int32_t* rays,
+                                                  const float* weights_sum, const float* image, uint32_t M, uint32_t N, float* grad_sigmas,
+                                                  float* grad_rgbs, uint32_t* step_live, const nerftex_step_loss_desc* desc, void* stream) {
     clear_error();
+    StepCriterion crit;
+    if (!take_step_loss_kind(desc, crit, "composite_tail_backward_ex")) return NERFTEX_ERR_INVALID;
     if (N == 0) return NERFTEX_OK;
     const TailBackward tail{grad_loss, scale, image_out, target, bg, loss_mul, step_live};
     {
         KernelTimer kt("composite_tail_bwd_kernel", as_stream(stream));
-        hipLaunchKernelGGL(composite_train_bwd_kernel<true>, dim3(div_up(N, kCompBlock / (uint32_t)kWave)), dim3(kCompBlock), 0, as_stream(stream), nullptr, nullptr,
-                           sigmas, rgbs, deltas, rays, weights_sum, image, M, N, grad_sigmas, grad_rgbs, tail);
+        const dim3 grid(div_up(N, kCompBlock / (uint32_t)kWave)), block(kCompBlock);
+        if (desc == nullptr)
+            hipLaunchKernelGGL(composite_train_bwd_kernel<true>, grid, block, 0, as_stream(stream), nullptr, nullptr, sigmas, rgbs, deltas, rays, weights_sum, image, M,
+                               N, grad_sigmas, grad_rgbs, tail);
+        else
+            hipLaunchKernelGGL((composite_train_bwd_kernel<true, true>), grid, block, 0, as_stream(stream), nullptr, nullptr, sigmas, rgbs, deltas, rays, weights_sum,
+                               image, M, N, grad_sigmas, grad_rgbs, TailBackwardEx{tail, crit.kind, crit.param});
     }
     return check_launch("composite_tail_backward");
 }
@@ -1568,7 +1627,20 @@ extern "C" int nerftex_composite_step(const float* sigmas, const float* rgbs, co
                                       const float* nears, const float* fars, const float* target, float bg, float loss_mul, const float* scale,
                                       float* weights_sum, float* depth, float* image, float* image_out, float* depth_out, float* err, float* loss,
                                       float* scaled_loss, float* grad_sigmas, float* grad_rgbs, uint32_t* step_live, void* stream) {
+    return nerftex_composite_step_ex(sigmas, rgbs, deltas, rays, M, N, nears, fars, target, bg, loss_mul, scale, weights_sum, depth, image, image_out, depth_out, err,
+                                     loss, scaled_loss, grad_sigmas, grad_rgbs, step_live, nullptr, stream);
+}
+
+// ... with the step's criterion, per-ray loss and error map (nerftex_step_loss_desc; NULL: the MSE launches, as they always were).  err[] is then
+// the criterion summed over each ray's channels: the loss launch -- or nerftex_field_backward_live_consume's nerftex_step_loss -- is the same.
+extern "C" int nerftex_composite_step_ex(const float* sigmas, const float* rgbs, const float* deltas, const int32_t* rays, uint32_t M, uint32_t N,
+                                         const float* nears, const float* fars, const float* target, float bg, float loss_mul, const float* scale,
+                                         float* weights_sum, float* depth, float* image, float* image_out, float* depth_out, float* err, float* loss,
+                                         float* scaled_loss, float* grad_sigmas, float* grad_rgbs, uint32_t* step_live, const nerftex_step_loss_desc* desc,
+                                         void* stream) {
     clear_error();
+    StepCriterion crit;
+    if (!take_step_loss_desc(desc, crit, "composite_step_ex")) return NERFTEX_ERR_INVALID;
     if (N == 0 || M == 0) {
         set_error("composite_step: no rays / no samples (use the three entries it replaces)");
         return NERFTEX_ERR_INVALID;
@@ -1582,6 +1654,11 @@ extern "C" int nerftex_composite_step(const float* sigmas, const float* rgbs, co
         KernelTimer kt("composite_step_kernel", as_stream(stream));
         const int keep = knob(kKnobCompositeKeep);
         const dim3 grid(div_up(N, kCompBlock / (uint32_t)kWave)), block(kCompBlock);
+        if (desc != nullptr) {  // the general instantiation: compiled for four kept chunks, keeps as many as the knob says
+            const StepTailEx ex{tail, crit, (float)((size_t)N * 3), (keep == 1 || keep == 3 || keep == 4) ? (uint32_t)keep : 2u};
+            hipLaunchKernelGGL((composite_step_kernel<4, true>), grid, block, 0, as_stream(stream), sigmas, rgbs, deltas, rays, M, N, weights_sum, depth, image,
+                               grad_sigmas, grad_rgbs, ex);
+        } else {
 #define NERFTEX_STEP(K) \
     hipLaunchKernelGGL(composite_step_kernel<K>, grid, block, 0, as_stream(stream), sigmas, rgbs, deltas, rays, M, N, weights_sum, depth, image, grad_sigmas, \
                        grad_rgbs, tail)
@@ -1590,6 +1667,7 @@ extern "C" int nerftex_composite_step(const float* sigmas, const float* rgbs, co
         else if (keep == 4) NERFTEX_STEP(4);
         else NERFTEX_STEP(2);
 #undef NERFTEX_STEP
+        }
     }
     int rc = check_launch("composite_step");
     if (rc != NERFTEX_OK || loss == nullptr) return rc;  // (loss NULL: the caller hands err[] to nerftex_field_backward_live_consume's nerftex_step_loss)

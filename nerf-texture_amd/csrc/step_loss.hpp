@@ -1,4 +1,4 @@
-// The loss of a training step from the rays' squared errors -- err[N] -> loss, scaled loss -- in render_tail_forward_kernel's summation order
+// The loss of a training step from the rays' errors (squared, or the step's criterion summed over the channels) -- err[N] -> loss, scaled loss -- in render_tail_forward_kernel's summation order
 // (trainstep.hip): 64 consecutive rays by a shuffle tree, four such sums one after the other (its 256-ray workgroup), the workgroups' sums strided
 // over 256 accumulators, those by the same tree.  ONE workgroup does it: nerftex_composite_step's second launch, or -- when the step's field
 // backward follows (nerftex_field_backward_live_consume) -- an extra workgroup of its weight-gradient reduction launch, where it costs nothing.
@@ -20,6 +20,90 @@ struct StepLossLds {
     float part[kStepLossMaxRays / 256];
     float last[4];
 };
+
+// The criterion of a step that is not the plain MSE one (nerftex_step_loss_desc): what the general instantiations of the tail kernels carry as
+// wave-uniform fields.  err[n] is, for every kind, the sum over the ray's three channels of the elementwise criterion -- step_loss_sum below is
+// the same sum for all of them.  torch's semantics: mse_loss, l1_loss (abs backward: sign, 0 at 0), huber_loss (quadratic where |d| <= delta).
+struct StepCriterion {
+    uint32_t kind = NERFTEX_LOSS_MSE;
+    float param = 0.0f;                   // Huber's delta
+    float* ray_loss = nullptr;            // optional [N]: err / 3, the reference's criterion(pred, gt).mean(-1)
+    float* error_map = nullptr;           // optional [error_cells]
+    const int64_t* error_inds = nullptr;  // [N] flat cell per ray; outside [0, error_cells): the ray updates nothing
+    uint64_t error_cells = 0;
+    float keep = 0.1f, take = 0.9f;
+};
+struct NoCriterion {};  // what the MSE instantiations take in its place
+
+__device__ __forceinline__ float criterion_element(uint32_t kind, float delta, float d) {
+#pragma clang fp contract(off)
+    if (kind == NERFTEX_LOSS_L1) return fabsf(d);
+    if (kind == NERFTEX_LOSS_HUBER) {
+        const float a = fabsf(d);
+        return a <= delta ? 0.5f * a * a : delta * (a - 0.5f * delta);
+    }
+    return d * d;
+}
+// de/dd of the L1 and Huber elements (the MSE gradient keeps its own expression: ray_loss_gradient / render_tail_backward_kernel)
+__device__ __forceinline__ float criterion_slope(uint32_t kind, float delta, float d) {
+#pragma clang fp contract(off)
+    const float sign = d > 0.0f ? 1.0f : (d < 0.0f ? -1.0f : 0.0f);
+    if (kind == NERFTEX_LOSS_HUBER) return fabsf(d) <= delta ? d : delta * sign;
+    return sign;
+}
+// one channel of grad_image for L1 / Huber: (de/dd) * g / (3N)
+__device__ __forceinline__ float criterion_grad(uint32_t kind, float delta, float d, float g, float count) {
+#pragma clang fp contract(off)
+    return criterion_slope(kind, delta, d) * g / count;
+}
+// ONE thread per ray calls this with the ray's err: the per-ray loss and the error map's moving average (nerf/utils.py:617-632:
+// 0.1 * old + 0.9 * error).  A plain read-modify-write: the rays' cells are distinct (multinomial without replacement); with duplicates one
+// of the candidates lands, as in torch's scatter_.
+__device__ __forceinline__ void record_ray_loss(const StepCriterion& k, uint32_t index, float err) {
+#pragma clang fp contract(off)
+    const float mean = err / 3.0f;
+    if (k.ray_loss != nullptr) k.ray_loss[index] = mean;
+    if (k.error_map != nullptr) {
+        const int64_t cell = k.error_inds[index];
+        if (cell >= 0 && (uint64_t)cell < k.error_cells) {
+            const float old = k.error_map[cell];
+            k.error_map[cell] = k.keep * old + k.take * mean;
+        }
+    }
+}
+
+// the criterion of a nerftex_step_loss_desc (all a backward reads); false (error set): unusable.  NULL: the MSE.
+inline bool take_step_loss_kind(const nerftex_step_loss_desc* d, StepCriterion& out, const char* who) {
+    out = StepCriterion{};
+    if (d == nullptr) return true;
+    if (d->kind != NERFTEX_LOSS_MSE && d->kind != NERFTEX_LOSS_L1 && d->kind != NERFTEX_LOSS_HUBER) {
+        set_error("%s: unknown criterion kind %u (NERFTEX_LOSS_MSE, _L1 or _HUBER)", who, d->kind);
+        return false;
+    }
+    if (d->kind == NERFTEX_LOSS_HUBER && !(d->param > 0.0f && d->param <= 3.4028234e38f)) {
+        set_error("%s: the Huber criterion needs a finite delta > 0, got %g", who, (double)d->param);
+        return false;
+    }
+    out.kind = d->kind;
+    out.param = d->param;
+    return true;
+}
+// ... with its outputs: the per-ray loss and the error map
+inline bool take_step_loss_desc(const nerftex_step_loss_desc* d, StepCriterion& out, const char* who) {
+    if (!take_step_loss_kind(d, out, who)) return false;
+    if (d == nullptr) return true;
+    if ((d->error_map != nullptr) != (d->error_inds != nullptr)) {
+        set_error("%s: error_map and error_inds go together (a map needs the rays' cells, the cells need a map)", who);
+        return false;
+    }
+    out.ray_loss = d->ray_loss;
+    out.error_map = d->error_map;
+    out.error_inds = d->error_inds;
+    out.error_cells = d->error_cells;
+    out.keep = d->keep;
+    out.take = d->take;
+    return true;
+}
 
 template <uint32_t THREADS>
 __device__ __forceinline__ void step_loss_sum(const StepLossJob& job, StepLossLds& lds) {

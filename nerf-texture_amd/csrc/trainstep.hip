@@ -1,9 +1,10 @@
 // The two ends of a training step that the framework otherwise runs as ~25 small launches and three passes over the
 // hash table (harness level, like fieldglue.hip: not reference entry points, the reference leaves this to torch).
 //
-//  render tail   nerf/renderer.py:417-425 + the MSE of nerf/utils.py:602-640: background blend of the composited image, depth
+//  render tail   nerf/renderer.py:417-425 + the criterion of nerf/utils.py:602-640: background blend of the composited image, depth
 //                normalisation, squared error against the target pixels and its mean -- one kernel; its backward (gradient of
-//                the mean squared error with respect to the raw image and the opacity sum) -- one kernel.
+//                the mean squared error with respect to the raw image and the opacity sum) -- one kernel.  The _ex entries: the same
+//                with torch's L1 or Huber loss in the squared error's place, the rays' losses and the error map (step_loss.hpp).
 //  table Adam    main_nerf.py:128 trains the hash table with Adam under a GradScaler.  The framework path per step: widen the
 //                fp16 gradient to fp32 (75 MB), non-finite check (100 MB), fused Adam (400 MB), narrow the fp32 table to fp16 for
 //                the next forward (75 MB).  Here one streaming kernel reads the fp16 gradient as produced by the encoder
@@ -16,6 +17,7 @@
 
 #include "adam_math.hpp"  // AdamConsts, AdamStep, adam_one: shared with the hash-grid backward that applies the update from its tiles
 #include "common.hpp"
+#include "step_loss.hpp"  // StepCriterion: the criterion, the per-ray loss and the error map of the _ex entries
 
 namespace nerftex {
 namespace {
@@ -36,6 +38,9 @@ __device__ __forceinline__ float block_sum(float v, float* lds) {
 
 // one thread per ray.  partial[block] = sum of squared errors of the block's rays; the last block to finish (ticket counter)
 // adds the partials in index order: the loss does not depend on the order the blocks ran in.
+// EX (nerftex_render_tail_forward_ex): the one general instantiation -- the element is the criterion's, and the ray's thread leaves the per-ray
+// loss and the error map's moving average (record_ray_loss)
+template <bool EX>
 __global__ __launch_bounds__(kTailThreads) void render_tail_forward_kernel(const float* __restrict__ weights_sum, const float* __restrict__ depth,
                                                                            const float* __restrict__ image, const float* __restrict__ nears,
                                                                            const float* __restrict__ fars, const float* __restrict__ target,
@@ -44,7 +49,8 @@ __global__ __launch_bounds__(kTailThreads) void render_tail_forward_kernel(const
                                                                            float* __restrict__ partial, uint32_t* __restrict__ ticket,
                                                                            float* __restrict__ loss, const float* __restrict__ scale,
                                                                            float* __restrict__ scaled_loss, uint32_t* __restrict__ step_live,
-                                                                           const uint32_t n_steps) {
+                                                                           const uint32_t n_steps,
+                                                                           const std::conditional_t<EX, StepCriterion, NoCriterion> crit) {
 #pragma clang fp contract(off)  // the framework's blend is a multiply, then an add
     __shared__ float lds[kTailThreads / 64];
     __shared__ bool last;
@@ -60,9 +66,11 @@ __global__ __launch_bounds__(kTailThreads) void render_tail_forward_kernel(const
             const float v = image[(size_t)n * 3 + c] + back;
             image_out[(size_t)n * 3 + c] = v;
             const float d = v - target[(size_t)n * 3 + c];
-            err += d * d;
+            if constexpr (EX) err += criterion_element(crit.kind, crit.param, d);
+            else err += d * d;
         }
         depth_out[n] = fmaxf(depth[n] - nears[n], 0.0f) / (fars[n] - nears[n]);
+        if constexpr (EX) record_ray_loss(crit, n, err);
     }
     const float s = block_sum(err, lds);
     if (threadIdx.x == 0) {
@@ -86,10 +94,13 @@ __global__ __launch_bounds__(kTailThreads) void render_tail_forward_kernel(const
 }
 
 // grad_image = (2 / 3N) * (image_out - target) * grad_loss   (mse_loss backward: norm * (a - b) * g),  grad_ws = -(sum_c grad_image) * bg
+// EX, L1 / Huber: grad_image = (de/dd) * g / 3N
+template <bool EX>
 __global__ __launch_bounds__(kTailThreads) void render_tail_backward_kernel(const float* __restrict__ grad_loss, const float* __restrict__ scale, const float loss_mul,
                                                                             const float* __restrict__ image_out, const float* __restrict__ target,
                                                                             const float bg, const uint32_t N, float* __restrict__ grad_image,
-                                                                            float* __restrict__ grad_ws) {
+                                                                            float* __restrict__ grad_ws,
+                                                                            const std::conditional_t<EX, StepCriterion, NoCriterion> crit) {
 #pragma clang fp contract(off)
     const uint32_t n = blockIdx.x * kTailThreads + threadIdx.x;
     if (n >= N) return;
@@ -98,7 +109,10 @@ __global__ __launch_bounds__(kTailThreads) void render_tail_backward_kernel(cons
     float sum = 0.0f;
 #pragma unroll
     for (int c = 0; c < 3; c++) {
-        const float gi = norm * (image_out[(size_t)n * 3 + c] - target[(size_t)n * 3 + c]) * g;
+        const float d = image_out[(size_t)n * 3 + c] - target[(size_t)n * 3 + c];
+        float gi = norm * d * g;
+        if constexpr (EX)
+            if (crit.kind != NERFTEX_LOSS_MSE) gi = criterion_grad(crit.kind, crit.param, d, g, (float)((size_t)N * 3));
         grad_image[(size_t)n * 3 + c] = gi;
         sum += gi;
     }
@@ -379,29 +393,57 @@ extern "C" int nerftex_render_tail_forward_live(const float* weights_sum, const 
                                                 const float* fars, const float* target, float bg, float loss_mul, uint32_t N, float* image_out,
                                                 float* depth_out, float* partial, uint32_t* ticket, float* loss, const float* scale,
                                                 float* scaled_loss, uint32_t* step_live, uint32_t n_steps, void* stream) {
+    return nerftex_render_tail_forward_ex(weights_sum, depth, image, nears, fars, target, bg, loss_mul, N, image_out, depth_out, partial, ticket, loss, scale,
+                                          scaled_loss, step_live, n_steps, nullptr, stream);
+}
+
+// ... with the step's criterion, per-ray loss and error map (nerftex_step_loss_desc; NULL: the MSE launch above, as it always was)
+extern "C" int nerftex_render_tail_forward_ex(const float* weights_sum, const float* depth, const float* image, const float* nears,
+                                              const float* fars, const float* target, float bg, float loss_mul, uint32_t N, float* image_out,
+                                              float* depth_out, float* partial, uint32_t* ticket, float* loss, const float* scale,
+                                              float* scaled_loss, uint32_t* step_live, uint32_t n_steps, const nerftex_step_loss_desc* desc,
+                                              void* stream) {
     clear_error();
     if (N == 0) {
         set_error("render_tail: empty batch");
         return NERFTEX_ERR_INVALID;
     }
+    StepCriterion crit;
+    if (!take_step_loss_desc(desc, crit, "render_tail_forward_ex")) return NERFTEX_ERR_INVALID;
     hipStream_t st = as_stream(stream);
     {
         KernelTimer kt("render_tail_forward_kernel", st);
-        hipLaunchKernelGGL(render_tail_forward_kernel, dim3(div_up(N, kTailThreads)), dim3(kTailThreads), 0, st, weights_sum, depth, image, nears,
-                           fars, target, bg, loss_mul, N, image_out, depth_out, partial, ticket, loss, scale, scaled_loss, step_live, n_steps);
+        if (desc == nullptr)
+            hipLaunchKernelGGL(render_tail_forward_kernel<false>, dim3(div_up(N, kTailThreads)), dim3(kTailThreads), 0, st, weights_sum, depth, image, nears,
+                               fars, target, bg, loss_mul, N, image_out, depth_out, partial, ticket, loss, scale, scaled_loss, step_live, n_steps, NoCriterion{});
+        else
+            hipLaunchKernelGGL(render_tail_forward_kernel<true>, dim3(div_up(N, kTailThreads)), dim3(kTailThreads), 0, st, weights_sum, depth, image, nears,
+                               fars, target, bg, loss_mul, N, image_out, depth_out, partial, ticket, loss, scale, scaled_loss, step_live, n_steps, crit);
     }
     return check_launch("render_tail_forward");
 }
 
 extern "C" int nerftex_render_tail_backward(const float* grad_loss, const float* scale, float loss_mul, const float* image_out, const float* target, float bg,
                                             uint32_t N, float* grad_image, float* grad_weights_sum, void* stream) {
+    return nerftex_render_tail_backward_ex(grad_loss, scale, loss_mul, image_out, target, bg, N, grad_image, grad_weights_sum, nullptr, stream);
+}
+
+// ... for the criterion of the forward's descriptor (only kind and param are read)
+extern "C" int nerftex_render_tail_backward_ex(const float* grad_loss, const float* scale, float loss_mul, const float* image_out, const float* target, float bg,
+                                               uint32_t N, float* grad_image, float* grad_weights_sum, const nerftex_step_loss_desc* desc, void* stream) {
     clear_error();
+    StepCriterion crit;
+    if (!take_step_loss_kind(desc, crit, "render_tail_backward_ex")) return NERFTEX_ERR_INVALID;
     if (N == 0) return NERFTEX_OK;
     hipStream_t st = as_stream(stream);
     {
         KernelTimer kt("render_tail_backward_kernel", st);
-        hipLaunchKernelGGL(render_tail_backward_kernel, dim3(div_up(N, kTailThreads)), dim3(kTailThreads), 0, st, grad_loss, scale, loss_mul, image_out,
-                           target, bg, N, grad_image, grad_weights_sum);
+        if (desc == nullptr)
+            hipLaunchKernelGGL(render_tail_backward_kernel<false>, dim3(div_up(N, kTailThreads)), dim3(kTailThreads), 0, st, grad_loss, scale, loss_mul, image_out,
+                               target, bg, N, grad_image, grad_weights_sum, NoCriterion{});
+        else
+            hipLaunchKernelGGL(render_tail_backward_kernel<true>, dim3(div_up(N, kTailThreads)), dim3(kTailThreads), 0, st, grad_loss, scale, loss_mul, image_out,
+                               target, bg, N, grad_image, grad_weights_sum, crit);
     }
     return check_launch("render_tail_backward");
 }

@@ -15,6 +15,7 @@ from ._build import CSRC, LIB_PATH, PKG_ROOT  # noqa: F401
 F32, F16 = 0, 1
 LAYOUT_LBC, LAYOUT_BLC = 0, 1
 LAYOUT_GRAD_OVERWRITE = 0x100  # backward: grad_embeddings is uninitialised and gets overwritten
+LOSS_MSE, LOSS_L1, LOSS_HUBER = 0, 1, 2  # nerftex_step_loss_desc.kind
 
 
 def rows_auto(n_rays, slots_per_ray):
@@ -76,6 +77,11 @@ _SIGNATURES = {
     "nerftex_composite_step": [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "nerftex_render_tail_forward_live": [_vp, _vp, _vp, _vp, _vp, _vp, _f32, _f32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp],
     "nerftex_composite_tail_backward_live": [_vp, _vp, _f32, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp],
+    "nerftex_render_tail_forward_ex": [_vp, _vp, _vp, _vp, _vp, _vp, _f32, _f32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp],
+    "nerftex_render_tail_backward_ex": [_vp, _vp, _f32, _vp, _vp, _f32, _u32, _vp, _vp, _vp, _vp],
+    "nerftex_composite_tail_backward_ex": [_vp, _vp, _f32, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp],
+    "nerftex_composite_step_ex": [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                  _vp],
     "nerftex_grid_encode_backward_adam": [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _f32, _u32, _u32, _i, _i, _i, _f32, _f32, _vp, _vp, _vp],
     "nerftex_field_forward_bf16": [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "nerftex_field_density_bf16": [_vp, _vp, _u32, _vp, _vp],
@@ -161,6 +167,12 @@ class GridClusterDesc(C.Structure):
 class StepLoss(C.Structure):
     """nerftex_step_loss of include/nerftex_hip.h, field for field."""
     _fields_ = [("err", _vp), ("n_rays", _u32), ("loss_mul", _f32), ("scale", _vp), ("loss", _vp), ("scaled_loss", _vp)]
+
+
+class StepLossDesc(C.Structure):
+    """nerftex_step_loss_desc of include/nerftex_hip.h, field for field: the criterion of a step, its per-ray loss and the error map."""
+    _fields_ = [("kind", _u32), ("param", _f32), ("ray_loss", _vp), ("error_map", _vp), ("error_inds", _vp), ("error_cells", _u64), ("keep", _f32),
+                ("take", _f32)]
 
 
 EXPORTS = ["nerftex_last_error", "nerftex_version", "nerftex_tune_get", "nerftex_workspace_slots_touched"] + list(_SIGNATURES)

@@ -44,10 +44,11 @@ RING = 16
 class AcceleratedTrainer:
     def __init__(self, renderer, rays_per_batch=None, lr=1e-2, betas=(0.9, 0.99), eps=1e-15, dt_gamma=1 / 128, bg_color=1, perturb=True, max_steps=1024,
                  amp_dtype=torch.float16, graph=True, steps_per_call=1, march_across_ring_end=False, pipeline_adam=0, skip_dead_samples=None,
-                 fused_table_update=None, fused_composite_step=None, lr_scheduler=None, total_steps=None):
+                 fused_table_update=None, fused_composite_step=None, lr_scheduler=None, total_steps=None, criterion=None, error_map=None):
         from .model import NGPField
 
         _refuse_options(lr_scheduler, pipeline_adam)
+        self._init_criterion(criterion, error_map)
         field = renderer.field
         assert isinstance(field, NGPField), "accelerate() knows the ngp field (hash grid + two MLPs)"
         self._init_loop(renderer, field, rays_per_batch, dt_gamma, bg_color, perturb, max_steps, amp_dtype, graph, steps_per_call, march_across_ring_end)
@@ -102,6 +103,18 @@ class AcceleratedTrainer:
         renderer.root_one = self._one if self.fused_composite_step else None
         renderer.defer_step_loss = bool(self.fused_composite_step)  # (`_shade` reads the loss after the backward: the field's backward may finish it)
         self._attach_schedule(lr_scheduler, total_steps)
+
+    def _init_criterion(self, criterion, error_map):
+        """criterion / error_map of accelerate(): refused here, before the renderer is looked at, when they are not what the kernels do.  With
+        neither, the step makes the very calls it always made (the MSE entries); with either, `trainer.ray_loss` is the last step's [N] per-ray
+        loss, criterion(pred, gt).mean(-1), and `step(..., error_inds=)` updates the map in place (fused.step_loss_desc)."""
+        self._loss_outputs = criterion is not None or error_map is not None
+        self.criterion = parse_criterion("mse" if criterion is None else criterion)
+        if error_map is not None and not (isinstance(error_map, torch.Tensor) and error_map.dtype == torch.float32 and error_map.is_contiguous()):
+            raise ValueError("error_map: a contiguous float32 device tensor (any shape; it is updated in place at flat cell indices)")
+        self.error_map = error_map
+        self.ray_loss = None
+        self._ray_loss, self._error_inds = None, None  # static per-ring-slot buffers, beside the targets
 
     def _init_loop(self, renderer, field, rays_per_batch, dt_gamma, bg_color, perturb, max_steps, amp_dtype, graph, steps_per_call, march_across_ring_end):
         """What the step loop keeps, whatever the field and its optimizer (both constructors start here)."""
@@ -182,7 +195,7 @@ class AcceleratedTrainer:
         else:
             self.opt.zero_grad(set_to_none=True)
         with torch.autocast("cuda", dtype=self.amp_dtype):
-            image, depth, loss, scaled = r.shade_train(marched, self.bg_color, target=tgt, scale=self.amp.scale if self.amp else None)
+            image, depth, loss, scaled = r.shade_train(marched, self.bg_color, target=tgt, scale=self.amp.scale if self.amp else None, **self._loss_args(slot))
         if self.amp:
             scaled.backward(self._one)
             self.amp.step()
@@ -193,6 +206,13 @@ class AcceleratedTrainer:
             self.scaler.step(self.opt)
             self.scaler.update()
         self.loss.copy_(loss.detach().reshape(()))
+
+    def _loss_args(self, slot):
+        """shade_train's criterion / per-ray loss / error map arguments of a step at ring slot `slot`: none unless accelerate() was given any."""
+        if not self._loss_outputs:
+            return {}
+        return dict(criterion=self.criterion, ray_loss=self._ray_loss[slot], error_map=self.error_map,
+                    error_inds=None if self.error_map is None else self._error_inds[slot])
 
     def _capture(self):
         """Record the graphs: a march graph per ring slot into `_graphs`, a shade graph (shade + backward + optimizer of its `group` steps) per
@@ -237,6 +257,12 @@ class AcceleratedTrainer:
             self._ray_d = torch.empty(RING, n_rays, 3, dtype=torch.float32, device=self.dev)
             self._rays = [(self._ray_o[g], self._ray_d[g]) for g in range(RING)]
             self._targets = torch.empty(RING, n_rays, 3, dtype=torch.float32, device=self.dev)
+            if self._loss_outputs:
+                self._ray_loss = torch.zeros(RING, n_rays, dtype=torch.float32, device=self.dev)
+                self.ray_loss = self._ray_loss[0]
+            if self.error_map is not None:
+                assert self.error_map.device == self.dev, "error_map lives on the field's device"
+                self._error_inds = torch.full((RING, n_rays), -1, dtype=torch.int64, device=self.dev)
         assert n_rays == self.n_rays, "a captured step has a fixed batch size"
 
     def _ring_end(self, ready):
@@ -253,27 +279,32 @@ class AcceleratedTrainer:
             r.update_mean_count()
         self._resize()
 
-    def step_group(self, rays_o, rays_d, target, next_rays=None):
+    def step_group(self, rays_o, rays_d, target, next_rays=None, error_inds=None):
         """steps_per_call = k consecutive training steps in one call: rays_o / rays_d / target [k, N, 3] -- batch i is step i's (FRESH rays every
         call: they are copied into the graphs' static buffers).  next_rays = (rays_o, rays_d) [k, N, 3] of the NEXT call: their k marches start
         now, on the second stream, beside this group's kernels; the next call must pass those very tensors.  Same arithmetic as k calls of
         `step`: the same kernels in the same order on the same data (tests/test_gpu_round4.py::test_step_group_trains_like_single_steps).
+        error_inds [k, N] int64 (accelerate(error_map=)): each ray's flat cell of the map; omitted, no cell is updated.
         Returns the last step's loss (device scalar)."""
         assert self.group > 1 and rays_o.dim() == 3 and rays_o.shape[0] == self.group, "step_group: [steps_per_call, N, 3] rays (steps_per_call > 1)"
-        return self._steps(rays_o, rays_d, target, next_rays)
+        return self._steps(rays_o, rays_d, target, next_rays, error_inds)
 
-    def step(self, rays_o, rays_d, target, next_rays=None):
+    def step(self, rays_o, rays_d, target, next_rays=None, error_inds=None):
         """One training step on a batch of rays [N,3], [N,3] and their target colours [N,3] (device tensors; N fixed after the first call).
         next_rays = (rays_o, rays_d) of the batch the NEXT call will pass: its march starts now, beside this step (module docstring).
+        error_inds [N] int64 (accelerate(error_map=)): each ray's flat cell of the map; omitted, no cell is updated.
         Returns the loss as a device scalar that the NEXT call overwrites.  It is `step_group` with one batch."""
         # views, for contiguous rays: the hand-over of `next_rays` is recognised by the address of these tensors (a reshape of a non-contiguous
         # tensor would be a fresh copy with a fresh address every call)
-        return self._steps(rays_o.reshape(1, -1, 3), rays_d.reshape(1, -1, 3), target.reshape(1, -1, 3), next_rays)
+        return self._steps(rays_o.reshape(1, -1, 3), rays_d.reshape(1, -1, 3), target.reshape(1, -1, 3), next_rays,
+                           None if error_inds is None else error_inds.reshape(1, -1))
 
-    def _steps(self, rays_o, rays_d, target, next_rays):
+    def _steps(self, rays_o, rays_d, target, next_rays, error_inds=None):
         """The k steps of one call, on ring slots g0 .. g0 + k: `step_group`, and `step` as its k = 1.  rays_o / rays_d / target: [k, N, 3]."""
         r, k = self.renderer, rays_o.shape[0]
         assert rays_o.is_contiguous() and rays_d.is_contiguous(), "rays_o / rays_d must be contiguous tensors (next_rays are recognised by their address)"
+        if error_inds is not None and self.error_map is None:
+            raise ValueError("error_inds without a map: pass accelerate(..., error_map=) the tensor they index")
         self._ensure_buffers(rays_o.shape[1])
         if self._lr_sched is not None:
             self._lr_sched.check(k)
@@ -283,7 +314,7 @@ class AcceleratedTrainer:
             # the ring slot is a multiple of `group` when the graphs start
             assert self._ahead is None
             for i in range(k):
-                self._eager_step(rays_o[i], rays_d[i], target[i])
+                self._eager_step(rays_o[i], rays_d[i], target[i], None if error_inds is None else error_inds[i])
             return self.loss
         g0 = r.local_step
         assert k == self.group, "this trainer was built with steps_per_call > 1: call step_group"
@@ -304,12 +335,15 @@ class AcceleratedTrainer:
             for g in range(g0, g0 + k):
                 self._graphs[g][0].replay()
         self._targets[g0:g0 + k].copy_(target, non_blocking=True)
+        self._set_error_inds(g0, k, error_inds)
         ready = None
         if next_rays is not None:
             ready = torch.cuda.Event()
             ready.record(main)  # everything enqueued so far (the production of the next rays, an occupancy update, this call's marches) -- NOT the rest of this call
         self._groups[g0 // k].replay()
         r.local_step = g0 + k
+        if self._loss_outputs:
+            self.ray_loss = self._ray_loss[g0 + k - 1]
         if self._lr_sched is not None:
             self._lr_sched.advance(k)
         if g0 + k < RING:
@@ -321,7 +355,16 @@ class AcceleratedTrainer:
                 self._march_ahead(0, k, next_rays, ready)
         return self.loss
 
-    def _eager_step(self, rays_o, rays_d, target):
+    def _set_error_inds(self, slot, k, error_inds):
+        """The map cells of the k steps at ring slots slot .. slot + k into their static buffers: -1 (no cell) where the caller names none."""
+        if self._error_inds is None:
+            return
+        if error_inds is None:
+            self._error_inds[slot:slot + k].fill_(-1)
+        else:
+            self._error_inds[slot:slot + k].copy_(error_inds.reshape(k, self.n_rays), non_blocking=True)
+
+    def _eager_step(self, rays_o, rays_d, target, error_inds=None):
         """One step launched kernel by kernel, through the static buffers of its ring slot (graph=False keeps the same buffer-size policy)."""
         r = self.renderer
         g = r.local_step % RING
@@ -330,8 +373,11 @@ class AcceleratedTrainer:
         sized = self._primed >= RING
         (ro, rd), tg = self._rays[g], self._targets[g]
         ro.copy_(rays_o, non_blocking=True), rd.copy_(rays_d, non_blocking=True), tg.copy_(target, non_blocking=True)
+        self._set_error_inds(g, 1, error_inds)
         marched, _ = self._march(ro, rd, mean_count=self._M if sized else None)
         self._shade(marched, g)
+        if self._loss_outputs:
+            self.ray_loss = self._ray_loss[g]
         if self._lr_sched is not None:
             self._lr_sched.advance(1)
         self._primed += 1
@@ -387,6 +433,44 @@ def _host_lrs(opt):
     return [None if isinstance(g["lr"], torch.Tensor) else float(g["lr"]) for g in opt.param_groups]
 
 
+LOSS_KINDS = {"mse": 0, "l1": 1, "huber": 2}  # NERFTEX_LOSS_MSE / _L1 / _HUBER of include/nerftex_hip.h
+
+
+def parse_criterion(criterion):
+    """-> (kind, param) of a nerftex_step_loss_desc.  Accepted: "mse", "l1", ("huber", delta) with a finite delta > 0; an already parsed
+    (kind, param); and the reference Trainer's own `criterion=` objects -- torch.nn.MSELoss, L1Loss, HuberLoss instances with reduction 'mean'
+    or 'none' (the reference takes .mean(-1).mean() of the unreduced loss: rows of equal length, so the same number).  Anything else -- reduction
+    'sum', other modules, bare callables -- is a ValueError: the kernels would train another objective.  Host only."""
+    import math
+
+    accepted = ('criterion: "mse", "l1", ("huber", delta > 0), or a torch.nn.MSELoss / L1Loss / HuberLoss instance with reduction "mean" or "none"')
+
+    def huber(delta):
+        if isinstance(delta, bool) or not isinstance(delta, (int, float)) or not (math.isfinite(delta) and delta > 0):
+            raise ValueError(f"{accepted}; got a Huber delta of {delta!r}")
+        return LOSS_KINDS["huber"], float(delta)
+
+    if isinstance(criterion, str):
+        if criterion in ("mse", "l1"):
+            return LOSS_KINDS[criterion], 0.0
+        raise ValueError(f"{accepted}; got {criterion!r}" + (" (Huber needs its delta)" if criterion == "huber" else ""))
+    if isinstance(criterion, tuple) and len(criterion) == 2:
+        if criterion[0] == "huber":
+            return huber(criterion[1])
+        if not isinstance(criterion[0], bool) and isinstance(criterion[0], int) and criterion[0] in LOSS_KINDS.values():
+            return huber(criterion[1]) if criterion[0] == LOSS_KINDS["huber"] else (int(criterion[0]), 0.0)
+        raise ValueError(f"{accepted}; got {criterion!r}")
+    if isinstance(criterion, torch.nn.Module):
+        kinds = {torch.nn.MSELoss: "mse", torch.nn.L1Loss: "l1", torch.nn.HuberLoss: "huber"}
+        name = kinds.get(type(criterion))
+        if name is None:
+            raise ValueError(f"{accepted}; got a {type(criterion).__name__}")
+        if criterion.reduction not in ("mean", "none"):
+            raise ValueError(f"{accepted}; got reduction={criterion.reduction!r}")
+        return huber(criterion.delta) if name == "huber" else (LOSS_KINDS[name], 0.0)
+    raise ValueError(f"{accepted}; got {criterion!r}")
+
+
 def _refuse_options(lr_scheduler, pipeline_adam):
     """What neither trainer does is refused at construction, before the renderer is looked at: the removed pipeline_adam (the keyword stays so
     that callers passing 0 keep working), and a learning-rate schedule where the rate cannot be read from the device schedule -- never run at
@@ -419,15 +503,19 @@ class CurvedTrainer(AcceleratedTrainer):
     gradient: at 1e-8 / (2^19 * 4) it would flush to zero).  The level of each step of a ring is drawn at the ring's start with the
     reference's own np.random call (draw_ring_levels) into a device int32[16] the slot graphs index.  trainer.loss = image loss + regulariser,
     trainer.reg_loss = the regulariser: device scalars, nothing is read back.  The fp32 parameters are current after every step (no sync()).
+    criterion="l1" is main.py:187's (the reference trains this field with torch.nn.L1Loss; the default stays the MSE); error_map= is its
+    --error_map (nerf/utils.py:617-632).
     Not here: prob_model (the log-variance table), world size > 1, and the ngp field's fused AMP options (HalfLeafAdam, fused table update,
     dead-sample skipping, the one-launch composite step), which are refused if asked for."""
 
     def __init__(self, renderer, regular_weight=1e-8, rays_per_batch=None, lr=1e-2, betas=(0.9, 0.99), eps=1e-15, dt_gamma=1 / 128, bg_color=1,
                  perturb=True, max_steps=1024, amp_dtype=torch.float16, graph=True, steps_per_call=1, march_across_ring_end=False, pipeline_adam=0,
-                 skip_dead_samples=None, fused_table_update=None, fused_composite_step=None, lr_scheduler=None, total_steps=None):
+                 skip_dead_samples=None, fused_table_update=None, fused_composite_step=None, lr_scheduler=None, total_steps=None, criterion=None,
+                 error_map=None):
         from .curved import CurvedField
 
         _refuse_options(lr_scheduler, pipeline_adam)
+        self._init_criterion(criterion, error_map)
 
         field = renderer.field
         assert isinstance(field, CurvedField), "CurvedTrainer trains a curved.CurvedField"
@@ -471,7 +559,7 @@ class CurvedTrainer(AcceleratedTrainer):
             p.grad = None
         self._centres_grad.zero_()
         with torch.autocast("cuda", dtype=self.amp_dtype):
-            image, depth, loss, scaled = r.shade_train(marched, self.bg_color, target=self._targets[slot], scale=None)
+            image, depth, loss, scaled = r.shade_train(marched, self.bg_color, target=self._targets[slot], scale=None, **self._loss_args(slot))
         self.scaler.scale(scaled).backward()
         from gridencoder.grid_clustering import grid_cluster_step
 
@@ -489,7 +577,10 @@ def accelerate(renderer, **kw):
     """See the module docstring.  Keyword arguments: rays_per_batch, lr, betas, eps, dt_gamma, bg_color, perturb, max_steps, amp_dtype, graph,
     steps_per_call (k > 1: `step_group` takes the batches of k consecutive steps and replays one graph for them), march_across_ring_end,
     lr_scheduler + total_steps (a factory `lambda optimizer: LambdaLR(optimizer, lr_lambda)`, as the reference's Trainer takes it, and the number
-    of training steps its device table covers: every step, replayed or eager, trains at the rate LambdaLR gives it; `trainer.lr_scheduler`).
+    of training steps its device table covers: every step, replayed or eager, trains at the rate LambdaLR gives it; `trainer.lr_scheduler`),
+    criterion ("mse" -- the default --, "l1", ("huber", delta), or the reference Trainer's MSELoss / L1Loss / HuberLoss object: `parse_criterion`)
+    and error_map (a contiguous fp32 device tensor updated in place as 0.1 * old + 0.9 * ray loss at the cells `step(..., error_inds=)` names; the
+    map is written by every step, skipped by the loss scaler or not; `trainer.ray_loss` is the last step's per-ray loss).
     A renderer over a curved.CurvedField gets a CurvedTrainer (its docstring; regular_weight, default 1e-8)."""
     from .curved import CurvedField
 

@@ -350,6 +350,27 @@ def ngp_field(x, dirs, encoder, sigma_net, color_net, bound, training, live=None
     return _ngp_field.apply(x, dirs, encoder._table(), encoder.offsets, sigma_net._weights(), color_net._weights(), encoder, bool(training), live, mlp_dtype)
 
 
+def step_loss_desc(criterion, ray_loss, error_map, error_inds, n_rays, dev):
+    """The nerftex_step_loss_desc of a tail call, or None when nothing was asked for (the call is then the MSE entry it always was).
+    criterion: anything `accelerate.parse_criterion` takes; ray_loss: fp32 [N] that receives criterion(pred, gt).mean(-1); error_map: contiguous
+    fp32 tensor of any shape, updated in place at the flat cells error_inds (int64 [N]; a cell outside the map, -1 say, updates nothing) as
+    0.1 * old + 0.9 * ray_loss.  The cells of one call are distinct; with duplicates one of the candidates lands, as with torch's scatter_."""
+    if criterion is None and ray_loss is None and error_map is None and error_inds is None:
+        return None
+    from nerftex_hip import StepLossDesc
+
+    from .accelerate import parse_criterion
+
+    kind, param = parse_criterion("mse" if criterion is None else criterion)
+    if (error_map is None) != (error_inds is None):
+        raise ValueError("error_map and error_inds go together: the map is updated at the rays' cells (pass -1 for a ray that has none)")
+    for name, t, dtype, shape in (("ray_loss", ray_loss, torch.float32, (n_rays,)), ("error_map", error_map, torch.float32, None),
+                                  ("error_inds", error_inds, torch.int64, (n_rays,))):
+        if t is not None and not (t.dtype == dtype and t.device == dev and t.is_contiguous() and (shape is None or tuple(t.shape) == shape)):
+            raise ValueError(f"{name}: a contiguous {dtype} tensor on {dev}" + (f" of shape {shape}" if shape else "") + f", got {t.dtype} {tuple(t.shape)} on {t.device}")
+    return StepLossDesc(kind, param, ptr(ray_loss), ptr(error_map), ptr(error_inds), 0 if error_map is None else error_map.numel(), 0.1, 0.9)
+
+
 class _render_tail(Function):
     """image + (1 - weights_sum) * bg, depth normalisation and mean squared error against `target` in one launch
     (nerf/renderer.py:417-425 + the MSE of nerf/utils.py:602-640); returns (image_out, depth_out, loss * loss_mul, scaled loss).
@@ -357,7 +378,7 @@ class _render_tail(Function):
     backward on -- it carries the gradient to `image` and `weights_sum`; the first three are plain outputs."""
 
     @staticmethod
-    def forward(ctx, weights_sum, depth, image, nears, fars, target, bg, loss_mul, scale):
+    def forward(ctx, weights_sum, depth, image, nears, fars, target, bg, loss_mul, scale, crit=None):
         args = [t.contiguous().float() for t in (weights_sum, depth, image, nears, fars, target)]
         weights_sum, depth, image, nears, fars, target = args
         N, dev = weights_sum.shape[0], weights_sum.device
@@ -367,9 +388,15 @@ class _render_tail(Function):
         depth_out = torch.empty_like(depth)
         losses = torch.empty(2, dtype=torch.float32, device=dev)
         scratch = _tail_scratch(dev, (N + 255) // 256)
-        check(lib.nerftex_render_tail_forward(ptr(weights_sum), ptr(depth), ptr(image), ptr(nears), ptr(fars), ptr(target), float(bg),
-                                              float(loss_mul), N, ptr(image_out), ptr(depth_out), ptr(scratch[1]), ptr(scratch[0]), ptr(losses),
-                                              ptr(scale), losses.data_ptr() + 4, stream()))
+        ctx.desc = desc = None if crit is None else step_loss_desc(*crit, N, dev)
+        if desc is None:
+            check(lib.nerftex_render_tail_forward(ptr(weights_sum), ptr(depth), ptr(image), ptr(nears), ptr(fars), ptr(target), float(bg),
+                                                  float(loss_mul), N, ptr(image_out), ptr(depth_out), ptr(scratch[1]), ptr(scratch[0]), ptr(losses),
+                                                  ptr(scale), losses.data_ptr() + 4, stream()))
+        else:
+            check(lib.nerftex_render_tail_forward_ex(ptr(weights_sum), ptr(depth), ptr(image), ptr(nears), ptr(fars), ptr(target), float(bg),
+                                                     float(loss_mul), N, ptr(image_out), ptr(depth_out), ptr(scratch[1]), ptr(scratch[0]), ptr(losses),
+                                                     ptr(scale), losses.data_ptr() + 4, None, 0, ctypes.byref(desc), stream()))
         ctx.save_for_backward(image_out, target, scale)
         ctx.consts = (float(bg), float(loss_mul))
         loss, scaled = losses[0], losses[1]
@@ -381,15 +408,19 @@ class _render_tail(Function):
     def backward(ctx, _gi, _gd, _gl, grad_scaled):
         image_out, target, scale = ctx.saved_tensors
         if grad_scaled is None:
-            return (None,) * 9
+            return (None,) * 10
         bg, loss_mul = ctx.consts
         N = image_out.shape[0]
         grad_scaled = grad_scaled.contiguous().float()
         grad_image = torch.empty_like(image_out)
         grad_ws = torch.empty(N, dtype=torch.float32, device=image_out.device)
-        check(lib.nerftex_render_tail_backward(ptr(grad_scaled), ptr(scale), loss_mul, ptr(image_out), ptr(target), bg, N, ptr(grad_image),
-                                               ptr(grad_ws), stream()))
-        return grad_ws, None, grad_image, None, None, None, None, None, None
+        if ctx.desc is None:
+            check(lib.nerftex_render_tail_backward(ptr(grad_scaled), ptr(scale), loss_mul, ptr(image_out), ptr(target), bg, N, ptr(grad_image),
+                                                   ptr(grad_ws), stream()))
+        else:
+            check(lib.nerftex_render_tail_backward_ex(ptr(grad_scaled), ptr(scale), loss_mul, ptr(image_out), ptr(target), bg, N, ptr(grad_image),
+                                                      ptr(grad_ws), ctypes.byref(ctx.desc), stream()))
+        return grad_ws, None, grad_image, None, None, None, None, None, None, None
 
 
 class _composite_tail(Function):
@@ -402,7 +433,7 @@ class _composite_tail(Function):
     the loss); the backward returns them when the root gradient is that very tensor, and runs the backward launch as before for any other."""
 
     @staticmethod
-    def forward(ctx, sigmas, rgbs, deltas, rays, nears, fars, target, bg, loss_mul, scale, live_holder=None, one=None):
+    def forward(ctx, sigmas, rgbs, deltas, rays, nears, fars, target, bg, loss_mul, scale, live_holder=None, one=None, crit=None):
         sigmas, rgbs, deltas = sigmas.contiguous().float(), rgbs.contiguous().float(), deltas.contiguous().float()
         nears, fars, target = nears.contiguous().float(), fars.contiguous().float(), target.contiguous().float()
         rays = rays.contiguous()
@@ -414,6 +445,8 @@ class _composite_tail(Function):
         image, image_out = per_ray[3:6].view(N, 3), per_ray[6:9].view(N, 3)
         losses = torch.empty(2, dtype=torch.float32, device=dev)
         ctx.step_grads = None
+        # crit = (criterion, ray_loss, error_map, error_inds) or None: the _ex entries with a nerftex_step_loss_desc, else the MSE entries as ever
+        ctx.desc = desc = None if crit is None or N == 0 else step_loss_desc(*crit, N, dev)
         if one is not None and 0 < N <= 262144 and M > 0 and (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
             assert one.dtype == torch.float32 and one.numel() == 1 and one.device == dev
             grads = torch.empty(4 * M, dtype=torch.float32, device=dev)
@@ -428,9 +461,13 @@ class _composite_tail(Function):
             # the loss: the field's backward finishes it (an extra workgroup of its weight-gradient reduction: `loss` and `scaled` are COMPLETE AFTER THE
             # BACKWARD, which is when a training step reads them) when it has announced that it will; else a one-workgroup launch of this call's
             defer = live_holder is not None and live_holder.get("field_consumes", False) and live_holder.get("defer_loss", False)
-            check(lib.nerftex_composite_step(ptr(sigmas), ptr(rgbs), ptr(deltas), ptr(rays), M, N, ptr(nears), ptr(fars), ptr(target), float(bg),
-                                             float(loss_mul), ptr(scale), ptr(weights_sum), ptr(depth), ptr(image), ptr(image_out), ptr(depth_out), ptr(err),
-                                             None if defer else ptr(losses), losses.data_ptr() + 4, ptr(grads), grads.data_ptr() + 4 * M, ptr(flags), stream()))
+            step_args = (ptr(sigmas), ptr(rgbs), ptr(deltas), ptr(rays), M, N, ptr(nears), ptr(fars), ptr(target), float(bg), float(loss_mul), ptr(scale),
+                         ptr(weights_sum), ptr(depth), ptr(image), ptr(image_out), ptr(depth_out), ptr(err), None if defer else ptr(losses),
+                         losses.data_ptr() + 4, ptr(grads), grads.data_ptr() + 4 * M, ptr(flags))
+            if desc is None:
+                check(lib.nerftex_composite_step(*step_args, stream()))
+            else:
+                check(lib.nerftex_composite_step_ex(*step_args, ctypes.byref(desc), stream()))
             if defer:
                 live_holder["loss_job"] = (err, N, float(loss_mul), scale, losses)
             ctx.step_grads, ctx.one_ptr = (grads[:M], grads[M:].view(M, 3)), one.data_ptr()
@@ -451,9 +488,13 @@ class _composite_tail(Function):
         ctx.live_holder, ctx.step_live = live_holder, None
         if live_holder is not None and M > 0:
             ctx.step_live = torch.empty((M + 31) // 32, dtype=torch.int32, device=dev)
-        check(lib.nerftex_render_tail_forward_live(ptr(weights_sum), ptr(depth), ptr(image), ptr(nears), ptr(fars), ptr(target), float(bg), float(loss_mul), N,
-                                                   ptr(image_out), ptr(depth_out), ptr(scratch[1]), ptr(scratch[0]), ptr(losses), ptr(scale),
-                                                   losses.data_ptr() + 4, ptr(ctx.step_live), 0 if ctx.step_live is None else ctx.step_live.numel(), stream()))
+        tail_args = (ptr(weights_sum), ptr(depth), ptr(image), ptr(nears), ptr(fars), ptr(target), float(bg), float(loss_mul), N, ptr(image_out), ptr(depth_out),
+                     ptr(scratch[1]), ptr(scratch[0]), ptr(losses), ptr(scale), losses.data_ptr() + 4, ptr(ctx.step_live),
+                     0 if ctx.step_live is None else ctx.step_live.numel())
+        if desc is None:
+            check(lib.nerftex_render_tail_forward_live(*tail_args, stream()))
+        else:
+            check(lib.nerftex_render_tail_forward_ex(*tail_args, ctypes.byref(desc), stream()))
         ctx.save_for_backward(sigmas, rgbs, deltas, rays, weights_sum, image, image_out, target, scale)
         ctx.consts = (float(bg), float(loss_mul))
         loss, scaled = losses[0], losses[1]
@@ -465,13 +506,13 @@ class _composite_tail(Function):
     def backward(ctx, _gi, _gd, _gl, grad_scaled):
         sigmas, rgbs, deltas, rays, weights_sum, image, image_out, target, scale = ctx.saved_tensors
         if grad_scaled is None:
-            return (None,) * 12
+            return (None,) * 13
         if ctx.step_grads is not None and grad_scaled.data_ptr() == ctx.one_ptr and grad_scaled.numel() == 1:
-            return (*ctx.step_grads, None, None, None, None, None, None, None, None, None, None)  # computed by the forward's launch
+            return (*ctx.step_grads, None, None, None, None, None, None, None, None, None, None, None)  # computed by the forward's launch
         bg, loss_mul = ctx.consts
         M, N = sigmas.shape[0], rays.shape[0]
         if N == 0 or M == 0:
-            return torch.zeros_like(sigmas), torch.zeros_like(rgbs), None, None, None, None, None, None, None, None, None, None
+            return torch.zeros_like(sigmas), torch.zeros_like(rgbs), None, None, None, None, None, None, None, None, None, None, None
         grad_scaled = grad_scaled.contiguous().float()
         # PRECONDITION of the uninitialised gradient buffers below: `rays` are the records of THIS library's march with the counter at zero
         # on entry (march_rays_train / march_rays_train_fresh: record n = ray n, offsets an exclusive prefix sum from 0), so that the rows past
@@ -480,18 +521,33 @@ class _composite_tail(Function):
         # rows the rays do not cover (the tail of a buffer sized by the mean count) get no gradient: zeros, like the reference's buffers --
         grads = torch.empty(4 * M, dtype=torch.float32, device=sigmas.device)  # (zeroed where no ray writes by the launch itself)
         grad_sigmas, grad_rgbs = grads[:M], grads[M:].view(M, 3)
-        check(lib.nerftex_composite_tail_backward_live(ptr(grad_scaled), ptr(scale), loss_mul, ptr(image_out), ptr(target), bg, ptr(sigmas), ptr(rgbs), ptr(deltas),
-                                                       ptr(rays), ptr(weights_sum), ptr(image), M, N, ptr(grad_sigmas), ptr(grad_rgbs), ptr(ctx.step_live), stream()))
+        bwd_args = (ptr(grad_scaled), ptr(scale), loss_mul, ptr(image_out), ptr(target), bg, ptr(sigmas), ptr(rgbs), ptr(deltas), ptr(rays), ptr(weights_sum),
+                    ptr(image), M, N, ptr(grad_sigmas), ptr(grad_rgbs), ptr(ctx.step_live))
+        if ctx.desc is None:
+            check(lib.nerftex_composite_tail_backward_live(*bwd_args, stream()))
+        else:
+            check(lib.nerftex_composite_tail_backward_ex(*bwd_args, ctypes.byref(ctx.desc), stream()))
         if ctx.step_live is not None and ctx.step_grads is None:
             ctx.live_holder["flags"] = ctx.live_holder["last"] = ctx.step_live  # ("last" stays for whoever wants to look: bench.py's dead-step fraction)
-        return grad_sigmas, grad_rgbs, None, None, None, None, None, None, None, None, None, None
+        return grad_sigmas, grad_rgbs, None, None, None, None, None, None, None, None, None, None, None
 
 
-def composite_tail(sigmas, rgbs, deltas, rays, nears, fars, target, bg=1.0, loss_mul=1.0, scale=None, live_holder=None, one=None):
-    """-> (image_out, depth_out, loss, scaled_loss): compositing, background blend, depth normalisation and MSE; one backward launch.
+def _crit(criterion, ray_loss, error_map, error_inds):
+    """What the tail nodes carry: None when nothing was asked for (they then make the very calls they always made)."""
+    if criterion is None and ray_loss is None and error_map is None and error_inds is None:
+        return None
+    return (criterion, ray_loss, error_map, error_inds)
+
+
+def composite_tail(sigmas, rgbs, deltas, rays, nears, fars, target, bg=1.0, loss_mul=1.0, scale=None, live_holder=None, one=None, criterion=None,
+                   ray_loss=None, error_map=None, error_inds=None):
+    """-> (image_out, depth_out, loss, scaled_loss): compositing, background blend, depth normalisation and the loss; one backward launch.
     live_holder: a dict shared with the fused field's backward (Renderer.shade_train, skip_dead_samples): the backward leaves its step flags there.
-    one: the root-gradient tensor of the coming `scaled_loss.backward(one)` (a device 1.0): forward + backward become one launch."""
-    return _composite_tail.apply(sigmas, rgbs, deltas, rays, nears, fars, target, bg, loss_mul, scale, live_holder, one)
+    one: the root-gradient tensor of the coming `scaled_loss.backward(one)` (a device 1.0): forward + backward become one launch.
+    criterion / ray_loss / error_map / error_inds (`step_loss_desc`): the loss is the criterion's (default: MSE), the rays' losses and the error
+    map's moving average are written by the forward's launch, in either form."""
+    return _composite_tail.apply(sigmas, rgbs, deltas, rays, nears, fars, target, bg, loss_mul, scale, live_holder, one,
+                                 _crit(criterion, ray_loss, error_map, error_inds))
 
 
 _SCRATCH = {}
@@ -506,6 +562,8 @@ def _tail_scratch(dev, blocks):
     return s
 
 
-def render_tail(weights_sum, depth, image, nears, fars, target, bg=1.0, loss_mul=1.0, scale=None):
-    """-> (image_out, depth_out, loss, scaled_loss); call backward on scaled_loss (== loss when scale is None)."""
-    return _render_tail.apply(weights_sum, depth, image, nears, fars, target, bg, loss_mul, scale)
+def render_tail(weights_sum, depth, image, nears, fars, target, bg=1.0, loss_mul=1.0, scale=None, criterion=None, ray_loss=None, error_map=None,
+                error_inds=None):
+    """-> (image_out, depth_out, loss, scaled_loss); call backward on scaled_loss (== loss when scale is None).
+    criterion / ray_loss / error_map / error_inds: as for `composite_tail`."""
+    return _render_tail.apply(weights_sum, depth, image, nears, fars, target, bg, loss_mul, scale, _crit(criterion, ray_loss, error_map, error_inds))
