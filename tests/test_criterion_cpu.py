@@ -33,6 +33,11 @@ def test_accepted_spellings(spelling, want):
     assert got == want and isinstance(got[0], int) and isinstance(got[1], float)
 
 
+def _ident(v):
+    """a test id that is the same in every process: a function's repr carries its address"""
+    return f"<function {v.__name__}>" if isinstance(v, (types.FunctionType, types.BuiltinFunctionType)) else repr(v)[:40]
+
+
 REFUSED = [
     "huber", "L1", "smooth_l1", "", None, 1, ("huber",), ("huber", 0), ("huber", 0.0), ("huber", -1.0), ("huber", math.inf), ("huber", math.nan),
     ("huber", "0.1"), ("huber", True), ("l1", 0.0), (7, 0.0), (HUBER, 0.0),
@@ -41,13 +46,13 @@ REFUSED = [
 ]
 
 
-@pytest.mark.parametrize("spelling", REFUSED, ids=lambda v: repr(v)[:40])
+@pytest.mark.parametrize("spelling", REFUSED, ids=_ident)
 def test_refused_spellings(spelling):
     with pytest.raises(ValueError, match="criterion: .*mse.*l1.*huber.*MSELoss.*reduction"):
         parse_criterion(spelling)
 
 
-@pytest.mark.parametrize("spelling", ["huber", torch.nn.L1Loss(reduction="sum"), torch.nn.functional.mse_loss, ("huber", 0)], ids=lambda v: repr(v)[:40])
+@pytest.mark.parametrize("spelling", ["huber", torch.nn.L1Loss(reduction="sum"), torch.nn.functional.mse_loss, ("huber", 0)], ids=_ident)
 def test_trainers_refuse_before_the_renderer_is_looked_at(spelling):
     nothing = types.SimpleNamespace(field=None)
     for cls in (AcceleratedTrainer, CurvedTrainer):

@@ -61,7 +61,7 @@ def _composite_problem(seed, n_rays=40):
     rays[:, 2] = counts
     rays[:, 1] = np.concatenate([[0], np.cumsum(counts)[:-1]])
     M = int(counts.sum()) + 8  # slack rows: the kernels drop a ray whose samples reach the buffer's end (raymarching.cu:720 `offset + num_steps >= M`)
-    sigmas = rng.uniform(0, 6, M).astype(np.float32)  # with deltas ~0.02: no ray gets near the kernels' T < 1e-4 early stop
+    sigmas = rng.uniform(0, 6, M).astype(np.float32)  # with deltas ~0.02: thin rays (the training kernels have no early stop; only the inference kernel composite_rays_kernel stops at T < 1e-4)
     rgbs = rng.uniform(0, 1, (M, 3)).astype(np.float32)
     deltas = np.stack([rng.uniform(0.005, 0.03, M), rng.uniform(0.005, 0.03, M)], -1).astype(np.float32)
     g_ws = rng.standard_normal(n_rays).astype(np.float32)
