@@ -903,6 +903,28 @@ int nerftex_amp_check_mixed(int count, const void* const* grads16, const uint64_
 int nerftex_amp_update(float* scale, int32_t* growth_tracker, float* found_inf, float* step, double growth_factor,
                        double backoff_factor, int growth_interval, void* stream);
 
+/* Extension: an exponential moving average of the parameters, kept on the device by the training step itself (the reference trainer wraps its
+ * parameters in torch_ema.ExponentialMovingAverage(decay=0.95) and calls update() after every optimizer step: nerf/utils.py:460-462, :1027-1028).
+ * One streaming launch, 12 B per parameter, over `count` fp32 tensors of n[t] elements: torch_ema's update() with use_num_updates=True,
+ *     u = *num_updates + 1;  d = min(decay, (1 + u) / (10 + u)) in double;  w = (float)(1.0 - d);
+ *     per element  tmp = s - p;  tmp = tmp * w;  s = s - tmp      (three fp32 roundings, no fma: the bits of torch's sub, mul_, sub_)
+ * p comes from param1[t] when `live` is given and *live & 1, else from param0[t]: behind the last launch of a double-buffered optimizer step
+ * (nerftex_adam_mixed_step_amp_db) the live word names the step's parameters, whether the step was applied (flipped) or skipped (left).
+ * Every block reads *num_updates and *live once, at its start; with advance != 0 the block that finishes last stores *num_updates = u (ticket:
+ * zero on entry, left zero).  count is 1..8 per call: a model with more tensors makes several calls, advance set on the LAST one only -- they
+ * all read the same *num_updates and so behave as one update over their union.  Tensors with n[t] == 0 are skipped.
+ * NERFTEX_ERR_INVALID, nothing launched: a NULL descriptor, num_updates, ticket, shadow, param0 or n (or a NULL buffer of a non-empty tensor);
+ * decay outside (0, 1); count outside 1..8; live without param1; a buffer that is not 16-byte aligned.                                        */
+typedef struct nerftex_ema_desc {
+    double decay;          /* the cap, 0 < decay < 1 */
+    uint32_t* num_updates; /* device word: updates done so far */
+    uint32_t* ticket;      /* device word: zero on entry, left zero */
+    const uint32_t* live;  /* NULL, or the double-buffered optimizer's live word */
+    int advance;           /* != 0: the launch's last block stores *num_updates + 1 */
+} nerftex_ema_desc;
+int nerftex_ema_update(const nerftex_ema_desc* desc, int count, float* const* shadow, const float* const* param0,
+                       const float* const* param1 /* NULL without live */, const uint64_t* n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -375,6 +375,86 @@ __global__ void lr_publish_kernel(const LrSched sched, const LrPublish pub) {
     *sched.iter = t + 1u;
 }
 
+// ---- parameter EMA (nerftex_ema_update): torch_ema's update() behind the optimizer's last launch of a step ----
+// launch shape, measured (tools/probes/ema_shapes.hip, profiles/ema_shapes_probe.txt): the ticket is one atomic per block on ONE address, ~6 ns
+// each and all at the launch's end, where nothing hides them -- 2048 blocks of 256 threads paid 12 us for them on a 21 us stream, 512 blocks
+// of 512 threads with four 16-byte groups in flight per thread pay 0.1 us and stream as fast
+constexpr uint32_t kEmaThreads = 512;
+constexpr uint32_t kEmaBlocksPerCu = 2;  // per tensor
+constexpr uint32_t kEmaUnroll = 4;
+constexpr uint32_t kEmaVec = 4;  // floats per 16-byte access
+
+struct EmaTensors {
+    float* shadow[kMaxTensors];
+    const float* param[2][kMaxTensors];  // the two sets of a double-buffered optimizer; [1] is unused without `live`
+    uint64_t n[kMaxTensors];
+    uint32_t block_end[kMaxTensors];  // blocks [block_end[t-1], block_end[t]) work on tensor t
+    int count;
+};
+
+// s -= (s - p) * w: torch's sub, mul_, sub_ -- three roundings, never an fma
+__device__ __forceinline__ float ema_one(const float s, const float p, const float w) {
+#pragma clang fp contract(off)
+    float tmp = s - p;
+    tmp = tmp * w;
+    return s - tmp;
+}
+
+__device__ __forceinline__ float4 ema_four(const float4 s, const float4 p, const float w) {
+    return float4{ema_one(s.x, p.x, w), ema_one(s.y, p.y, w), ema_one(s.z, p.z, w), ema_one(s.w, p.w, w)};
+}
+
+// 12 B per parameter.  A block finds its tensor, then grid-strides inside it, four 16-byte groups per thread in flight.  The two device words
+// are read by ONE thread per block, before anything else, and handed round through LDS: that thread's ticket then says its block is past them
+__global__ __launch_bounds__(kEmaThreads) void ema_kernel(const EmaTensors tens, const double decay, uint32_t* num_updates, uint32_t* ticket,
+                                                          const uint32_t* live, const int advance) {
+    __shared__ uint32_t words[2];
+    if (threadIdx.x == 0) {
+        words[0] = *num_updates;
+        words[1] = live ? *live : 0u;
+    }
+    __syncthreads();
+    const uint32_t num_v = words[0], from = words[1] & 1u;
+    if (tens.count > 0 && blockIdx.x < tens.block_end[tens.count - 1]) {
+        // torch_ema, use_num_updates: num_updates += 1; decay = min(decay, (1 + num_updates) / (10 + num_updates)); one_minus_decay = 1.0 - decay
+        const double nu = (double)num_v + 1.0;
+        const float w = (float)(1.0 - fmin(decay, (1.0 + nu) / (10.0 + nu)));
+        int t = 0;
+        while (t + 1 < tens.count && blockIdx.x >= tens.block_end[t]) t++;
+        const uint32_t first = t ? tens.block_end[t - 1] : 0u;
+        const uint32_t nblocks = tens.block_end[t] - first, block = blockIdx.x - first;
+        float* __restrict__ s = tens.shadow[t];
+        const float* __restrict__ p = tens.param[from][t];
+        const uint64_t n = tens.n[t], groups = n / kEmaVec, stride = (uint64_t)nblocks * kEmaThreads;
+        float4* s4 = reinterpret_cast<float4*>(s);
+        const float4* p4 = reinterpret_cast<const float4*>(p);
+        uint64_t i = (uint64_t)block * kEmaThreads + threadIdx.x;
+        for (; i + (kEmaUnroll - 1) * stride < groups; i += kEmaUnroll * stride) {
+            float4 a[kEmaUnroll], b[kEmaUnroll];
+#pragma unroll
+            for (uint32_t u = 0; u < kEmaUnroll; u++) {
+                a[u] = s4[i + u * stride];
+                b[u] = p4[i + u * stride];
+            }
+#pragma unroll
+            for (uint32_t u = 0; u < kEmaUnroll; u++) s4[i + u * stride] = ema_four(a[u], b[u], w);
+        }
+        for (; i < groups; i += stride) s4[i] = ema_four(s4[i], p4[i], w);
+        // ragged end (n not a multiple of 4): the tensor's first block, first lanes
+        const uint64_t rest = groups * kEmaVec + threadIdx.x;
+        if (block == 0 && rest < n) s[rest] = ema_one(s[rest], p[rest], w);
+    }
+    // the counter, by whichever block finishes last.  No fence, as in adam_half_kernel's tail: the last block consumes nothing the others wrote,
+    // it only needs every block's thread 0 to be past its read of *num_updates -- which that thread's own ticket (issued after the read's value
+    // went through LDS) says
+    if (advance && threadIdx.x == 0) {
+        if (atomicAdd(ticket, 1u) == gridDim.x - 1) {
+            *num_updates = num_v + 1u;
+            *ticket = 0u;
+        }
+    }
+}
+
 }  // namespace
 }  // namespace nerftex
 
@@ -740,4 +820,57 @@ extern "C" int nerftex_amp_update(float* scale, int32_t* growth_tracker, float* 
                            growth_interval, (uint32_t*)nullptr, (uint32_t*)nullptr);
     }
     return check_launch("amp_update");
+}
+
+// torch_ema's ExponentialMovingAverage.update() (use_num_updates=True) over up to 8 tensors as one launch; see include/nerftex_hip.h
+extern "C" int nerftex_ema_update(const nerftex_ema_desc* desc, int count, float* const* shadow, const float* const* param0, const float* const* param1,
+                                  const uint64_t* n, void* stream) {
+    clear_error();
+    if (!desc || !shadow || !param0 || !n || !desc->num_updates || !desc->ticket) {
+        set_error("ema_update: the descriptor, its num_updates and ticket words, shadow, param0 and n must not be NULL");
+        return NERFTEX_ERR_INVALID;
+    }
+    if (!(desc->decay > 0.0 && desc->decay < 1.0)) {
+        set_error("ema_update: decay must lie in (0, 1), got %g", desc->decay);
+        return NERFTEX_ERR_INVALID;
+    }
+    if (count < 1 || count > kMaxTensors) {
+        set_error("ema_update: 1 to %d tensors per call (more: several calls, advance set on the last), got %d", kMaxTensors, count);
+        return NERFTEX_ERR_INVALID;
+    }
+    if (desc->live && !param1) {
+        set_error("ema_update: a live word needs the second parameter set (param1)");
+        return NERFTEX_ERR_INVALID;
+    }
+    EmaTensors tens{};
+    uint32_t blocks = 0;
+    for (int t = 0; t < count; t++) {
+        if (n[t] == 0) continue;
+        if (!shadow[t] || !param0[t] || (desc->live && !param1[t])) {
+            set_error("ema_update: tensor %d has a NULL buffer", t);
+            return NERFTEX_ERR_INVALID;
+        }
+        if (misaligned(shadow[t]) || misaligned(param0[t]) || (desc->live && misaligned(param1[t]))) {
+            set_error("ema_update: buffers must be 16-byte aligned");
+            return NERFTEX_ERR_INVALID;
+        }
+        const int k = tens.count++;
+        tens.shadow[k] = shadow[t];
+        tens.param[0][k] = param0[t];
+        tens.param[1][k] = desc->live ? param1[t] : param0[t];
+        tens.n[k] = n[t];
+        blocks += (uint32_t)std::min<uint64_t>(std::max<uint64_t>(div_up(n[t] / kEmaVec, (uint64_t)kEmaThreads), 1), (uint64_t)device_cus() * kEmaBlocksPerCu);
+        tens.block_end[k] = blocks;
+    }
+    if (tens.count == 0) {
+        if (!desc->advance) return NERFTEX_OK;
+        blocks = 1;  // nothing to average: the update still counts
+    }
+    hipStream_t st = as_stream(stream);
+    {
+        KernelTimer kt("ema_kernel", st);
+        hipLaunchKernelGGL(ema_kernel, dim3(blocks), dim3(kEmaThreads), 0, st, tens, desc->decay, desc->num_updates, desc->ticket, desc->live,
+                           desc->advance ? 1 : 0);
+    }
+    return check_launch("ema_update");
 }

@@ -66,6 +66,7 @@ _SIGNATURES = {
     "nerftex_adam_mixed_step_amp_db_sched": [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _f64, _vp, _f64, _f64, _f64, _vp, _vp, _vp, _vp,
                                              _f64, _f64, _i, _vp, _vp, _vp, _vp, _u64, _vp],
     "nerftex_lr_schedule_publish": [_vp, _vp, _vp, _u32, _vp],
+    "nerftex_ema_update": [_vp, _i, _vp, _vp, _vp, _vp, _vp],
     "nerftex_field_backward_live": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "nerftex_field_backward_live_bf16": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "nerftex_field_backward_live_consume": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
@@ -144,6 +145,15 @@ _SIGNATURES = {
 class LrSchedule(C.Structure):
     """nerftex_lr_schedule of include/nerftex_hip.h, field for field."""
     _fields_ = [("factor", _vp), ("n", _u32), ("iter", _vp)]
+
+
+class EmaDesc(C.Structure):
+    """nerftex_ema_desc of include/nerftex_hip.h, field for field."""
+    _fields_ = [("decay", _f64), ("num_updates", _vp), ("ticket", _vp), ("live", _vp), ("advance", _i)]
+
+
+# the launch shape of nerftex_ema_update (csrc/trainstep.hip: kEmaThreads, kEmaVec, kEmaBlocksPerCu, kEmaUnroll, kMaxTensors)
+EMA_THREADS, EMA_VEC, EMA_BLOCKS_PER_CU, EMA_UNROLL, EMA_MAX_TENSORS = 512, 4, 2, 4, 8
 
 
 class TableAdam(C.Structure):

@@ -29,6 +29,9 @@ into the graphs; a trainer cannot):
     mean itself and silently drops the rays that do not fit, raymarching.cu:419; with the margin none are dropped); every 16 steps the
     mean is read back (the reference does the same in update_extra_state) and, if it left the size, two eager steps at the new size
     and a new capture follow.
+  * `ema_decay=0.95`: the reference trainer's EMA of the parameters (torch_ema), kept by the step's last launch (ema.DeviceEMA: `trainer.ema`
+    has update / store / copy_to / restore / average_parameters / state_dict); evaluate and save the "best" checkpoint under
+    `with trainer.ema.average_parameters():` -- `step` raises while the average is swapped in.
 The occupancy update stays the caller's (`renderer.update_extra_state_device()` every 16 steps writes grid and bitfield in place: the
 graphs keep reading the same tensors).  A march started by `next_rays` reads the grid as it is at that moment: hand the next rays over
 AFTER the update when one is due (the ring's end, where nothing is marched ahead anyway: the read-back comes first there).
@@ -44,10 +47,11 @@ RING = 16
 class AcceleratedTrainer:
     def __init__(self, renderer, rays_per_batch=None, lr=1e-2, betas=(0.9, 0.99), eps=1e-15, dt_gamma=1 / 128, bg_color=1, perturb=True, max_steps=1024,
                  amp_dtype=torch.float16, graph=True, steps_per_call=1, march_across_ring_end=False, pipeline_adam=0, skip_dead_samples=None,
-                 fused_table_update=None, fused_composite_step=None, lr_scheduler=None, total_steps=None, criterion=None, error_map=None):
+                 fused_table_update=None, fused_composite_step=None, lr_scheduler=None, total_steps=None, criterion=None, error_map=None,
+                 ema_decay=None):
         from .model import NGPField
 
-        _refuse_options(lr_scheduler, pipeline_adam)
+        _refuse_options(lr_scheduler, pipeline_adam, ema_decay)
         self._init_criterion(criterion, error_map)
         field = renderer.field
         assert isinstance(field, NGPField), "accelerate() knows the ngp field (hash grid + two MLPs)"
@@ -103,6 +107,7 @@ class AcceleratedTrainer:
         renderer.root_one = self._one if self.fused_composite_step else None
         renderer.defer_step_loss = bool(self.fused_composite_step)  # (`_shade` reads the loss after the backward: the field's backward may finish it)
         self._attach_schedule(lr_scheduler, total_steps)
+        self._attach_ema(ema_decay)
 
     def _init_criterion(self, criterion, error_map):
         """criterion / error_map of accelerate(): refused here, before the renderer is looked at, when they are not what the kernels do.  With
@@ -168,6 +173,17 @@ class AcceleratedTrainer:
             self._lr_sched.use_tensor_lr(self.opt)  # torch's fused Adam reads an fp32 tensor written by nerftex_lr_schedule_publish
         self.lr_scheduler = sched
 
+    def _attach_ema(self, ema_decay):
+        """ema_decay = the reference Trainer's (0.95 in main.py:190 / main_nerf.py:133): `trainer.ema` is an ema.DeviceEMA over the field's
+        non-integer parameters in the reference's order (nerf/utils.py:461), updated by the last launch of every step, applied or skipped.
+        None: no buffer, no launch, the same captured graphs."""
+        self.ema = None
+        if ema_decay is None:
+            return
+        from .ema import DeviceEMA
+
+        self.ema = DeviceEMA([p for p in self.field.parameters() if p.dtype != torch.long], ema_decay, optimizer=self.opt)
+
     def _lr_guard(self):
         """Without a schedule the replayed launches train at the rate they were captured with: refuse to replay after it changed."""
         if self._lr_sched is None and self._captured_lr is not None and self._captured_lr != _host_lrs(self.opt):
@@ -206,6 +222,8 @@ class AcceleratedTrainer:
             self.scaler.step(self.opt)
             self.scaler.update()
         self.loss.copy_(loss.detach().reshape(()))
+        if self.ema is not None:
+            self.ema.update()  # the step's last launch: behind the optimizer's, reads the set its live word names (a skipped step: the unchanged one)
 
     def _loss_args(self, slot):
         """shade_train's criterion / per-ray loss / error map arguments of a step at ring slot `slot`: none unless accelerate() was given any."""
@@ -305,6 +323,9 @@ class AcceleratedTrainer:
         assert rays_o.is_contiguous() and rays_d.is_contiguous(), "rays_o / rays_d must be contiguous tensors (next_rays are recognised by their address)"
         if error_inds is not None and self.error_map is None:
             raise ValueError("error_inds without a map: pass accelerate(..., error_map=) the tensor they index")
+        if self.ema is not None and self.ema.swapped_in:
+            raise RuntimeError("the EMA is swapped in (trainer.ema.copy_to() without restore()): the parameters are the average, not the weights being "
+                               "trained; call trainer.ema.restore() before the next step")
         self._ensure_buffers(rays_o.shape[1])
         if self._lr_sched is not None:
             self._lr_sched.check(k)
@@ -471,10 +492,13 @@ def parse_criterion(criterion):
     raise ValueError(f"{accepted}; got {criterion!r}")
 
 
-def _refuse_options(lr_scheduler, pipeline_adam):
+def _refuse_options(lr_scheduler, pipeline_adam, ema_decay=None):
     """What neither trainer does is refused at construction, before the renderer is looked at: the removed pipeline_adam (the keyword stays so
-    that callers passing 0 keep working), and a learning-rate schedule where the rate cannot be read from the device schedule -- never run at
-    a constant rate instead."""
+    that callers passing 0 keep working), an ema_decay that is not a float in (0, 1), and a learning-rate schedule where the rate cannot be
+    read from the device schedule -- never run at a constant rate instead."""
+    from .ema import check_decay
+
+    check_decay(ema_decay)
     if pipeline_adam:
         raise ValueError(f"pipeline_adam={pipeline_adam!r}: pipelined Adam was removed (built, bit-identical, measured slower, and GradScaler could no "
                          "longer skip a whole step: DESIGN_HISTORY.md, VERDICT r4 item 2 row; profiles/r05_pipeline_adam.json); pass 0 or leave it out")
@@ -511,10 +535,10 @@ class CurvedTrainer(AcceleratedTrainer):
     def __init__(self, renderer, regular_weight=1e-8, rays_per_batch=None, lr=1e-2, betas=(0.9, 0.99), eps=1e-15, dt_gamma=1 / 128, bg_color=1,
                  perturb=True, max_steps=1024, amp_dtype=torch.float16, graph=True, steps_per_call=1, march_across_ring_end=False, pipeline_adam=0,
                  skip_dead_samples=None, fused_table_update=None, fused_composite_step=None, lr_scheduler=None, total_steps=None, criterion=None,
-                 error_map=None):
+                 error_map=None, ema_decay=None):
         from .curved import CurvedField
 
-        _refuse_options(lr_scheduler, pipeline_adam)
+        _refuse_options(lr_scheduler, pipeline_adam, ema_decay)
         self._init_criterion(criterion, error_map)
 
         field = renderer.field
@@ -548,6 +572,7 @@ class CurvedTrainer(AcceleratedTrainer):
         self._other_params = [p for p in field.parameters() if id(p) not in keep]
         self.reg_loss = torch.zeros((), dtype=torch.float32, device=self.dev)
         self._attach_schedule(lr_scheduler, total_steps)  # (the optimizer's learning rates become fp32 tensors the schedule writes)
+        self._attach_ema(ema_decay)
 
     def _ring_start(self):
         self.ring_levels = draw_ring_levels(self.field.encoder.num_levels)
@@ -571,6 +596,8 @@ class CurvedTrainer(AcceleratedTrainer):
         self.scaler.step(self.opt)
         self.scaler.update()
         self.loss.copy_(loss.detach().reshape(()) + self.reg_loss)
+        if self.ema is not None:
+            self.ema.update()
 
 
 def accelerate(renderer, **kw):
@@ -580,7 +607,9 @@ def accelerate(renderer, **kw):
     of training steps its device table covers: every step, replayed or eager, trains at the rate LambdaLR gives it; `trainer.lr_scheduler`),
     criterion ("mse" -- the default --, "l1", ("huber", delta), or the reference Trainer's MSELoss / L1Loss / HuberLoss object: `parse_criterion`)
     and error_map (a contiguous fp32 device tensor updated in place as 0.1 * old + 0.9 * ray loss at the cells `step(..., error_inds=)` names; the
-    map is written by every step, skipped by the loss scaler or not; `trainer.ray_loss` is the last step's per-ray loss).
+    map is written by every step, skipped by the loss scaler or not; `trainer.ray_loss` is the last step's per-ray loss),
+    ema_decay (a float in (0, 1), the reference Trainer's 0.95: `trainer.ema` is an ema.DeviceEMA -- torch_ema's interface -- whose update is the
+    last launch of every step, applied or skipped; None, the default: no average).
     A renderer over a curved.CurvedField gets a CurvedTrainer (its docstring; regular_weight, default 1e-8)."""
     from .curved import CurvedField
 

@@ -18,9 +18,11 @@ def model_state(renderer):
     return out
 
 
-def save_checkpoint(path, renderer, epoch=0, global_step=0, stats=None, optimizer=None, scaler=None, lr_scheduler=None):
+def save_checkpoint(path, renderer, epoch=0, global_step=0, stats=None, optimizer=None, scaler=None, lr_scheduler=None, ema=None):
     """Write what Trainer.save_checkpoint(full=optimizer is not None) writes (nerf/utils.py:1485-1523).  lr_scheduler: the reference's
-    'lr_scheduler' entry, LambdaLR.state_dict() (a trainer's `trainer.lr_scheduler` is kept current on the host: nothing is read back)."""
+    'lr_scheduler' entry, LambdaLR.state_dict() (a trainer's `trainer.lr_scheduler` is kept current on the host: nothing is read back).
+    ema: the reference's 'ema' entry (nerf/utils.py:1504-1505), `trainer.ema.state_dict()` of an accelerate(..., ema_decay=) trainer.  The
+    reference's "best" checkpoint holds the averaged weights as the model: `with trainer.ema.average_parameters(): save_checkpoint(...)`."""
     state = {"epoch": epoch, "global_step": global_step, "stats": stats or {"loss": [], "valid_loss": [], "results": [], "checkpoints": [], "best_result": None},
              # plain Python numbers, as nerf/utils.py:1496-1497 stores them (the device-side occupancy update keeps mean_density as a view of
              # a buffer every later update overwrites: never pickle that)
@@ -31,6 +33,8 @@ def save_checkpoint(path, renderer, epoch=0, global_step=0, stats=None, optimize
         state["scaler"] = scaler.state_dict()
     if lr_scheduler is not None:
         state["lr_scheduler"] = lr_scheduler.state_dict()
+    if ema is not None:
+        state["ema"] = ema.state_dict()
     torch.save(state, path)
     return state
 
@@ -57,12 +61,13 @@ def load_model_state(renderer, model_sd, strict=True):
     return missing, unexpected
 
 
-def load_checkpoint(path, renderer, optimizer=None, scaler=None, model_only=False, map_location=None, lr_scheduler=None):
+def load_checkpoint(path, renderer, optimizer=None, scaler=None, model_only=False, map_location=None, lr_scheduler=None, ema=None):
     """Trainer.load_checkpoint (nerf/utils.py:1537-1602): model (non-strict, like the reference), mean_count / mean_density, then -- unless
     model_only -- optimizer, scaler and lr_scheduler state.  The scheduler of an accelerate(..., lr_scheduler=) trainer gets its last_epoch
     into the device step counter and the host mirror (a reference checkpoint is accepted when its base_lrs, one per reference param group,
     all equal this optimizer's); any other scheduler its own load_state_dict.  Returns the checkpoint dict (epoch, global_step, stats are
-    the caller's)."""
+    the caller's).  ema: a trainer's `trainer.ema`; the checkpoint's 'ema' entry, when it has one, is loaded into it in place
+    (nerf/utils.py:1567-1568)."""
     ckpt = torch.load(path, map_location=map_location, weights_only=False)
     if "model" not in ckpt:
         load_model_state(renderer, ckpt, strict=True)
@@ -87,4 +92,6 @@ def load_checkpoint(path, renderer, optimizer=None, scaler=None, model_only=Fals
 
         dev = device_schedule_of(lr_scheduler)
         (dev or lr_scheduler).load_state_dict(ckpt["lr_scheduler"])
+    if ema is not None and "ema" in ckpt:
+        ema.load_state_dict(ckpt["ema"])
     return ckpt
