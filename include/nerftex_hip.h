@@ -726,6 +726,63 @@ int nerftex_curved_mid_forward(const void* h, const float* normal, const float* 
                                void* stream);
 int nerftex_curved_out_forward(const void* hc, uint32_t row_stride, const void* sigma_raw, const uint8_t* mask, uint32_t B, void* sigma, void* color,
                                void* stream);
+/* -------------------------------------------------------------------------
+ * Extension: the curved field's whole no-grad forward as ONE call in the device-count form of nerftex_grid_encode_forward_rows /
+ * nerftex_field_forward_rows, so that a renderer's inference iteration over a CurvedField can sit in a recorded HIP graph:
+ *   neighbour search -> projector (writes FreqEncoder(height) as 16-bit values straight into the sigma net's input) -> hash-grid gather ->
+ *   sigma net 48 -> 32 -> 16 -> trunc_exp / reflected view direction / SH -> colour net 32 -> 64 -> 64 -> 3 -> sigmoid + height mask,
+ * eight launches enqueued on `stream`; nothing is allocated, the host never waits, the call can be captured.
+ *   live = min(B, units_dev[0] * rows_per_unit)  (rows_per_unit a plain number or NERFTEX_ROWS_AUTO(N, F); units_dev NULL: live = B),
+ *   read by every kernel of the chain from the same device word.
+ *   rows >= live                      no work; sigma / rgbs keep what they held.
+ *   live rows the march marked unused (dirs[row][0] > 1e29, nerftex_march_rays_dev): no search, no traversal, no table read;
+ *                                     sigma = 0, rgbs = 0.
+ *   every other live row              bit for bit what nerftex_knn_query, nerftex_curved_project, nerftex_grid_encode_forward_affine,
+ *                                     nerftex_curved_pack_inputs, nerftex_ffmlp_inference, nerftex_curved_mid_forward, nerftex_ffmlp_inference
+ *                                     and nerftex_curved_out_forward give one after the other, widened to fp32.
+ * NERFTEX_ERR_INVALID with a message, before anything is launched: a NULL descriptor or a NULL handle / buffer, B % 128 != 0, K outside
+ * 1..16 (or above the number of mesh vertices), n_verts outside 1..2^31-1, anything but the default curved field's shapes (n_freqs 12; table 3-D, 2 features x 8 levels,
+ * fp16; sigma net 48 / 32 / 2 layers / 16; colour net 32 / 64 / 3 layers / 3), scratch smaller than nerftex_curved_field_infer_scratch_bytes(B).
+ * B == 0: NERFTEX_OK, nothing launched.
+ * ------------------------------------------------------------------------- */
+typedef struct nerftex_curved_infer_desc {
+    const nerftex_knn* knn;            /* the mesh vertices' neighbour grid (nerftex_knn_create)                                  */
+    const nerftex_raytracer* tracer;   /* the mesh's BVH (nerftex_create_raytracer)                                               */
+    const float* xyz;                  /* [B,3] sample positions                                                                  */
+    const float* dirs;                 /* [B,3] view directions; dirs[row][0] > 1e29 marks an unused slot                         */
+    uint32_t B;
+    uint32_t n_verts;
+    const float* mesh_vertices;        /* [n_verts,3]                                                                             */
+    const float* vertex_normals;       /* [n_verts,3]                                                                             */
+    const float* tbn;                  /* [F,9] per-face frames: carried for the fine-normal net, not read by the static light model */
+    uint32_t K;                        /* neighbours per point                                                                    */
+    uint32_t n_freqs;                  /* FreqEncoder(height) bands (multires)                                                    */
+    float dir_vec_wdist;               /* weight distance of the mean direction among the normal candidates (tools/map.py:473-481) */
+    float h_threshold;                 /* |height| below min(9.5, h_threshold) sets the mask                                      */
+    const void* table;                 /* fp16 hash table [rows, C]                                                               */
+    const int32_t* offsets;            /* [L + 1] level offsets (device)                                                          */
+    uint32_t D, C, L;                  /* the gather's constants, as nerftex_grid_encode_forward_rows takes them                  */
+    float S;
+    uint32_t H;
+    uint32_t gridtype;
+    int align_corners;
+    float in_add, in_mul;              /* the gather reads (p_sur + in_add) * in_mul                                              */
+    const void* sigma_weights;         /* fp16, 16-byte aligned                                                                   */
+    uint32_t sigma_in, sigma_hidden, sigma_layers, sigma_out;
+    const void* color_weights;         /* fp16, 16-byte aligned                                                                   */
+    uint32_t color_in, color_hidden, color_layers, color_out;
+    float fc_weight;
+    int eval;                          /* the eval bits of nerftex_curved_mid_forward                                             */
+    float* sigma;                      /* [B] fp32                                                                                */
+    float* rgbs;                       /* [B,3] fp32                                                                              */
+    const int32_t* units_dev;
+    uint32_t rows_per_unit;
+    void* scratch;                     /* caller-owned, 256-byte aligned, >= nerftex_curved_field_infer_scratch_bytes(B) bytes    */
+    size_t scratch_bytes;
+} nerftex_curved_infer_desc;
+size_t nerftex_curved_field_infer_scratch_bytes(uint32_t B);
+int nerftex_curved_field_infer(const nerftex_curved_infer_desc* d, void* stream);
+
 /* grad_hc [B,16] fp16 = sigmoid backward of the fp16-narrowed grad_rgbs, columns 3..15 zero                      */
 int nerftex_field_out_backward(const float* grad_rgbs, const float* rgbs, uint32_t B, void* grad_hc, void* stream);
 

@@ -110,5 +110,13 @@ __host__ __device__ __forceinline__ uint32_t unit_rows(uint32_t code, uint32_t c
     const uint32_t q = F * N / (count ? count : 1u);
     return q < F ? F : (q > 8u * F ? 8u * F : q);
 }
+// the rows of a B-row launch that carry anything: min(B, units_dev[0] * rows per unit); units_dev == NULL = all of them
+__device__ __forceinline__ uint32_t live_rows(uint32_t B, const int32_t* __restrict__ units_dev, uint32_t rows_per_unit) {
+    if (!units_dev) return B;
+    const uint32_t n = (uint32_t)units_dev[0];
+    return min(B, n * unit_rows(rows_per_unit, n));
+}
+// the mark nerftex_march_rays_dev leaves in the sample slots a ray does not use (1e30 as the direction's first component)
+__device__ __forceinline__ bool slot_unused(const float* __restrict__ dirs, size_t row) { return dirs[row * 3] > 1e29f; }
 
 }  // namespace nerftex

@@ -27,6 +27,7 @@
 // STREAM forms), as the reference's threadblock_layer reads each layer from global memory (ffmlp.cu:47-129).
 #include <cstring>
 #include "common.hpp"
+#include "curved_infer.hpp"
 #include "step_trailer.hpp"
 #include "sh_common.hpp"  // the SH basis of the fused field kernel (switches fp contraction off for what follows ...)
 #include "workspace.hpp"
@@ -49,6 +50,19 @@ __device__ __forceinline__ float4_t mfma16(const elem8_t& a, const elem8_t& b, c
 #include "ffmlp_body.inc"
 }  // namespace
 }  // namespace ffmlp_f16
+
+int ffmlp_inference_rows(const void* inputs, const void* weights, uint32_t B, uint32_t IN, uint32_t H, uint32_t NL, void* outputs,
+                         const int32_t* units_dev, uint32_t rows_per_unit, hipStream_t st) {
+    if (B % ffmlp_f16::kRowsPerBlock != 0 || reinterpret_cast<uintptr_t>(weights) & 15) {
+        set_error("curved_field_infer: the batch must be a multiple of %d rows and the weight vectors 16-byte aligned", ffmlp_f16::kRowsPerBlock);
+        return NERFTEX_ERR_INVALID;
+    }
+    if (B == 0) return NERFTEX_OK;
+    if (IN == 48 && H == 32 && NL == 2) return ffmlp_f16::launch_inference_rows<32>(inputs, weights, B, IN, NL, outputs, units_dev, rows_per_unit, st);
+    if (IN == 32 && H == 64 && NL == 3) return ffmlp_f16::launch_inference_rows<64>(inputs, weights, B, IN, NL, outputs, units_dev, rows_per_unit, st);
+    set_error("curved_field_infer: no rows form of the FFMLP inference kernel for %u -> %u x %u", IN, H, NL);
+    return NERFTEX_ERR_INVALID;
+}
 
 }  // namespace nerftex
 

@@ -132,13 +132,23 @@ __device__ __forceinline__ void store4(elem_t* p, const float4_t& v) {
 // network are 0.3-1 MB: L2-resident) between two barriers -- what the reference's threadblock_layer does for every width (ffmlp.cu:47-129 reads
 // the layer's weights from global inside the block loop).  The four waves of a workgroup run the same number of row steps (B % 128 == 0), so the
 // barriers inside the row loop are uniform.
-template <int HIDDEN, bool INFERENCE, bool STAGED, int ACT, int OUT_ACT, bool STREAM = false>  // STAGED: forward_buffer rows leave through an LDS patch; ACT: see act_fwd
+// ROWS (nerftex_curved_field_infer): only the first units_dev[0] * rows_per_unit rows carry anything (a launch sized by an upper bound of a count
+// that lives on the device).  A workgroup whose 128 rows all lie past them exits before it stages a weight; one that holds the last live row runs
+// its whole 128-row step -- rows are independent through the MFMA chain (a batch row is one column of every B operand), so what the rows behind
+// the live ones compute from stale scratch touches no live row, and the loop stays uniform across the workgroup's four waves.
+template <int HIDDEN, bool INFERENCE, bool STAGED, int ACT, int OUT_ACT, bool STREAM = false, bool ROWS = false>  // STAGED: forward_buffer rows leave through an LDS patch; ACT: see act_fwd
 __global__ __launch_bounds__(kBlockThreads) void ffmlp_forward_kernel(const elem_t* __restrict__ X, const elem_t* __restrict__ W,
                                                                       elem_t* __restrict__ fwd, elem_t* __restrict__ out, uint32_t B,
-                                                                      uint32_t IN, uint32_t NL, uint32_t act, uint32_t out_act) {
+                                                                      uint32_t IN, uint32_t NL, uint32_t act, uint32_t out_act,
+                                                                      const int32_t* __restrict__ units_dev, uint32_t rows_per_unit) {
     constexpr int OT = HIDDEN / 16;         // result tiles per hidden layer
     constexpr int KSH = (HIDDEN + 31) / 32;  // 32-deep steps over a hidden layer
     constexpr int NT = kTilesPerWave;
+    uint32_t live = B;
+    if constexpr (ROWS) {
+        live = live_rows(B, units_dev, rows_per_unit);
+        if (blockIdx.x * kRowsPerBlock >= live) return;  // (the persistent grid walks upwards from here: nothing below `live` is left to this workgroup)
+    }
     extern __shared__ __attribute__((aligned(16))) char smem[];
     elem8_t* frags = reinterpret_cast<elem8_t*>(smem);
 
@@ -178,7 +188,8 @@ __global__ __launch_bounds__(kBlockThreads) void ffmlp_forward_kernel(const elem
     constexpr int kRowPitch = HIDDEN + 8;  // halfs; +16 B keeps ds_read_b128 alignment and staggers the banks
     elem_t* patch = reinterpret_cast<elem_t*>(smem + patch_offset) + (size_t)wave * 16 * NT * kRowPitch;
 
-    for (uint32_t row0 = blockIdx.x * kRowsPerBlock + wave * 16 * NT; row0 < B; row0 += gridDim.x * kRowsPerBlock) {
+    // (ROWS: the bound is tested on the workgroup's first row, B % 128 == 0 keeps every row of the step inside the buffers)
+    for (uint32_t row0 = blockIdx.x * kRowsPerBlock + wave * 16 * NT; ROWS ? row0 - wave * 16 * NT < live : row0 < B; row0 += gridDim.x * kRowsPerBlock) {
         float4_t acc[NT][OT];
 #pragma unroll
         for (int t = 0; t < NT; t++)
@@ -1382,9 +1393,27 @@ int launch_forward(const void* inputs, const void* weights, uint32_t B, uint32_t
     {
         KernelTimer kt(INF ? "ffmlp_inference_kernel" : "ffmlp_forward_kernel", st);
         hipLaunchKernelGGL(kernel, dim3(persistent_grid(B, lds)), dim3(kBlockThreads), lds, st, (const elem_t*)inputs, (const elem_t*)weights,
-                           (elem_t*)fwd, (elem_t*)outputs, B, IN, NL, act, out_act);
+                           (elem_t*)fwd, (elem_t*)outputs, B, IN, NL, act, out_act, (const int32_t*)nullptr, 0u);
     }
     return check_launch(INF ? "ffmlp_inference" : "ffmlp_forward");
+}
+
+// the inference kernel in its rows form, with the template arguments launch_forward<H, true> picks for a ReLU network without an output
+// activation: the same instructions per row
+template <int H>
+int launch_inference_rows(const void* inputs, const void* weights, uint32_t B, uint32_t IN, uint32_t NL, void* outputs, const int32_t* units_dev,
+                          uint32_t rows_per_unit, hipStream_t st) {
+    const size_t lds = lds_bytes_forward(H, IN, NL, false);
+    int rc = lds_check(lds);
+    if (rc != NERFTEX_OK) return rc;
+    auto kernel = ffmlp_forward_kernel<H, true, false, H == 64 ? (int)kRelu : -1, H == 64 ? (int)kNone : -1, false, true>;
+    if ((rc = set_lds(kernel, lds)) != NERFTEX_OK) return rc;
+    {
+        KernelTimer kt("ffmlp_inference_rows_kernel", st);
+        hipLaunchKernelGGL(kernel, dim3(persistent_grid(B, lds)), dim3(kBlockThreads), lds, st, (const elem_t*)inputs, (const elem_t*)weights, (elem_t*)nullptr,
+                           (elem_t*)outputs, B, IN, NL, (uint32_t)kRelu, (uint32_t)kNone, units_dev, rows_per_unit);
+    }
+    return check_launch("curved_field_infer(ffmlp)");
 }
 
 template <bool INF>

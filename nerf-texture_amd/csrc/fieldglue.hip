@@ -8,7 +8,10 @@
 // with the arithmetic of the framework ops reproduced step by step (same roundings: fp32 exp of the half logit; SH in fp32
 // narrowed to half; sigmoid in fp32 narrowed to half and widened again; gradients narrowed to half where autograd would).
 #include "common.hpp"
+#include "curved_infer.hpp"
 #include "sh_common.hpp"
+
+#include <cmath>
 
 namespace nerftex {
 namespace {
@@ -127,12 +130,9 @@ __global__ __launch_bounds__(256) void curved_pack_inputs_kernel(const half_t* _
 // h [B,16] half (the sigma net's output), normal [B,3] fp32 (MeshFeatureField's normalised coarse normal; eval bit 1: the projector's RAW normal), dirs [B,3] fp32
 //   -> sigma [B] half = half(exp(h[:,0]))  (trunc_exp forward, tools/activation.py:5-17, on a half tensor)
 //      cin [B,32] half = [SH4(2 ((wr + 1) / 2) - 1) | h[:,1:16] | 1],  wr = the view direction reflected about the normal (:283-306)
-__global__ __launch_bounds__(256) void curved_mid_forward_kernel(const half_t* __restrict__ h, const float* __restrict__ normal, const float* __restrict__ dirs,
-                                                                uint32_t B, const float fc, const int eval, half_t* __restrict__ sigma,
-                                                                half_t* __restrict__ cin) {
+__device__ __forceinline__ void curved_mid_row(const uint32_t b, const half_t* __restrict__ h, const float* __restrict__ normal, const float* __restrict__ dirs,
+                                               const float fc, const int eval, half_t* __restrict__ sigma, half_t* __restrict__ cin) {
 #pragma clang fp contract(off)  // every framework op rounds on its own
-    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
     const half8_t h0 = *reinterpret_cast<const half8_t*>(h + (size_t)b * 16);
     const half8_t h1 = *reinterpret_cast<const half8_t*>(h + (size_t)b * 16 + 8);
     sigma[b] = narrow(expf((float)h0[0]));
@@ -180,21 +180,99 @@ __global__ __launch_bounds__(256) void curved_mid_forward_kernel(const half_t* _
     out[0] = o0; out[1] = o1; out[2] = o2; out[3] = o3;
 }
 
+__global__ __launch_bounds__(256) void curved_mid_forward_kernel(const half_t* __restrict__ h, const float* __restrict__ normal, const float* __restrict__ dirs,
+                                                                uint32_t B, const float fc, const int eval, half_t* __restrict__ sigma,
+                                                                half_t* __restrict__ cin) {
+    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    curved_mid_row(b, h, normal, dirs, fc, eval, sigma, cin);
+}
+
 // hc: the colour net's output rows (3 of `stride` halfs used), sigma_raw [B] half, mask [B] bytes
 //   -> sigma [B] half = mask ? sigma_raw : 0,  color [B,3] half = mask ? half(sigmoid(hc)) : 0
+//   O: half, or float = the half values widened (what the framework's `.float()` on the half outputs gives)
+template <typename O>
+__device__ __forceinline__ void curved_out_row(const uint32_t b, const half_t* __restrict__ hc, uint32_t stride, const half_t* __restrict__ sigma_raw,
+                                               const uint8_t* __restrict__ mask, O* __restrict__ sigma, O* __restrict__ color) {
+    const bool m = mask[b] != 0;
+    sigma[b] = (O)(m ? sigma_raw[b] : (half_t)0.0f);
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        const float x = (float)hc[(size_t)b * stride + c];
+        color[(size_t)b * 3 + c] = (O)(m ? narrow(1.0f / (1.0f + expf(-x))) : (half_t)0.0f);
+    }
+}
+
 __global__ __launch_bounds__(256) void curved_out_forward_kernel(const half_t* __restrict__ hc, uint32_t stride, const half_t* __restrict__ sigma_raw,
                                                                 const uint8_t* __restrict__ mask, uint32_t B, half_t* __restrict__ sigma,
                                                                 half_t* __restrict__ color) {
     const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
-    const bool m = mask[b] != 0;
-    sigma[b] = m ? sigma_raw[b] : (half_t)0.0f;
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-        const float x = (float)hc[(size_t)b * stride + c];
-        color[(size_t)b * 3 + c] = m ? narrow(1.0f / (1.0f + expf(-x))) : (half_t)0.0f;
-    }
+    curved_out_row<half_t>(b, hc, stride, sigma_raw, mask, sigma, color);
 }
+
+// ---- the rows forms of nerftex_curved_field_infer: the same rows for the live, unmarked slots of an inference iteration --------------------------------
+
+// the gather's level-major features x_lbc [8, B, 2] half -> columns 0..15 of the sigma net's input xin [B,48] (columns 16..47 are the projector's)
+__global__ __launch_bounds__(256) void curved_pack_features_rows_kernel(const half_t* __restrict__ x_lbc, uint32_t B, half_t* __restrict__ xin,
+                                                                       const int32_t* __restrict__ units_dev, uint32_t rows_per_unit) {
+    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= live_rows(B, units_dev, rows_per_unit)) return;
+    typedef uint32_t u4 __attribute__((ext_vector_type(4)));
+    u4 w[2];
+#pragma unroll
+    for (int l = 0; l < 8; l++) w[l / 4][l % 4] = *reinterpret_cast<const uint32_t*>(x_lbc + ((size_t)l * B + b) * 2);
+    u4* dst = reinterpret_cast<u4*>(xin + (size_t)b * 48);
+    dst[0] = w[0]; dst[1] = w[1];
+}
+
+__global__ __launch_bounds__(256) void curved_mid_rows_kernel(const half_t* __restrict__ h, const float* __restrict__ normal, const float* __restrict__ dirs,
+                                                             uint32_t B, const float fc, const int eval, half_t* __restrict__ sigma, half_t* __restrict__ cin,
+                                                             const int32_t* __restrict__ units_dev, uint32_t rows_per_unit) {
+    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= live_rows(B, units_dev, rows_per_unit) || slot_unused(dirs, b)) return;  // (a marked row's cin stays what the scratch held: rows are independent)
+    curved_mid_row(b, h, normal, dirs, fc, eval, sigma, cin);
+}
+
+// ... and the chain's outputs as fp32: a marked row is exactly sigma = 0, rgb = 0 whatever the networks made of its stale inputs
+__global__ __launch_bounds__(256) void curved_out_rows_kernel(const half_t* __restrict__ hc, const half_t* __restrict__ sigma_raw, const uint8_t* __restrict__ mask,
+                                                             const float* __restrict__ dirs, uint32_t B, float* __restrict__ sigma, float* __restrict__ rgbs,
+                                                             const int32_t* __restrict__ units_dev, uint32_t rows_per_unit) {
+    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= live_rows(B, units_dev, rows_per_unit)) return;
+    if (slot_unused(dirs, b)) {
+        sigma[b] = 0.0f;
+#pragma unroll
+        for (int c = 0; c < 3; c++) rgbs[(size_t)b * 3 + c] = 0.0f;
+        return;
+    }
+    curved_out_row<float>(b, hc, 16, sigma_raw, mask, sigma, rgbs);
+}
+
+// the scratch of one nerftex_curved_field_infer call: every buffer starts on a 256-byte boundary
+struct CurvedScratch {
+    size_t idx, dist, p_sur, normal, mask, x_lbc, xin, h, sigma_raw, cin, hc, total;
+    explicit CurvedScratch(size_t B) {
+        size_t at = 0;
+        auto take = [&](size_t bytes_per_row) {
+            const size_t here = at;
+            at += (B * bytes_per_row + 255) / 256 * 256;
+            return here;
+        };
+        idx = take(16 * sizeof(int32_t));  // (sized for the largest K)
+        dist = take(16 * sizeof(float));
+        p_sur = take(3 * sizeof(float));
+        normal = take(3 * sizeof(float));
+        mask = take(1);
+        x_lbc = take(16 * sizeof(half_t));
+        xin = take(48 * sizeof(half_t));
+        h = take(16 * sizeof(half_t));
+        sigma_raw = take(sizeof(half_t));
+        cin = take(32 * sizeof(half_t));
+        hc = take(16 * sizeof(half_t));
+        total = at;
+    }
+};
 
 }  // namespace
 }  // namespace nerftex
@@ -240,6 +318,91 @@ extern "C" int nerftex_curved_out_forward(const void* hc, uint32_t row_stride, c
                            static_cast<const half_t*>(sigma_raw), mask, B, static_cast<half_t*>(sigma), static_cast<half_t*>(color));
     }
     return check_launch("curved_out_forward");
+}
+
+extern "C" size_t nerftex_curved_field_infer_scratch_bytes(uint32_t B) { return CurvedScratch(B).total; }
+
+extern "C" int nerftex_curved_field_infer(const nerftex_curved_infer_desc* d, void* stream) {
+    clear_error();
+    if (!d) {
+        set_error("curved_field_infer: NULL descriptor");
+        return NERFTEX_ERR_INVALID;
+    }
+    if (d->B % 128 != 0) {
+        set_error("curved_field_infer: the batch must be a multiple of 128 rows, but got %u", d->B);
+        return NERFTEX_ERR_INVALID;
+    }
+    if (d->B != 0 && (d->n_verts == 0 || d->n_verts > 0x7fffffffu)) {
+        set_error("curved_field_infer: the mesh needs between 1 and 2^31 - 1 vertices, but got %u", d->n_verts);
+        return NERFTEX_ERR_INVALID;
+    }
+    if (d->K == 0 || d->K > 16) {
+        set_error("curved_field_infer: 1 <= K <= 16 neighbours per point, but got %u", d->K);
+        return NERFTEX_ERR_INVALID;
+    }
+    if (d->n_freqs != 12 || d->D != 3 || d->C != 2 || d->L != 8 || d->sigma_in != 48 || d->sigma_hidden != 32 || d->sigma_layers != 2 || d->sigma_out != 16 ||
+        d->color_in != 32 || d->color_hidden != 64 || d->color_layers != 3 || d->color_out != 3) {
+        set_error("curved_field_infer: the kernels serve the default curved field only (12 height bands, a 3-D table of 8 levels x 2 features, "
+                  "sigma net 48 -> 32 x 2 -> 16, colour net 32 -> 64 x 3 -> 3)");
+        return NERFTEX_ERR_INVALID;
+    }
+    if (d->B == 0) return NERFTEX_OK;
+    const CurvedScratch at(d->B);
+    if (!d->knn || !d->tracer || !d->xyz || !d->dirs || !d->mesh_vertices || !d->vertex_normals || !d->table || !d->offsets || !d->sigma_weights ||
+        !d->color_weights || !d->sigma || !d->rgbs || !d->scratch || (reinterpret_cast<uintptr_t>(d->scratch) & 255) || d->scratch_bytes < at.total) {
+        set_error("curved_field_infer: handles, inputs, table, weights and outputs must not be NULL, and scratch must be 256-byte aligned and hold %zu bytes",
+                  at.total);
+        return NERFTEX_ERR_INVALID;
+    }
+    if (((reinterpret_cast<uintptr_t>(d->sigma_weights) | reinterpret_cast<uintptr_t>(d->color_weights)) & 15) || !(d->in_mul > 0.0f) || !std::isfinite(d->in_mul)) {
+        set_error("curved_field_infer: the weight vectors must be 16-byte aligned and the gather's input scale positive and finite");
+        return NERFTEX_ERR_INVALID;
+    }
+    hipStream_t st = as_stream(stream);
+    char* sc = static_cast<char*>(d->scratch);
+    int32_t* idx = reinterpret_cast<int32_t*>(sc + at.idx);
+    float* dist = reinterpret_cast<float*>(sc + at.dist);
+    float* p_sur = reinterpret_cast<float*>(sc + at.p_sur);
+    float* normal = reinterpret_cast<float*>(sc + at.normal);
+    uint8_t* mask = reinterpret_cast<uint8_t*>(sc + at.mask);
+    half_t* x_lbc = reinterpret_cast<half_t*>(sc + at.x_lbc);
+    half_t* xin = reinterpret_cast<half_t*>(sc + at.xin);
+    half_t* h = reinterpret_cast<half_t*>(sc + at.h);
+    half_t* sigma_raw = reinterpret_cast<half_t*>(sc + at.sigma_raw);
+    half_t* cin = reinterpret_cast<half_t*>(sc + at.cin);
+    half_t* hc = reinterpret_cast<half_t*>(sc + at.hc);
+    const uint32_t B = d->B, rpu = d->rows_per_unit;
+    const int32_t* units = d->units_dev;
+    const dim3 grid(div_up(B, 256u)), block(256);
+
+    int rc = knn_query_rows(d->knn, d->xyz, d->dirs, B, d->K, idx, dist, units, rpu, st);
+    if (rc != NERFTEX_OK) return rc;
+    rc = curved_project_rows(d->tracer, d->xyz, d->dirs, idx, dist, B, d->K, d->mesh_vertices, d->vertex_normals, d->n_verts, d->dir_vec_wdist, d->h_threshold,
+                             p_sur, mask, normal, xin, units, rpu, st);
+    if (rc != NERFTEX_OK) return rc;
+    // (an exported entry of this library: it clears the error text, which holds nothing at this point, and checks the gather's own arguments)
+    rc = nerftex_grid_encode_forward_rows(p_sur, d->table, d->offsets, x_lbc, B, d->D, d->C, d->L, d->S, d->H, d->gridtype, d->align_corners, NERFTEX_F16,
+                                          NERFTEX_LAYOUT_LBC, d->in_add, d->in_mul, units, rpu, stream);
+    if (rc != NERFTEX_OK) return rc;
+    {
+        KernelTimer kt("curved_pack_features_rows_kernel", st);
+        hipLaunchKernelGGL(curved_pack_features_rows_kernel, grid, block, 0, st, x_lbc, B, xin, units, rpu);
+    }
+    if ((rc = check_launch("curved_field_infer(pack)")) != NERFTEX_OK) return rc;
+    rc = ffmlp_inference_rows(xin, d->sigma_weights, B, 48, 32, 2, h, units, rpu, st);
+    if (rc != NERFTEX_OK) return rc;
+    {
+        KernelTimer kt("curved_mid_rows_kernel", st);
+        hipLaunchKernelGGL(curved_mid_rows_kernel, grid, block, 0, st, h, normal, d->dirs, B, d->fc_weight, d->eval, sigma_raw, cin, units, rpu);
+    }
+    if ((rc = check_launch("curved_field_infer(mid)")) != NERFTEX_OK) return rc;
+    rc = ffmlp_inference_rows(cin, d->color_weights, B, 32, 64, 3, hc, units, rpu, st);
+    if (rc != NERFTEX_OK) return rc;
+    {
+        KernelTimer kt("curved_out_rows_kernel", st);
+        hipLaunchKernelGGL(curved_out_rows_kernel, grid, block, 0, st, hc, sigma_raw, mask, d->dirs, B, d->sigma, d->rgbs, units, rpu);
+    }
+    return check_launch("curved_field_infer(out)");
 }
 
 extern "C" int nerftex_field_mid_forward(const void* h, const float* dirs, uint32_t B, float* sigma, void* cin, void* stream) {

@@ -50,7 +50,7 @@ __global__ __launch_bounds__(256) void grid_forward_kernel(const float* __restri
                                                            const bool calc_grad_inputs, T* __restrict__ dy_dx,
                                                            const uint32_t gridtype, const bool align_corners) {
     const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
+    if (b >= live_rows(B, lc.units_dev, lc.rows_per_unit)) return;  // (the rows forms: a launch sized by an upper bound of a device-side count)
 
     float x[D];
     bool oob = false;

@@ -16,6 +16,7 @@
 //     the query to the nearest face of the block that still has cells behind it; stop once best[K-1] <= reach.
 //     Sample points sit within a few cell sizes of the surface, so the first block (nine contiguous row ranges) decides nearly all.
 #include "common.hpp"
+#include "curved_infer.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -81,11 +82,8 @@ __device__ __forceinline__ void scan_range(const P4* __restrict__ points, uint32
 // x fastest, so a ROW of the block (cells x0..x1 at one y, z) is ONE contiguous range: nine ranges for the first block instead of 27
 // cells.  A larger block adds whole rows on its new y / z faces and the two end cells of the rows it already covered.
 template <int K>
-__global__ __launch_bounds__(256) void knn_query_kernel(uint32_t N, const float* __restrict__ xyz, const GridDesc g, const uint32_t* __restrict__ cell_start,
-                                                        const P4* __restrict__ points, uint32_t k_out, int32_t* __restrict__ idx,
-                                                        float* __restrict__ dist) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= N) return;
+__device__ __forceinline__ void knn_query_point(const uint32_t i, const float* __restrict__ xyz, const GridDesc& g, const uint32_t* __restrict__ cell_start,
+                                                const P4* __restrict__ points, uint32_t k_out, int32_t* __restrict__ idx, float* __restrict__ dist) {
     const float q[3] = {xyz[3 * (size_t)i], xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2]};
     int c[3];
 #pragma unroll
@@ -148,6 +146,27 @@ __global__ __launch_bounds__(256) void knn_query_kernel(uint32_t N, const float*
             idx[(size_t)i * k_out + k] = ids[k];
             dist[(size_t)i * k_out + k] = sqrtf(best[k]);
         }
+}
+
+template <int K>
+__global__ __launch_bounds__(256) void knn_query_kernel(uint32_t N, const float* __restrict__ xyz, const GridDesc g, const uint32_t* __restrict__ cell_start,
+                                                        const P4* __restrict__ points, uint32_t k_out, int32_t* __restrict__ idx,
+                                                        float* __restrict__ dist) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N) return;
+    knn_query_point<K>(i, xyz, g, cell_start, points, k_out, idx, dist);
+}
+
+// the rows form (nerftex_curved_field_infer): the same search for the live rows that hold a sample; a slot the march marked unused would start
+// from a clamped corner cell and walk the grid for nothing -- its row of idx / dist is not written (the projector's rows form does not read it)
+template <int K>
+__global__ __launch_bounds__(256) void knn_query_rows_kernel(uint32_t N, const float* __restrict__ xyz, const float* __restrict__ dirs, const GridDesc g,
+                                                             const uint32_t* __restrict__ cell_start, const P4* __restrict__ points, uint32_t k_out,
+                                                             int32_t* __restrict__ idx, float* __restrict__ dist, const int32_t* __restrict__ units_dev,
+                                                             uint32_t rows_per_unit) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= live_rows(N, units_dev, rows_per_unit) || slot_unused(dirs, i)) return;
+    knn_query_point<K>(i, xyz, g, cell_start, points, k_out, idx, dist);
 }
 
 }  // namespace
@@ -228,6 +247,35 @@ extern "C" int nerftex_knn_destroy(nerftex_knn* kn) {
     return NERFTEX_OK;
 }
 
+static GridDesc grid_desc(const nerftex_knn* kn) {
+    GridDesc g;
+    for (int d = 0; d < 3; d++) { g.dims[d] = kn->dims[d]; g.lo[d] = kn->lo[d]; }
+    g.cell = kn->cell;
+    g.inv_cell = kn->inv_cell;
+    g.eps = kn->eps;
+    return g;
+}
+
+int nerftex::knn_query_rows(const nerftex_knn* kn, const float* xyz, const float* dirs, uint32_t N, uint32_t K, int32_t* idx, float* dist,
+                            const int32_t* units_dev, uint32_t rows_per_unit, hipStream_t st) {
+    if (!kn || K == 0 || K > (uint32_t)kMaxK || K > kn->n_points) {
+        set_error("curved_field_infer: need a neighbour grid and 1 <= K <= min(%d, number of mesh vertices)", kMaxK);
+        return NERFTEX_ERR_INVALID;
+    }
+    if (N == 0) return NERFTEX_OK;
+    const GridDesc g = grid_desc(kn);
+    const dim3 grid(div_up(N, 256u)), block(256);
+    const uint32_t* cs = static_cast<const uint32_t*>(kn->cell_start);
+    const P4* pts = static_cast<const P4*>(kn->points);
+    {
+        KernelTimer kt("knn_query_rows_kernel", st);
+        if (K <= 4) hipLaunchKernelGGL(knn_query_rows_kernel<4>, grid, block, 0, st, N, xyz, dirs, g, cs, pts, K, idx, dist, units_dev, rows_per_unit);
+        else if (K <= 8) hipLaunchKernelGGL(knn_query_rows_kernel<8>, grid, block, 0, st, N, xyz, dirs, g, cs, pts, K, idx, dist, units_dev, rows_per_unit);
+        else hipLaunchKernelGGL(knn_query_rows_kernel<16>, grid, block, 0, st, N, xyz, dirs, g, cs, pts, K, idx, dist, units_dev, rows_per_unit);
+    }
+    return check_launch("curved_field_infer(knn)");
+}
+
 extern "C" int nerftex_knn_query(const nerftex_knn* kn, const float* xyz, uint32_t N, uint32_t K, int32_t* idx, float* dist, void* stream) {
     clear_error();
     if (!kn || K == 0 || K > (uint32_t)kMaxK || K > kn->n_points) {
@@ -235,11 +283,7 @@ extern "C" int nerftex_knn_query(const nerftex_knn* kn, const float* xyz, uint32
         return NERFTEX_ERR_INVALID;
     }
     if (N == 0) return NERFTEX_OK;
-    GridDesc g;
-    for (int d = 0; d < 3; d++) { g.dims[d] = kn->dims[d]; g.lo[d] = kn->lo[d]; }
-    g.cell = kn->cell;
-    g.inv_cell = kn->inv_cell;
-    g.eps = kn->eps;
+    const GridDesc g = grid_desc(kn);
     const dim3 grid(div_up(N, 256u)), block(256);
     const uint32_t* cs = static_cast<const uint32_t*>(kn->cell_start);
     const P4* pts = static_cast<const P4*>(kn->points);

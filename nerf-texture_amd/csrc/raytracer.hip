@@ -13,6 +13,7 @@
 //     ~1 MiB of L2-resident nodes + triangles; one-wave workgroups spread small batches over the CUs.
 // Arithmetic follows oracle/src/orc_raytracer.c expression by expression (explicit fmaf, no other contraction).
 #include "common.hpp"
+#include "curved_infer.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -242,18 +243,19 @@ __global__ __launch_bounds__(64) void raytrace_kernel(uint32_t N, const float* r
 //   tools/encoding.py:5-43).  The reference runs this as ~35 framework launches + two trace launches and materialises every
 //   intermediate ([N,K,3] gathers, two full hit records); the neighbour search itself (frnn, un-vendored) stays outside.
 constexpr int kMaxK = 16;
-__global__ __launch_bounds__(64) void curved_project_kernel(uint32_t N, const float* __restrict__ xyz, const int32_t* __restrict__ knn_idx,
-                                                            const float* __restrict__ knn_dist, uint32_t K, const float* __restrict__ verts,
-                                                            const float* __restrict__ vnormals, int n_verts, float dir_vec_wdist, float h_limit,
-                                                            const Node* __restrict__ nodes, const Tri* __restrict__ tris,
-                                                            const float* __restrict__ tbn, uint32_t n_freqs, float* __restrict__ p_sur,
-                                                            float* __restrict__ sdf_out, uint8_t* __restrict__ h_mask, float* __restrict__ normal_out,
-                                                            int64_t* __restrict__ face_idx, float* __restrict__ tbn_out, float* __restrict__ z_embed) {
-    // TWO lanes per point, one per trace direction: the kernel is bound by the latency of its dependent node loads, and a batch of a few
-    // hundred thousand points with two traversals back to back per thread does not even fill the chip's wave slots once
-    const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t i = tid >> 1, side = tid & 1u;
-    if (i >= N) return;  // N odd: the partner of the last point's lane 0 exists (same i), nobody is left alone in a pair
+constexpr uint32_t kInferFreqs = 12;  // multires of the curved field: z_embed has 1 + 2 * 12 = 25 columns
+// One point of the projector, run by the TWO lanes of a pair (side 0: the trace along +normal, which also writes; side 1: along -normal) -- both
+// lanes must arrive here together: the traces meet in an __shfl_xor.
+// INFER (nerftex_curved_field_infer): no height, face or frame output, and FreqEncoder(height) leaves as the 16-bit values the sigma net reads --
+// z_embed is then the point's row of that net's [N,48] half input, columns 16..40 = half(z), 41..47 = the padding ones.
+template <bool INFER>
+__device__ __forceinline__ void curved_project_point(const uint32_t i, const uint32_t side, const float* __restrict__ xyz, const int32_t* __restrict__ knn_idx,
+                                                     const float* __restrict__ knn_dist, uint32_t K, const float* __restrict__ verts,
+                                                     const float* __restrict__ vnormals, int n_verts, float dir_vec_wdist, float h_limit,
+                                                     const Node* __restrict__ nodes, const Tri* __restrict__ tris, const float* __restrict__ tbn,
+                                                     uint32_t n_freqs, float* __restrict__ p_sur, float* __restrict__ sdf_out, uint8_t* __restrict__ h_mask,
+                                                     float* __restrict__ normal_out, int64_t* __restrict__ face_idx, float* __restrict__ tbn_out,
+                                                     void* __restrict__ z_embed) {
     const V3 x = load3(xyz + 3 * (size_t)i);
     // ---- knn(): weighted normal (both lanes of a pair: the same loads, served once)
     V3 mean_dir{0, 0, 0}, nsum{0, 0, 0}, acc{0, 0, 0};
@@ -306,9 +308,31 @@ __global__ __launch_bounds__(64) void curved_project_kernel(uint32_t N, const fl
     p_sur[3 * (size_t)i] = fmaf(d, dir.x, x.x);
     p_sur[3 * (size_t)i + 1] = fmaf(d, dir.y, x.y);
     p_sur[3 * (size_t)i + 2] = fmaf(d, dir.z, x.z);
-    sdf_out[i] = sdf;
     h_mask[i] = fabsf(sdf) < h_limit ? 1 : 0;
     normal_out[3 * (size_t)i] = nrm.x; normal_out[3 * (size_t)i + 1] = nrm.y; normal_out[3 * (size_t)i + 2] = nrm.z;
+    if constexpr (INFER) {
+        // the fp32 value the plain form stores is narrowed as nerftex_curved_pack_inputs narrows it after reading it back (the empty asm keeps
+        // the conversion from being folded into the operation that produces the value)
+        auto narrow = [](float v) {
+            asm volatile("" : "+v"(v));
+            return (half_t)v;
+        };
+        half8_t o[4];
+        o[0][0] = narrow(sdf);
+        float f = 1.0f;
+#pragma unroll
+        for (uint32_t k = 0; k < kInferFreqs; k++, f *= 2.0f) {
+            o[(1 + 2 * k) / 8][(1 + 2 * k) % 8] = narrow(sinf(sdf * f));
+            o[(2 + 2 * k) / 8][(2 + 2 * k) % 8] = narrow(cosf(sdf * f));
+        }
+#pragma unroll
+        for (int c = 1 + 2 * (int)kInferFreqs; c < 32; c++) o[c / 8][c % 8] = (half_t)1.0f;
+        half8_t* dst = reinterpret_cast<half8_t*>(static_cast<half_t*>(z_embed) + (size_t)i * 48 + 16);
+#pragma unroll
+        for (int q = 0; q < 4; q++) dst[q] = o[q];
+        return;
+    }
+    sdf_out[i] = sdf;
     const int64_t face = best >= 0 ? tris[best].id : -1;
     face_idx[i] = face;
     if (tbn_out) {
@@ -316,7 +340,7 @@ __global__ __launch_bounds__(64) void curved_project_kernel(uint32_t N, const fl
         for (int k = 0; k < 9; k++) tbn_out[9 * (size_t)i + k] = tbn[9 * (size_t)(face >= 0 ? face : (int64_t)0) + k];  // face -1 indexes the last row in torch; the mask covers it
     }
     if (z_embed) {  // FreqEncoder(input_dim=1, log sampling): [h, sin(h 2^0), cos(h 2^0), sin(h 2^1), ...]
-        float* z = z_embed + (size_t)i * (1 + 2 * n_freqs);
+        float* z = static_cast<float*>(z_embed) + (size_t)i * (1 + 2 * n_freqs);
         z[0] = sdf;
         float f = 1.0f;
         for (uint32_t k = 0; k < n_freqs; k++, f *= 2.0f) {
@@ -324,6 +348,55 @@ __global__ __launch_bounds__(64) void curved_project_kernel(uint32_t N, const fl
             z[2 + 2 * k] = cosf(sdf * f);
         }
     }
+}
+
+__global__ __launch_bounds__(64) void curved_project_kernel(uint32_t N, const float* __restrict__ xyz, const int32_t* __restrict__ knn_idx,
+                                                            const float* __restrict__ knn_dist, uint32_t K, const float* __restrict__ verts,
+                                                            const float* __restrict__ vnormals, int n_verts, float dir_vec_wdist, float h_limit,
+                                                            const Node* __restrict__ nodes, const Tri* __restrict__ tris,
+                                                            const float* __restrict__ tbn, uint32_t n_freqs, float* __restrict__ p_sur,
+                                                            float* __restrict__ sdf_out, uint8_t* __restrict__ h_mask, float* __restrict__ normal_out,
+                                                            int64_t* __restrict__ face_idx, float* __restrict__ tbn_out, float* __restrict__ z_embed) {
+    // TWO lanes per point, one per trace direction: the kernel is bound by the latency of its dependent node loads, and a batch of a few
+    // hundred thousand points with two traversals back to back per thread does not even fill the chip's wave slots once
+    const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t i = tid >> 1, side = tid & 1u;
+    if (i >= N) return;  // N odd: the partner of the last point's lane 0 exists (same i), nobody is left alone in a pair
+    curved_project_point<false>(i, side, xyz, knn_idx, knn_dist, K, verts, vnormals, n_verts, dir_vec_wdist, h_limit, nodes, tris, tbn, n_freqs, p_sur, sdf_out,
+                                h_mask, normal_out, face_idx, tbn_out, z_embed);
+}
+
+// the rows form (nerftex_curved_field_infer).  Both tests are on the point index i, which the two lanes of a pair share: a pair leaves, or answers a
+// marked slot, or walks the tree TOGETHER -- no lane reaches the __shfl_xor of the traces without its partner.
+__global__ __launch_bounds__(64) void curved_project_rows_kernel(uint32_t N, const float* __restrict__ xyz, const float* __restrict__ dirs,
+                                                                 const int32_t* __restrict__ knn_idx, const float* __restrict__ knn_dist, uint32_t K,
+                                                                 const float* __restrict__ verts, const float* __restrict__ vnormals, int n_verts,
+                                                                 float dir_vec_wdist, float h_limit, const Node* __restrict__ nodes, const Tri* __restrict__ tris,
+                                                                 float* __restrict__ p_sur, uint8_t* __restrict__ h_mask, float* __restrict__ normal_out,
+                                                                 half_t* __restrict__ xin, const int32_t* __restrict__ units_dev, uint32_t rows_per_unit) {
+    const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t i = tid >> 1, side = tid & 1u;
+    if (i >= live_rows(N, units_dev, rows_per_unit)) return;
+    if (slot_unused(dirs, i)) {  // no neighbour list to read, no tree to walk: the constants that make the rest of the chain answer zeros cheaply
+        if (side) return;
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            p_sur[3 * (size_t)i + c] = 1e30f;  // far outside the box: the gather writes zeros without touching the table
+            normal_out[3 * (size_t)i + c] = 0.0f;
+        }
+        h_mask[i] = 0;
+        half8_t z8, tail;
+#pragma unroll
+        for (int c = 0; c < 8; c++) {
+            z8[c] = (half_t)0.0f;
+            tail[c] = c == 0 ? (half_t)0.0f : (half_t)1.0f;  // column 40 is z's last, 41..47 the padding ones
+        }
+        half8_t* dst = reinterpret_cast<half8_t*>(xin + (size_t)i * 48 + 16);
+        dst[0] = z8; dst[1] = z8; dst[2] = z8; dst[3] = tail;
+        return;
+    }
+    curved_project_point<true>(i, side, xyz, knn_idx, knn_dist, K, verts, vnormals, n_verts, dir_vec_wdist, h_limit, nodes, tris, nullptr, kInferFreqs, p_sur,
+                               nullptr, h_mask, normal_out, nullptr, nullptr, xin);
 }
 
 // depth of the BVH-4 (root = 1)
@@ -414,6 +487,25 @@ extern "C" int nerftex_raytracer_trace(const nerftex_raytracer* rt, const float*
                            static_cast<const Node*>(rt->nodes), static_cast<const Tri*>(rt->triangles));
     }
     return check_launch("raytracer_trace");
+}
+
+int nerftex::curved_project_rows(const nerftex_raytracer* rt, const float* xyz, const float* dirs, const int32_t* knn_idx, const float* knn_dist, uint32_t N,
+                                 uint32_t K, const float* mesh_vertices, const float* vertex_normals, uint32_t n_verts, float dir_vec_wdist,
+                                 float h_threshold, float* p_sur, uint8_t* h_mask, float* normal, void* xin, const int32_t* units_dev,
+                                 uint32_t rows_per_unit, hipStream_t st) {
+    if (!rt || K == 0 || K > (uint32_t)kMaxK || n_verts == 0 || n_verts > 0x7fffffffu) {
+        set_error("curved_field_infer: need a raytracer, 1 <= K <= %d neighbours per point and a non-empty vertex array", kMaxK);
+        return NERFTEX_ERR_INVALID;
+    }
+    if (N == 0) return NERFTEX_OK;
+    const float h_limit = fminf(9.5f, h_threshold);  // depth_threshold of tools/map.py:407
+    {
+        KernelTimer kt("curved_project_rows_kernel", st);
+        hipLaunchKernelGGL(curved_project_rows_kernel, dim3(div_up(2 * N, 64u)), dim3(64), 0, st, N, xyz, dirs, knn_idx, knn_dist, K, mesh_vertices, vertex_normals,
+                           (int)n_verts, dir_vec_wdist, h_limit, static_cast<const Node*>(rt->nodes), static_cast<const Tri*>(rt->triangles), p_sur, h_mask, normal,
+                           static_cast<half_t*>(xin), units_dev, rows_per_unit);
+    }
+    return check_launch("curved_field_infer(project)");
 }
 
 extern "C" int nerftex_curved_project(const nerftex_raytracer* rt, const float* xyz, const int32_t* knn_idx, const float* knn_dist, uint32_t N, uint32_t K,

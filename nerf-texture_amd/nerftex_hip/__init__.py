@@ -46,6 +46,7 @@ _SIGNATURES = {
     "nerftex_curved_pack_inputs": [_vp, _vp, _u32, _vp, _vp],
     "nerftex_curved_mid_forward": [_vp, _vp, _vp, _u32, _f32, _i, _vp, _vp, _vp],
     "nerftex_curved_out_forward": [_vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp],
+    "nerftex_curved_field_infer": [_vp, _vp],
     "nerftex_field_mid_backward": [_vp, _vp, _vp, _u32, _vp, _vp],
     "nerftex_field_out_forward": [_vp, _u32, _vp, _vp],
     "nerftex_field_out_backward": [_vp, _vp, _u32, _vp, _vp],
@@ -185,7 +186,17 @@ class StepLossDesc(C.Structure):
                 ("take", _f32)]
 
 
-EXPORTS = ["nerftex_last_error", "nerftex_version", "nerftex_tune_get", "nerftex_workspace_slots_touched"] + list(_SIGNATURES)
+class CurvedInferDesc(C.Structure):
+    """nerftex_curved_infer_desc of include/nerftex_hip.h, field for field: the curved field's no-grad forward as one device-count call."""
+    _fields_ = [("knn", _vp), ("tracer", _vp), ("xyz", _vp), ("dirs", _vp), ("B", _u32), ("n_verts", _u32), ("mesh_vertices", _vp), ("vertex_normals", _vp),
+                ("tbn", _vp), ("K", _u32), ("n_freqs", _u32), ("dir_vec_wdist", _f32), ("h_threshold", _f32), ("table", _vp), ("offsets", _vp), ("D", _u32),
+                ("C", _u32), ("L", _u32), ("S", _f32), ("H", _u32), ("gridtype", _u32), ("align_corners", _i), ("in_add", _f32), ("in_mul", _f32),
+                ("sigma_weights", _vp), ("sigma_in", _u32), ("sigma_hidden", _u32), ("sigma_layers", _u32), ("sigma_out", _u32), ("color_weights", _vp),
+                ("color_in", _u32), ("color_hidden", _u32), ("color_layers", _u32), ("color_out", _u32), ("fc_weight", _f32), ("eval", _i), ("sigma", _vp),
+                ("rgbs", _vp), ("units_dev", _vp), ("rows_per_unit", _u32), ("scratch", _vp), ("scratch_bytes", _sz)]
+
+
+EXPORTS = ["nerftex_last_error", "nerftex_version", "nerftex_tune_get", "nerftex_workspace_slots_touched", "nerftex_curved_field_infer_scratch_bytes"] + list(_SIGNATURES)
 
 
 def _load():
@@ -201,6 +212,8 @@ def _load():
     lib.nerftex_tune_get.restype = C.c_long
     lib.nerftex_workspace_slots_touched.argtypes = []
     lib.nerftex_workspace_slots_touched.restype = C.c_uint
+    lib.nerftex_curved_field_infer_scratch_bytes.argtypes = [_u32]
+    lib.nerftex_curved_field_infer_scratch_bytes.restype = _sz
     for name, args in _SIGNATURES.items():
         fn = getattr(lib, name)  # AttributeError here == a symbol the header declares is not exported
         fn.argtypes = args

@@ -568,6 +568,89 @@ class CurvedField(torch.nn.Module):
         color = torch.sigmoid(h)
         return torch.where(h_mask, sigma, torch.zeros_like(sigma)), torch.where(h_mask.unsqueeze(-1), color, torch.zeros_like(color)), {}
 
+    def graph_stamp(self):
+        """What a recorded graph of `infer` bakes in besides the parameters (Renderer.render_infer_graphed adds it to its stamp): the neighbour
+        grid's and the tracer's handles, the mesh buffers' storage, the projector's and the field's scalars, train / eval, the fused switch."""
+        p = self.projector
+        return (p._knn.value, p.tracer._handle.value, p.mesh_vertices.data_ptr(), p.vertex_normals.data_ptr(), p.tbn.data_ptr(), int(p.K),
+                p._height_limit(...), float(self.fc_weight), float(self.bound), bool(self.training), bool(getattr(self, "fused_glue", True)))
+
+    def _infer_fused(self, x, d):
+        """Whether nerftex_curved_field_infer serves this call: _glue_fused(), the shapes the entry's kernels are built for (it refuses every
+        other one), an fp16 table, and what the entry asks of its buffers.  Everything else goes through forward()."""
+        B = x.shape[0]
+        enc, s, c = self.encoder, self.sigma_net, self.color_net
+        return (self._glue_fused() and B % 128 == 0 and B > 0 and x.dtype == torch.float32 and d.dtype == torch.float32 and x.is_contiguous()
+                and d.is_contiguous() and s.dtype == torch.float16 and c.dtype == torch.float16
+                and (s.input_dim, s.hidden_dim, s.num_layers, s.padded_output_dim) == (48, 32, 2, 16)
+                and (c.input_dim, c.hidden_dim, c.num_layers, c.output_dim) == (32, 64, 3, 3)
+                and (enc.input_dim, enc.level_dim, enc.num_levels, self.multires) == (3, 2, 8, 12) and 1 <= self.projector.K <= 16
+                and enc._table().dtype == torch.float16)
+
+    def _infer_desc(self, x, d, live, sigma, rgbs, scratch):
+        """The nerftex_curved_infer_desc of one call (and the tensors it points into, to be kept until the call is enqueued).  The 16-bit table
+        and weights are kept between calls and re-made when a parameter changes, as GridEncoder._table() and fused.ngp_field_infer keep theirs."""
+        from gridencoder.grid import register_offsets
+        from nerftex_hip import CurvedInferDesc, ptr
+
+        enc, p, s, c = self.encoder, self.projector, self.sigma_net, self.color_net
+        table = enc._table()
+        ws, wc = s._weights(), c._weights()
+        stamp = (ws._version, ws.data_ptr(), wc._version, wc.data_ptr())
+        cache = getattr(self, "_infer_cache", None)
+        if cache is None or cache[0] != stamp:
+            register_offsets(enc.offsets, enc.num_levels)
+            cache = self._infer_cache = (stamp, ws.detach().to(torch.float16), wc.detach().to(torch.float16))
+        _, ws_h, wc_h = cache
+        units, rows_per_unit = (ptr(live[0]), int(live[1])) if live is not None else (None, 0)
+        desc = CurvedInferDesc(
+            knn=p._knn.value, tracer=p.tracer._handle.value, xyz=ptr(x), dirs=ptr(d), B=x.shape[0], n_verts=p.mesh_vertices.shape[0],
+            mesh_vertices=ptr(p.mesh_vertices), vertex_normals=ptr(p.vertex_normals), tbn=ptr(p.tbn), K=int(p.K), n_freqs=int(self.multires),
+            dir_vec_wdist=0.05, h_threshold=p._height_limit(...), table=ptr(table), offsets=ptr(enc.offsets), D=int(enc.input_dim), C=int(enc.level_dim),
+            L=int(enc.num_levels), S=float(np.log2(enc.per_level_scale)), H=int(enc.base_resolution), gridtype=int(enc.gridtype_id),
+            align_corners=int(bool(enc.align_corners)), in_add=float(self.bound), in_mul=float(np.float32(1.0) / np.float32(2 * self.bound)),
+            sigma_weights=ptr(ws_h), sigma_in=s.input_dim, sigma_hidden=s.hidden_dim, sigma_layers=s.num_layers, sigma_out=s.padded_output_dim,
+            color_weights=ptr(wc_h), color_in=c.input_dim, color_hidden=c.hidden_dim, color_layers=c.num_layers, color_out=c.output_dim,
+            fc_weight=float(self.fc_weight), eval=2 | int(not self.training), sigma=ptr(sigma), rgbs=ptr(rgbs), units_dev=units,
+            rows_per_unit=rows_per_unit, scratch=ptr(scratch), scratch_bytes=scratch.numel())
+        return desc, (table, ws_h, wc_h)
+
+    @torch.no_grad()
+    def infer(self, x, d, live=None):
+        """(sigma fp32 [B], rgbs fp32 [B,3]) of forward(x, d) without an autograd node: the whole chain as ONE library call
+        (nerftex_curved_field_infer) in the device-count form a renderer's inference iteration needs -- live = (int32 device tensor, rows per
+        unit or NERFTEX_ROWS_AUTO code): rows past live[0][0] * rows per unit are not touched, the slots the march marked unused (direction 1e30)
+        cost no neighbour search, no traversal and no table read and come out as exactly 0; every other row holds forward()'s values, bit for
+        bit.  The scratch is one buffer per stream, grown to the largest batch seen (under a graph capture: the graph's pool keeps it).
+        Where the fused chain does not apply (no fp16 autocast, prob_model, other shapes, fused_glue = False, a batch that is no multiple of
+        128) this is forward(x, d) on all rows, cast to fp32: slower, the same image."""
+        if not self._infer_fused(x, d):
+            sigma, rgbs, _ = self.forward(x, d)
+            return sigma.float(), rgbs.float()
+        import ctypes
+
+        from nerftex_hip import check, lib, stream
+
+        B, st = x.shape[0], stream()
+        nbytes = lib.nerftex_curved_field_infer_scratch_bytes(B)
+        if torch.cuda.is_current_stream_capturing():
+            scratch = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+        else:
+            # one buffer per stream (the ray ranges of a pipelined frame run side by side), grown to the largest batch seen: the loop's batch
+            # size changes with nearly every iteration.  A buffer that is replaced goes back to the allocator, which hands it out again only
+            # behind the work this stream still has queued on it
+            held = getattr(self, "_infer_scratch", None)
+            if held is None:
+                held = self._infer_scratch = {}
+            scratch = held.get((x.device, st))
+            if scratch is None or scratch.numel() < nbytes:
+                scratch = held[(x.device, st)] = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+        out = torch.empty(4 * B, dtype=torch.float32, device=x.device)  # [sigma | rgb] in one allocation
+        sigma, rgbs = out[:B], out[B:].view(B, 3)
+        desc, _keep = self._infer_desc(x, d, live, sigma, rgbs, scratch)
+        check(lib.nerftex_curved_field_infer(ctypes.byref(desc), st))
+        return sigma, rgbs
+
     @torch.no_grad()
     def forward_graphed(self, x, d):
         """The no-grad forward (a renderer's inference iteration, the occupancy update's query) as ONE replayed HIP graph (round 6):

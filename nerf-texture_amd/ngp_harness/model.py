@@ -613,6 +613,8 @@ class Renderer(nn.Module):
                  float(self.density_scale), float(self.bound), int(self.cascade), int(self.grid_size), float(self.min_near), torch.get_autocast_dtype("cuda"), bool(_InferGraphPart.COUNT_MIRROR),
                  torch.is_autocast_enabled(),
                  tuple(t.data_ptr() for t in leaves) if have_leaves else tuple((p.data_ptr(), p._version) for p in field.parameters()))
+        if hasattr(field, "graph_stamp"):  # a field whose kernels read more than its parameters (CurvedField: the mesh, its search structures, scalars)
+            stamp = stamp + (field.graph_stamp(),)
         st = getattr(self, "_infer_graphs", None)
         main = torch.cuda.current_stream()
         if st is None or st["stamp"] != stamp:
