@@ -886,6 +886,44 @@ int nerftex_composite_step_ex(const float* sigmas, const float* rgbs, const floa
                               float* scaled_loss, float* grad_sigmas, float* grad_rgbs, uint32_t* step_live, const nerftex_step_loss_desc* desc,
                               void* stream);
 
+/* A background per ray and RGBA pixels: what the reference's train_step does for every image with an alpha channel (nerf/utils.py:602-615)
+ *   bg_color = torch.rand_like(images[..., :3]);  gt_rgb = images[..., :3] * images[..., 3:] + bg_color * (1 - images[..., 3:])
+ * and renderer.py:424 blends image + (1 - weights_sum)[:, None] * bg_color.  The four _px entries are the _ex entries with a second descriptor;
+ * the scalar `bg` argument is then ignored.  fp32, every operation rounded on its own, in the order of the torch expressions:
+ *   target     gt[c] = rgba[c] * a + bg[c] * (1 - a),  a = rgba[3]   -- written to target_out by the two forwards (nerftex_render_tail_forward_px,
+ *              nerftex_composite_step_px, which also keeps it in registers); the two backwards read target_out as their target
+ *   blend      image_out[c] = image[c] + (1 - weights_sum) * bg[c]
+ *   criterion, ray_loss, error map, loss, scaled loss: unchanged, on d = image_out - gt
+ *   opacity    sum = 0; sum += gi0 * bg[0]; sum += gi1 * bg[1]; sum += gi2 * bg[2]; grad_weights_sum = -sum   (bg == 1: the scalar form's bits)
+ * Without rgba the entry's `target` [N,3] is the target, as in the _ex entries.  The step flags, the deferred loss (nerftex_step_loss) and the
+ * trailer see err[] and the gradients only: they work with these entries as with _ex.
+ * NOT produced: a gradient with respect to the background or to alpha.  Out of scope: the background network (bg_radius > 0), whose colours
+ * would need that gradient, and color_space == 'linear'.
+ * NERFTEX_ERR_INVALID, nothing launched: bg_rays NULL; rgba and target both given, or neither; rgba without target_out.
+ * pixels NULL: the call is the _ex entry it extends -- the same launch, the same bits.                                                      */
+typedef struct nerftex_step_pixels_desc {
+    const float* bg_rays; /* [N,3] per-ray background; required */
+    const float* rgba;    /* [N,4] or NULL; non-NULL: the target is formed from it and `target` must be NULL */
+    float* target_out;    /* [N,3]; required iff rgba: the blended gt_rgb, written by the forward */
+} nerftex_step_pixels_desc;
+int nerftex_render_tail_forward_px(const float* weights_sum, const float* depth, const float* image, const float* nears, const float* fars,
+                                   const float* target, float bg, float loss_mul, uint32_t N, float* image_out, float* depth_out, float* partial,
+                                   uint32_t* ticket, float* loss, const float* scale, float* scaled_loss, uint32_t* step_live, uint32_t n_steps,
+                                   const nerftex_step_loss_desc* desc, const nerftex_step_pixels_desc* pixels, void* stream);
+int nerftex_render_tail_backward_px(const float* grad_loss, const float* scale, float loss_mul, const float* image_out, const float* target,
+                                    float bg, uint32_t N, float* grad_image, float* grad_weights_sum, const nerftex_step_loss_desc* desc,
+                                    const nerftex_step_pixels_desc* pixels, void* stream);
+int nerftex_composite_tail_backward_px(const float* grad_loss, const float* scale, float loss_mul, const float* image_out, const float* target,
+                                       float bg, const float* sigmas, const float* rgbs, const float* deltas, const int32_t* rays,
+                                       const float* weights_sum, const float* image, uint32_t M, uint32_t N, float* grad_sigmas, float* grad_rgbs,
+                                       uint32_t* step_live, const nerftex_step_loss_desc* desc, const nerftex_step_pixels_desc* pixels,
+                                       void* stream);
+int nerftex_composite_step_px(const float* sigmas, const float* rgbs, const float* deltas, const int32_t* rays, uint32_t M, uint32_t N,
+                              const float* nears, const float* fars, const float* target, float bg, float loss_mul, const float* scale,
+                              float* weights_sum, float* depth, float* image, float* image_out, float* depth_out, float* err, float* loss,
+                              float* scaled_loss, float* grad_sigmas, float* grad_rgbs, uint32_t* step_live, const nerftex_step_loss_desc* desc,
+                              const nerftex_step_pixels_desc* pixels, void* stream);
+
 /* One Adam step (main_nerf.py:128: betas (0.9, 0.99), eps 1e-15, no weight decay) of an fp32 master table from the
  * fp16 gradient the encoder backward produced, writing the fp16 copy the next forward reads: param, exp_avg,
  * exp_avg_sq [n] fp32 in place, grad_half [n] fp16 in, param_half [n] fp16 out.  step: device float, already

@@ -928,6 +928,10 @@ struct TailBackwardEx : TailBackward {
     uint32_t kind;
     float param;
 };
+// ... of the pixel instantiation (nerftex_composite_tail_backward_px): a background per ray; `target` is the [N,3] the forward blended
+struct TailBackwardPx : TailBackwardEx {
+    const float* bg_rays;
+};
 
 __global__ __launch_bounds__(kCompBlock) void composite_train_fwd_kernel(const float* __restrict__ sigmas, const float* __restrict__ rgbs,
                                                                         const float* __restrict__ deltas, const int* __restrict__ rays,
@@ -1000,6 +1004,18 @@ __device__ __forceinline__ RayGrad ray_criterion_gradient(uint32_t kind, float d
     return q;
 }
 
+// ... with a background per ray (step_loss.hpp: pixel_grad, opacity_gradient)
+__device__ __forceinline__ RayGrad ray_pixels_gradient(uint32_t kind, float delta, float norm, float count, float gl, const float* bg, const float* out,
+                                                       const float* tgt) {
+#pragma clang fp contract(off)
+    RayGrad q;
+    q.gi0 = pixel_grad(kind, delta, norm, count, out[0] - tgt[0], gl);
+    q.gi1 = pixel_grad(kind, delta, norm, count, out[1] - tgt[1], gl);
+    q.gi2 = pixel_grad(kind, delta, norm, count, out[2] - tgt[2], gl);
+    q.gws = opacity_gradient(q.gi0, q.gi1, q.gi2, bg);
+    return q;
+}
+
 // one sample's gradients (raymarching.cu:855-870) + its step flag: the first live lane of a 32-sample step (the lanes of one step are consecutive
 // inside the 64-sample window that starts at row `window0`) sets the step's word
 __device__ __forceinline__ void sample_backward(bool on, size_t i, uint32_t window0, uint32_t lane, float d0, const ChunkOut& o, float c0r, float c1g, float c2b,
@@ -1029,7 +1045,7 @@ __device__ __forceinline__ void sample_backward(bool on, size_t i, uint32_t wind
     }
 }
 
-template <bool TAIL, bool EX = false>
+template <bool TAIL, bool EX = false, bool PX = false>
 __global__ __launch_bounds__(kCompBlock) void composite_train_bwd_kernel(const float* __restrict__ grad_weights_sum,
                                                                         const float* __restrict__ grad_image,
                                                                         const float* __restrict__ sigmas, const float* __restrict__ rgbs,
@@ -1037,8 +1053,9 @@ __global__ __launch_bounds__(kCompBlock) void composite_train_bwd_kernel(const f
                                                                         const float* __restrict__ weights_sum, const float* __restrict__ image,
                                                                         uint32_t M, uint32_t N, float* __restrict__ grad_sigmas,
                                                                         float* __restrict__ grad_rgbs,
-                                                                        const std::conditional_t<EX, TailBackwardEx, TailBackward> tail) {
+                                                                        const std::conditional_t<PX, TailBackwardPx, std::conditional_t<EX, TailBackwardEx, TailBackward>> tail) {
     static_assert(TAIL || !EX, "the criterion belongs to the tail");
+    static_assert(EX || !PX, "the pixel form is an instantiation of the general one");
     const uint32_t n = blockIdx.x * (kCompBlock / kWave) + threadIdx.x / kWave;
     const uint32_t lane = threadIdx.x & (kWave - 1);
     if (n >= N) return;
@@ -1053,7 +1070,10 @@ __global__ __launch_bounds__(kCompBlock) void composite_train_bwd_kernel(const f
         const float norm = (float)(2.0 / (double)((size_t)N * 3));
         const float out[3] = {tail.image_out[(size_t)index * 3], tail.image_out[(size_t)index * 3 + 1], tail.image_out[(size_t)index * 3 + 2]};
         const float tgt[3] = {tail.target[(size_t)index * 3], tail.target[(size_t)index * 3 + 1], tail.target[(size_t)index * 3 + 2]};
-        if constexpr (EX) q = ray_criterion_gradient(tail.kind, tail.param, norm, (float)((size_t)N * 3), gl, tail.bg, out, tgt);
+        if constexpr (PX) {  // (the ray's background: three wave-uniform loads beside the six above)
+            const float bg[3] = {tail.bg_rays[(size_t)index * 3], tail.bg_rays[(size_t)index * 3 + 1], tail.bg_rays[(size_t)index * 3 + 2]};
+            q = ray_pixels_gradient(tail.kind, tail.param, norm, (float)((size_t)N * 3), gl, bg, out, tgt);
+        } else if constexpr (EX) q = ray_criterion_gradient(tail.kind, tail.param, norm, (float)((size_t)N * 3), gl, tail.bg, out, tgt);
         else q = ray_loss_gradient(norm, gl, tail.bg, out, tgt);
     } else {
         q.gws = grad_weights_sum[index];
@@ -1102,6 +1122,12 @@ struct StepTailEx : StepTail {
     uint32_t keep;  // 1 .. the instantiation's KEEP
 };
 
+// ... of the pixel instantiation (nerftex_composite_step_px): the ray's background and, with rgba, its pixel -- the target is then formed in
+// registers (and written to target_out: the reference's train_step returns gt_rgb)
+struct StepTailPx : StepTailEx {
+    StepPixels px;
+};
+
 struct RayTail { float out[3], depth_out, err; };
 template <bool EX = false>
 __device__ __forceinline__ RayTail ray_tail_forward(float ws, float d, float i0, float i1, float i2, float near, float far, const float* tgt, float bg,
@@ -1124,13 +1150,33 @@ __device__ __forceinline__ RayTail ray_tail_forward(float ws, float d, float i0,
     return t;
 }
 
-template <int KEEP, bool EX = false>
+// ... with a background per channel (render_tail_forward_kernel<true, true>'s arithmetic)
+__device__ __forceinline__ RayTail ray_tail_forward_px(float ws, float d, float i0, float i1, float i2, float near, float far, const float* tgt, const float* bg,
+                                                       uint32_t kind, float delta) {
+#pragma clang fp contract(off)
+    RayTail t;
+    const float rest = 1.0f - ws;
+    const float img[3] = {i0, i1, i2};
+    float err = 0.0f;
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        const float v = img[c] + rest * bg[c];
+        t.out[c] = v;
+        err += criterion_element(kind, delta, v - tgt[c]);
+    }
+    t.err = err;
+    t.depth_out = fmaxf(d - near, 0.0f) / (far - near);
+    return t;
+}
+
+template <int KEEP, bool EX = false, bool PX = false>
 __global__ __launch_bounds__(kCompBlock) void composite_step_kernel(const float* __restrict__ sigmas, const float* __restrict__ rgbs,
                                                                     const float* __restrict__ deltas, const int* __restrict__ rays, uint32_t M,
                                                                     uint32_t N, float* __restrict__ weights_sum, float* __restrict__ depth,
                                                                     float* __restrict__ image, float* __restrict__ grad_sigmas,
                                                                     float* __restrict__ grad_rgbs,
-                                                                    const std::conditional_t<EX, StepTailEx, StepTail> tail) {
+                                                                    const std::conditional_t<PX, StepTailPx, std::conditional_t<EX, StepTailEx, StepTail>> tail) {
+    static_assert(EX || !PX, "the pixel form is an instantiation of the general one");
     uint32_t keep = (uint32_t)KEEP;  // chunks kept in registers: the instantiation's, or fewer at the general one's word
     if constexpr (EX) keep = tail.keep;
     const uint32_t n = blockIdx.x * (kCompBlock / kWave) + threadIdx.x / kWave;
@@ -1144,14 +1190,18 @@ __global__ __launch_bounds__(kCompBlock) void composite_step_kernel(const float*
     // behind the ray record instead of one per use (the compiler sinks a load to its first use: the scale's sat behind the tail's stores)
     const float scale_now = tail.scale ? *tail.scale : 1.0f;
     const float near = tail.nears[index], far = tail.fars[index];
-    const float tgt[3] = {tail.target[3 * (size_t)index], tail.target[3 * (size_t)index + 1], tail.target[3 * (size_t)index + 2]};
+    float tgt[3] = {0.0f, 0.0f, 0.0f};  // (the pixel form has its target once the ray's totals are formed)
+    if constexpr (!PX) {
+        tgt[0] = tail.target[3 * (size_t)index]; tgt[1] = tail.target[3 * (size_t)index + 1]; tgt[2] = tail.target[3 * (size_t)index + 2];
+    }
     ChunkIn in[KEEP];
 #pragma unroll
     for (int c = 0; c < KEEP; c++) {
         const uint32_t k = (uint32_t)c * kWave + lane;
         in[c] = load_chunk(sigmas, rgbs, deltas, (size_t)offset + k, k < steps && (uint32_t)c < keep);
     }
-    asm volatile("" ::"v"(scale_now), "v"(near), "v"(far), "v"(tgt[0]), "v"(tgt[1]), "v"(tgt[2]));  // (issued here, not where they are used)
+    if constexpr (PX) asm volatile("" ::"v"(scale_now), "v"(near), "v"(far));
+    else asm volatile("" ::"v"(scale_now), "v"(near), "v"(far), "v"(tgt[0]), "v"(tgt[1]), "v"(tgt[2]));  // (issued here, not where they are used)
     zero_uncovered_rows(rays, n, lane, offset, num_steps, M, N, grad_sigmas, grad_rgbs);
 
     RayCarry c;
@@ -1166,7 +1216,17 @@ __global__ __launch_bounds__(kCompBlock) void composite_step_kernel(const float*
     }
     const RayCarry fin = c;
     RayTail rt;
-    if constexpr (EX) rt = ray_tail_forward<true>(fin.ws, fin.d, fin.r, fin.g, fin.b, near, far, tgt, tail.bg, tail.crit.kind, tail.crit.param);
+    float bg[3] = {0.0f, 0.0f, 0.0f};
+    if constexpr (PX) {
+        // the seven values of the ray's background and pixel: wave-uniform loads, made once, here -- not held in registers across the walk
+        const RayPixels p = load_ray_pixels(tail.px, tail.target, index);
+#pragma unroll
+        for (int ch = 0; ch < 3; ch++) {
+            bg[ch] = p.bg[ch];
+            tgt[ch] = p.gt[ch];
+        }
+        rt = ray_tail_forward_px(fin.ws, fin.d, fin.r, fin.g, fin.b, near, far, tgt, bg, tail.crit.kind, tail.crit.param);
+    } else if constexpr (EX) rt = ray_tail_forward<true>(fin.ws, fin.d, fin.r, fin.g, fin.b, near, far, tgt, tail.bg, tail.crit.kind, tail.crit.param);
     else rt = ray_tail_forward(fin.ws, fin.d, fin.r, fin.g, fin.b, near, far, tgt, tail.bg);
     if (lane == 0) {
         weights_sum[index] = fin.ws;
@@ -1176,10 +1236,15 @@ __global__ __launch_bounds__(kCompBlock) void composite_step_kernel(const float*
         tail.depth_out[index] = rt.depth_out;
         tail.err[index] = rt.err;
         if constexpr (EX) record_ray_loss(tail.crit, index, rt.err);  // (the lane that holds the ray's error: no launch, no atomics)
+        if constexpr (PX)
+            if (tail.px.target_out != nullptr) {
+                tail.px.target_out[3 * (size_t)index] = tgt[0]; tail.px.target_out[3 * (size_t)index + 1] = tgt[1]; tail.px.target_out[3 * (size_t)index + 2] = tgt[2];
+            }
     }
     if (dead) return;
     RayGrad q;  // (TailBackward with grad_loss = 1: 1.0f * scale is scale)
-    if constexpr (EX) q = ray_criterion_gradient(tail.crit.kind, tail.crit.param, tail.norm, tail.count, scale_now * tail.loss_mul, tail.bg, rt.out, tgt);
+    if constexpr (PX) q = ray_pixels_gradient(tail.crit.kind, tail.crit.param, tail.norm, tail.count, scale_now * tail.loss_mul, bg, rt.out, tgt);
+    else if constexpr (EX) q = ray_criterion_gradient(tail.crit.kind, tail.crit.param, tail.norm, tail.count, scale_now * tail.loss_mul, tail.bg, rt.out, tgt);
     else q = ray_loss_gradient(tail.norm, scale_now * tail.loss_mul, tail.bg, rt.out, tgt);
 #pragma unroll
     for (int j = 0; j < KEEP; j++)
@@ -1602,15 +1667,30 @@ extern "C" int nerftex_composite_tail_backward_ex(const float* grad_loss, const 
                                                   float bg, const float* sigmas, const float* rgbs, const float* deltas, const int32_t* rays,
                                                   const float* weights_sum, const float* image, uint32_t M, uint32_t N, float* grad_sigmas,
                                                   float* grad_rgbs, uint32_t* step_live, const nerftex_step_loss_desc* desc, void* stream) {
+    return nerftex_composite_tail_backward_px(grad_loss, scale, loss_mul, image_out, target, bg, sigmas, rgbs, deltas, rays, weights_sum, image, M, N, grad_sigmas,
+                                              grad_rgbs, step_live, desc, nullptr, stream);
+}
+
+// ... for the pixels descriptor of the forward (bg_rays is read; with rgba, target_out is this launch's target; NULL: the _ex launch, as it always was)
+extern "C" int nerftex_composite_tail_backward_px(const float* grad_loss, const float* scale, float loss_mul, const float* image_out, const float* target,
+                                                  float bg, const float* sigmas, const float* rgbs, const float* deltas, const int32_t* rays,
+                                                  const float* weights_sum, const float* image, uint32_t M, uint32_t N, float* grad_sigmas,
+                                                  float* grad_rgbs, uint32_t* step_live, const nerftex_step_loss_desc* desc,
+                                                  const nerftex_step_pixels_desc* pixels, void* stream) {
     clear_error();
     StepCriterion crit;
     if (!take_step_loss_kind(desc, crit, "composite_tail_backward_ex")) return NERFTEX_ERR_INVALID;
+    StepPixels px;
+    if (pixels != nullptr && !take_step_pixels_backward(pixels, target, px, "composite_tail_backward_px")) return NERFTEX_ERR_INVALID;
     if (N == 0) return NERFTEX_OK;
     const TailBackward tail{grad_loss, scale, image_out, target, bg, loss_mul, step_live};
     {
         KernelTimer kt("composite_tail_bwd_kernel", as_stream(stream));
         const dim3 grid(div_up(N, kCompBlock / (uint32_t)kWave)), block(kCompBlock);
-        if (desc == nullptr)
+        if (pixels != nullptr)
+            hipLaunchKernelGGL((composite_train_bwd_kernel<true, true, true>), grid, block, 0, as_stream(stream), nullptr, nullptr, sigmas, rgbs, deltas, rays,
+                               weights_sum, image, M, N, grad_sigmas, grad_rgbs, TailBackwardPx{{tail, crit.kind, crit.param}, px.bg_rays});
+        else if (desc == nullptr)
             hipLaunchKernelGGL(composite_train_bwd_kernel<true>, grid, block, 0, as_stream(stream), nullptr, nullptr, sigmas, rgbs, deltas, rays, weights_sum, image, M,
                                N, grad_sigmas, grad_rgbs, tail);
         else
@@ -1638,9 +1718,22 @@ extern "C" int nerftex_composite_step_ex(const float* sigmas, const float* rgbs,
                                          float* weights_sum, float* depth, float* image, float* image_out, float* depth_out, float* err, float* loss,
                                          float* scaled_loss, float* grad_sigmas, float* grad_rgbs, uint32_t* step_live, const nerftex_step_loss_desc* desc,
                                          void* stream) {
+    return nerftex_composite_step_px(sigmas, rgbs, deltas, rays, M, N, nears, fars, target, bg, loss_mul, scale, weights_sum, depth, image, image_out, depth_out, err,
+                                     loss, scaled_loss, grad_sigmas, grad_rgbs, step_live, desc, nullptr, stream);
+}
+
+// ... with a background per ray and RGBA pixels (nerftex_step_pixels_desc; NULL: the _ex launches, as they always were): the blended target is
+// formed in the wave's registers and written to target_out
+extern "C" int nerftex_composite_step_px(const float* sigmas, const float* rgbs, const float* deltas, const int32_t* rays, uint32_t M, uint32_t N,
+                                         const float* nears, const float* fars, const float* target, float bg, float loss_mul, const float* scale,
+                                         float* weights_sum, float* depth, float* image, float* image_out, float* depth_out, float* err, float* loss,
+                                         float* scaled_loss, float* grad_sigmas, float* grad_rgbs, uint32_t* step_live, const nerftex_step_loss_desc* desc,
+                                         const nerftex_step_pixels_desc* pixels, void* stream) {
     clear_error();
     StepCriterion crit;
     if (!take_step_loss_desc(desc, crit, "composite_step_ex")) return NERFTEX_ERR_INVALID;
+    StepPixels px;
+    if (pixels != nullptr && !take_step_pixels_desc(pixels, target, px, "composite_step_px")) return NERFTEX_ERR_INVALID;
     if (N == 0 || M == 0) {
         set_error("composite_step: no rays / no samples (use the three entries it replaces)");
         return NERFTEX_ERR_INVALID;
@@ -1654,7 +1747,11 @@ extern "C" int nerftex_composite_step_ex(const float* sigmas, const float* rgbs,
         KernelTimer kt("composite_step_kernel", as_stream(stream));
         const int keep = knob(kKnobCompositeKeep);
         const dim3 grid(div_up(N, kCompBlock / (uint32_t)kWave)), block(kCompBlock);
-        if (desc != nullptr) {  // the general instantiation: compiled for four kept chunks, keeps as many as the knob says
+        if (pixels != nullptr) {  // the pixel instantiation of the general one
+            const StepTailPx pxt{{tail, crit, (float)((size_t)N * 3), (keep == 1 || keep == 3 || keep == 4) ? (uint32_t)keep : 2u}, px};
+            hipLaunchKernelGGL((composite_step_kernel<4, true, true>), grid, block, 0, as_stream(stream), sigmas, rgbs, deltas, rays, M, N, weights_sum, depth, image,
+                               grad_sigmas, grad_rgbs, pxt);
+        } else if (desc != nullptr) {  // the general instantiation: compiled for four kept chunks, keeps as many as the knob says
             const StepTailEx ex{tail, crit, (float)((size_t)N * 3), (keep == 1 || keep == 3 || keep == 4) ? (uint32_t)keep : 2u};
             hipLaunchKernelGGL((composite_step_kernel<4, true>), grid, block, 0, as_stream(stream), sigmas, rgbs, deltas, rays, M, N, weights_sum, depth, image,
                                grad_sigmas, grad_rgbs, ex);

@@ -105,6 +105,84 @@ inline bool take_step_loss_desc(const nerftex_step_loss_desc* d, StepCriterion& 
     return true;
 }
 
+// Per-ray backgrounds and RGBA pixels (nerftex_step_pixels_desc): what the pixel instantiations of the tail kernels carry beside the criterion.
+// nerf/utils.py:602-615 draws bg_color = torch.rand_like(images[..., :3]) and blends gt_rgb = rgb * a + bg_color * (1 - a); renderer.py:424
+// blends image + (1 - weights_sum)[:, None] * bg_color.  Every operation below is rounded on its own (contraction off), in torch's order.
+struct StepPixels {
+    const float* bg_rays = nullptr;  // [N,3]
+    const float* rgba = nullptr;     // [N,4] or nullptr: the target is then the caller's [N,3]
+    float* target_out = nullptr;     // [N,3] with rgba: the blended target, written by a forward, read by a backward
+};
+struct StepCriterionPx : StepCriterion {
+    StepPixels px;
+};
+struct RayPixels { float bg[3], gt[3]; };
+// ONE ray's seven new values (three of the background, four of the pixel) and its target; `target` is read when there is no rgba
+__device__ __forceinline__ RayPixels load_ray_pixels(const StepPixels& px, const float* __restrict__ target, size_t n) {
+#pragma clang fp contract(off)
+    RayPixels p;
+#pragma unroll
+    for (int c = 0; c < 3; c++) p.bg[c] = px.bg_rays[3 * n + c];
+    if (px.rgba != nullptr) {
+        const float a = px.rgba[4 * n + 3];
+        const float rest = 1.0f - a;
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            const float fore = px.rgba[4 * n + c] * a;
+            const float back = p.bg[c] * rest;
+            p.gt[c] = fore + back;
+        }
+    } else {
+#pragma unroll
+        for (int c = 0; c < 3; c++) p.gt[c] = target[3 * n + c];
+    }
+    return p;
+}
+// grad_weights_sum of image_out[c] = image[c] + (1 - weights_sum) * bg[c]; with bg == 1 the bits of the scalar form's -(sum * 1)
+__device__ __forceinline__ float opacity_gradient(float gi0, float gi1, float gi2, const float* bg) {
+#pragma clang fp contract(off)
+    float sum = 0.0f;
+    sum += gi0 * bg[0];
+    sum += gi1 * bg[1];
+    sum += gi2 * bg[2];
+    return -sum;
+}
+// one channel of grad_image for any criterion: the MSE's own expression (render_tail_backward_kernel), else criterion_grad
+__device__ __forceinline__ float pixel_grad(uint32_t kind, float delta, float norm, float count, float d, float g) {
+#pragma clang fp contract(off)
+    if (kind == NERFTEX_LOSS_MSE) return norm * d * g;
+    return criterion_grad(kind, delta, d, g, count);
+}
+
+// a nerftex_step_pixels_desc beside the entry's `target`; false (error set): unusable
+inline bool take_step_pixels_desc(const nerftex_step_pixels_desc* d, const float* target, StepPixels& out, const char* who) {
+    out = StepPixels{};
+    if (d->bg_rays == nullptr) {
+        set_error("%s: the pixels descriptor needs bg_rays, the [N,3] per-ray background", who);
+        return false;
+    }
+    if ((d->rgba != nullptr) == (target != nullptr)) {
+        set_error("%s: exactly one of the pixels descriptor's rgba [N,4] and the entry's target [N,3] (got %s)", who, target ? "both" : "neither");
+        return false;
+    }
+    if (d->rgba != nullptr && d->target_out == nullptr) {
+        set_error("%s: rgba needs target_out, the [N,3] buffer of the blended target", who);
+        return false;
+    }
+    out.bg_rays = d->bg_rays;
+    out.rgba = d->rgba;
+    out.target_out = d->rgba != nullptr ? d->target_out : nullptr;
+    return true;
+}
+// ... of a backward entry: its target is the [N,3] the forward wrote
+inline bool take_step_pixels_backward(const nerftex_step_pixels_desc* d, const float*& target, StepPixels& out, const char* who) {
+    if (!take_step_pixels_desc(d, target, out, who)) return false;
+    if (out.rgba != nullptr) target = out.target_out;
+    out.rgba = nullptr;
+    out.target_out = nullptr;
+    return true;
+}
+
 template <uint32_t THREADS>
 __device__ __forceinline__ void step_loss_sum(const StepLossJob& job, StepLossLds& lds) {
     static_assert(THREADS >= 256 && THREADS % 64 == 0, "");

@@ -40,7 +40,9 @@ __device__ __forceinline__ float block_sum(float v, float* lds) {
 // adds the partials in index order: the loss does not depend on the order the blocks ran in.
 // EX (nerftex_render_tail_forward_ex): the one general instantiation -- the element is the criterion's, and the ray's thread leaves the per-ray
 // loss and the error map's moving average (record_ray_loss)
-template <bool EX>
+// PX (nerftex_render_tail_forward_px): the general instantiation with a background per ray and, with rgba, the target blended here and written to
+// target_out (step_loss.hpp: load_ray_pixels); the scalar bg is not read
+template <bool EX, bool PX = false>
 __global__ __launch_bounds__(kTailThreads) void render_tail_forward_kernel(const float* __restrict__ weights_sum, const float* __restrict__ depth,
                                                                            const float* __restrict__ image, const float* __restrict__ nears,
                                                                            const float* __restrict__ fars, const float* __restrict__ target,
@@ -50,8 +52,9 @@ __global__ __launch_bounds__(kTailThreads) void render_tail_forward_kernel(const
                                                                            float* __restrict__ loss, const float* __restrict__ scale,
                                                                            float* __restrict__ scaled_loss, uint32_t* __restrict__ step_live,
                                                                            const uint32_t n_steps,
-                                                                           const std::conditional_t<EX, StepCriterion, NoCriterion> crit) {
+                                                                           const std::conditional_t<PX, StepCriterionPx, std::conditional_t<EX, StepCriterion, NoCriterion>> crit) {
 #pragma clang fp contract(off)  // the framework's blend is a multiply, then an add
+    static_assert(EX || !PX, "the pixel form is an instantiation of the general one");
     __shared__ float lds[kTailThreads / 64];
     __shared__ bool last;
     const uint32_t n = blockIdx.x * kTailThreads + threadIdx.x;
@@ -60,6 +63,17 @@ __global__ __launch_bounds__(kTailThreads) void render_tail_forward_kernel(const
         for (uint32_t i = n; i < n_steps; i += gridDim.x * kTailThreads) step_live[i] = 0u;
     float err = 0.0f;
     if (n < N) {
+        if constexpr (PX) {
+            const RayPixels p = load_ray_pixels(crit.px, target, n);
+            const float rest = 1.0f - weights_sum[n];
+#pragma unroll
+            for (int c = 0; c < 3; c++) {
+                if (crit.px.target_out != nullptr) crit.px.target_out[(size_t)n * 3 + c] = p.gt[c];
+                const float v = image[(size_t)n * 3 + c] + rest * p.bg[c];
+                image_out[(size_t)n * 3 + c] = v;
+                err += criterion_element(crit.kind, crit.param, v - p.gt[c]);
+            }
+        } else {
         const float back = (1.0f - weights_sum[n]) * bg;
 #pragma unroll
         for (int c = 0; c < 3; c++) {
@@ -68,6 +82,7 @@ __global__ __launch_bounds__(kTailThreads) void render_tail_forward_kernel(const
             const float d = v - target[(size_t)n * 3 + c];
             if constexpr (EX) err += criterion_element(crit.kind, crit.param, d);
             else err += d * d;
+        }
         }
         depth_out[n] = fmaxf(depth[n] - nears[n], 0.0f) / (fars[n] - nears[n]);
         if constexpr (EX) record_ray_loss(crit, n, err);
@@ -95,17 +110,30 @@ __global__ __launch_bounds__(kTailThreads) void render_tail_forward_kernel(const
 
 // grad_image = (2 / 3N) * (image_out - target) * grad_loss   (mse_loss backward: norm * (a - b) * g),  grad_ws = -(sum_c grad_image) * bg
 // EX, L1 / Huber: grad_image = (de/dd) * g / 3N
-template <bool EX>
+// PX: grad_ws = -(gi0 * bg0 + gi1 * bg1 + gi2 * bg2), summed from zero in that order (opacity_gradient)
+template <bool EX, bool PX = false>
 __global__ __launch_bounds__(kTailThreads) void render_tail_backward_kernel(const float* __restrict__ grad_loss, const float* __restrict__ scale, const float loss_mul,
                                                                             const float* __restrict__ image_out, const float* __restrict__ target,
                                                                             const float bg, const uint32_t N, float* __restrict__ grad_image,
                                                                             float* __restrict__ grad_ws,
-                                                                            const std::conditional_t<EX, StepCriterion, NoCriterion> crit) {
+                                                                            const std::conditional_t<PX, StepCriterionPx, std::conditional_t<EX, StepCriterion, NoCriterion>> crit) {
 #pragma clang fp contract(off)
+    static_assert(EX || !PX, "the pixel form is an instantiation of the general one");
     const uint32_t n = blockIdx.x * kTailThreads + threadIdx.x;
     if (n >= N) return;
     const float g = (scale ? *grad_loss * *scale : *grad_loss) * loss_mul;  // backward of (mse * loss_mul) * scale
     const float norm = (float)(2.0 / (double)((size_t)N * 3));
+    if constexpr (PX) {
+        const RayPixels p = load_ray_pixels(crit.px, target, n);
+        float gi[3];
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            gi[c] = pixel_grad(crit.kind, crit.param, norm, (float)((size_t)N * 3), image_out[(size_t)n * 3 + c] - p.gt[c], g);
+            grad_image[(size_t)n * 3 + c] = gi[c];
+        }
+        grad_ws[n] = opacity_gradient(gi[0], gi[1], gi[2], p.bg);
+        return;
+    }
     float sum = 0.0f;
 #pragma unroll
     for (int c = 0; c < 3; c++) {
@@ -483,6 +511,16 @@ extern "C" int nerftex_render_tail_forward_ex(const float* weights_sum, const fl
                                               float* depth_out, float* partial, uint32_t* ticket, float* loss, const float* scale,
                                               float* scaled_loss, uint32_t* step_live, uint32_t n_steps, const nerftex_step_loss_desc* desc,
                                               void* stream) {
+    return nerftex_render_tail_forward_px(weights_sum, depth, image, nears, fars, target, bg, loss_mul, N, image_out, depth_out, partial, ticket, loss, scale,
+                                          scaled_loss, step_live, n_steps, desc, nullptr, stream);
+}
+
+// ... with a background per ray and RGBA pixels (nerftex_step_pixels_desc; NULL: the _ex launch above, as it always was)
+extern "C" int nerftex_render_tail_forward_px(const float* weights_sum, const float* depth, const float* image, const float* nears,
+                                              const float* fars, const float* target, float bg, float loss_mul, uint32_t N, float* image_out,
+                                              float* depth_out, float* partial, uint32_t* ticket, float* loss, const float* scale,
+                                              float* scaled_loss, uint32_t* step_live, uint32_t n_steps, const nerftex_step_loss_desc* desc,
+                                              const nerftex_step_pixels_desc* pixels, void* stream) {
     clear_error();
     if (N == 0) {
         set_error("render_tail: empty batch");
@@ -490,10 +528,16 @@ extern "C" int nerftex_render_tail_forward_ex(const float* weights_sum, const fl
     }
     StepCriterion crit;
     if (!take_step_loss_desc(desc, crit, "render_tail_forward_ex")) return NERFTEX_ERR_INVALID;
+    StepCriterionPx cpx;
+    if (pixels != nullptr && !take_step_pixels_desc(pixels, target, cpx.px, "render_tail_forward_px")) return NERFTEX_ERR_INVALID;
     hipStream_t st = as_stream(stream);
     {
         KernelTimer kt("render_tail_forward_kernel", st);
-        if (desc == nullptr)
+        if (pixels != nullptr) {
+            static_cast<StepCriterion&>(cpx) = crit;
+            hipLaunchKernelGGL((render_tail_forward_kernel<true, true>), dim3(div_up(N, kTailThreads)), dim3(kTailThreads), 0, st, weights_sum, depth, image,
+                               nears, fars, target, bg, loss_mul, N, image_out, depth_out, partial, ticket, loss, scale, scaled_loss, step_live, n_steps, cpx);
+        } else if (desc == nullptr)
             hipLaunchKernelGGL(render_tail_forward_kernel<false>, dim3(div_up(N, kTailThreads)), dim3(kTailThreads), 0, st, weights_sum, depth, image, nears,
                                fars, target, bg, loss_mul, N, image_out, depth_out, partial, ticket, loss, scale, scaled_loss, step_live, n_steps, NoCriterion{});
         else
@@ -511,14 +555,27 @@ extern "C" int nerftex_render_tail_backward(const float* grad_loss, const float*
 // ... for the criterion of the forward's descriptor (only kind and param are read)
 extern "C" int nerftex_render_tail_backward_ex(const float* grad_loss, const float* scale, float loss_mul, const float* image_out, const float* target, float bg,
                                                uint32_t N, float* grad_image, float* grad_weights_sum, const nerftex_step_loss_desc* desc, void* stream) {
+    return nerftex_render_tail_backward_px(grad_loss, scale, loss_mul, image_out, target, bg, N, grad_image, grad_weights_sum, desc, nullptr, stream);
+}
+
+// ... for the pixels descriptor of the forward (bg_rays is read; with rgba, target_out is this launch's target)
+extern "C" int nerftex_render_tail_backward_px(const float* grad_loss, const float* scale, float loss_mul, const float* image_out, const float* target, float bg,
+                                               uint32_t N, float* grad_image, float* grad_weights_sum, const nerftex_step_loss_desc* desc,
+                                               const nerftex_step_pixels_desc* pixels, void* stream) {
     clear_error();
     StepCriterion crit;
     if (!take_step_loss_kind(desc, crit, "render_tail_backward_ex")) return NERFTEX_ERR_INVALID;
+    StepCriterionPx cpx;
+    if (pixels != nullptr && !take_step_pixels_backward(pixels, target, cpx.px, "render_tail_backward_px")) return NERFTEX_ERR_INVALID;
     if (N == 0) return NERFTEX_OK;
     hipStream_t st = as_stream(stream);
     {
         KernelTimer kt("render_tail_backward_kernel", st);
-        if (desc == nullptr)
+        if (pixels != nullptr) {
+            static_cast<StepCriterion&>(cpx) = crit;
+            hipLaunchKernelGGL((render_tail_backward_kernel<true, true>), dim3(div_up(N, kTailThreads)), dim3(kTailThreads), 0, st, grad_loss, scale, loss_mul,
+                               image_out, target, bg, N, grad_image, grad_weights_sum, cpx);
+        } else if (desc == nullptr)
             hipLaunchKernelGGL(render_tail_backward_kernel<false>, dim3(div_up(N, kTailThreads)), dim3(kTailThreads), 0, st, grad_loss, scale, loss_mul, image_out,
                                target, bg, N, grad_image, grad_weights_sum, NoCriterion{});
         else

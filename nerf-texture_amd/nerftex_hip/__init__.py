@@ -84,6 +84,12 @@ _SIGNATURES = {
     "nerftex_composite_tail_backward_ex": [_vp, _vp, _f32, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp],
     "nerftex_composite_step_ex": [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                   _vp],
+    # the four _ex entries with a nerftex_step_pixels_desc (StepPixelsDesc) before the stream
+    "nerftex_render_tail_forward_px": [_vp, _vp, _vp, _vp, _vp, _vp, _f32, _f32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp],
+    "nerftex_render_tail_backward_px": [_vp, _vp, _f32, _vp, _vp, _f32, _u32, _vp, _vp, _vp, _vp, _vp],
+    "nerftex_composite_tail_backward_px": [_vp, _vp, _f32, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp],
+    "nerftex_composite_step_px": [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                  _vp, _vp],
     "nerftex_grid_encode_backward_adam": [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _f32, _u32, _u32, _i, _i, _i, _f32, _f32, _vp, _vp, _vp],
     "nerftex_field_forward_bf16": [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "nerftex_field_density_bf16": [_vp, _vp, _u32, _vp, _vp],
@@ -184,6 +190,11 @@ class StepLossDesc(C.Structure):
     """nerftex_step_loss_desc of include/nerftex_hip.h, field for field: the criterion of a step, its per-ray loss and the error map."""
     _fields_ = [("kind", _u32), ("param", _f32), ("ray_loss", _vp), ("error_map", _vp), ("error_inds", _vp), ("error_cells", _u64), ("keep", _f32),
                 ("take", _f32)]
+
+
+class StepPixelsDesc(C.Structure):
+    """nerftex_step_pixels_desc of include/nerftex_hip.h, field for field: a training step's per-ray background and RGBA pixels."""
+    _fields_ = [("bg_rays", _vp), ("rgba", _vp), ("target_out", _vp)]
 
 
 class CurvedInferDesc(C.Structure):

@@ -48,10 +48,11 @@ class AcceleratedTrainer:
     def __init__(self, renderer, rays_per_batch=None, lr=1e-2, betas=(0.9, 0.99), eps=1e-15, dt_gamma=1 / 128, bg_color=1, perturb=True, max_steps=1024,
                  amp_dtype=torch.float16, graph=True, steps_per_call=1, march_across_ring_end=False, pipeline_adam=0, skip_dead_samples=None,
                  fused_table_update=None, fused_composite_step=None, lr_scheduler=None, total_steps=None, criterion=None, error_map=None,
-                 ema_decay=None):
+                 ema_decay=None, target_channels=3, bg_generator=None):
         from .model import NGPField
 
         _refuse_options(lr_scheduler, pipeline_adam, ema_decay)
+        self._init_pixels(bg_color, target_channels, bg_generator)
         self._init_criterion(criterion, error_map)
         field = renderer.field
         assert isinstance(field, NGPField), "accelerate() knows the ngp field (hash grid + two MLPs)"
@@ -120,6 +121,73 @@ class AcceleratedTrainer:
         self.error_map = error_map
         self.ray_loss = None
         self._ray_loss, self._error_inds = None, None  # static per-ring-slot buffers, beside the targets
+
+    def _init_pixels(self, bg_color, target_channels, bg_generator):
+        """bg_color / target_channels / bg_generator of accelerate(): refused here, before the renderer is looked at, when they are not what the
+        kernels do.  The reference's train_step draws a background per pixel and blends RGBA images over it (nerf/utils.py:602-615):
+        bg_color="random" draws it per call, "given" takes it from `step(..., bg=)`; target_channels=4 makes the batches [N,4] RGBA pixels.
+        With a number and 3 channels the step makes the very calls it always made: no descriptor, no buffer.  Both are constants of the graphs."""
+        if isinstance(bg_color, str):
+            if bg_color not in ("random", "given"):
+                raise ValueError(f'bg_color: a number, "random" (a colour per ray drawn every call) or "given" (step(..., bg=) passes them); got {bg_color!r}')
+            self.bg_mode = bg_color
+        else:
+            try:
+                float(bg_color)
+            except (TypeError, ValueError):
+                raise ValueError(f'bg_color: a number, "random" (a colour per ray drawn every call) or "given" (step(..., bg=) passes them); got {bg_color!r}') from None
+            self.bg_mode = None
+        if isinstance(target_channels, bool) or target_channels not in (3, 4):
+            raise ValueError(f"target_channels: 3 (RGB targets) or 4 (RGBA pixels, blended over the background by the step); got {target_channels!r}")
+        if bg_generator is not None and not (self.bg_mode == "random" and isinstance(bg_generator, torch.Generator)):
+            raise ValueError('bg_generator: a torch.Generator on the field\'s device, with bg_color="random" (it seeds the per-call draw)')
+        self.target_channels, self.bg_generator = int(target_channels), bg_generator
+        self._pixels = self.bg_mode is not None or self.target_channels == 4
+        self._bg, self._gt = None, None  # static per-ring-slot buffers, beside the targets: the rays' backgrounds, the blended targets
+        self.gt_rgb, self.last_bg = None, None  # after a call: the last step's target [N,3] (blended, with RGBA pixels) and background [N,3]
+
+    def _check_batch(self, target, bg, grouped):
+        """A call's targets and backgrounds against the trainer's constants: ValueError before anything is copied or launched (shapes and dtypes
+        only: nothing on the device is looked at)."""
+        if bg is not None and self.bg_mode != "given":
+            raise ValueError('bg= without bg_color="given": this trainer ' + ("draws its backgrounds itself" if self.bg_mode == "random" else "blends over a constant colour"))
+        if self.bg_mode == "given" and bg is None:
+            raise ValueError('bg_color="given": pass the rays\' backgrounds, step(..., bg=[N,3]) / step_group(..., bg=[k,N,3])')
+        if not self._pixels:
+            return
+        dims, C = (3 if grouped else 2), self.target_channels
+        if not (isinstance(target, torch.Tensor) and target.dim() == dims and target.shape[-1] == C and target.dtype.is_floating_point):
+            got = f"{target.dtype} {tuple(target.shape)}" if isinstance(target, torch.Tensor) else repr(type(target))
+            raise ValueError(f"target: a floating-point {'[k,N,' if grouped else '[N,'}{C}] tensor (this trainer was built with target_channels={C}), got {got}")
+        if bg is not None and not (isinstance(bg, torch.Tensor) and bg.dtype == torch.float32 and tuple(bg.shape) == tuple(target.shape[:-1]) + (3,)):
+            got = f"{bg.dtype} {tuple(bg.shape)}" if isinstance(bg, torch.Tensor) else repr(type(bg))
+            raise ValueError(f"bg: a torch.float32 tensor of shape {tuple(target.shape[:-1]) + (3,)}, one colour per ray, got {got}")
+
+    def _fill_backgrounds(self, slot0, k, bg):
+        """The backgrounds of the k steps at ring slots slot0 .. slot0 + k into their static buffers, on the step's stream in front of the steps and
+        outside the graphs: "given" copies them like the targets; "random" is ONE torch.rand of [k,N,3] per call -- the reference's
+        torch.rand_like, reproducible from bg_generator (a call of k steps draws once: k single steps draw the same numbers only for k = 1)."""
+        if self.bg_mode is None:
+            return
+        if slot0 + k <= RING:
+            dst = self._bg[slot0:slot0 + k]
+            if self.bg_mode == "given":
+                dst.copy_(bg.reshape(k, self.n_rays, 3), non_blocking=True)
+            else:
+                torch.rand(dst.shape, generator=self.bg_generator, out=dst)
+            return
+        # (eager steps that cross the ring's end: `step` and `step_group` mixed before the graphs run)
+        src = bg.reshape(k, self.n_rays, 3) if self.bg_mode == "given" else torch.rand((k, self.n_rays, 3), generator=self.bg_generator, device=self.dev)
+        for i in range(k):
+            self._bg[(slot0 + i) % RING].copy_(src[i], non_blocking=True)
+
+    def _published(self, slot):
+        """After a call whose last step ran at ring slot `slot`: what the step trained against."""
+        if self._loss_outputs:
+            self.ray_loss = self._ray_loss[slot]
+        if self._pixels:
+            self.gt_rgb = self._gt[slot] if self._gt is not None else self._targets[slot]
+            self.last_bg = self._bg[slot]
 
     def _init_loop(self, renderer, field, rays_per_batch, dt_gamma, bg_color, perturb, max_steps, amp_dtype, graph, steps_per_call, march_across_ring_end):
         """What the step loop keeps, whatever the field and its optimizer (both constructors start here)."""
@@ -211,7 +279,8 @@ class AcceleratedTrainer:
         else:
             self.opt.zero_grad(set_to_none=True)
         with torch.autocast("cuda", dtype=self.amp_dtype):
-            image, depth, loss, scaled = r.shade_train(marched, self.bg_color, target=tgt, scale=self.amp.scale if self.amp else None, **self._loss_args(slot))
+            image, depth, loss, scaled = r.shade_train(marched, self._bg_arg(slot), target=tgt, scale=self.amp.scale if self.amp else None,
+                                                       **self._loss_args(slot))[:4]  # (a fifth, with RGBA pixels: the blended target, which is _gt[slot])
         if self.amp:
             scaled.backward(self._one)
             self.amp.step()
@@ -226,11 +295,19 @@ class AcceleratedTrainer:
             self.ema.update()  # the step's last launch: behind the optimizer's, reads the set its live word names (a skipped step: the unchanged one)
 
     def _loss_args(self, slot):
-        """shade_train's criterion / per-ray loss / error map arguments of a step at ring slot `slot`: none unless accelerate() was given any."""
-        if not self._loss_outputs:
-            return {}
-        return dict(criterion=self.criterion, ray_loss=self._ray_loss[slot], error_map=self.error_map,
-                    error_inds=None if self.error_map is None else self._error_inds[slot])
+        """shade_train's criterion / per-ray loss / error map / blended-target arguments of a step at ring slot `slot`: none unless accelerate()
+        was given any."""
+        kw = {}
+        if self._loss_outputs:
+            kw.update(criterion=self.criterion, ray_loss=self._ray_loss[slot], error_map=self.error_map,
+                      error_inds=None if self.error_map is None else self._error_inds[slot])
+        if self._gt is not None:
+            kw.update(target_out=self._gt[slot])
+        return kw
+
+    def _bg_arg(self, slot):
+        """shade_train's bg_color of a step at ring slot `slot`: the number, or the slot's static [N,3] backgrounds."""
+        return self.bg_color if self._bg is None else self._bg[slot]
 
     def _capture(self):
         """Record the graphs: a march graph per ring slot into `_graphs`, a shade graph (shade + backward + optimizer of its `group` steps) per
@@ -274,7 +351,11 @@ class AcceleratedTrainer:
             self._ray_o = torch.empty(RING, n_rays, 3, dtype=torch.float32, device=self.dev)
             self._ray_d = torch.empty(RING, n_rays, 3, dtype=torch.float32, device=self.dev)
             self._rays = [(self._ray_o[g], self._ray_d[g]) for g in range(RING)]
-            self._targets = torch.empty(RING, n_rays, 3, dtype=torch.float32, device=self.dev)
+            self._targets = torch.empty(RING, n_rays, self.target_channels, dtype=torch.float32, device=self.dev)
+            if self._pixels:  # (a number under RGBA pixels: spread over the rays once, here)
+                self._bg = torch.full((RING, n_rays, 3), 0.0 if self.bg_mode is not None else float(self.bg_color), dtype=torch.float32, device=self.dev)
+            if self.target_channels == 4:
+                self._gt = torch.zeros(RING, n_rays, 3, dtype=torch.float32, device=self.dev)
             if self._loss_outputs:
                 self._ray_loss = torch.zeros(RING, n_rays, dtype=torch.float32, device=self.dev)
                 self.ray_loss = self._ray_loss[0]
@@ -297,28 +378,34 @@ class AcceleratedTrainer:
             r.update_mean_count()
         self._resize()
 
-    def step_group(self, rays_o, rays_d, target, next_rays=None, error_inds=None):
+    def step_group(self, rays_o, rays_d, target, next_rays=None, error_inds=None, bg=None):
         """steps_per_call = k consecutive training steps in one call: rays_o / rays_d / target [k, N, 3] -- batch i is step i's (FRESH rays every
         call: they are copied into the graphs' static buffers).  next_rays = (rays_o, rays_d) [k, N, 3] of the NEXT call: their k marches start
         now, on the second stream, beside this group's kernels; the next call must pass those very tensors.  Same arithmetic as k calls of
         `step`: the same kernels in the same order on the same data (tests/test_gpu_round4.py::test_step_group_trains_like_single_steps).
         error_inds [k, N] int64 (accelerate(error_map=)): each ray's flat cell of the map; omitted, no cell is updated.
+        target [k, N, 4] with accelerate(target_channels=4); bg [k, N, 3] fp32 with accelerate(bg_color="given"): the rays' backgrounds.
         Returns the last step's loss (device scalar)."""
         assert self.group > 1 and rays_o.dim() == 3 and rays_o.shape[0] == self.group, "step_group: [steps_per_call, N, 3] rays (steps_per_call > 1)"
-        return self._steps(rays_o, rays_d, target, next_rays, error_inds)
+        self._check_batch(target, bg, True)
+        return self._steps(rays_o, rays_d, target, next_rays, error_inds, bg)
 
-    def step(self, rays_o, rays_d, target, next_rays=None, error_inds=None):
+    def step(self, rays_o, rays_d, target, next_rays=None, error_inds=None, bg=None):
         """One training step on a batch of rays [N,3], [N,3] and their target colours [N,3] (device tensors; N fixed after the first call).
         next_rays = (rays_o, rays_d) of the batch the NEXT call will pass: its march starts now, beside this step (module docstring).
         error_inds [N] int64 (accelerate(error_map=)): each ray's flat cell of the map; omitted, no cell is updated.
+        target [N,4] RGBA pixels with accelerate(target_channels=4): the step blends them over the rays' backgrounds (`trainer.gt_rgb` is the
+        blended target afterwards, `trainer.last_bg` the backgrounds); bg [N,3] fp32 with accelerate(bg_color="given").
         Returns the loss as a device scalar that the NEXT call overwrites.  It is `step_group` with one batch."""
+        self._check_batch(target, bg, False)
         # views, for contiguous rays: the hand-over of `next_rays` is recognised by the address of these tensors (a reshape of a non-contiguous
         # tensor would be a fresh copy with a fresh address every call)
-        return self._steps(rays_o.reshape(1, -1, 3), rays_d.reshape(1, -1, 3), target.reshape(1, -1, 3), next_rays,
-                           None if error_inds is None else error_inds.reshape(1, -1))
+        return self._steps(rays_o.reshape(1, -1, 3), rays_d.reshape(1, -1, 3), target.reshape(1, -1, self.target_channels), next_rays,
+                           None if error_inds is None else error_inds.reshape(1, -1), None if bg is None else bg.reshape(1, -1, 3))
 
-    def _steps(self, rays_o, rays_d, target, next_rays, error_inds=None):
-        """The k steps of one call, on ring slots g0 .. g0 + k: `step_group`, and `step` as its k = 1.  rays_o / rays_d / target: [k, N, 3]."""
+    def _steps(self, rays_o, rays_d, target, next_rays, error_inds=None, bg=None):
+        """The k steps of one call, on ring slots g0 .. g0 + k: `step_group`, and `step` as its k = 1.  rays_o / rays_d: [k, N, 3]; target
+        [k, N, target_channels]; bg: [k, N, 3] or None (`_check_batch` has seen both)."""
         r, k = self.renderer, rays_o.shape[0]
         assert rays_o.is_contiguous() and rays_d.is_contiguous(), "rays_o / rays_d must be contiguous tensors (next_rays are recognised by their address)"
         if error_inds is not None and self.error_map is None:
@@ -334,6 +421,7 @@ class AcceleratedTrainer:
             # after every change of the buffer size -- eager steps at the size the graphs will be recorded with: two, or `group` of them, so that
             # the ring slot is a multiple of `group` when the graphs start
             assert self._ahead is None
+            self._fill_backgrounds(r.local_step % RING, k, bg)
             for i in range(k):
                 self._eager_step(rays_o[i], rays_d[i], target[i], None if error_inds is None else error_inds[i])
             return self.loss
@@ -356,6 +444,7 @@ class AcceleratedTrainer:
             for g in range(g0, g0 + k):
                 self._graphs[g][0].replay()
         self._targets[g0:g0 + k].copy_(target, non_blocking=True)
+        self._fill_backgrounds(g0, k, bg)
         self._set_error_inds(g0, k, error_inds)
         ready = None
         if next_rays is not None:
@@ -363,8 +452,7 @@ class AcceleratedTrainer:
             ready.record(main)  # everything enqueued so far (the production of the next rays, an occupancy update, this call's marches) -- NOT the rest of this call
         self._groups[g0 // k].replay()
         r.local_step = g0 + k
-        if self._loss_outputs:
-            self.ray_loss = self._ray_loss[g0 + k - 1]
+        self._published(g0 + k - 1)
         if self._lr_sched is not None:
             self._lr_sched.advance(k)
         if g0 + k < RING:
@@ -397,8 +485,7 @@ class AcceleratedTrainer:
         self._set_error_inds(g, 1, error_inds)
         marched, _ = self._march(ro, rd, mean_count=self._M if sized else None)
         self._shade(marched, g)
-        if self._loss_outputs:
-            self.ray_loss = self._ray_loss[g]
+        self._published(g)
         if self._lr_sched is not None:
             self._lr_sched.advance(1)
         self._primed += 1
@@ -535,10 +622,11 @@ class CurvedTrainer(AcceleratedTrainer):
     def __init__(self, renderer, regular_weight=1e-8, rays_per_batch=None, lr=1e-2, betas=(0.9, 0.99), eps=1e-15, dt_gamma=1 / 128, bg_color=1,
                  perturb=True, max_steps=1024, amp_dtype=torch.float16, graph=True, steps_per_call=1, march_across_ring_end=False, pipeline_adam=0,
                  skip_dead_samples=None, fused_table_update=None, fused_composite_step=None, lr_scheduler=None, total_steps=None, criterion=None,
-                 error_map=None, ema_decay=None):
+                 error_map=None, ema_decay=None, target_channels=3, bg_generator=None):
         from .curved import CurvedField
 
         _refuse_options(lr_scheduler, pipeline_adam, ema_decay)
+        self._init_pixels(bg_color, target_channels, bg_generator)
         self._init_criterion(criterion, error_map)
 
         field = renderer.field
@@ -584,7 +672,7 @@ class CurvedTrainer(AcceleratedTrainer):
             p.grad = None
         self._centres_grad.zero_()
         with torch.autocast("cuda", dtype=self.amp_dtype):
-            image, depth, loss, scaled = r.shade_train(marched, self.bg_color, target=self._targets[slot], scale=None, **self._loss_args(slot))
+            image, depth, loss, scaled = r.shade_train(marched, self._bg_arg(slot), target=self._targets[slot], scale=None, **self._loss_args(slot))[:4]
         self.scaler.scale(scaled).backward()
         from gridencoder.grid_clustering import grid_cluster_step
 
@@ -609,7 +697,12 @@ def accelerate(renderer, **kw):
     and error_map (a contiguous fp32 device tensor updated in place as 0.1 * old + 0.9 * ray loss at the cells `step(..., error_inds=)` names; the
     map is written by every step, skipped by the loss scaler or not; `trainer.ray_loss` is the last step's per-ray loss),
     ema_decay (a float in (0, 1), the reference Trainer's 0.95: `trainer.ema` is an ema.DeviceEMA -- torch_ema's interface -- whose update is the
-    last launch of every step, applied or skipped; None, the default: no average).
+    last launch of every step, applied or skipped; None, the default: no average),
+    bg_color (a number, the default 1; "random": the reference's per-pixel torch.rand_like background, one torch.rand of [k,N,3] per call in front
+    of the replay, seeded by bg_generator; "given": `step(..., bg=[N,3])` / `step_group(..., bg=[k,N,3])` pass it) and target_channels (3, or 4:
+    the batches are RGBA pixels [N,4] the step blends over the background, nerf/utils.py:602-615; `trainer.gt_rgb` / `trainer.last_bg` are the
+    last step's blended target and background).  Not here: color_space == 'linear', the background network (bg_radius > 0), gradients to the
+    background or to alpha; eval_step's blend over white is one torch expression on the caller's side.
     A renderer over a curved.CurvedField gets a CurvedTrainer (its docstring; regular_weight, default 1e-8)."""
     from .curved import CurvedField
 

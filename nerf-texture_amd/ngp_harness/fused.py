@@ -371,6 +371,43 @@ def step_loss_desc(criterion, ray_loss, error_map, error_inds, n_rays, dev):
     return StepLossDesc(kind, param, ptr(ray_loss), ptr(error_map), ptr(error_inds), 0 if error_map is None else error_map.numel(), 0.1, 0.9)
 
 
+def step_pixels(bg, target, n_rays, dev, target_out=None):
+    """The nerftex_step_pixels_desc of a tail call -- the reference's per-pixel random background and RGBA images (nerf/utils.py:602-615) -- or
+    None when bg is a number and target is [N,3] (the call is then the entry it always was).  bg: a number, or a contiguous fp32 [N,3] tensor,
+    one colour per ray; target: [N,3], or [N,4] RGBA -- the kernels then blend gt = rgb * a + bg * (1 - a) into `target_out` ([N,3] fp32, made
+    here when not given).  A number with an RGBA target is spread over the rays.  No gradient reaches bg or alpha.
+    -> (desc, bg_rays, the [N,3] target the entry takes or None, the blended target or None): the tensors are what the descriptor points at."""
+    from nerftex_hip import StepPixelsDesc
+
+    tensor_bg = isinstance(bg, torch.Tensor)
+    if target.dim() != 2 or target.shape[0] != n_rays or target.shape[1] not in (3, 4):
+        raise ValueError(f"target: [N,3] colours or [N,4] RGBA pixels for N = {n_rays} rays, got {tuple(target.shape)}")
+    rgba = target.shape[1] == 4
+    if not tensor_bg and not rgba:
+        if target_out is not None:
+            raise ValueError("target_out: only an [N,4] RGBA target is blended; an [N,3] target is the target")
+        return None
+    if tensor_bg:
+        if not (bg.dtype == torch.float32 and tuple(bg.shape) == (n_rays, 3) and bg.device == dev and bg.is_contiguous()):
+            raise ValueError(f"bg: a number, or a contiguous torch.float32 tensor of shape {(n_rays, 3)} on {dev}, got {bg.dtype} {tuple(bg.shape)} on {bg.device}")
+        bg_rays = bg.detach()
+    else:
+        bg_rays = torch.full((n_rays, 3), float(bg), dtype=torch.float32, device=dev)
+    if not rgba:
+        return StepPixelsDesc(ptr(bg_rays), None, None), bg_rays, target, None
+    if not (target.dtype == torch.float32 and target.is_contiguous() and target.device == dev):
+        raise ValueError(f"target: RGBA pixels are a contiguous torch.float32 tensor on {dev}, got {target.dtype} on {target.device}")
+    if target_out is None:
+        target_out = torch.empty(n_rays, 3, dtype=torch.float32, device=dev)
+    elif not (target_out.dtype == torch.float32 and tuple(target_out.shape) == (n_rays, 3) and target_out.device == dev and target_out.is_contiguous()):
+        raise ValueError(f"target_out: a contiguous torch.float32 tensor of shape {(n_rays, 3)} on {dev}, got {target_out.dtype} {tuple(target_out.shape)}")
+    return StepPixelsDesc(ptr(bg_rays), ptr(target), ptr(target_out)), bg_rays, None, target_out
+
+
+def _by(desc):
+    return None if desc is None else ctypes.byref(desc)
+
+
 class _render_tail(Function):
     """image + (1 - weights_sum) * bg, depth normalisation and mean squared error against `target` in one launch
     (nerf/renderer.py:417-425 + the MSE of nerf/utils.py:602-640); returns (image_out, depth_out, loss * loss_mul, scaled loss).
@@ -382,6 +419,11 @@ class _render_tail(Function):
         args = [t.contiguous().float() for t in (weights_sum, depth, image, nears, fars, target)]
         weights_sum, depth, image, nears, fars, target = args
         N, dev = weights_sum.shape[0], weights_sum.device
+        # a tensor bg or an [N,4] target: the _px entries with a nerftex_step_pixels_desc (step_pixels); else the calls below, as ever
+        pixels = step_pixels(bg, target, N, dev)
+        ctx.pixels = pixels is not None  # (a flag: the tensors go through save_for_backward)
+        if pixels is not None:
+            return _render_tail._forward_px(ctx, weights_sum, depth, image, nears, fars, pixels, loss_mul, scale, crit)
         assert image.shape == (N, 3) and target.shape == (N, 3) and depth.shape == (N,)
         assert scale is None or (scale.dtype == torch.float32 and scale.numel() == 1 and scale.device == dev)
         image_out = torch.empty_like(image)
@@ -405,10 +447,46 @@ class _render_tail(Function):
         return image_out, depth_out, loss, scaled
 
     @staticmethod
-    def backward(ctx, _gi, _gd, _gl, grad_scaled):
-        image_out, target, scale = ctx.saved_tensors
+    def _forward_px(ctx, weights_sum, depth, image, nears, fars, pixels, loss_mul, scale, crit):
+        """The forward with a pixels descriptor -> (image_out, depth_out, loss, scaled) and, with an RGBA target, the blended target as a fifth."""
+        px, bg_rays, target, gt = pixels
+        N, dev = weights_sum.shape[0], weights_sum.device
+        assert image.shape == (N, 3) and depth.shape == (N,)
+        assert scale is None or (scale.dtype == torch.float32 and scale.numel() == 1 and scale.device == dev)
+        image_out, depth_out = torch.empty_like(image), torch.empty_like(depth)
+        losses = torch.empty(2, dtype=torch.float32, device=dev)
+        scratch = _tail_scratch(dev, (N + 255) // 256)
+        ctx.desc = desc = None if crit is None else step_loss_desc(*crit, N, dev)
+        check(lib.nerftex_render_tail_forward_px(ptr(weights_sum), ptr(depth), ptr(image), ptr(nears), ptr(fars), ptr(target), 0.0, float(loss_mul), N,
+                                                 ptr(image_out), ptr(depth_out), ptr(scratch[1]), ptr(scratch[0]), ptr(losses), ptr(scale),
+                                                 losses.data_ptr() + 4, None, 0, _by(desc), ctypes.byref(px), stream()))
+        ctx.save_for_backward(image_out, target if gt is None else gt, scale, bg_rays)
+        ctx.consts = (0.0, float(loss_mul))
+        loss, scaled = losses[0], losses[1]
+        ctx.set_materialize_grads(False)
+        if gt is None:
+            ctx.mark_non_differentiable(image_out, depth_out, loss)
+            return image_out, depth_out, loss, scaled
+        ctx.mark_non_differentiable(image_out, depth_out, loss, gt)
+        return image_out, depth_out, loss, scaled, gt
+
+    @staticmethod
+    def backward(ctx, _gi, _gd, _gl, grad_scaled, _gt=None):
         if grad_scaled is None:
             return (None,) * 10
+        if ctx.pixels:
+            from nerftex_hip import StepPixelsDesc
+
+            image_out, target, scale, bg_rays = ctx.saved_tensors
+            N = image_out.shape[0]
+            grad_scaled = grad_scaled.contiguous().float()
+            grad_image = torch.empty_like(image_out)
+            grad_ws = torch.empty(N, dtype=torch.float32, device=image_out.device)
+            px = StepPixelsDesc(ptr(bg_rays), None, None)  # (the target is the [N,3] the forward took or blended)
+            check(lib.nerftex_render_tail_backward_px(ptr(grad_scaled), ptr(scale), ctx.consts[1], ptr(image_out), ptr(target), 0.0, N, ptr(grad_image),
+                                                      ptr(grad_ws), _by(ctx.desc), ctypes.byref(px), stream()))
+            return grad_ws, None, grad_image, None, None, None, None, None, None, None
+        image_out, target, scale = ctx.saved_tensors
         bg, loss_mul = ctx.consts
         N = image_out.shape[0]
         grad_scaled = grad_scaled.contiguous().float()
@@ -433,12 +511,21 @@ class _composite_tail(Function):
     the loss); the backward returns them when the root gradient is that very tensor, and runs the backward launch as before for any other."""
 
     @staticmethod
-    def forward(ctx, sigmas, rgbs, deltas, rays, nears, fars, target, bg, loss_mul, scale, live_holder=None, one=None, crit=None):
+    def forward(ctx, sigmas, rgbs, deltas, rays, nears, fars, target, bg, loss_mul, scale, live_holder=None, one=None, crit=None, target_out=None):
         sigmas, rgbs, deltas = sigmas.contiguous().float(), rgbs.contiguous().float(), deltas.contiguous().float()
         nears, fars, target = nears.contiguous().float(), fars.contiguous().float(), target.contiguous().float()
         rays = rays.contiguous()
         M, N, dev = sigmas.shape[0], rays.shape[0], sigmas.device
-        assert target.shape == (N, 3) and rays.dtype == torch.int32
+        # a tensor bg or an [N,4] target: the _px entries with a nerftex_step_pixels_desc (step_pixels) -- `target` is then the [N,3] the entries
+        # take (None with RGBA pixels), `gt` the blended target they write and this node returns as a fifth output; else the calls below, as ever
+        pixels = step_pixels(bg, target, N, dev, target_out)
+        px, bg_rays, gt = None, None, None
+        if pixels is not None:
+            px, bg_rays, target, gt = pixels
+            bg = 0.0  # (not read by the _px entries)
+        else:
+            assert target.shape == (N, 3)
+        assert rays.dtype == torch.int32
         assert scale is None or (scale.dtype == torch.float32 and scale.numel() == 1 and scale.device == dev)
         per_ray = torch.empty(9, N, dtype=torch.float32, device=dev)  # weights_sum, depth, depth_out | image [N,3] | image_out [N,3]
         weights_sum, depth, depth_out = per_ray[0], per_ray[1], per_ray[2]
@@ -464,7 +551,9 @@ class _composite_tail(Function):
             step_args = (ptr(sigmas), ptr(rgbs), ptr(deltas), ptr(rays), M, N, ptr(nears), ptr(fars), ptr(target), float(bg), float(loss_mul), ptr(scale),
                          ptr(weights_sum), ptr(depth), ptr(image), ptr(image_out), ptr(depth_out), ptr(err), None if defer else ptr(losses),
                          losses.data_ptr() + 4, ptr(grads), grads.data_ptr() + 4 * M, ptr(flags))
-            if desc is None:
+            if px is not None:
+                check(lib.nerftex_composite_step_px(*step_args, _by(desc), ctypes.byref(px), stream()))
+            elif desc is None:
                 check(lib.nerftex_composite_step(*step_args, stream()))
             else:
                 check(lib.nerftex_composite_step_ex(*step_args, ctypes.byref(desc), stream()))
@@ -475,12 +564,7 @@ class _composite_tail(Function):
             if flags is not None:
                 live_holder["flags"], live_holder["consume"] = flags, True
                 live_holder["last"] = flags.clone() if live_holder.get("keep_last") else None
-            ctx.save_for_backward(sigmas, rgbs, deltas, rays, weights_sum, image, image_out, target, scale)
-            ctx.consts = (float(bg), float(loss_mul))
-            loss, scaled = losses[0], losses[1]
-            ctx.mark_non_differentiable(image_out, depth_out, loss)
-            ctx.set_materialize_grads(False)
-            return image_out, depth_out, loss, scaled
+            return _composite_tail._finish(ctx, sigmas, rgbs, deltas, rays, weights_sum, image, image_out, depth_out, target, scale, bg, loss_mul, losses, bg_rays, gt)
         scratch = _tail_scratch(dev, (N + 255) // 256)
         check(lib.nerftex_composite_rays_train_forward(ptr(sigmas), ptr(rgbs), ptr(deltas), ptr(rays), M, N, ptr(weights_sum), ptr(depth), ptr(image), stream()))
         # live_holder (a dict the field's backward shares: Renderer.shade_train): this node's backward leaves one flag per 32 samples in it -- 0 = all 32
@@ -491,28 +575,39 @@ class _composite_tail(Function):
         tail_args = (ptr(weights_sum), ptr(depth), ptr(image), ptr(nears), ptr(fars), ptr(target), float(bg), float(loss_mul), N, ptr(image_out), ptr(depth_out),
                      ptr(scratch[1]), ptr(scratch[0]), ptr(losses), ptr(scale), losses.data_ptr() + 4, ptr(ctx.step_live),
                      0 if ctx.step_live is None else ctx.step_live.numel())
-        if desc is None:
+        if px is not None:
+            check(lib.nerftex_render_tail_forward_px(*tail_args, _by(desc), ctypes.byref(px), stream()))
+        elif desc is None:
             check(lib.nerftex_render_tail_forward_live(*tail_args, stream()))
         else:
             check(lib.nerftex_render_tail_forward_ex(*tail_args, ctypes.byref(desc), stream()))
-        ctx.save_for_backward(sigmas, rgbs, deltas, rays, weights_sum, image, image_out, target, scale)
-        ctx.consts = (float(bg), float(loss_mul))
-        loss, scaled = losses[0], losses[1]
-        ctx.mark_non_differentiable(image_out, depth_out, loss)
-        ctx.set_materialize_grads(False)
-        return image_out, depth_out, loss, scaled
+        return _composite_tail._finish(ctx, sigmas, rgbs, deltas, rays, weights_sum, image, image_out, depth_out, target, scale, bg, loss_mul, losses, bg_rays, gt)
 
     @staticmethod
-    def backward(ctx, _gi, _gd, _gl, grad_scaled):
-        sigmas, rgbs, deltas, rays, weights_sum, image, image_out, target, scale = ctx.saved_tensors
+    def _finish(ctx, sigmas, rgbs, deltas, rays, weights_sum, image, image_out, depth_out, target, scale, bg, loss_mul, losses, bg_rays, gt):
+        """What both forms of the forward end with: the tensors the backward reads, the outputs (five with a blended target)."""
+        # (the backward's target: the [N,3] the forward took, or the one it blended; bg_rays: None without a pixels descriptor)
+        ctx.save_for_backward(sigmas, rgbs, deltas, rays, weights_sum, image, image_out, target if gt is None else gt, scale, bg_rays)
+        ctx.consts = (float(bg), float(loss_mul))
+        loss, scaled = losses[0], losses[1]
+        ctx.set_materialize_grads(False)
+        if gt is None:
+            ctx.mark_non_differentiable(image_out, depth_out, loss)
+            return image_out, depth_out, loss, scaled
+        ctx.mark_non_differentiable(image_out, depth_out, loss, gt)
+        return image_out, depth_out, loss, scaled, gt
+
+    @staticmethod
+    def backward(ctx, _gi, _gd, _gl, grad_scaled, _gt=None):
+        sigmas, rgbs, deltas, rays, weights_sum, image, image_out, target, scale, bg_rays = ctx.saved_tensors
         if grad_scaled is None:
-            return (None,) * 13
+            return (None,) * 14
         if ctx.step_grads is not None and grad_scaled.data_ptr() == ctx.one_ptr and grad_scaled.numel() == 1:
-            return (*ctx.step_grads, None, None, None, None, None, None, None, None, None, None, None)  # computed by the forward's launch
+            return (*ctx.step_grads, None, None, None, None, None, None, None, None, None, None, None, None)  # computed by the forward's launch
         bg, loss_mul = ctx.consts
         M, N = sigmas.shape[0], rays.shape[0]
         if N == 0 or M == 0:
-            return torch.zeros_like(sigmas), torch.zeros_like(rgbs), None, None, None, None, None, None, None, None, None, None, None
+            return torch.zeros_like(sigmas), torch.zeros_like(rgbs), None, None, None, None, None, None, None, None, None, None, None, None
         grad_scaled = grad_scaled.contiguous().float()
         # PRECONDITION of the uninitialised gradient buffers below: `rays` are the records of THIS library's march with the counter at zero
         # on entry (march_rays_train / march_rays_train_fresh: record n = ray n, offsets an exclusive prefix sum from 0), so that the rows past
@@ -523,13 +618,18 @@ class _composite_tail(Function):
         grad_sigmas, grad_rgbs = grads[:M], grads[M:].view(M, 3)
         bwd_args = (ptr(grad_scaled), ptr(scale), loss_mul, ptr(image_out), ptr(target), bg, ptr(sigmas), ptr(rgbs), ptr(deltas), ptr(rays), ptr(weights_sum),
                     ptr(image), M, N, ptr(grad_sigmas), ptr(grad_rgbs), ptr(ctx.step_live))
-        if ctx.desc is None:
+        if bg_rays is not None:
+            from nerftex_hip import StepPixelsDesc
+
+            px = StepPixelsDesc(ptr(bg_rays), None, None)  # (the target is the [N,3] the forward took or blended)
+            check(lib.nerftex_composite_tail_backward_px(*bwd_args, _by(ctx.desc), ctypes.byref(px), stream()))
+        elif ctx.desc is None:
             check(lib.nerftex_composite_tail_backward_live(*bwd_args, stream()))
         else:
             check(lib.nerftex_composite_tail_backward_ex(*bwd_args, ctypes.byref(ctx.desc), stream()))
         if ctx.step_live is not None and ctx.step_grads is None:
             ctx.live_holder["flags"] = ctx.live_holder["last"] = ctx.step_live  # ("last" stays for whoever wants to look: bench.py's dead-step fraction)
-        return grad_sigmas, grad_rgbs, None, None, None, None, None, None, None, None, None, None, None
+        return grad_sigmas, grad_rgbs, None, None, None, None, None, None, None, None, None, None, None, None
 
 
 def _crit(criterion, ray_loss, error_map, error_inds):
@@ -540,14 +640,17 @@ def _crit(criterion, ray_loss, error_map, error_inds):
 
 
 def composite_tail(sigmas, rgbs, deltas, rays, nears, fars, target, bg=1.0, loss_mul=1.0, scale=None, live_holder=None, one=None, criterion=None,
-                   ray_loss=None, error_map=None, error_inds=None):
+                   ray_loss=None, error_map=None, error_inds=None, target_out=None):
     """-> (image_out, depth_out, loss, scaled_loss): compositing, background blend, depth normalisation and the loss; one backward launch.
     live_holder: a dict shared with the fused field's backward (Renderer.shade_train, skip_dead_samples): the backward leaves its step flags there.
     one: the root-gradient tensor of the coming `scaled_loss.backward(one)` (a device 1.0): forward + backward become one launch.
     criterion / ray_loss / error_map / error_inds (`step_loss_desc`): the loss is the criterion's (default: MSE), the rays' losses and the error
-    map's moving average are written by the forward's launch, in either form."""
+    map's moving average are written by the forward's launch, in either form.
+    bg: a number, or an fp32 [N,3] tensor with one background colour per ray; target: [N,3], or [N,4] RGBA pixels, which the forward blends
+    over bg (`step_pixels`: the reference's random background, nerf/utils.py:602-615) -- the blended target, the reference's gt_rgb, is then a
+    FIFTH output (written into `target_out` when given).  No gradient reaches bg or alpha."""
     return _composite_tail.apply(sigmas, rgbs, deltas, rays, nears, fars, target, bg, loss_mul, scale, live_holder, one,
-                                 _crit(criterion, ray_loss, error_map, error_inds))
+                                 _crit(criterion, ray_loss, error_map, error_inds), target_out)
 
 
 _SCRATCH = {}
@@ -565,5 +668,5 @@ def _tail_scratch(dev, blocks):
 def render_tail(weights_sum, depth, image, nears, fars, target, bg=1.0, loss_mul=1.0, scale=None, criterion=None, ray_loss=None, error_map=None,
                 error_inds=None):
     """-> (image_out, depth_out, loss, scaled_loss); call backward on scaled_loss (== loss when scale is None).
-    criterion / ray_loss / error_map / error_inds: as for `composite_tail`."""
+    criterion / ray_loss / error_map / error_inds: as for `composite_tail`; so are a tensor bg and an [N,4] target (a fifth output: the blended target)."""
     return _render_tail.apply(weights_sum, depth, image, nears, fars, target, bg, loss_mul, scale, _crit(criterion, ray_loss, error_map, error_inds))

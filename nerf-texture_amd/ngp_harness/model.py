@@ -400,14 +400,15 @@ class Renderer(nn.Module):
         self.local_step = 0
 
     def render_train(self, rays_o, rays_d, dt_gamma=0.0, bg_color=1, perturb=True, force_all_rays=False, max_steps=1024, counter=None,
-                     mean_count=None, target=None, loss_mul=1.0, scale=None, criterion=None, ray_loss=None, error_map=None, error_inds=None):
+                     mean_count=None, target=None, loss_mul=1.0, scale=None, criterion=None, ray_loss=None, error_map=None, error_inds=None,
+                     target_out=None):
         """Training branch of run_cuda (:361-425). Returns image [N,3], depth [N], and the sample count tensor.
 
         counter / mean_count: for graph replay the caller supplies a fixed counter tensor and a fixed buffer size and does the
         step-counter ring bookkeeping itself (`commit_counter`); by default both come from the ring like in the reference."""
         marched, counter = self.march_train(rays_o, rays_d, dt_gamma, perturb, force_all_rays, max_steps, counter, mean_count)
         if target is not None:  # fused tail: (image, depth, loss, scaled loss, counter)
-            return (*self.shade_train(marched, bg_color, target, loss_mul, scale, criterion, ray_loss, error_map, error_inds), counter)
+            return (*self.shade_train(marched, bg_color, target, loss_mul, scale, criterion, ray_loss, error_map, error_inds, target_out), counter)
         image, depth = self.shade_train(marched, bg_color)
         return image, depth, counter
 
@@ -439,13 +440,16 @@ class Renderer(nn.Module):
                                                                 128, force_all_rays, dt_gamma, max_steps)
         return (nears, fars, xyzs, dirs, deltas, rays), counter
 
-    def shade_train(self, marched, bg_color=1, target=None, loss_mul=1.0, scale=None, criterion=None, ray_loss=None, error_map=None, error_inds=None):
+    def shade_train(self, marched, bg_color=1, target=None, loss_mul=1.0, scale=None, criterion=None, ray_loss=None, error_map=None, error_inds=None,
+                    target_out=None):
         """Second half (:389-425): field evaluation, compositing, background.
 
-        target [N,3] (with a scalar bg_color): the blend, the depth normalisation and the MSE against the target pixels run as one
+        target [N,3]: the blend, the depth normalisation and the MSE against the target pixels run as one
         kernel (ngp_harness/fused.py composite_tail); returns (image, depth, loss * loss_mul, that times the loss scaler's `scale`)
         instead of (image, depth); backward goes through the last one.  criterion / ray_loss / error_map / error_inds (with a target):
-        another criterion than the MSE, the rays' losses and the error map's update, by the same kernel (fused.step_loss_desc)."""
+        another criterion than the MSE, the rays' losses and the error map's update, by the same kernel (fused.step_loss_desc).
+        bg_color: a number, or an fp32 [N,3] tensor -- the reference's per-pixel random background (nerf/utils.py:602); target [N,4]: RGBA
+        pixels, blended over bg_color by the same kernel, the blended target (gt_rgb) returned as a fifth value (fused.step_pixels)."""
         nears, fars, xyzs, dirs, deltas, rays = marched
         # skip_dead_samples (round 6; accelerate sets it): the compositing backward flags the 32-sample steps that carry a gradient -- in a trained
         # scene most samples sit behind the point where their ray's transmittance has underflowed and get exactly zero (raymarching.cu:843-870) --
@@ -476,8 +480,10 @@ class Renderer(nn.Module):
 
             # compositing + blend + depth + MSE: one launch per direction; root_one (accelerate, fused AMP step): the tensor
             # `scaled.backward(one)` will be called with -- forward + backward in one launch
-            return fused.composite_tail(sigmas, rgbs, deltas, rays, nears, fars, target, float(bg_color), loss_mul, scale, holder, self.root_one, criterion,
-                                        ray_loss, error_map, error_inds)
+            # (a one-element tensor is the number it always was)
+            bg = bg_color if isinstance(bg_color, torch.Tensor) and bg_color.numel() != 1 else float(bg_color)
+            return fused.composite_tail(sigmas, rgbs, deltas, rays, nears, fars, target, bg, loss_mul, scale, holder, self.root_one, criterion,
+                                        ray_loss, error_map, error_inds, target_out)
         weights_sum, depth, image = raymarching.composite_rays_train(sigmas, rgbs, deltas, rays)
         image = image + (1 - weights_sum).unsqueeze(-1) * bg_color
         depth = torch.clamp(depth - nears, min=0) / (fars - nears)

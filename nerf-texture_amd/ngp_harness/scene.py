@@ -133,10 +133,12 @@ def train_batch(n_rays, H=800, W=800, radius=2.0, seed=0, n_views=1):
     return np.concatenate(o), np.concatenate(d)
 
 
-def render_targets(sc, rays_o, rays_d, n_samples=384, near=0.2, far=None, bg=1.0):
+def render_targets(sc, rays_o, rays_d, n_samples=384, near=0.2, far=None, bg=1.0, opacity=False):
     """Target colours of rays through the ANALYTIC scene `sc` (torch, on the rays' device; bench / test preparation, never timed): the blobs' density
     composited front to back over `n_samples` uniform samples with a smooth analytic colour field c(x) = 0.5 + 0.5 sin(4 x + phase), white
-    background.  What a trainer of this scene would be given as ground truth -- a field trained against it turns opaque where the blobs are."""
+    background.  What a trainer of this scene would be given as ground truth -- a field trained against it turns opaque where the blobs are.
+    opacity=True: -> (colours, the rays' opacity [N]: the compositing weights' sum) -- with bg=0 the colours are premultiplied by it: what an
+    RGBA image of the scene holds, colours / opacity over the opacity."""
     import torch
 
     dev = rays_o.device
@@ -160,4 +162,5 @@ def render_targets(sc, rays_o, rays_d, n_samples=384, near=0.2, far=None, bg=1.0
     alpha = 1.0 - torch.exp(-sigma * dt)
     T = torch.cumprod(torch.cat([torch.ones_like(alpha[:, :1]), 1.0 - alpha[:, :-1]], 1), 1)
     w = alpha * T
-    return (w[..., None] * col).sum(1) + (1.0 - w.sum(1, keepdim=True)) * bg
+    colours = (w[..., None] * col).sum(1) + (1.0 - w.sum(1, keepdim=True)) * bg
+    return (colours, w.sum(1)) if opacity else colours
