@@ -783,6 +783,49 @@ typedef struct nerftex_curved_infer_desc {
 size_t nerftex_curved_field_infer_scratch_bytes(uint32_t B);
 int nerftex_curved_field_infer(const nerftex_curved_infer_desc* d, void* stream);
 
+/* -------------------------------------------------------------------------
+ * Extension: the SH light head of the curved field -- SH_EnvmapMaterialNet.forward behind its BRDF MLP (nerf/sh_light_model.py:554-616) -- as one
+ * streaming kernel per direction instead of ~40 framework ops per sample batch, the framework's arithmetic at its rounding points:
+ *   albedo = half(sigmoid(brdf[:, :3])), spec_w = half(sigmoid(brdf[:, 3]))              (fp32 sigmoid narrowed to half)
+ *   diffuse  = albedo * clamp0(sum_{k<9} env_shs[k] lobe[k] Y_k(n))                      (svox2 basis; lobe = [3.14, 2.09 x 3, 0.79 x 5] / pi)
+ *   specular = spec_w * sum_{k<9} env_shs[k] lobe[k] Y_k(w),  w = normalize(2 cos n + r), r = d / (|d| + 1e-9), cos = -(r . n)   (SPECULAR flag;
+ *              the glossiness brdf[:, 4] does not enter: the reference's band attenuation is exp(0) as executed)
+ *   color    = safe_pow(clamp0(diffuse + specular), 1 / gamma);  specular / diffuse out = safe_pow(clamp01(.), 1 / gamma);  albedo out = clamp01(albedo)
+ * all fp32 behind the sigmoids, every operation rounded on its own.  Rows with mask[b] == 0 give 0 in every output and receive a zero grad_brdf row.
+ * nerftex_sh_light_backward recomputes the forward from the inputs (nothing saved) and writes
+ *   grad_brdf    [B, brdf_stride] fp16: columns 0..3 through the fp16 sigmoid backward (half(g) (1 - y)) y, columns 4.. zero
+ *   grad_env_shs [n_sh, n_color] fp32, OVERWRITTEN: rows 0..8 the sum over B -- wave sums, workgroup partials in `scratch`, a closing launch that adds
+ *                them in an order fixed by B alone: the same bits on every run -- rows 9.. zero.
+ * B == 0: NERFTEX_OK; the backward still writes grad_env_shs = 0.  NERFTEX_ERR_INVALID with a message, before anything is launched: a NULL descriptor
+ * or a NULL buffer that the call needs, n_sh < 9, n_color other than 1 or 3, brdf_stride < 5, gamma not positive and finite, an unknown flag, a
+ * scratch smaller than nerftex_sh_light_scratch_bytes(B).  Nothing is allocated and the host never waits: both calls can be captured.
+ * ------------------------------------------------------------------------- */
+#define NERFTEX_SH_LIGHT_SPECULAR 1
+typedef struct nerftex_sh_light_desc { /* device pointers unless noted */
+    const void* brdf;                  /* [B, brdf_stride] fp16, columns 0..4 used (stride 16 from the BRDF MLP)                  */
+    uint32_t brdf_stride;
+    const float* normals;              /* [B,3] fp32 shading normals, already normalised                                          */
+    const float* dirs;                 /* [B,3] fp32 view directions                                                              */
+    const float* env_shs;              /* [n_sh, n_color] fp32; n_sh >= 9; n_color 1 (white light) or 3                           */
+    uint32_t n_sh, n_color;
+    const uint8_t* mask;               /* [B] bytes or NULL: rows with 0 give 0 and receive 0                                     */
+    uint32_t B;
+    float gamma;                       /* host value                                                                              */
+    uint32_t flags;                    /* NERFTEX_SH_LIGHT_SPECULAR                                                               */
+    float* color;                      /* [B,3] fp32                                                                              */
+    float* specular;                   /* [B,3] fp32 or NULL                                                                      */
+    float* diffuse;                    /* [B,3] fp32 or NULL                                                                      */
+    float* albedo;                     /* [B,3] fp32 or NULL                                                                      */
+    const float* grad_color;           /* backward: [B,3] fp32 in                                                                 */
+    void* grad_brdf;                   /* backward: [B, brdf_stride] fp16 out                                                     */
+    float* grad_env_shs;               /* backward: [n_sh, n_color] fp32 out                                                      */
+    void* scratch;                     /* backward: caller-owned, >= nerftex_sh_light_scratch_bytes(B) bytes                      */
+    size_t scratch_bytes;
+} nerftex_sh_light_desc;
+int nerftex_sh_light_forward(const nerftex_sh_light_desc* d, void* stream);
+int nerftex_sh_light_backward(const nerftex_sh_light_desc* d, void* stream);
+size_t nerftex_sh_light_scratch_bytes(uint32_t B);
+
 /* grad_hc [B,16] fp16 = sigmoid backward of the fp16-narrowed grad_rgbs, columns 3..15 zero                      */
 int nerftex_field_out_backward(const float* grad_rgbs, const float* rgbs, uint32_t B, void* grad_hc, void* stream);
 

@@ -450,3 +450,6 @@ extern "C" int nerftex_field_out_backward(const float* grad_rgbs, const float* r
     }
     return check_launch("field_out_backward");
 }
+
+// ---- the SH light head of the curved field (nerftex_sh_light_forward / _backward) ----------------------------------------------------------------------
+#include "shlight.inc"

@@ -47,6 +47,8 @@ _SIGNATURES = {
     "nerftex_curved_mid_forward": [_vp, _vp, _vp, _u32, _f32, _i, _vp, _vp, _vp],
     "nerftex_curved_out_forward": [_vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp],
     "nerftex_curved_field_infer": [_vp, _vp],
+    "nerftex_sh_light_forward": [_vp, _vp],
+    "nerftex_sh_light_backward": [_vp, _vp],
     "nerftex_field_mid_backward": [_vp, _vp, _vp, _u32, _vp, _vp],
     "nerftex_field_out_forward": [_vp, _u32, _vp, _vp],
     "nerftex_field_out_backward": [_vp, _vp, _u32, _vp, _vp],
@@ -207,7 +209,18 @@ class CurvedInferDesc(C.Structure):
                 ("rgbs", _vp), ("units_dev", _vp), ("rows_per_unit", _u32), ("scratch", _vp), ("scratch_bytes", _sz)]
 
 
-EXPORTS = ["nerftex_last_error", "nerftex_version", "nerftex_tune_get", "nerftex_workspace_slots_touched", "nerftex_curved_field_infer_scratch_bytes"] + list(_SIGNATURES)
+SH_LIGHT_SPECULAR = 1  # nerftex_sh_light_desc.flags
+
+
+class SHLightDesc(C.Structure):
+    """nerftex_sh_light_desc of include/nerftex_hip.h, field for field: the SH light head's forward and backward."""
+    _fields_ = [("brdf", _vp), ("brdf_stride", _u32), ("normals", _vp), ("dirs", _vp), ("env_shs", _vp), ("n_sh", _u32), ("n_color", _u32), ("mask", _vp),
+                ("B", _u32), ("gamma", _f32), ("flags", _u32), ("color", _vp), ("specular", _vp), ("diffuse", _vp), ("albedo", _vp), ("grad_color", _vp),
+                ("grad_brdf", _vp), ("grad_env_shs", _vp), ("scratch", _vp), ("scratch_bytes", _sz)]
+
+
+EXPORTS = ["nerftex_last_error", "nerftex_version", "nerftex_tune_get", "nerftex_workspace_slots_touched", "nerftex_curved_field_infer_scratch_bytes",
+           "nerftex_sh_light_scratch_bytes"] + list(_SIGNATURES)
 
 
 def _load():
@@ -225,6 +238,8 @@ def _load():
     lib.nerftex_workspace_slots_touched.restype = C.c_uint
     lib.nerftex_curved_field_infer_scratch_bytes.argtypes = [_u32]
     lib.nerftex_curved_field_infer_scratch_bytes.restype = _sz
+    lib.nerftex_sh_light_scratch_bytes.argtypes = [_u32]
+    lib.nerftex_sh_light_scratch_bytes.restype = _sz
     for name, args in _SIGNATURES.items():
         fn = getattr(lib, name)  # AttributeError here == a symbol the header declares is not exported
         fn.argtypes = args

@@ -605,6 +605,25 @@ def draw_ring_levels(num_levels, count=RING):
     return np.array([int(np.random.choice(np.arange(num_levels), [1])[0]) for _ in range(count)], dtype=np.int32)
 
 
+def normal_cosine_loss(normal_grad, normal_est, threshold=None):
+    """nerf/utils.py:646-657 on the per-ray composited normals [N,3]: -mean(min(n_grad . n_est, cos(pi / 8))) over the rays whose supervising
+    normal is a number, both normalised with + 1e-5.  The reference selects those rays with a boolean mask (a read-back of their count); here
+    they are selected with torch.where and counted on the device: nothing is read back and the expression can be recorded into a graph.  No
+    such ray: 0 / 0, not a number, as the reference's mean over an empty selection."""
+    import math
+
+    threshold = math.cos(math.pi / 8) if threshold is None else threshold
+    normal_grad = normal_grad.detach().float()
+    normal_est = normal_est.float()
+    valid = torch.logical_not(normal_grad.isnan().any(dim=-1))
+    g = torch.where(valid.unsqueeze(-1), normal_grad, torch.zeros_like(normal_grad))
+    e = torch.where(valid.unsqueeze(-1), normal_est, torch.zeros_like(normal_est))
+    g = g / (g.norm(dim=-1, keepdim=True) + 1e-5)
+    e = e / (e.norm(dim=-1, keepdim=True) + 1e-5)
+    cos = torch.minimum((g * e).sum(dim=-1), torch.full_like(g[..., 0], threshold))
+    return -torch.where(valid, cos, torch.zeros_like(cos)).sum() / valid.sum()
+
+
 class CurvedTrainer(AcceleratedTrainer):
     """accelerate() of a Renderer over `curved.CurvedField`: the NeRF-Texture training step (main.py:85-190, nerf/utils.py:637-666) --
     image loss + regular_weight * clustering loss, torch's fused capturable Adam over field.get_params(lr) (cluster centres included) under
@@ -616,13 +635,15 @@ class CurvedTrainer(AcceleratedTrainer):
     trainer.reg_loss = the regulariser: device scalars, nothing is read back.  The fp32 parameters are current after every step (no sync()).
     criterion="l1" is main.py:187's (the reference trains this field with torch.nn.L1Loss; the default stays the MSE); error_map= is its
     --error_map (nerf/utils.py:617-632).
+    normal_loss=True (a field with light_model="SH"): the step adds the reference's cosine term on the per-ray composited normals
+    (nerf/utils.py:650-657, `normal_cosine_loss`); trainer.normal_loss is its value, a device scalar.
     Not here: prob_model (the log-variance table), world size > 1, and the ngp field's fused AMP options (HalfLeafAdam, fused table update,
     dead-sample skipping, the one-launch composite step), which are refused if asked for."""
 
     def __init__(self, renderer, regular_weight=1e-8, rays_per_batch=None, lr=1e-2, betas=(0.9, 0.99), eps=1e-15, dt_gamma=1 / 128, bg_color=1,
                  perturb=True, max_steps=1024, amp_dtype=torch.float16, graph=True, steps_per_call=1, march_across_ring_end=False, pipeline_adam=0,
                  skip_dead_samples=None, fused_table_update=None, fused_composite_step=None, lr_scheduler=None, total_steps=None, criterion=None,
-                 error_map=None, ema_decay=None, target_channels=3, bg_generator=None):
+                 error_map=None, ema_decay=None, target_channels=3, bg_generator=None, normal_loss=False):
         from .curved import CurvedField
 
         _refuse_options(lr_scheduler, pipeline_adam, ema_decay)
@@ -632,6 +653,8 @@ class CurvedTrainer(AcceleratedTrainer):
         field = renderer.field
         assert isinstance(field, CurvedField), "CurvedTrainer trains a curved.CurvedField"
         assert field.encoder_var is None, "accelerate(): prob_model=True (the log-variance table) is not on the graphed path (main.py:86 trains without it)"
+        assert not normal_loss or getattr(field, "light_model", None) == "SH", "accelerate(normal_loss=True) supervises the fine normal of CurvedField(light_model='SH')"
+        self.use_normal_loss = bool(normal_loss)
         dist = torch.distributed
         assert not (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1), "accelerate() of the curved field: world size 1"
         for name, v in (("skip_dead_samples", skip_dead_samples), ("fused_table_update", fused_table_update), ("fused_composite_step", fused_composite_step)):
@@ -659,6 +682,7 @@ class CurvedTrainer(AcceleratedTrainer):
         keep = {id(c) for c in centres}
         self._other_params = [p for p in field.parameters() if id(p) not in keep]
         self.reg_loss = torch.zeros((), dtype=torch.float32, device=self.dev)
+        self.normal_loss = torch.zeros((), dtype=torch.float32, device=self.dev)
         self._attach_schedule(lr_scheduler, total_steps)  # (the optimizer's learning rates become fp32 tensors the schedule writes)
         self._attach_ema(ema_decay)
 
@@ -671,8 +695,14 @@ class CurvedTrainer(AcceleratedTrainer):
         for p in self._other_params:
             p.grad = None
         self._centres_grad.zero_()
+        extras = {} if self.use_normal_loss else None
         with torch.autocast("cuda", dtype=self.amp_dtype):
-            image, depth, loss, scaled = r.shade_train(marched, self._bg_arg(slot), target=self._targets[slot], scale=None, **self._loss_args(slot))[:4]
+            image, depth, loss, scaled = r.shade_train(marched, self._bg_arg(slot), target=self._targets[slot], scale=None, extras_out=extras,
+                                                       **self._loss_args(slot))[:4]
+        if extras is not None:
+            normal_error = normal_cosine_loss(extras["normal_grad"], extras["normal"])
+            self.normal_loss.copy_(normal_error.detach())
+            scaled, loss = scaled + normal_error, loss + normal_error.detach()
         self.scaler.scale(scaled).backward()
         from gridencoder.grid_clustering import grid_cluster_step
 

@@ -11,7 +11,9 @@ xatlas, open3d, trimesh).
                      ++ geo (31, padded to 32) -> FFMLP 32-64-64-3 -> sigmoid; both masked by the height mask.  A field
                      `ngp_harness.model.Renderer` can march.  The tcnn networks are served by the in-tree FFMLP (the reference's own
                      transplant of the same fully-fused kernel): tests/golden/ref_python_curvedfield.npz pins the chain against the
-                     reference's modules executed with exactly that substitution;
+                     reference's modules executed with exactly that substitution.  light_model="SH" (main.py's model, :272-349):
+                     no direction encoding and no colour MLP; the SH light head (light.SHLightNet) shades with the fine normal of the
+                     factorized normal net;
   CurvedFieldLookup  round 1's minimal chain (analytic normals -> traces -> hash lookup), kept for its test.
 """
 import numpy as np
@@ -442,8 +444,15 @@ class CurvedField(torch.nn.Module):
     unless no_noise."""
 
     def __init__(self, vertices, faces, bound=1.0, h_threshold=0.05, K=8, num_level=8, hidden_dim=32, geo_feat_dim=15, hidden_dim_color=64,
-                 num_layers=2, num_layers_color=3, dir_degree=4, prob_model=False, vertex_normals=None, tbn=None, pred_normal=False):
+                 num_layers=2, num_layers_color=3, dir_degree=4, prob_model=False, vertex_normals=None, tbn=None, pred_normal=False, light_model=None, white_light=True,
+                 use_specular=True):
         super().__init__()
+        if light_model in ("SG", "Envmap"):
+            raise NotImplementedError(f"CurvedField(light_model={light_model!r}): of the reference's light models only 'SH' (main.py's) is built here; "
+                                      "the SG and Envmap models, imported environment maps and visibility probes are out of scope")
+        if light_model not in (None, "SH"):
+            raise ValueError(f"CurvedField: light_model is None (the static light model) or 'SH', but got {light_model!r}")
+        pred_normal = pred_normal or light_model == "SH"  # the light head shades with the fine normal
         from ffmlp import FFMLP
         from gridencoder import GridEncoder
         from shencoder import SHEncoder
@@ -456,15 +465,23 @@ class CurvedField(torch.nn.Module):
         self.encoder_var = GridEncoder(**kw) if prob_model else None
         if prob_model:
             torch.nn.init.normal_(self.encoder_var.embeddings, std=1e-5)  # reset_parameters(std=1e-5), tools/map.py:566
-        # pred_normal (the reference's default, tools/map.py:547, :585-588): the factorized fine-normal net; its consumer -- the light models of
-        # network_curvedfield.py:331-380 -- is out of scope, so forward() keeps the coarse normal (render_light_model False, :283) and the fine
-        # normal is what `embed(..., with_fine_normal=True)` / `fine_normal()` return
+        # pred_normal (the reference's default, tools/map.py:547, :585-588): the factorized fine-normal net.  Its consumer is the light model
+        # (network_curvedfield.py:331-380): with light_model="SH" forward() shades with the fine normal; without a light model forward() keeps
+        # the coarse normal (render_light_model False, :283) and the fine normal is what `embed(..., with_fine_normal=True)` / `fine_normal()` return
         self.normal_net = FactorizedNormalNet(x_dim=self.encoder.output_dim, z_dim=1 + 2 * self.multires) if pred_normal else None
         if pred_normal:
             self.normal_net.encoder.embeddings.data.uniform_(0, 1e-3)  # tools/map.py:588
         self.in_dim = self.encoder.output_dim + 1 + 2 * self.multires  # 16 + 25
         self.in_pad = (self.in_dim + 15) // 16 * 16
         self.sigma_net = FFMLP(input_dim=self.in_pad, output_dim=1 + geo_feat_dim, hidden_dim=hidden_dim, num_layers=num_layers)
+        self.light_model = light_model
+        if light_model == "SH":  # network_curvedfield.py:115-118, :207-208: the light head instead of the direction encoding and the colour MLP
+            from .light import SHLightNet
+
+            self.light_net = SHLightNet(input_dim=geo_feat_dim, white_light=white_light, use_specular=use_specular)  # (NeRFNetwork's keywords and defaults, :61)
+            self.light_visual_mode, self.smooth_grad_weight = "Full", 1e-1
+            self.encoder_dir = self.color_net = None
+            return
         self.encoder_dir = SHEncoder(input_dim=3, degree=dir_degree)
         self.color_in = self.encoder_dir.output_dim + geo_feat_dim
         self.color_pad = (self.color_in + 15) // 16 * 16
@@ -540,10 +557,42 @@ class CurvedField(torch.nn.Module):
 
     def _glue_fused(self, x_dtype_ok=True):
         """The three glue launches (csrc/fieldglue.hip, round 6) serve the default shapes under fp16 autocast without the probabilistic table."""
-        return (getattr(self, "fused_glue", True) and self.encoder_var is None and self.in_dim == 41 and self.in_pad == 48 and self.color_pad == 32
+        return (getattr(self, "light_model", None) is None and getattr(self, "fused_glue", True) and self.encoder_var is None and self.in_dim == 41 and self.in_pad == 48 and self.color_pad == 32
                 and self.geo_feat_dim == 15 and self.encoder_dir.output_dim == 16 and torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.float16)
 
+    def _forward_light(self, x, d, normal_supervision=False):
+        """network_curvedfield.py:272-301, 327-349, 396-409 with the SH light model: the head shades with the fine normal -- detached in training
+        (:331), blended with the coarse normal by fc_weight and renormalised in eval (:293-301) -- and the view direction as it is.  In eval
+        `light_visual_mode` picks the head's output.  normal_supervision (training): the reference's ret_dict, 'normal' = the fine normal on the
+        graph, 'normal_grad' = the density normal (first order, detached: the reference detaches it too) blended with the coarse normal by
+        smooth_grad_weight and renormalised (:274-277); samples whose density normal is not a number leave the mask (:258).
+        The reference differentiates sigma on EVERY training forward of a light-model network (:236-258), so there its training mask always
+        drops those samples; here a training call without normal_supervision does not evaluate the density normal and keeps them.  With
+        normal_supervision the projector and the table lookup run twice, once in embed() and once in density_normal()."""
+        embed, normal_coarse, h_mask, normal_fine = self.embed(x, with_fine_normal=True)
+        sigma, geo = self._sigma(embed)
+        ret = {}
+        if self.training and normal_supervision:
+            _, normal_grad, h_mask = self.density_normal(x)
+            sup = normal_grad.detach() * (1 - self.smooth_grad_weight) + normal_coarse * self.smooth_grad_weight
+            ret = {"normal": normal_fine, "normal_grad": sup / (sup.norm(dim=-1, keepdim=True) + 1e-5)}
+        normal = normal_fine / (normal_fine.norm(dim=-1, keepdim=True) + 1e-5)
+        if self.training:
+            normal = normal.detach()
+        else:
+            coarse = normal_coarse / (normal_coarse.norm(dim=-1, keepdim=True) + 1e-5)
+            normal = self.fc_weight * normal + (1 - self.fc_weight) * coarse
+            normal = normal / (normal.norm(dim=-1, keepdim=True) + 1e-5)
+        full, specular, diffuse, albedo = self.light_net(geo, normal, d, mask=h_mask)
+        modes = {"Full": full, "Specular": specular, "Diffuse": diffuse, "Albedo": albedo}
+        if not self.training and self.light_visual_mode not in modes:
+            raise ValueError(f"CurvedField.light_visual_mode is one of {sorted(modes)}, but got {self.light_visual_mode!r}")
+        color = full if self.training else modes[self.light_visual_mode]
+        return torch.where(h_mask, sigma, torch.zeros_like(sigma)), color, ret
+
     def forward(self, x, d, **kwargs):
+        if getattr(self, "light_model", None) == "SH":
+            return self._forward_light(x, d, normal_supervision=bool(kwargs.get("normal_supervision", False)))
         if self._glue_fused():
             p_sur, sdf, h_mask, normal, local_tbn, _, z_embed = self.projector.project_fused(x, multires=self.multires)
             x_embed = self.encoder(p_sur, bound=self.bound)
@@ -573,7 +622,14 @@ class CurvedField(torch.nn.Module):
         grid's and the tracer's handles, the mesh buffers' storage, the projector's and the field's scalars, train / eval, the fused switch."""
         p = self.projector
         return (p._knn.value, p.tracer._handle.value, p.mesh_vertices.data_ptr(), p.vertex_normals.data_ptr(), p.tbn.data_ptr(), int(p.K),
-                p._height_limit(...), float(self.fc_weight), float(self.bound), bool(self.training), bool(getattr(self, "fused_glue", True)))
+                p._height_limit(...), float(self.fc_weight), float(self.bound), bool(self.training), bool(getattr(self, "fused_glue", True))) + self._light_stamp()
+
+    def _light_stamp(self):
+        """graph_stamp()'s share of the light model: nothing without one (the stamp of today's field is unchanged)."""
+        if getattr(self, "light_model", None) is None:
+            return ()
+        net = self.light_net
+        return (self.light_model, self.light_visual_mode, float(net.gamma), bool(net.use_specular), bool(net.fused), net.envSHs.data_ptr(), tuple(net.envSHs.shape))
 
     def _infer_fused(self, x, d):
         """Whether nerftex_curved_field_infer serves this call: _glue_fused(), the shapes the entry's kernels are built for (it refuses every

@@ -441,7 +441,7 @@ class Renderer(nn.Module):
         return (nears, fars, xyzs, dirs, deltas, rays), counter
 
     def shade_train(self, marched, bg_color=1, target=None, loss_mul=1.0, scale=None, criterion=None, ray_loss=None, error_map=None, error_inds=None,
-                    target_out=None):
+                    target_out=None, extras_out=None):
         """Second half (:389-425): field evaluation, compositing, background.
 
         target [N,3]: the blend, the depth normalisation and the MSE against the target pixels run as one
@@ -449,7 +449,10 @@ class Renderer(nn.Module):
         instead of (image, depth); backward goes through the last one.  criterion / ray_loss / error_map / error_inds (with a target):
         another criterion than the MSE, the rays' losses and the error map's update, by the same kernel (fused.step_loss_desc).
         bg_color: a number, or an fp32 [N,3] tensor -- the reference's per-pixel random background (nerf/utils.py:602); target [N,4]: RGBA
-        pixels, blended over bg_color by the same kernel, the blended target (gt_rgb) returned as a fifth value (fused.step_pixels)."""
+        pixels, blended over bg_color by the same kernel, the blended target (gt_rgb) returned as a fifth value (fused.step_pixels).
+        extras_out: a dict -- the field is asked for its normal supervision (`normal_supervision=True`: a light-model curved field) and every
+        entry of its third return value whose key contains `normal` is composited per ray over a zero background with the detached densities
+        (nerf/renderer.py:428-433) and stored in the dict, [N,3] fp32.  The positional returns do not change."""
         nears, fars, xyzs, dirs, deltas, rays = marched
         # skip_dead_samples (round 6; accelerate sets it): the compositing backward flags the 32-sample steps that carry a gradient -- in a trained
         # scene most samples sit behind the point where their ray's transmittance has underflowed and get exactly zero (raymarching.cu:843-870) --
@@ -469,12 +472,21 @@ class Renderer(nn.Module):
             enc.step_live_holder = holder
             self.last_step_live = holder  # (after the backward: holder["last"] = the step's flags)
         try:
-            sigmas, rgbs, _ = self.field(xyzs, dirs)
+            if extras_out is None:
+                sigmas, rgbs, _ = self.field(xyzs, dirs)
+            else:
+                if getattr(self.field, "light_model", None) is None:
+                    raise ValueError("shade_train(extras_out=): the field has no normal supervision to composite (a curved.CurvedField with a light model has)")
+                sigmas, rgbs, data = self.field(xyzs, dirs, normal_supervision=True)
         finally:
             if holder is not None:
                 enc.step_live_holder = None
         if self.density_scale != 1:  # x * 1.0 is x: not launched
             sigmas = self.density_scale * sigmas
+        if extras_out is not None:
+            for key, value in data.items():
+                if value is not None and "normal" in key:
+                    extras_out[key] = raymarching.composite_rays_train(sigmas.detach(), value, deltas, rays)[2]
         if target is not None:
             from . import fused
 

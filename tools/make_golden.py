@@ -499,6 +499,10 @@ def reference_python_goldens():
 
 def main():
     os.makedirs(OUT, exist_ok=True)
+    if "--sh-light-only" in sys.argv:
+        sh_light_goldens()
+        sh_field_goldens()
+        return
     if "--round5-only" in sys.argv:
         round5_goldens()
         return
@@ -592,7 +596,8 @@ def _install_map_imports():
     class Network(torch.nn.Module):
         def __init__(self, n_input_dims, n_output_dims, network_config):
             super().__init__()
-            assert network_config["otype"] == "FullyFusedMLP" and network_config["activation"] == "ReLU" and network_config["output_activation"] == "None"
+            # (case-insensitive: nerf/sh_light_model.py:538 spells it "Relu")
+            assert network_config["otype"] == "FullyFusedMLP" and network_config["activation"].lower() == "relu" and network_config["output_activation"] == "None"
             self.n_in, self.n_out = n_input_dims, n_output_dims
             self.pad_in = (n_input_dims + 15) // 16 * 16
             self.net = FFMLP(input_dim=self.pad_in, output_dim=n_output_dims, hidden_dim=network_config["n_neurons"],
@@ -697,7 +702,7 @@ def round3_goldens():
     # ---- 8. the curved field: MeshFeatureField.forward (tools/map.py:620-641, 717-737; hash=True, clustering, no prob model, no normal net)
     # and network_curvedfield.NeRFNetwork.forward / density (nerf/network_curvedfield.py:229-243, 283-300, 382-409) with the light model off
     for name, cls in (("sg_light_model", "SG_EnvmapMaterialNet"), ("sh_light_model", "SH_EnvmapMaterialNet"), ("envmap_light_model", "Envmap_EnvmapMaterialNet")):
-        _stub("nerf." + name, **{cls: None})  # relighting models (imageio, cv2, ...): out of scope, light_model=None never builds one
+        _stub("nerf." + name, **{cls: None})  # this fixture runs with light_model=None, which never builds one (the SH model: sh_light_goldens)
     import nerf.network_curvedfield as ref_cf
     from tools.encoding import get_encoder
 
@@ -970,6 +975,160 @@ def round5_goldens():
     np.savez_compressed(os.path.join(OUT, "ref_python_normal_net.npz"), **out)
     print("ref_python_normal_net.npz: theta", float(theta.min()), float(theta.max()), "phi", float(phi.min()), float(phi.max()), "regularization", float(reg),
           "rows with a gradient", int(nz.shape[0]), "|dL/dp_sur| max", float(p_sur.grad.abs().max()))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The SH light head: nerf/sh_light_model.py's SH_EnvmapMaterialNet.forward (:554-616) and its autograd, executed
+# ---------------------------------------------------------------------------------------------------------------------------
+def sh_light_goldens():
+    """ref_python_sh_light.npz: the real nerf.sh_light_model imported (cv2, imageio and tools.shape_tools stubbed: file output and image
+    loading, never reached; tinycudann = the stand-in of _install_map_imports) and SH_EnvmapMaterialNet.forward run on the CPU under the
+    emulated autocast with its backward, 768 samples per case.  Cases `w<white_light>s<use_specular>` + `dark` (coloured light whose
+    irradiance changes sign over the sphere: the clamps and safe_pow's threshold are exercised).  Per case: geo_feat, normals, dirs, the BRDF
+    MLP's weights, envSHs, brdf (the MLP's 5 outputs as the head saw them), the four outputs, grad_color and the gradients that reached
+    brdf and envSHs.  Writes this one file; no other fixture is touched."""
+    import torch
+
+    _install_map_imports()
+    for name in ("imageio", "tools.shape_tools"):
+        _stub(name, write_ply_rgb=None)
+    sys.modules.pop("nerf.sh_light_model", None)  # (round3_goldens stubs it when it ran first)
+    import nerf.sh_light_model as ref_sh
+
+    N = 768
+    rng = np.random.default_rng(71)
+    out = {}
+    for case, white, spec in (("w1s1", True, True), ("w1s0", True, False), ("w0s1", False, True), ("w0s0", False, False), ("dark", False, True)):
+        net = ref_sh.SH_EnvmapMaterialNet(input_dim=15, sh_order=3, white_light=white, use_specular=spec)
+        C = 1 if white else 3
+        env = net.envSHs.data  # zeros with row 0 = 3: the reference's initialisation
+        if case == "dark":
+            env[0] = 0.05
+            env[1:] = torch.from_numpy(rng.normal(0, 0.4, (15, C)).astype(np.float32))
+        else:
+            env[1:] = torch.from_numpy(rng.normal(0, 0.1, (15, C)).astype(np.float32))
+        geo = torch.from_numpy(rng.normal(0, 1.0, (N, 15)).astype(np.float32)).half()
+        n = rng.normal(size=(N, 3))
+        n = torch.from_numpy((n / np.linalg.norm(n, axis=-1, keepdims=True)).astype(np.float32))
+        d = rng.normal(size=(N, 3))
+        d = torch.from_numpy((d / np.linalg.norm(d, axis=-1, keepdims=True) * rng.uniform(0.5, 2.0, (N, 1))).astype(np.float32))
+        gc = torch.from_numpy(rng.normal(size=(N, 3)).astype(np.float32))
+        seen = {}
+        handle = net.brdf_layer.register_forward_hook(lambda m, i, o: (o.retain_grad(), seen.__setitem__("brdf", o))[1])
+        net.train()
+        with emulated_autocast():
+            color, specular, diffuse, albedo = net(geo, n, d)
+            (color * gc).sum().backward()
+        handle.remove()
+        brdf = seen["brdf"]
+        assert brdf.dtype == torch.float16 and brdf.shape == (N, 5) and color.dtype == torch.float32 and albedo.dtype == torch.float16
+        out.update({f"{case}_geo_feat": geo.numpy(), f"{case}_normals": n.numpy(), f"{case}_dirs": d.numpy(), f"{case}_grad_color": gc.numpy(),
+                    f"{case}_w_brdf": net.brdf_layer.net.weights.detach().numpy().copy(), f"{case}_env_shs": env.numpy().copy(),
+                    f"{case}_brdf": brdf.detach().numpy().copy(), f"{case}_color": color.detach().numpy(), f"{case}_specular": specular.detach().float().numpy(),
+                    f"{case}_diffuse": diffuse.detach().numpy(), f"{case}_albedo": albedo.detach().float().numpy(),
+                    f"{case}_g_brdf": brdf.grad.numpy().copy(), f"{case}_g_env_shs": net.envSHs.grad.numpy().copy(),
+                    f"{case}_g_w_brdf": net.brdf_layer.net.weights.grad.numpy().copy()})
+        print(f"ref_python_sh_light.npz[{case}]: color range", float(color.min()), float(color.max()), "|g_brdf[:, 4]| max", float(brdf.grad[:, 4].abs().max()),
+              "g_env rows >= 9 abs max", float(net.envSHs.grad[9:].abs().max()))
+    sd = net.state_dict()
+    out["state_dict_keys"] = np.array(sorted(sd))
+    out["state_dict_shapes"] = np.array([",".join(map(str, sd[k].shape)) + ":" + str(sd[k].dtype) for k in sorted(sd)])
+    out["gamma"] = np.float64(net.gamma)
+    np.savez_compressed(os.path.join(OUT, "ref_python_sh_light.npz"), **out)
+
+
+def sh_field_goldens():
+    """ref_python_curvedfield_sh.npz: network_curvedfield.NeRFNetwork.forward executed with render_light_model=True (light_model 'SH', the
+    real SH_EnvmapMaterialNet, white light as NeRFNetwork's default) over MeshFeatureField(pred_normal=True) with the reference's
+    Factorized_Normal_Net, on the mesh and points of ref_python_projector.npz -- the setup of ref_python_curvedfield.npz plus the normal
+    net and the light head.  Eval with fc_weight = 0.7 (the fine / coarse blend of :299-301 is exercised) and the four light_visual_modes;
+    train (the branch of :236-258 that differentiates sigma, create_graph and all) with the ret_dict; in both, the shading normal and the
+    view direction as the light head receives them (:331-341), captured by a hook on the head.  Values only.  Reads two existing
+    fixtures; writes this one file."""
+    import torch
+
+    _install_map_imports()
+    _stub("imageio")
+    for name in ("nerf.sh_light_model", "nerf.network_curvedfield", "tools.shape_tools"):  # (stubs of earlier functions: tools/map.py needs the real shape_tools)
+        sys.modules.pop(name, None)
+    for name, cls in (("sg_light_model", "SG_EnvmapMaterialNet"), ("envmap_light_model", "Envmap_EnvmapMaterialNet")):
+        _stub("nerf." + name, **{cls: None})
+    import nerf.network_curvedfield as ref_cf
+    import nerf.sh_light_model as ref_sh
+    import tools.map as ref_map
+    from RayTracer import RayTracer as RefRayTracer
+    from tools.encoding import get_encoder
+
+    g = np.load(os.path.join(OUT, "ref_python_projector.npz"))
+    c = np.load(os.path.join(OUT, "ref_python_curvedfield.npz"))
+    v, f, vn, tbn, pts, dirs = g["vertices"], g["faces"], g["vertex_normals"], g["tbn"], g["xyz"], c["dirs"]
+    mp = object.__new__(ref_map.MeshProjector)
+    mp.mesh_vertices, mp.vertex_normals, mp.tbn = torch.from_numpy(v), torch.from_numpy(vn), torch.from_numpy(tbn)
+    mp.grid, mp.radius, mp.max_K, mp.depth_threshold = None, 100.0, v.shape[0], 9.5
+    mp.raytracer = RefRayTracer(v, f)
+    torch.manual_seed(0)
+    mff = object.__new__(ref_map.MeshFeatureField)
+    torch.nn.Module.__init__(mff)
+    mff.h_threshold, mff.K, mff.bound, mff.hash, mff.prob_model, mff.pred_normal, mff.clustering = 0.05, 8, 1, True, False, True, True
+    mff.imported, mff.imported_type = False, None
+    mff.encoder, mff.encoder_f_out_dim = get_encoder("hashgrid_clustering", desired_resolution=1024, input_dim=3, num_levels=8, level_dim=2, base_resolution=512,
+                                                     log2_hashmap_size=19, align_corners=True)
+    mff.encoder_z, mff.encoder_z_outdim = get_encoder("frequency", input_dim=1, multires=12)
+    mff.meshprojector = mp
+    gen = torch.Generator().manual_seed(int(c["table_seed"]))
+    mff.encoder.embeddings.data.copy_(torch.rand(mff.encoder.embeddings.shape, generator=gen) - 0.5)
+    torch.manual_seed(11)
+    mff.normal_net = ref_map.Factorized_Normal_Net(x_dim=mff.encoder_f_out_dim, z_dim=mff.encoder_z_outdim, lip=True, direct_pred_coor=False, bound_output=False)
+    gen = torch.Generator().manual_seed(12)
+    with torch.no_grad():
+        mff.normal_net.encoder.embeddings.copy_(torch.rand(mff.normal_net.encoder.embeddings.shape, generator=gen) - 0.5)
+    net = object.__new__(ref_cf.NeRFNetwork)
+    torch.nn.Module.__init__(net)
+    net.visual_mode, net.render_light_model, net.use_grad_normal, net.fc_weight, net.dir_degree = "RGB", True, False, 0.7, 4
+    net.optimize_gamma, net.meshfea_field, net.light_model, net.smooth_grad_weight = False, mff, "SH", 1e-1
+    net.use_coarse_normal, net.coarse_as_primary, net.no_visibility, net.shade_visibility, net.light_visual_mode = False, False, False, True, "Full"
+    tcnn = sys.modules["tinycudann"]
+    torch.manual_seed(42)
+    net.sigma_net = tcnn.Network(n_input_dims=mff.encoder_z_outdim + mff.encoder_f_out_dim, n_output_dims=16,
+                                 network_config={"otype": "FullyFusedMLP", "activation": "ReLU", "output_activation": "None", "n_neurons": 32, "n_hidden_layers": 1})
+    assert np.array_equal(net.sigma_net.net.weights.detach().numpy(), c["w_sigma"]), "the sigma net of ref_python_curvedfield.npz"
+    net.color_net = None
+    net.light_net = ref_sh.SH_EnvmapMaterialNet(input_dim=15, sh_order=3, white_light=True, use_specular=True)
+    rng = np.random.default_rng(91)
+    with torch.no_grad():
+        # bands 1 and 2 comparable to the DC term: the colour then depends on WHICH normal shades the sample (fine, coarse or their blend)
+        net.light_net.envSHs[1:] = torch.from_numpy(rng.normal(0, 1.5, (15, 1)).astype(np.float32))
+    x, d = torch.from_numpy(pts), torch.from_numpy(dirs)
+    out = dict(table_seed=int(c["table_seed"]), normal_table_seed=12, fc_weight=0.7, w_sigma=c["w_sigma"], w_brdf=net.light_net.brdf_layer.net.weights.detach().numpy().copy(),
+               env_shs=net.light_net.envSHs.detach().numpy().copy())
+    for name, mlp in (("phi", mff.normal_net.phi_net), ("theta", mff.normal_net.theta_net)):
+        for i, layer in enumerate(mlp.layers):
+            out[f"{name}_W{i}"], out[f"{name}_b{i}"], out[f"{name}_c{i}"] = layer.W.detach().numpy().copy(), layer.b.detach().numpy().copy(), float(layer.c)
+    handed = {}  # what NeRFNetwork.forward hands to the light head (:341): the shading normal and the view direction
+    net.light_net.register_forward_pre_hook(lambda m, a: handed.update(normal=a[1].detach().float().numpy().copy(), view_dirs=a[2].detach().float().numpy().copy(),
+                                                                       normal_attached=bool(a[1].requires_grad)))
+    net.eval()
+    with torch.no_grad(), emulated_autocast():
+        _, nc, nf, hm = mff(x)
+        out.update(eval_normal_coarse=nc.float().numpy(), eval_normal_fine=nf.float().numpy(), eval_h_mask=hm.numpy())
+        for mode in ("Full", "Specular", "Diffuse", "Albedo"):
+            net.light_visual_mode = mode
+            sigma, color, ret = net(x, d, is_gui_mode=False)
+            assert ret == {}
+            out["eval_sigma"], out["eval_color_" + mode.lower()] = sigma.float().numpy(), color.float().numpy()
+        net.light_visual_mode = "Full"
+        out.update(eval_shading_normal=handed["normal"], eval_view_dirs=handed["view_dirs"])
+    net.train()
+    with emulated_autocast():
+        sigma, color, ret = net(x.clone(), d)
+    assert sorted(ret) == ["normal", "normal_grad"] and ret["normal"].requires_grad
+    assert not handed["normal_attached"], "the training head shades with the detached normal (:331)"
+    out.update(train_shading_normal=handed["normal"], train_view_dirs=handed["view_dirs"])
+    out.update(train_sigma=sigma.detach().float().numpy(), train_color=color.detach().float().numpy(), train_normal=ret["normal"].detach().float().numpy(),
+               train_normal_grad=ret["normal_grad"].detach().float().numpy(), train_h_mask=(sigma.detach() != 0).numpy() | (color.detach() != 0).any(-1).numpy())
+    np.savez_compressed(os.path.join(OUT, "ref_python_curvedfield_sh.npz"), **out)
+    print("ref_python_curvedfield_sh.npz: eval colour", float(out["eval_color_full"].min()), float(out["eval_color_full"].max()), "inside", float(out["eval_h_mask"].mean()),
+          "train rows shaded", float(out["train_h_mask"].mean()), "normal_grad not a number on", int(np.isnan(out["train_normal_grad"]).any(-1).sum()), "rows")
 
 
 if __name__ == "__main__":
