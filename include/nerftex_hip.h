@@ -784,6 +784,89 @@ size_t nerftex_curved_field_infer_scratch_bytes(uint32_t B);
 int nerftex_curved_field_infer(const nerftex_curved_infer_desc* d, void* stream);
 
 /* -------------------------------------------------------------------------
+ * Extension: the same ONE call for the curved field with the SH light model (CurvedField(light_model="SH")), under the same rows contract:
+ *   neighbour search -> projector (+ the hit face's frame) -> hash-grid gather of the texture table -> gather of the normal net's table ->
+ *   sigma net 48 -> 32 -> 16 -> light mid: exp / BRDF input / the factorized fine-normal net (two 16-wide LipMLPs, toCoor, the frame's
+ *   rotation, the normalisations, in eval the fc_weight blend with the coarse normal) -> BRDF net 16 -> 64 x 3 -> 16 -> light out: the SH
+ *   light head (the row function of nerftex_sh_light_forward) + the height mask,
+ * ten launches enqueued on `stream`; nothing is allocated, the host never waits, the call can be captured.
+ *   rows >= live                      no work; sigma / rgbs / shading_normal keep what they held.
+ *   live rows the march marked unused no search, no traversal, no table read; sigma = 0, rgbs = 0, shading_normal = 0.
+ *   every other live row              sigma = mask ? exp(h[:, 0]) : 0 in fp32 (what the field's forward() gives, bit for bit);
+ *                                     rgbs = mask ? the output visual_mode selects : 0;  shading_normal = the normal the head shades with.
+ * The normal net's arithmetic at the framework's rounding points under fp16 autocast: every LipLayer product W_n x is a half GEMM (inputs and
+ * normalised weights half, fp32 accumulation in ascending input order, the result rounded to half), bias and ReLU fp32, the next layer rounds
+ * to half again; the rotation by the face frame is a half product too; everything else fp32, every operation rounded on its own.
+ * normal_weights: the six normalised weight matrices as fp16, row-major [out, in], one after the other -- phi net [16,20] [16,16] [1,16] (inputs:
+ * the 8 features of the normal table, then the first 12 height bands), theta net [16,28] [16,16] [1,16] (inputs: the first 16 texture features,
+ * then the same 12 bands): NERFTEX_NORMAL_NET_WEIGHTS values; normal_biases: their fp32 biases in the same order, NERFTEX_NORMAL_NET_BIASES values.
+ * NERFTEX_ERR_INVALID with a message, before anything is launched, in this order: a NULL descriptor; B % 128 != 0; n_verts, K or a shape other
+ * than the default SH field's (n_freqs 12; texture table 3-D, 2 x 8; normal table 2 x 4; sigma net 48 / 32 / 2 / 16; normal nets 16 wide with 2
+ * hidden layers; BRDF net 16 / 64 / 3 / 5; n_sh >= 9, n_color 1 or 3, gamma positive and finite, flags, visual_mode, eval 0 or 1); then
+ * B == 0 returns NERFTEX_OK; then NULL handles / buffers, alignment, a scratch smaller than nerftex_curved_light_infer_scratch_bytes(B).
+ * ------------------------------------------------------------------------- */
+#define NERFTEX_LIGHT_VISUAL_FULL 0
+#define NERFTEX_LIGHT_VISUAL_SPECULAR 1
+#define NERFTEX_LIGHT_VISUAL_DIFFUSE 2
+#define NERFTEX_LIGHT_VISUAL_ALBEDO 3
+#define NERFTEX_NORMAL_NET_WEIGHTS 1312 /* 16 x 20 + 16 x 16 + 16 + 16 x 28 + 16 x 16 + 16 */
+#define NERFTEX_NORMAL_NET_BIASES 66    /* 16 + 16 + 1 + 16 + 16 + 1                       */
+typedef struct nerftex_curved_light_infer_desc {
+    const nerftex_knn* knn;            /* as nerftex_curved_infer_desc, down to in_mul                                            */
+    const nerftex_raytracer* tracer;
+    const float* xyz;
+    const float* dirs;
+    uint32_t B;
+    uint32_t n_verts;
+    const float* mesh_vertices;
+    const float* vertex_normals;
+    const float* tbn;                  /* [F,9] per-face frames (rows t, b, n): read for the hit face of every unmarked live row   */
+    uint32_t K;
+    uint32_t n_freqs;
+    float dir_vec_wdist;
+    float h_threshold;
+    const void* table;
+    const int32_t* offsets;
+    uint32_t D, C, L;
+    float S;
+    uint32_t H;
+    uint32_t gridtype;
+    int align_corners;
+    float in_add, in_mul;
+    const void* normal_table;          /* the normal net's own fp16 hash table [rows, normal_C], read at the same surface point    */
+    const int32_t* normal_offsets;     /* [normal_L + 1] (device)                                                                 */
+    uint32_t normal_C, normal_L;       /* 2 features x 4 levels                                                                   */
+    float normal_S;
+    uint32_t normal_H;
+    uint32_t normal_gridtype;
+    int normal_align_corners;
+    float normal_in_add, normal_in_mul;
+    const void* sigma_weights;         /* fp16, 16-byte aligned                                                                   */
+    uint32_t sigma_in, sigma_hidden, sigma_layers, sigma_out;
+    const void* normal_weights;        /* fp16 [NERFTEX_NORMAL_NET_WEIGHTS], 4-byte aligned: see above                            */
+    const float* normal_biases;        /* fp32 [NERFTEX_NORMAL_NET_BIASES]                                                        */
+    uint32_t normal_hidden, normal_layers; /* 16, 2                                                                               */
+    const void* brdf_weights;          /* fp16, 16-byte aligned                                                                   */
+    uint32_t brdf_in, brdf_hidden, brdf_layers, brdf_out;
+    const float* env_shs;              /* [n_sh, n_color] fp32, as nerftex_sh_light_desc                                          */
+    uint32_t n_sh, n_color;
+    float gamma;
+    uint32_t flags;                    /* NERFTEX_SH_LIGHT_SPECULAR                                                               */
+    uint32_t visual_mode;              /* NERFTEX_LIGHT_VISUAL_*: which of the head's four outputs rgbs receives                  */
+    float fc_weight;
+    int eval;                          /* 1: the shading normal is fc_weight x fine + (1 - fc_weight) x coarse, renormalised; 0: the fine normal */
+    float* sigma;                      /* [B] fp32                                                                                */
+    float* rgbs;                       /* [B,3] fp32                                                                              */
+    float* shading_normal;             /* [B,3] fp32 or NULL (not written)                                                        */
+    const int32_t* units_dev;
+    uint32_t rows_per_unit;
+    void* scratch;                     /* caller-owned, 256-byte aligned, >= nerftex_curved_light_infer_scratch_bytes(B) bytes    */
+    size_t scratch_bytes;
+} nerftex_curved_light_infer_desc;
+size_t nerftex_curved_light_infer_scratch_bytes(uint32_t B);
+int nerftex_curved_light_infer(const nerftex_curved_light_infer_desc* d, void* stream);
+
+/* -------------------------------------------------------------------------
  * Extension: the SH light head of the curved field -- SH_EnvmapMaterialNet.forward behind its BRDF MLP (nerf/sh_light_model.py:554-616) -- as one
  * streaming kernel per direction instead of ~40 framework ops per sample batch, the framework's arithmetic at its rounding points:
  *   albedo = half(sigmoid(brdf[:, :3])), spec_w = half(sigmoid(brdf[:, 3]))              (fp32 sigmoid narrowed to half)

@@ -16,12 +16,16 @@ int knn_query_rows(const nerftex_knn* kn, const float* xyz, const float* dirs, u
 // nerftex_curved_project with n_freqs = 12 for unmarked live rows: p_sur [N,3], h_mask [N], normal [N,3], and half(z_embed) followed by the
 // seven padding ones straight into columns 16..47 of the sigma net's input xin [N,48] (what nerftex_curved_pack_inputs builds from z_embed).
 // A marked live row: p_sur = 1e30 (the gather answers zeros without a table read), h_mask = 0, normal = 0, z = 0 | ones.
+// tbn_out [N,9] (optional, with the per-face frames tbn [F,9]): the hit face's frame as nerftex_curved_project writes it, zeros for a marked
+// row; NULL: no frame is read or written (the static light model's chain).
 int curved_project_rows(const nerftex_raytracer* rt, const float* xyz, const float* dirs, const int32_t* knn_idx, const float* knn_dist, uint32_t N,
                         uint32_t K, const float* mesh_vertices, const float* vertex_normals, uint32_t n_verts, float dir_vec_wdist, float h_threshold,
-                        float* p_sur, uint8_t* h_mask, float* normal, void* xin, const int32_t* units_dev, uint32_t rows_per_unit, hipStream_t st);
+                        float* p_sur, uint8_t* h_mask, float* normal, void* xin, const int32_t* units_dev, uint32_t rows_per_unit, hipStream_t st,
+                        const float* tbn = nullptr, float* tbn_out = nullptr);
 
-// nerftex_ffmlp_inference (fp16, ReLU, no output activation) of the curved field's two networks -- (IN, H, NL) = (48, 32, 2) or (32, 64, 3) -- over
-// the 128-row workgroups that hold a live row; a workgroup wholly past the live rows exits before it stages its weights.
+// nerftex_ffmlp_inference (fp16, ReLU, no output activation) of the curved field's networks -- (IN, H, NL) = (48, 32, 2), (32, 64, 3) or the SH
+// light head's BRDF net (16, 64, 3) -- over the 128-row workgroups that hold a live row; a workgroup wholly past the live rows exits before it
+// stages its weights.
 int ffmlp_inference_rows(const void* inputs, const void* weights, uint32_t B, uint32_t IN, uint32_t H, uint32_t NL, void* outputs,
                          const int32_t* units_dev, uint32_t rows_per_unit, hipStream_t st);
 

@@ -59,7 +59,7 @@ int ffmlp_inference_rows(const void* inputs, const void* weights, uint32_t B, ui
     }
     if (B == 0) return NERFTEX_OK;
     if (IN == 48 && H == 32 && NL == 2) return ffmlp_f16::launch_inference_rows<32>(inputs, weights, B, IN, NL, outputs, units_dev, rows_per_unit, st);
-    if (IN == 32 && H == 64 && NL == 3) return ffmlp_f16::launch_inference_rows<64>(inputs, weights, B, IN, NL, outputs, units_dev, rows_per_unit, st);
+    if ((IN == 32 || IN == 16) && H == 64 && NL == 3) return ffmlp_f16::launch_inference_rows<64>(inputs, weights, B, IN, NL, outputs, units_dev, rows_per_unit, st);
     set_error("curved_field_infer: no rows form of the FFMLP inference kernel for %u -> %u x %u", IN, H, NL);
     return NERFTEX_ERR_INVALID;
 }

@@ -249,6 +249,147 @@ __global__ __launch_bounds__(256) void curved_out_rows_kernel(const half_t* __re
     curved_out_row<float>(b, hc, 16, sigma_raw, mask, sigma, rgbs);
 }
 
+// ---- the light mid of nerftex_curved_light_infer (the SH light model's chain; its closing kernel and the entry point: curved_light.inc) ------------------
+// The factorized fine-normal net (tools/map.py:231-337 as FactorizedNormalNet executes it under fp16 autocast): two LipMLPs in -> 16 -> 16 -> 1.
+constexpr int kNnH = 16, kNnBands = 12, kNnPhiIn = 8 + kNnBands, kNnThetaIn = 16 + kNnBands;
+constexpr int kNnPhiWeights = kNnH * kNnPhiIn + kNnH * kNnH + kNnH, kNnThetaWeights = kNnH * kNnThetaIn + kNnH * kNnH + kNnH;
+constexpr int kNnWeights = kNnPhiWeights + kNnThetaWeights, kNnNetBiases = 2 * kNnH + 1, kNnBiases = 2 * kNnNetBiases;
+static_assert(kNnWeights == NERFTEX_NORMAL_NET_WEIGHTS && kNnBiases == NERFTEX_NORMAL_NET_BIASES, "the packed block of include/nerftex_hip.h");
+
+// One LipLayer product as the framework's half GEMM: x and w hold half VALUES (their products are exact in fp32), added in ascending input order in
+// fp32, the sum rounded to half; the bias is added and the ReLU applied in fp32.  FP CONTRACTION: off, as in curved_mid_row -- an fma of an exact
+// product is the same rounding, but bias, ReLU and everything behind the net are framework ops that round on their own.
+template <int IN>
+__device__ __forceinline__ float lip_dot(const float (&x)[IN], const float* __restrict__ w) {
+#pragma clang fp contract(off)
+    float acc = 0.0f;
+#pragma unroll
+    for (int i = 0; i < IN; i++) acc = acc + w[i] * x[i];
+    return (float)narrow(acc);
+}
+
+template <int IN>
+__device__ __forceinline__ float lip_mlp_row(const float (&x)[IN], const float* __restrict__ w, const float* __restrict__ bias) {
+#pragma clang fp contract(off)
+    float a[kNnH], c[kNnH];
+#pragma unroll
+    for (int o = 0; o < kNnH; o++) {
+        const float y = lip_dot<IN>(x, w + o * IN) + bias[o];
+        a[o] = (float)narrow(y < 0.0f ? 0.0f : y);  // (the next layer's GEMM takes half inputs; torch.relu keeps a NaN and so does this)
+    }
+    w += kNnH * IN;
+#pragma unroll
+    for (int o = 0; o < kNnH; o++) {
+        const float y = lip_dot<kNnH>(a, w + o * kNnH) + bias[kNnH + o];
+        c[o] = (float)narrow(y < 0.0f ? 0.0f : y);
+    }
+    return lip_dot<kNnH>(c, w + kNnH * kNnH) + bias[2 * kNnH];
+}
+
+// h [B,16] half (the sigma net's output), xin [B,48] half (texture features | height bands | ones), n_lbc [4,B,2] half (the normal table's features,
+// level-major), normal [B,3] the projector's RAW coarse normal, tbn [B,9] the hit face's frame, w / bias: the net's weights (half values) and biases in LDS
+//   -> sigma_raw [B] fp32 = exp(h[:,0])  (trunc_exp on the half logit widened: _sigma() keeps it fp32)
+//      brdf_in [B,16] half = [h[:,1:16] | 1]
+//      shading [B,3] fp32: toCoor(phi, theta) rotated by the frame (a half product), normalised twice (tools/map.py:732, network_curvedfield.py:285);
+//      eval: fc x fine + (1 - fc) x coarse, renormalised (:293-301), coarse = the raw normal normalised twice (tools/map.py:720, :285)
+__device__ __forceinline__ void curved_light_mid_row(const uint32_t b, const uint32_t B, const half_t* __restrict__ h, const half_t* __restrict__ xin,
+                                                     const half_t* __restrict__ n_lbc, const float* __restrict__ normal, const float* __restrict__ tbn,
+                                                     const float* __restrict__ w, const float* __restrict__ bias, const float fc, const int eval,
+                                                     float* __restrict__ sigma_raw, half_t* __restrict__ brdf_in, float* __restrict__ shading) {
+#pragma clang fp contract(off)  // every framework op rounds on its own
+    const half8_t h0 = *reinterpret_cast<const half8_t*>(h + (size_t)b * 16);
+    const half8_t h1 = *reinterpret_cast<const half8_t*>(h + (size_t)b * 16 + 8);
+    sigma_raw[b] = expf((float)h0[0]);
+    half8_t o0, o1;
+#pragma unroll
+    for (int i = 0; i < 7; i++) o0[i] = h0[1 + i];
+    o0[7] = h1[0];
+#pragma unroll
+    for (int i = 0; i < 7; i++) o1[i] = h1[1 + i];
+    o1[7] = (half_t)1.0f;  // tcnn pads its inputs with ones
+    half8_t* out = reinterpret_cast<half8_t*>(brdf_in + (size_t)b * 16);
+    out[0] = o0; out[1] = o1;
+
+    const half8_t x0 = *reinterpret_cast<const half8_t*>(xin + (size_t)b * 48);
+    const half8_t x1 = *reinterpret_cast<const half8_t*>(xin + (size_t)b * 48 + 8);
+    const half8_t z0 = *reinterpret_cast<const half8_t*>(xin + (size_t)b * 48 + 16);
+    const half4_t z1 = *reinterpret_cast<const half4_t*>(xin + (size_t)b * 48 + 24);
+    float phi_in[kNnPhiIn], theta_in[kNnThetaIn];
+#pragma unroll
+    for (int l = 0; l < 4; l++) {
+        const half2_t f = *reinterpret_cast<const half2_t*>(n_lbc + ((size_t)l * B + b) * 2);
+        phi_in[2 * l] = (float)f[0];
+        phi_in[2 * l + 1] = (float)f[1];
+    }
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        theta_in[i] = (float)x0[i];
+        theta_in[8 + i] = (float)x1[i];
+    }
+#pragma unroll
+    for (int i = 0; i < kNnBands; i++) {
+        const float z = i < 8 ? (float)z0[i] : (float)z1[i - 8];
+        phi_in[8 + i] = z;
+        theta_in[16 + i] = z;
+    }
+    const float phi = lip_mlp_row<kNnPhiIn>(phi_in, w, bias);
+    const float theta = lip_mlp_row<kNnThetaIn>(theta_in, w + kNnPhiWeights, bias + kNnNetBiases);
+    const float st = sinf(theta);
+    const float local[3] = {st * cosf(phi), st * sinf(phi), cosf(theta)};  // toCoor
+    // einsum("nba,nb->na", frame, local) under autocast: a half product -- both operands rounded to half, fp32 sum in ascending b, rounded to half
+    float lh[3], th[9], n[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) lh[k] = (float)narrow(local[k]);
+#pragma unroll
+    for (int k = 0; k < 9; k++) th[k] = (float)(half_t)tbn[(size_t)b * 9 + k];
+#pragma unroll
+    for (int a = 0; a < 3; a++) n[a] = (float)narrow((th[a] * lh[0] + th[3 + a] * lh[1]) + th[6 + a] * lh[2]);
+    auto unit = [](float (&v)[3]) {  // v / (|v| + 1e-5)
+        const float len = sqrtf((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]) + 1e-5f;
+#pragma unroll
+        for (int c = 0; c < 3; c++) v[c] = v[c] / len;
+    };
+    unit(n);
+    unit(n);
+    if (eval & 1) {
+        float cn[3];
+#pragma unroll
+        for (int c = 0; c < 3; c++) cn[c] = normal[(size_t)b * 3 + c];
+        unit(cn);
+        unit(cn);
+#pragma unroll
+        for (int c = 0; c < 3; c++) n[c] = fc * n[c] + (1 - fc) * cn[c];
+        unit(n);
+    }
+#pragma unroll
+    for (int c = 0; c < 3; c++) shading[(size_t)b * 3 + c] = n[c];
+}
+
+// One thread per row.  The net's weights (1312 half values, 66 biases: 5.4 KiB as fp32) are staged once per workgroup in LDS -- every lane of a wave
+// reads the same word at the same time (a broadcast, no bank conflict), and 1.3 k words per row would not stay in scalar registers.  A workgroup wholly
+// past the live rows leaves before it stages anything.
+__global__ __launch_bounds__(256) void curved_light_mid_rows_kernel(const half_t* __restrict__ h, const half_t* __restrict__ xin, const half_t* __restrict__ n_lbc,
+                                                                   const float* __restrict__ normal, const float* __restrict__ tbn, const float* __restrict__ dirs,
+                                                                   const half_t* __restrict__ nn_weights, const float* __restrict__ nn_biases, uint32_t B,
+                                                                   const float fc, const int eval, float* __restrict__ sigma_raw, half_t* __restrict__ brdf_in,
+                                                                   float* __restrict__ shading, const int32_t* __restrict__ units_dev, uint32_t rows_per_unit) {
+    __shared__ float w_s[kNnWeights];
+    __shared__ float b_s[kNnBiases];
+    const uint32_t live = live_rows(B, units_dev, rows_per_unit);
+    if (blockIdx.x * blockDim.x >= live) return;  // (the whole workgroup: nobody is left waiting at the barrier)
+    for (uint32_t i = threadIdx.x; i < (uint32_t)kNnWeights; i += blockDim.x) w_s[i] = (float)nn_weights[i];
+    if (threadIdx.x < (uint32_t)kNnBiases) b_s[threadIdx.x] = nn_biases[threadIdx.x];
+    __syncthreads();
+    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= live) return;
+    if (slot_unused(dirs, b)) {  // (its sigma_raw and brdf_in stay what the scratch held: rows are independent, the closing kernel writes the zeros)
+#pragma unroll
+        for (int c = 0; c < 3; c++) shading[(size_t)b * 3 + c] = 0.0f;
+        return;
+    }
+    curved_light_mid_row(b, B, h, xin, n_lbc, normal, tbn, w_s, b_s, fc, eval, sigma_raw, brdf_in, shading);
+}
+
 // the scratch of one nerftex_curved_field_infer call: every buffer starts on a 256-byte boundary
 struct CurvedScratch {
     size_t idx, dist, p_sur, normal, mask, x_lbc, xin, h, sigma_raw, cin, hc, total;
@@ -453,3 +594,6 @@ extern "C" int nerftex_field_out_backward(const float* grad_rgbs, const float* r
 
 // ---- the SH light head of the curved field (nerftex_sh_light_forward / _backward) ----------------------------------------------------------------------
 #include "shlight.inc"
+
+// ---- the SH light model's inference chain (nerftex_curved_light_infer): its closing kernel shares the head's row function above ----------------------------
+#include "curved_light.inc"

@@ -330,6 +330,11 @@ __device__ __forceinline__ void curved_project_point(const uint32_t i, const uin
         half8_t* dst = reinterpret_cast<half8_t*>(static_cast<half_t*>(z_embed) + (size_t)i * 48 + 16);
 #pragma unroll
         for (int q = 0; q < 4; q++) dst[q] = o[q];
+        if (tbn_out) {  // (the light-model chain: the hit face's frame, as the plain form below)
+            const int64_t hit = best >= 0 ? tris[best].id : (int64_t)0;
+#pragma unroll
+            for (int k = 0; k < 9; k++) tbn_out[9 * (size_t)i + k] = tbn[9 * (size_t)hit + k];
+        }
         return;
     }
     sdf_out[i] = sdf;
@@ -373,7 +378,8 @@ __global__ __launch_bounds__(64) void curved_project_rows_kernel(uint32_t N, con
                                                                  const float* __restrict__ verts, const float* __restrict__ vnormals, int n_verts,
                                                                  float dir_vec_wdist, float h_limit, const Node* __restrict__ nodes, const Tri* __restrict__ tris,
                                                                  float* __restrict__ p_sur, uint8_t* __restrict__ h_mask, float* __restrict__ normal_out,
-                                                                 half_t* __restrict__ xin, const int32_t* __restrict__ units_dev, uint32_t rows_per_unit) {
+                                                                 half_t* __restrict__ xin, const int32_t* __restrict__ units_dev, uint32_t rows_per_unit,
+                                                                 const float* __restrict__ tbn, float* __restrict__ tbn_out) {
     const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t i = tid >> 1, side = tid & 1u;
     if (i >= live_rows(N, units_dev, rows_per_unit)) return;
@@ -393,10 +399,14 @@ __global__ __launch_bounds__(64) void curved_project_rows_kernel(uint32_t N, con
         }
         half8_t* dst = reinterpret_cast<half8_t*>(xin + (size_t)i * 48 + 16);
         dst[0] = z8; dst[1] = z8; dst[2] = z8; dst[3] = tail;
+        if (tbn_out) {
+#pragma unroll
+            for (int k = 0; k < 9; k++) tbn_out[9 * (size_t)i + k] = 0.0f;
+        }
         return;
     }
-    curved_project_point<true>(i, side, xyz, knn_idx, knn_dist, K, verts, vnormals, n_verts, dir_vec_wdist, h_limit, nodes, tris, nullptr, kInferFreqs, p_sur,
-                               nullptr, h_mask, normal_out, nullptr, nullptr, xin);
+    curved_project_point<true>(i, side, xyz, knn_idx, knn_dist, K, verts, vnormals, n_verts, dir_vec_wdist, h_limit, nodes, tris, tbn, kInferFreqs, p_sur,
+                               nullptr, h_mask, normal_out, nullptr, tbn_out, xin);
 }
 
 // depth of the BVH-4 (root = 1)
@@ -492,8 +502,8 @@ extern "C" int nerftex_raytracer_trace(const nerftex_raytracer* rt, const float*
 int nerftex::curved_project_rows(const nerftex_raytracer* rt, const float* xyz, const float* dirs, const int32_t* knn_idx, const float* knn_dist, uint32_t N,
                                  uint32_t K, const float* mesh_vertices, const float* vertex_normals, uint32_t n_verts, float dir_vec_wdist,
                                  float h_threshold, float* p_sur, uint8_t* h_mask, float* normal, void* xin, const int32_t* units_dev,
-                                 uint32_t rows_per_unit, hipStream_t st) {
-    if (!rt || K == 0 || K > (uint32_t)kMaxK || n_verts == 0 || n_verts > 0x7fffffffu) {
+                                 uint32_t rows_per_unit, hipStream_t st, const float* tbn, float* tbn_out) {
+    if (!rt || K == 0 || K > (uint32_t)kMaxK || n_verts == 0 || n_verts > 0x7fffffffu || (tbn_out && !tbn)) {
         set_error("curved_field_infer: need a raytracer, 1 <= K <= %d neighbours per point and a non-empty vertex array", kMaxK);
         return NERFTEX_ERR_INVALID;
     }
@@ -503,7 +513,7 @@ int nerftex::curved_project_rows(const nerftex_raytracer* rt, const float* xyz, 
         KernelTimer kt("curved_project_rows_kernel", st);
         hipLaunchKernelGGL(curved_project_rows_kernel, dim3(div_up(2 * N, 64u)), dim3(64), 0, st, N, xyz, dirs, knn_idx, knn_dist, K, mesh_vertices, vertex_normals,
                            (int)n_verts, dir_vec_wdist, h_limit, static_cast<const Node*>(rt->nodes), static_cast<const Tri*>(rt->triangles), p_sur, h_mask, normal,
-                           static_cast<half_t*>(xin), units_dev, rows_per_unit);
+                           static_cast<half_t*>(xin), units_dev, rows_per_unit, tbn, tbn_out);
     }
     return check_launch("curved_field_infer(project)");
 }

@@ -129,6 +129,17 @@ __device__ __forceinline__ void shade_row(const half_t (&x)[4], const float* __r
     for (int c = 0; c < 3; c++) r.sum[c] = r.diffuse[c] + r.spec[C == 3 ? c : 0];
 }
 
+// the head's four outputs of a shaded row, component c: 0 colour, 1 specular, 2 diffuse, 3 albedo (NERFTEX_LIGHT_VISUAL_*)
+template <int C>
+__device__ __forceinline__ float row_output(const Row<C>& r, const int c, const int which, const float inv_gamma) {
+    switch (which) {
+        case 0: return powf(safe_base(clamp0(r.sum[c])), inv_gamma);
+        case 1: return powf(safe_base(clamp01(r.spec[C == 3 ? c : 0])), inv_gamma);
+        case 2: return powf(safe_base(clamp01(r.diffuse[c])), inv_gamma);
+        default: return clamp01((float)r.a[c]);
+    }
+}
+
 template <int C>
 __global__ __launch_bounds__(kThreads) void sh_light_forward_kernel(const half_t* __restrict__ brdf, const uint32_t stride, const bool wide,
                                                                     const float* __restrict__ normals, const float* __restrict__ dirs,
@@ -155,10 +166,10 @@ __global__ __launch_bounds__(kThreads) void sh_light_forward_kernel(const half_t
     shade_row<C>(x, normals, dirs, b, el, use_specular, r);
 #pragma unroll
     for (int c = 0; c < 3; c++) {
-        color[(size_t)b * 3 + c] = powf(safe_base(clamp0(r.sum[c])), inv_gamma);
-        if (specular) specular[(size_t)b * 3 + c] = powf(safe_base(clamp01(r.spec[C == 3 ? c : 0])), inv_gamma);
-        if (diffuse) diffuse[(size_t)b * 3 + c] = powf(safe_base(clamp01(r.diffuse[c])), inv_gamma);
-        if (albedo) albedo[(size_t)b * 3 + c] = clamp01((float)r.a[c]);
+        color[(size_t)b * 3 + c] = row_output<C>(r, c, 0, inv_gamma);
+        if (specular) specular[(size_t)b * 3 + c] = row_output<C>(r, c, 1, inv_gamma);
+        if (diffuse) diffuse[(size_t)b * 3 + c] = row_output<C>(r, c, 2, inv_gamma);
+        if (albedo) albedo[(size_t)b * 3 + c] = row_output<C>(r, c, 3, inv_gamma);
     }
 }
 

@@ -47,6 +47,7 @@ _SIGNATURES = {
     "nerftex_curved_mid_forward": [_vp, _vp, _vp, _u32, _f32, _i, _vp, _vp, _vp],
     "nerftex_curved_out_forward": [_vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp],
     "nerftex_curved_field_infer": [_vp, _vp],
+    "nerftex_curved_light_infer": [_vp, _vp],
     "nerftex_sh_light_forward": [_vp, _vp],
     "nerftex_sh_light_backward": [_vp, _vp],
     "nerftex_field_mid_backward": [_vp, _vp, _vp, _u32, _vp, _vp],
@@ -209,6 +210,24 @@ class CurvedInferDesc(C.Structure):
                 ("rgbs", _vp), ("units_dev", _vp), ("rows_per_unit", _u32), ("scratch", _vp), ("scratch_bytes", _sz)]
 
 
+LIGHT_VISUAL = {"Full": 0, "Specular": 1, "Diffuse": 2, "Albedo": 3}  # NERFTEX_LIGHT_VISUAL_*
+NORMAL_NET_WEIGHTS, NORMAL_NET_BIASES = 1312, 66  # NERFTEX_NORMAL_NET_*
+
+
+class CurvedLightInferDesc(C.Structure):
+    """nerftex_curved_light_infer_desc of include/nerftex_hip.h, field for field: the SH-lit curved field's no-grad forward as one device-count call."""
+    _fields_ = [("knn", _vp), ("tracer", _vp), ("xyz", _vp), ("dirs", _vp), ("B", _u32), ("n_verts", _u32), ("mesh_vertices", _vp), ("vertex_normals", _vp),
+                ("tbn", _vp), ("K", _u32), ("n_freqs", _u32), ("dir_vec_wdist", _f32), ("h_threshold", _f32), ("table", _vp), ("offsets", _vp), ("D", _u32),
+                ("C", _u32), ("L", _u32), ("S", _f32), ("H", _u32), ("gridtype", _u32), ("align_corners", _i), ("in_add", _f32), ("in_mul", _f32),
+                ("normal_table", _vp), ("normal_offsets", _vp), ("normal_C", _u32), ("normal_L", _u32), ("normal_S", _f32), ("normal_H", _u32),
+                ("normal_gridtype", _u32), ("normal_align_corners", _i), ("normal_in_add", _f32), ("normal_in_mul", _f32), ("sigma_weights", _vp),
+                ("sigma_in", _u32), ("sigma_hidden", _u32), ("sigma_layers", _u32), ("sigma_out", _u32), ("normal_weights", _vp), ("normal_biases", _vp),
+                ("normal_hidden", _u32), ("normal_layers", _u32), ("brdf_weights", _vp), ("brdf_in", _u32), ("brdf_hidden", _u32), ("brdf_layers", _u32),
+                ("brdf_out", _u32), ("env_shs", _vp), ("n_sh", _u32), ("n_color", _u32), ("gamma", _f32), ("flags", _u32), ("visual_mode", _u32),
+                ("fc_weight", _f32), ("eval", _i), ("sigma", _vp), ("rgbs", _vp), ("shading_normal", _vp), ("units_dev", _vp), ("rows_per_unit", _u32),
+                ("scratch", _vp), ("scratch_bytes", _sz)]
+
+
 SH_LIGHT_SPECULAR = 1  # nerftex_sh_light_desc.flags
 
 
@@ -220,7 +239,7 @@ class SHLightDesc(C.Structure):
 
 
 EXPORTS = ["nerftex_last_error", "nerftex_version", "nerftex_tune_get", "nerftex_workspace_slots_touched", "nerftex_curved_field_infer_scratch_bytes",
-           "nerftex_sh_light_scratch_bytes"] + list(_SIGNATURES)
+           "nerftex_curved_light_infer_scratch_bytes", "nerftex_sh_light_scratch_bytes"] + list(_SIGNATURES)
 
 
 def _load():
@@ -238,6 +257,8 @@ def _load():
     lib.nerftex_workspace_slots_touched.restype = C.c_uint
     lib.nerftex_curved_field_infer_scratch_bytes.argtypes = [_u32]
     lib.nerftex_curved_field_infer_scratch_bytes.restype = _sz
+    lib.nerftex_curved_light_infer_scratch_bytes.argtypes = [_u32]
+    lib.nerftex_curved_light_infer_scratch_bytes.restype = _sz
     lib.nerftex_sh_light_scratch_bytes.argtypes = [_u32]
     lib.nerftex_sh_light_scratch_bytes.restype = _sz
     for name, args in _SIGNATURES.items():

@@ -629,7 +629,13 @@ class CurvedField(torch.nn.Module):
         if getattr(self, "light_model", None) is None:
             return ()
         net = self.light_net
-        return (self.light_model, self.light_visual_mode, float(net.gamma), bool(net.use_specular), bool(net.fused), net.envSHs.data_ptr(), tuple(net.envSHs.shape))
+        stamp = (self.light_model, self.light_visual_mode, float(net.gamma), bool(net.use_specular), bool(net.fused), net.envSHs.data_ptr(), tuple(net.envSHs.shape))
+        if not getattr(self, "fused_light_infer", False):
+            return stamp + (False,)
+        # the fused chain bakes in the normal net's table and the packed copy of its weights: the table's storage and every parameter's version
+        nn = self.normal_net
+        return stamp + (True, nn.encoder.embeddings.data_ptr(), nn.encoder.offsets.data_ptr(),
+                        tuple((q.data_ptr(), q._version) for q in list(nn.phi_net.parameters()) + list(nn.theta_net.parameters())))
 
     def _infer_fused(self, x, d):
         """Whether nerftex_curved_field_infer serves this call: _glue_fused(), the shapes the entry's kernels are built for (it refuses every
@@ -671,6 +677,120 @@ class CurvedField(torch.nn.Module):
             rows_per_unit=rows_per_unit, scratch=ptr(scratch), scratch_bytes=scratch.numel())
         return desc, (table, ws_h, wc_h)
 
+    def _infer_light_fused(self, x, d):
+        """Whether nerftex_curved_light_infer serves this call: the SH light model with the switch `fused_light_infer` set (default: not), fp16
+        autocast, the fused head (`light_net.fused`), no probabilistic table, the default shapes (the entry refuses every other one), no bounded
+        angles, a visual mode the head has, fp16 tables, and what the entry asks of its buffers.  Everything else goes through forward()."""
+        if not (getattr(self, "light_model", None) == "SH" and getattr(self, "fused_light_infer", False)):
+            return False
+        from nerftex_hip import LIGHT_VISUAL
+
+        B = x.shape[0]
+        enc, s, nn, net = self.encoder, self.sigma_net, self.normal_net, self.light_net
+        br = net.brdf_layer
+        return (torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.float16 and bool(net.fused) and self.encoder_var is None
+                and nn is not None and not nn.bound_output and (self.training or self.light_visual_mode in LIGHT_VISUAL)
+                and self.in_dim == 41 and self.in_pad == 48 and self.geo_feat_dim == 15 and B % 128 == 0 and B > 0
+                and x.is_cuda and x.dtype == torch.float32 and d.dtype == torch.float32 and x.is_contiguous() and d.is_contiguous()
+                and s.dtype == torch.float16 and br.dtype == torch.float16
+                and (s.input_dim, s.hidden_dim, s.num_layers, s.padded_output_dim) == (48, 32, 2, 16)
+                and (br.input_dim, br.hidden_dim, br.num_layers, br.output_dim) == (16, 64, 3, 5)
+                and (enc.input_dim, enc.level_dim, enc.num_levels, self.multires) == (3, 2, 8, 12) and 1 <= self.projector.K <= 16
+                and (nn.encoder.input_dim, nn.encoder.level_dim, nn.encoder.num_levels) == (3, 2, 4)
+                and (nn.low_freq_band_len_x, nn.low_freq_band_len_z) == (16, 12)
+                and [tuple(l.W.shape) for l in nn.phi_net.layers] == [(16, 20), (16, 16), (1, 16)]
+                and [tuple(l.W.shape) for l in nn.theta_net.layers] == [(16, 28), (16, 16), (1, 16)]
+                and net.envSHs.shape[0] >= 9 and net.envSHs.shape[1] in (1, 3) and net.envSHs.dtype == torch.float32
+                and enc._table().dtype == torch.float16 and nn.encoder._table().dtype == torch.float16)
+
+    def _infer_light_desc(self, x, d, live, sigma, rgbs, scratch, shading_normal=None):
+        """The nerftex_curved_light_infer_desc of one call (and the tensors it points into).  Kept between calls and re-made when a parameter
+        changes: the 16-bit MLP weights, and the normal net's packed block -- every LipLayer's normalization().half(), which is what the
+        framework's half GEMM multiplies with under autocast, and its fp32 biases, in the order include/nerftex_hip.h gives."""
+        from gridencoder.grid import register_offsets
+        from nerftex_hip import LIGHT_VISUAL, SH_LIGHT_SPECULAR, CurvedLightInferDesc, ptr
+
+        enc, p, s, nn, net = self.encoder, self.projector, self.sigma_net, self.normal_net, self.light_net
+        nenc, br = nn.encoder, net.brdf_layer
+        table, ntable = enc._table(), nenc._table()
+        ws, wb = s._weights(), br._weights()
+        layers = list(nn.phi_net.layers) + list(nn.theta_net.layers)
+        stamp = (ws._version, ws.data_ptr(), wb._version, wb.data_ptr(), tuple((q.data_ptr(), q._version) for l in layers for q in (l.W, l.b, l.c)))
+        cache = getattr(self, "_infer_light_cache", None)
+        if cache is None or cache[0] != stamp:
+            register_offsets(enc.offsets, enc.num_levels)
+            register_offsets(nenc.offsets, nenc.num_levels)
+            with torch.autocast("cuda", enabled=False):
+                nw = torch.cat([l.normalization().detach().float().half().reshape(-1) for l in layers]).contiguous()
+                nb = torch.cat([l.b.detach().float().reshape(-1) for l in layers]).contiguous()
+            cache = self._infer_light_cache = (stamp, ws.detach().to(torch.float16), wb.detach().to(torch.float16), nw, nb)
+        _, ws_h, wb_h, nw, nb = cache
+        env = net.envSHs.detach()
+        units, rows_per_unit = (ptr(live[0]), int(live[1])) if live is not None else (None, 0)
+        mode = "Full" if self.training else self.light_visual_mode
+        desc = CurvedLightInferDesc(
+            knn=p._knn.value, tracer=p.tracer._handle.value, xyz=ptr(x), dirs=ptr(d), B=x.shape[0], n_verts=p.mesh_vertices.shape[0],
+            mesh_vertices=ptr(p.mesh_vertices), vertex_normals=ptr(p.vertex_normals), tbn=ptr(p.tbn), K=int(p.K), n_freqs=int(self.multires),
+            dir_vec_wdist=0.05, h_threshold=p._height_limit(...), table=ptr(table), offsets=ptr(enc.offsets), D=int(enc.input_dim), C=int(enc.level_dim),
+            L=int(enc.num_levels), S=float(np.log2(enc.per_level_scale)), H=int(enc.base_resolution), gridtype=int(enc.gridtype_id),
+            align_corners=int(bool(enc.align_corners)), in_add=float(self.bound), in_mul=float(np.float32(1.0) / np.float32(2 * self.bound)),
+            normal_table=ptr(ntable), normal_offsets=ptr(nenc.offsets), normal_C=int(nenc.level_dim), normal_L=int(nenc.num_levels),
+            normal_S=float(np.log2(nenc.per_level_scale)), normal_H=int(nenc.base_resolution), normal_gridtype=int(nenc.gridtype_id),
+            normal_align_corners=int(bool(nenc.align_corners)), normal_in_add=1.0, normal_in_mul=float(np.float32(1.0) / np.float32(2)),  # (encoder(p_sur): bound 1)
+            sigma_weights=ptr(ws_h), sigma_in=s.input_dim, sigma_hidden=s.hidden_dim, sigma_layers=s.num_layers, sigma_out=s.padded_output_dim,
+            normal_weights=ptr(nw), normal_biases=ptr(nb), normal_hidden=16, normal_layers=2,
+            brdf_weights=ptr(wb_h), brdf_in=br.input_dim, brdf_hidden=br.hidden_dim, brdf_layers=br.num_layers, brdf_out=br.output_dim,
+            env_shs=ptr(env), n_sh=env.shape[0], n_color=env.shape[1], gamma=float(net.gamma), flags=SH_LIGHT_SPECULAR if net.use_specular else 0,
+            visual_mode=LIGHT_VISUAL[mode], fc_weight=float(self.fc_weight), eval=int(not self.training), sigma=ptr(sigma), rgbs=ptr(rgbs),
+            shading_normal=ptr(shading_normal), units_dev=units, rows_per_unit=rows_per_unit, scratch=ptr(scratch), scratch_bytes=scratch.numel())
+        return desc, (table, ntable, ws_h, wb_h, nw, nb, env)
+
+    def _light_scratch(self, nbytes, device, st):
+        """One scratch buffer per stream (the ray ranges of a pipelined frame run side by side), grown to the largest batch seen: the loop's
+        batch size changes with nearly every iteration.  A buffer that is replaced goes back to the allocator, which hands it out again only
+        behind the work this stream still has queued on it.  Under a graph capture: a fresh one (the graph's pool keeps it)."""
+        if torch.cuda.is_current_stream_capturing():
+            return torch.empty(nbytes, dtype=torch.uint8, device=device)
+        held = getattr(self, "_infer_light_scratch", None)
+        if held is None:
+            held = self._infer_light_scratch = {}
+        scratch = held.get((device, st))
+        if scratch is None or scratch.numel() < nbytes:
+            scratch = held[(device, st)] = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        return scratch
+
+    @torch.no_grad()
+    def infer_light(self, x, d, live=None, shading_normal=None):
+        """infer() of the SH-lit field through nerftex_curved_light_infer (see `_infer_light_fused`, which the caller has checked);
+        shading_normal: an fp32 [B,3] tensor that receives the normal the head shades with."""
+        import ctypes
+
+        from nerftex_hip import check, lib, stream
+
+        B, st = x.shape[0], stream()
+        scratch = self._light_scratch(lib.nerftex_curved_light_infer_scratch_bytes(B), x.device, st)
+        out = torch.empty(4 * B, dtype=torch.float32, device=x.device)  # [sigma | rgb] in one allocation
+        sigma, rgbs = out[:B], out[B:].view(B, 3)
+        desc, _keep = self._infer_light_desc(x, d, live, sigma, rgbs, scratch, shading_normal)
+        check(lib.nerftex_curved_light_infer(ctypes.byref(desc), st))
+        return sigma, rgbs
+
+    @torch.no_grad()
+    def infer_padded(self, x, d):
+        """infer(x, d) for a batch of ANY size (the reference loop's iterations, Renderer.render_infer): where the light model's fused chain
+        applies but for the batch's size, the batch is padded to the next multiple of 128 with marked slots (which cost nothing) -- every
+        sample then has the bits the device-count loops give it, whatever iteration it falls into."""
+        B = x.shape[0]
+        pad = -B % 128
+        if pad and B and getattr(self, "fused_light_infer", False):
+            xp = torch.full((B + pad, 3), 1e30, dtype=x.dtype, device=x.device)
+            dp = torch.full((B + pad, 3), 1e30, dtype=d.dtype, device=d.device)
+            xp[:B], dp[:B] = x, d
+            if self._infer_light_fused(xp, dp):
+                sigma, rgbs = self.infer_light(xp, dp)
+                return sigma[:B], rgbs[:B]
+        return self.infer(x, d)
+
     @torch.no_grad()
     def infer(self, x, d, live=None):
         """(sigma fp32 [B], rgbs fp32 [B,3]) of forward(x, d) without an autograd node: the whole chain as ONE library call
@@ -679,7 +799,12 @@ class CurvedField(torch.nn.Module):
         cost no neighbour search, no traversal and no table read and come out as exactly 0; every other row holds forward()'s values, bit for
         bit.  The scratch is one buffer per stream, grown to the largest batch seen (under a graph capture: the graph's pool keeps it).
         Where the fused chain does not apply (no fp16 autocast, prob_model, other shapes, fused_glue = False, a batch that is no multiple of
-        128) this is forward(x, d) on all rows, cast to fp32: slower, the same image."""
+        128) this is forward(x, d) on all rows, cast to fp32: slower, the same image.
+        light_model="SH": forward(x, d) on all rows unless `fused_light_infer` is set (default False) -- then the light model's own chain,
+        nerftex_curved_light_infer, under the same rows contract: sigma and the mask are forward()'s bit for bit, the shading normal and the
+        colour follow forward()'s arithmetic at its rounding points."""
+        if self._infer_light_fused(x, d):  # (opt-in: `fused_light_infer`; the SH light model's own chain, the same rows contract)
+            return self.infer_light(x, d, live)
         if not self._infer_fused(x, d):
             sigma, rgbs, _ = self.forward(x, d)
             return sigma.float(), rgbs.float()

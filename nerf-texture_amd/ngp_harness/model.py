@@ -533,7 +533,11 @@ class Renderer(nn.Module):
             xyzs, dirs, deltas = raymarching.march_rays(n_alive, n_step, rays_alive[i % 2], rays_t[i % 2], rays_o, rays_d, self.bound,
                                                         self.density_bitfield, self.cascade, self.grid_size, nears, fars, 128, perturb, dt_gamma,
                                                         max_steps)
-            sigmas, rgbs, _ = self.field(xyzs, dirs)
+            if getattr(self.field, "fused_light_infer", False) and hasattr(self.field, "infer_padded"):
+                # (a CurvedField whose light model renders through its fused chain: the same chain here, so that the three loops agree bit for bit)
+                sigmas, rgbs = self.field.infer_padded(xyzs.contiguous(), dirs.contiguous())
+            else:
+                sigmas, rgbs, _ = self.field(xyzs, dirs)
             if self.density_scale != 1:
                 sigmas = self.density_scale * sigmas
             raymarching.composite_rays(n_alive, n_step, rays_alive[i % 2], rays_t[i % 2], sigmas, rgbs, deltas, weights_sum, depth, image)
