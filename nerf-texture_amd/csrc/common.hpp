@@ -70,6 +70,7 @@ enum Knob {
     kKnobFfmlpBwdTr,     // 1: fused MLP backward builds its weight-gradient operands with ds_read_b64_tr_b16 instead of selection-matrix MFMAs (slower: A/B)
     kKnobGridBwdStage,   // binning: LDS record slots per fill workgroup (0 = default; the rest of a workgroup's block goes straight to memory)
     kKnobCompositeKeep,  // composite_step_kernel: 64-sample chunks a wave keeps in registers between its forward and backward walk (1..4; 0 = default 2)
+    kKnobMarchCountProbe,  // phase ablation of march_count_parallel_kernel for profiling: 1..3 = every segment stops after that phase (0 = off; results are garbage when set)
     kKnobCount
 };
 extern long g_knobs[kKnobCount];

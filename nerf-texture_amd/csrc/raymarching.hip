@@ -375,8 +375,12 @@ __device__ __forceinline__ float ray_t0(const Dda& s, float near, uint32_t pertu
 //     k -> first j > k with T_j >= tt(T_k)    otherwise (tt = exit parameter of the voxel at T_k).
 // So, per workgroup of 32 rays and per segment of 128 sequence members:
 //   phase 1  one lane per ray generates T (3 dependent instructions per member instead of a whole DDA iteration),
-//   phase 2  all 256 threads classify all (ray, k) in parallel with the very same probe() and store the jump distance,
-//   phase 3  one lane per ray follows the jumps through LDS and logs the members it lands on as samples.
+//   phase 2  32 threads per ray classify all (ray, k) in parallel with the very same probe() and keep the jump distance,
+//   phase 3  the ray's 32 threads follow the jumps together by pointer doubling: next[k] = k + max(jump[k], 1), the member the loop starts at
+//            is marked, and in each of at most 7 = log2(128) rounds every member hands its mark to next[k] and takes next[next[k]] as its next;
+//            the marked members are the ones the loop lands on,
+//   phase 4  the marked members without a jump are the samples: ranked with ballots (a ray is half a wave), cut at max_steps and logged.
+// Phases 2-4 of a ray run in ONE half-wave, so only phase 1 (one lane per ray, in wave 0) is fenced off by workgroup barriers.
 // Same floating-point expressions on the same values as the serial loop: the samples are bit-identical.
 #ifndef NERFTEX_MC_RAYS
 #define NERFTEX_MC_RAYS 32
@@ -388,9 +392,19 @@ constexpr uint32_t kMcSub = 32;       // threads per ray in phases 2 and 4 (two 
 constexpr uint32_t kMcThreads = kMcRays * kMcSub;
 constexpr uint32_t kMcPer = kMcSeg / kMcSub;  // members per thread in phases 2 / 4
 constexpr uint32_t kMcTPitch = kMcRays + 1;  // T[k][ray], +1: conflict-free for both access patterns
-constexpr uint32_t kMcJPitch = kMcSeg + 4;   // jump[ray][k] / visited[ray][k] bytes, +4: rows start in different banks
+constexpr uint32_t kMcJPitch = kMcSeg + 4;   // next[ray][k] / mark[ray][k] bytes, k = 0 .. kMcSeg (the last one: the end of the segment); 33 words: rows start in different banks
+constexpr uint32_t kMcRounds = 7;            // pointer-doubling rounds: a path has at most kMcSeg = 2^7 members
+static_assert((1u << kMcRounds) >= kMcSeg && kMcSeg <= 255, "a path is covered by the rounds; member indices fit a byte");
+static_assert(kMcSub == 32 && kWave == 64, "a ray is one half of a wave in phases 2-4 (ballot halves, wave-level ordering of LDS)");
 
-// LEAN: compiled for 64 registers instead of 88 (16 of them spill: 82 us alone instead of 68).  A march workgroup then holds half of a
+// orders the LDS accesses of one wave's lanes: the hardware runs a wave's LDS instructions in order, so it is the compiler that must not move them
+__device__ __forceinline__ void wave_lds_order() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// LEAN: compiled for 64 registers instead of 78 (12 of them spill: 50 us alone instead of 45).  A march workgroup then holds half of a
 // SIMD's register file instead of two thirds, and the kernels of another stream that share the CU with it -- the benchmarked step runs the
 // next steps' marches on a second stream -- keep two waves per SIMD where they kept one (the field forward: 44 us under the march instead
 // of 87).  Chosen by the `march_lean` knob at launch (bench.py sets it for the marches it runs ahead).
@@ -402,22 +416,25 @@ __global__ __launch_bounds__(kMcThreads, LEAN ? 8 : 4) void march_count_parallel
                                                                          int* __restrict__ rays, const int* __restrict__ counter,
                                                                          uint32_t* __restrict__ ws, uint32_t perturb, float* __restrict__ tlog,
                                                                          const float* __restrict__ aabb, float min_near,
-                                                                         float* __restrict__ nears_w, float* __restrict__ fars_w) {
+                                                                         float* __restrict__ nears_w, float* __restrict__ fars_w, const uint32_t probe) {
     // aabb != NULL (nerftex_march_rays_train_fresh): near / far are computed here (and stored for the callers further down the step) instead
     // of read, and the counter is taken as zero -- the near_far launch and the caller's counter.zero_() are not made
+    // probe (the `march_count_probe` knob, tools/march_count_budget.py): 1 .. 3 = every segment stops after that phase; wave-uniform, 0 in product use
     __shared__ float s_T[kMcSeg * kMcTPitch];
-    __shared__ uint8_t s_jump[kMcRays * kMcJPitch];
-    __shared__ uint8_t s_vis[kMcRays * kMcJPitch];  // 1 = this member is a sample of the ray
-    __shared__ uint32_t s_cnt[kMcRays];             // members of this segment below far
-    __shared__ uint32_t s_full[kMcRays];            // the sequence continues in the next segment
-    __shared__ uint32_t s_base[kMcRays];            // samples of this ray logged before this segment
+    __shared__ uint32_t s_next[kMcRays * kMcJPitch / 4];  // a byte per member: the member the loop goes to from this one
+    __shared__ uint32_t s_mark[kMcRays * kMcJPitch / 4];  // a byte per member: 1 = the loop lands on this member
+    __shared__ uint32_t s_cnt[kMcRays];               // members of this segment below far
+    __shared__ uint32_t s_full[kMcRays];              // the sequence continues in the next segment
+    __shared__ uint32_t s_num[kMcRays];               // samples of this ray logged so far
+    __shared__ uint32_t s_done[kMcRays];              // the ray needs no further segment
     __shared__ uint32_t s_live;
 
     const uint32_t tid = threadIdx.x;
-    // phase-1/3 role: lane r < 32 of wave 0 owns ray r.  phase-2/4 role: thread tid works for ray tid / kMcSub
+    // phase-1 role: lane r < 32 of wave 0 owns ray r.  phase-2/3/4 role: thread tid works for ray tid / kMcSub, on members sub + kMcSub * i
     const uint32_t own = tid, n_own = blockIdx.x * kMcRays + own;
     const bool owner = tid < kMcRays && n_own < N;
     const uint32_t r2 = tid / kMcSub, sub = tid % kMcSub, n2 = blockIdx.x * kMcRays + r2;
+    const uint32_t half = tid & 32u;  // shift that brings this ray's half of a wave ballot down
     const bool has2 = n2 < N;
     float near2 = 0.0f, far2 = 0.0f;
     if (has2) {
@@ -426,69 +443,100 @@ __global__ __launch_bounds__(kMcThreads, LEAN ? 8 : 4) void march_count_parallel
     }
     const Dda s2(rays_o + 3 * (size_t)(has2 ? n2 : 0), rays_d + 3 * (size_t)(has2 ? n2 : 0), bound, dt_gamma, max_steps, C, H, grid, far2);
     float* log_row2 = tlog + (size_t)(has2 ? n2 : 0) * max_steps;
+    // phase 3 role: thread sub owns the ray's members 4 * sub .. 4 * sub + 3, one word of each row
+    uint32_t* const next_w = s_next + r2 * (kMcJPitch / 4) + sub;
+    uint32_t* const mark_w = s_mark + r2 * (kMcJPitch / 4) + sub;
+    uint8_t* const next_b = reinterpret_cast<uint8_t*>(s_next + r2 * (kMcJPitch / 4));
+    uint8_t* const mark_b = reinterpret_cast<uint8_t*>(s_mark + r2 * (kMcJPitch / 4));
 
-    // owner state
-    float t_next = 0.0f, far = 0.0f, pending_tt = 0.0f;
-    bool pending = false, done = true;
-    uint32_t num = 0;
-    if (owner) {
-        float near;
-        if (aabb) {
-            near_far_of(rays_o, rays_d, aabb, min_near, (size_t)n_own, near, far);
-            nears_w[n_own] = near;
-            fars_w[n_own] = far;
-        } else {
-            far = fars[n_own];
-            near = nears[n_own];
+    // owner state: where the sequence stands
+    float t_next = 0.0f, far = 0.0f;
+    if (tid < kMcRays) {
+        bool done = true;
+        if (owner) {
+            float near;
+            if (aabb) {
+                near_far_of(rays_o, rays_d, aabb, min_near, (size_t)n_own, near, far);
+                nears_w[n_own] = near;
+                fars_w[n_own] = far;
+            } else {
+                far = fars[n_own];
+                near = nears[n_own];
+            }
+            t_next = ray_t0(s2, near, perturb, n_own, 42);  // s2.dt_min is all ray_t0 reads: the same for every ray
+            done = !(t_next < far);
         }
-        t_next = ray_t0(s2, near, perturb, n_own, 42);  // s2.dt_min is all ray_t0 reads: the same for every ray
-        done = !(t_next < far);
+        s_done[own] = done ? 1u : 0u;
+        s_num[own] = 0u;
     }
     const float dt_min = s2.dt_lo, dt_max = s2.dt_max;  // the step's clamp bounds (dt_lo: see Dda)
+    // state of the ray's loop, the same in all kMcSub threads of the ray
+    float pending_tt = 0.0f;  // a voxel skipped across the segment boundary: its exit parameter
+    bool pending = false;
+    uint32_t num = 0;
 
     for (;;) {
-        if (tid == 0) s_live = 0;
-        for (uint32_t i = tid; i < kMcRays * kMcJPitch / 4; i += kMcThreads) reinterpret_cast<uint32_t*>(s_vis)[i] = 0u;
-        __syncthreads();
+        if (tid == 0) s_live = 0;  // (wave 0 sets it again below, in program order; the others read it between this segment's two barriers)
         // ---- phase 1: the next kMcSeg members of the sequence (a 4-instruction dependent chain per member)
         if (tid < kMcRays) {
             uint32_t cnt = 0;
-            if (owner && !done) {
+            const bool run = owner && s_done[own] == 0;
+            if (run) {
                 // four members per round; clamp as one v_med3_f32 (x = t * dt_gamma is a positive finite number, so the median of
-                // (x, dt_min, dt_max) IS fmin(dt_max, fmax(dt_min, x))): 3 dependent instructions per member
+                // (x, dt_min, dt_max) IS fmin(dt_max, fmax(dt_min, x))): 3 dependent instructions per member.  No lane leaves the loop on
+                // its own (a ray past far goes on generating members nobody reads: they are increasing, so the count of those below far is
+                // all that matters, and it rides in the shadow of the dependent chain); the wave leaves it when all its rays are past far.
                 float t = t_next;
-                while (cnt < kMcSeg) {  // kMcSeg % 4 == 0
+#pragma unroll 2
+                for (uint32_t k = 0; k < kMcSeg; k += 4) {  // kMcSeg % 4 == 0
                     const float t0 = t;
                     const float t1 = t0 + __builtin_amdgcn_fmed3f(t0 * dt_gamma, dt_min, dt_max);
                     const float t2 = t1 + __builtin_amdgcn_fmed3f(t1 * dt_gamma, dt_min, dt_max);
                     const float t3 = t2 + __builtin_amdgcn_fmed3f(t2 * dt_gamma, dt_min, dt_max);
-                    s_T[(cnt + 0) * kMcTPitch + own] = t0;
-                    s_T[(cnt + 1) * kMcTPitch + own] = t1;
-                    s_T[(cnt + 2) * kMcTPitch + own] = t2;
-                    s_T[(cnt + 3) * kMcTPitch + own] = t3;
-                    if (!(t3 < far)) {  // the sequence leaves the box inside this round (members are increasing)
-                        cnt += (t0 < far ? 1u : 0u) + (t1 < far ? 1u : 0u) + (t2 < far ? 1u : 0u);
-                        t = far;  // anything not below far: the ray is finished after this segment
-                        break;
-                    }
-                    cnt += 4;
+                    s_T[(k + 0) * kMcTPitch + own] = t0;
+                    s_T[(k + 1) * kMcTPitch + own] = t1;
+                    s_T[(k + 2) * kMcTPitch + own] = t2;
+                    s_T[(k + 3) * kMcTPitch + own] = t3;
+                    cnt += (t0 < far ? 1u : 0u) + (t1 < far ? 1u : 0u) + (t2 < far ? 1u : 0u) + (t3 < far ? 1u : 0u);
                     t = t3 + __builtin_amdgcn_fmed3f(t3 * dt_gamma, dt_min, dt_max);
+                    if (!__any(t < far ? 1 : 0)) break;  // (a ray that leaves the box in this segment is finished after it, whatever t_next holds)
                 }
                 t_next = t;
                 atomicOr(&s_live, 1u);
             }
             s_cnt[own] = cnt;
-            s_full[own] = (owner && !done && cnt == kMcSeg && t_next < far) ? 1u : 0u;
-            s_base[own] = num;
+            s_full[own] = (run && cnt == kMcSeg && t_next < far) ? 1u : 0u;
         }
         __syncthreads();
         if (s_live == 0) break;
+        const uint32_t cnt = s_cnt[r2];
+        const bool full = s_full[r2] != 0;
+        if (probe == 1) {  // ablation: phase 1 only (every ray still runs all its segments)
+            if (sub == 0) s_done[r2] = full ? 0u : 1u;
+            __syncthreads();
+            continue;
+        }
 
         // ---- phase 2: classify every member; jump = 0 for a sample, else the distance to the first member at or past the voxel exit.
-        // All occupancy bytes of a thread's 16 members are requested before any is used (one memory latency, not sixteen); the
-        // voxel found on the way is kept (4 registers per member) for the exit computation.
+        // All occupancy bytes of a thread's members are requested before any is used (one memory latency, not four); the voxel found on
+        // the way is kept (4 registers per member) for the exit computation.
+        uint32_t jmp[kMcPer];  // this thread's jumps (members at or past cnt: 0)
+        float ext[kMcPer];     // exit parameter of the voxel a skipped member lies in
         {
-            const uint32_t cnt = s_cnt[r2];
+            // where the loop enters the segment: member 0, or past the leading members a pending skip still covers (members are increasing)
+            uint32_t k0 = 0;
+            if (__any(pending ? 1 : 0)) {
+                uint32_t c = 0;
+#pragma unroll
+                for (uint32_t i = 0; i < kMcPer; i++) {
+                    const uint32_t k = sub + kMcSub * i;
+                    c += (pending && k < cnt && s_T[k * kMcTPitch + r2] < pending_tt) ? 1u : 0u;
+                }
+#pragma unroll
+                for (int off = (int)kMcSub / 2; off > 0; off >>= 1) c += __shfl_xor(c, off, kMcSub);
+                k0 = c;
+                pending = pending && k0 == cnt && full;  // the whole of a full segment is still inside that voxel
+            }
             Dda::Cell cell[kMcPer];
             uint8_t occ_byte[kMcPer];
 #pragma unroll
@@ -504,6 +552,9 @@ __global__ __launch_bounds__(kMcThreads, LEAN ? 8 : 4) void march_count_parallel
 #pragma unroll
             for (uint32_t i = 0; i < kMcPer; i++) {
                 const uint32_t k = sub + kMcSub * i;
+                jmp[i] = 0;
+                ext[i] = 0.0f;
+                uint32_t to = cnt;  // members at or past cnt stand for the end of the segment, which goes to itself
                 if (k < cnt) {
                     uint32_t jump = 0;
                     if (!((occ_byte[i] >> (cell[i].packed >> 29)) & 1u)) {
@@ -518,77 +569,83 @@ __global__ __launch_bounds__(kMcThreads, LEAN ? 8 : 4) void march_count_parallel
                             if (c < 4) break;
                         }
                         jump = j - k;
+                        ext[i] = tt;
                     }
-                    s_jump[r2 * kMcJPitch + k] = (uint8_t)jump;
+                    jmp[i] = jump;
+                    to = k + (jump ? jump : 1u);  // the loop's move from member k: k + 1 from a sample, k + jump from a skip (never past cnt)
                 }
+                next_b[k] = (uint8_t)to;
+                mark_b[k] = (k < cnt && k == k0) ? 1 : 0;
             }
+            if (sub == 0) next_b[kMcSeg] = (uint8_t)kMcSeg;  // (cnt == kMcSeg: the end of the segment is no member)
         }
-        __syncthreads();
+        if (probe == 2) {  // ablation: + classification
+            if (sub == 0) s_done[r2] = full ? 0u : 1u;
+            __syncthreads();
+            continue;
+        }
 
-        // ---- phase 3: follow the jumps; nothing but the hop itself is on the dependent chain (samples are only MARKED here)
-        if (owner && !done) {
-            const uint32_t cnt = s_cnt[own];
-            const bool full = s_full[own] != 0;
-            const uint8_t* jr = s_jump + own * kMcJPitch;
-            uint8_t* vr = s_vis + own * kMcJPitch;
-            uint32_t k = 0;
-            if (pending) {  // a voxel skipped across the segment boundary: keep skipping until its exit is passed
-                while (k < cnt && s_T[k * kMcTPitch + own] < pending_tt) k++;
-                pending = k == cnt && full;
-            }
-            uint32_t last_skip = 0xffffffffu;  // member whose skip ran to the end of a full segment
-            while (k < cnt && num < max_steps) {  // branch-free body: the LDS read of the jump is the whole dependent chain
-                const uint32_t j = jr[k];
-                const uint32_t sample = j == 0 ? 1u : 0u;
-                vr[k] = (uint8_t)sample;
-                num += sample;
-                last_skip = (j != 0 && k + j == cnt) ? k : last_skip;
-                k += j + sample;
-            }
-            if (full && last_skip != 0xffffffffu && k == cnt && num < max_steps) {  // the skip may continue into the next segment
-                Dda::Cell c;
-                const float t = s_T[last_skip * kMcTPitch + own];
-                const Dda so(rays_o + 3 * (size_t)n_own, rays_d + 3 * (size_t)n_own, bound, dt_gamma, max_steps, C, H, grid, far);
-                (void)so.locate(t, c);
-                pending_tt = so.exit_of(t, c);
-                pending = true;
-            }
-            if (!full || num >= max_steps) done = true;
+        // ---- phase 3: follow the jumps by pointer doubling, a thread on four consecutive members (one word of each row).  Before round r a
+        // member's next is where the loop stands 2^r moves after it, and the members within 2^r moves of the entry are marked; all reads of a
+        // round come before its writes.
+        wave_lds_order();
+        for (uint32_t round = 0; round < kMcRounds; round++) {
+            const uint32_t nx = *next_w, mk = *mark_w;
+            bool more = false;  // a marked member whose next is not yet the end of the segment: members further on are still to be marked
+#pragma unroll
+            for (uint32_t i = 0; i < 4; i++) more = more || (((mk >> (8 * i)) & 0xffu) != 0 && ((nx >> (8 * i)) & 0xffu) != cnt);
+            if (!__any(more ? 1 : 0)) break;  // the same for the whole wave
+            uint32_t nn = 0;
+#pragma unroll
+            for (uint32_t i = 0; i < 4; i++) nn |= (uint32_t)next_b[(nx >> (8 * i)) & 0xffu] << (8 * i);
+            wave_lds_order();
+            *next_w = nn;
+#pragma unroll
+            for (uint32_t i = 0; i < 4; i++)
+                if ((mk >> (8 * i)) & 0xffu) mark_b[(nx >> (8 * i)) & 0xffu] = 1;
+            wave_lds_order();
         }
-        __syncthreads();
 
-        // ---- phase 4: log the marked members, 8 threads per ray, in order
-        {
-            uint32_t mine = 0;
-            uint32_t flags = 0;
+        // ---- phase 4: the marked members without a jump are the ray's samples, in order of k = sub + kMcSub * i: a ballot per i ranks them.
+        // Only the first max_steps samples of a ray count (the loop stops there).
+        uint32_t at = num;
+        bool last_skip = false;  // this thread holds the loop's last member of the segment, and it is a skip that runs to the segment's end
+        float last_ext = 0.0f;
 #pragma unroll
-            for (uint32_t i = 0; i < kMcPer; i++) {
-                const uint32_t k = sub * kMcPer + i;  // consecutive members per thread
-                const uint32_t v = s_vis[r2 * kMcJPitch + k];
-                flags |= v << i;
-                mine += v;
-            }
-            uint32_t incl = mine;  // inclusive scan over the kMcSub threads of the ray (an aligned lane group of the wave)
-#pragma unroll
-            for (int off = 1; off < (int)kMcSub; off <<= 1) {
-                const uint32_t o = __shfl_up(incl, off, kMcSub);
-                if ((int)sub >= off) incl += o;
-            }
-            uint32_t at = s_base[r2] + incl - mine;
-            if (has2 && flags) {
-#pragma unroll
-                for (uint32_t i = 0; i < kMcPer; i++)
-                    if ((flags >> i) & 1u) log_row2[at++] = s_T[(sub * kMcPer + i) * kMcTPitch + r2];
+        for (uint32_t i = 0; i < kMcPer; i++) {
+            const uint32_t k = sub + kMcSub * i;
+            const bool on = k < cnt && mark_b[k] != 0;
+            const bool vis = on && jmp[i] == 0;
+            const uint32_t mine = (uint32_t)(__ballot(vis ? 1 : 0) >> half);
+            const uint32_t rank = at + (uint32_t)__popc(mine & ((1u << sub) - 1u));
+            if (vis && rank < max_steps && probe != 3) log_row2[rank] = s_T[k * kMcTPitch + r2];
+            at += (uint32_t)__popc(mine);
+            if (on && jmp[i] != 0 && k + jmp[i] == cnt) {
+                last_skip = true;
+                last_ext = ext[i];
             }
         }
-        __syncthreads();  // s_vis / s_T are rewritten by the next segment
+        const bool capped = at >= max_steps;
+        num = capped ? max_steps : at;
+        const uint32_t holder = (uint32_t)(__ballot(last_skip ? 1 : 0) >> half);
+        const float carried = __shfl(last_ext, holder ? __ffs((int)holder) - 1 : 0, kMcSub);
+        if (holder != 0 && full && !capped) {  // the skip may continue into the next segment
+            pending_tt = carried;
+            pending = true;
+        }
+        if (sub == 0) {
+            s_num[r2] = num;
+            s_done[r2] = (!full || capped) ? 1u : 0u;
+        }
+        __syncthreads();  // s_T, s_done are read / rewritten by wave 0 for the next segment
     }
 
-    if (owner) rays[3 * (size_t)n_own + 2] = (int)num;
+    const uint32_t num_own = tid < kMcRays ? s_num[tid] : 0u;
+    if (owner) rays[3 * (size_t)n_own + 2] = (int)num_own;
     // sample totals per workgroup of kMcRays rays, plain stores (nothing to pre-zero): the expand pass adds kRayBlock / kMcRays of them per
     // 64-ray block
     if (tid < kWave) {
-        const uint32_t wsum = wave_sum(tid < kMcRays ? num : 0u);
+        const uint32_t wsum = wave_sum(num_own);
         if (tid == 0) {
             ws[1 + blockIdx.x] = wsum;
             if (blockIdx.x == 0) ws[0] = aabb ? 0u : (uint32_t)counter[0];
@@ -1487,14 +1544,15 @@ int march_train_impl(const float* rays_o, const float* rays_d, const uint8_t* gr
     }
     if (parallel_count) {
         KernelTimer kt("march_count_parallel_kernel", st);
+        const uint32_t mc_probe = (uint32_t)knob(kKnobMarchCountProbe);
         if (knob(kKnobMarchLean))
             hipLaunchKernelGGL(march_count_parallel_kernel<true>, dim3(div_up(N, kMcRays)), dim3(kMcThreads), 0, st, rays_o, rays_d, grid, bound, dt_gamma,
                                max_steps, N, C, H, nears, fars, rays, counter, ws, perturb, tlog, aabb, min_near, const_cast<float*>(nears),
-                               const_cast<float*>(fars));
+                               const_cast<float*>(fars), mc_probe);
         else
             hipLaunchKernelGGL(march_count_parallel_kernel<false>, dim3(div_up(N, kMcRays)), dim3(kMcThreads), 0, st, rays_o, rays_d, grid, bound, dt_gamma,
                                max_steps, N, C, H, nears, fars, rays, counter, ws, perturb, tlog, aabb, min_near, const_cast<float*>(nears),
-                               const_cast<float*>(fars));
+                               const_cast<float*>(fars), mc_probe);
     } else {
         KernelTimer kt("march_count_kernel", st);
         hipLaunchKernelGGL(march_count_kernel, dim3(nblocks), dim3(kRayBlock), 0, st, rays_o, rays_d, grid, bound, dt_gamma, max_steps, N,
