@@ -36,60 +36,30 @@ __global__ __launch_bounds__(kThreads) void curved_light_out_rows_kernel(const h
     for (int c = 0; c < 3; c++) rgbs[(size_t)b * 3 + c] = row_output<C>(r, c, which, inv_gamma);
 }
 
-// the scratch of one nerftex_curved_light_infer call: every buffer starts on a 256-byte boundary
+// the scratch of one nerftex_curved_light_infer call: the front half's buffers (fieldglue.hip), then its own
 struct CurvedLightScratch {
-    size_t idx, dist, p_sur, normal, tbn, mask, x_lbc, n_lbc, xin, h, sigma_raw, brdf_in, brdf, shading, total;
-    explicit CurvedLightScratch(size_t B) {
-        size_t at = 0;
-        auto take = [&](size_t bytes_per_row) {
-            const size_t here = at;
-            at += (B * bytes_per_row + 255) / 256 * 256;
-            return here;
-        };
-        idx = take(16 * sizeof(int32_t));  // (sized for the largest K)
-        dist = take(16 * sizeof(float));
-        p_sur = take(3 * sizeof(float));
-        normal = take(3 * sizeof(float));
-        tbn = take(9 * sizeof(float));
-        mask = take(1);
-        x_lbc = take(16 * sizeof(half_t));
-        n_lbc = take(8 * sizeof(half_t));
-        xin = take(48 * sizeof(half_t));
-        h = take(16 * sizeof(half_t));
-        sigma_raw = take(sizeof(float));
-        brdf_in = take(16 * sizeof(half_t));
-        brdf = take(16 * sizeof(half_t));
-        shading = take(3 * sizeof(float));  // (used when the caller does not ask for the shading normal)
-        total = at;
-    }
+    ScratchCarver carve;
+    CurvedFront f;
+    float* tbn;
+    half_t* n_lbc;
+    float* sigma_raw;
+    half_t *brdf_in, *brdf;
+    float* shading;  // (used when the caller does not ask for the shading normal)
+    CurvedLightScratch(void* scratch, size_t B)
+        : carve{reinterpret_cast<uintptr_t>(scratch), B}, f(carve), tbn(carve.take<float>(9)), n_lbc(carve.take<half_t>(8)), sigma_raw(carve.take<float>(1)),
+          brdf_in(carve.take<half_t>(16)), brdf(carve.take<half_t>(16)), shading(carve.take<float>(3)) {}
 };
 
 }  // namespace
 }  // namespace nerftex
 
-extern "C" size_t nerftex_curved_light_infer_scratch_bytes(uint32_t B) { return CurvedLightScratch(B).total; }
+extern "C" size_t nerftex_curved_light_infer_scratch_bytes(uint32_t B) { return CurvedLightScratch(nullptr, B).carve.at; }
 
 extern "C" int nerftex_curved_light_infer(const nerftex_curved_light_infer_desc* d, void* stream) {
     clear_error();
-    if (!d) {
-        set_error("curved_light_infer: NULL descriptor");
-        return NERFTEX_ERR_INVALID;
-    }
-    if (d->B % 128 != 0) {
-        set_error("curved_light_infer: the batch must be a multiple of 128 rows, but got %u", d->B);
-        return NERFTEX_ERR_INVALID;
-    }
-    if (d->B != 0 && (d->n_verts == 0 || d->n_verts > 0x7fffffffu)) {
-        set_error("curved_light_infer: the mesh needs between 1 and 2^31 - 1 vertices, but got %u", d->n_verts);
-        return NERFTEX_ERR_INVALID;
-    }
-    if (d->K == 0 || d->K > 16) {
-        set_error("curved_light_infer: 1 <= K <= 16 neighbours per point, but got %u", d->K);
-        return NERFTEX_ERR_INVALID;
-    }
-    if (d->n_freqs != 12 || d->D != 3 || d->C != 2 || d->L != 8 || d->normal_C != 2 || d->normal_L != 4 || d->sigma_in != 48 || d->sigma_hidden != 32 ||
-        d->sigma_layers != 2 || d->sigma_out != 16 || d->normal_hidden != 16 || d->normal_layers != 2 || d->brdf_in != 16 || d->brdf_hidden != 64 ||
-        d->brdf_layers != 3 || d->brdf_out != 5) {
+    if (!front_batch_ok(d, "curved_light_infer")) return NERFTEX_ERR_INVALID;
+    if (!front_shapes_ok(d) || d->normal_C != 2 || d->normal_L != 4 || d->normal_hidden != 16 || d->normal_layers != 2 || d->brdf_in != 16 ||
+        d->brdf_hidden != 64 || d->brdf_layers != 3 || d->brdf_out != 5) {
         set_error("curved_light_infer: the kernels serve the default SH-lit curved field only (12 height bands, a 3-D table of 8 levels x 2 features, a normal "
                   "table of 4 levels x 2 features, sigma net 48 -> 32 x 2 -> 16, normal nets 16 wide with 2 hidden layers, BRDF net 16 -> 64 x 3 -> 5)");
         return NERFTEX_ERR_INVALID;
@@ -105,78 +75,51 @@ extern "C" int nerftex_curved_light_infer(const nerftex_curved_light_infer_desc*
         return NERFTEX_ERR_INVALID;
     }
     if (d->B == 0) return NERFTEX_OK;
-    const CurvedLightScratch at(d->B);
-    if (!d->knn || !d->tracer || !d->xyz || !d->dirs || !d->mesh_vertices || !d->vertex_normals || !d->tbn || !d->table || !d->offsets || !d->normal_table ||
-        !d->normal_offsets || !d->sigma_weights || !d->normal_weights || !d->normal_biases || !d->brdf_weights || !d->env_shs || !d->sigma || !d->rgbs ||
-        !d->scratch || (reinterpret_cast<uintptr_t>(d->scratch) & 255) || d->scratch_bytes < at.total) {
+    const CurvedLightScratch sc(d->scratch, d->B);
+    if (!front_pointers_ok(d, sc.carve.at) || !d->tbn || !d->normal_table || !d->normal_offsets || !d->normal_weights || !d->normal_biases || !d->brdf_weights ||
+        !d->env_shs) {
         set_error("curved_light_infer: handles, inputs, frames, tables, weights, lighting and outputs must not be NULL, and scratch must be 256-byte aligned "
-                  "and hold %zu bytes", at.total);
+                  "and hold %zu bytes", sc.carve.at);
         return NERFTEX_ERR_INVALID;
     }
-    if (((reinterpret_cast<uintptr_t>(d->sigma_weights) | reinterpret_cast<uintptr_t>(d->brdf_weights)) & 15) ||
-        ((reinterpret_cast<uintptr_t>(d->normal_weights) | reinterpret_cast<uintptr_t>(d->normal_biases)) & 3) || !(d->in_mul > 0.0f) || !std::isfinite(d->in_mul) ||
-        !(d->normal_in_mul > 0.0f) || !std::isfinite(d->normal_in_mul)) {
+    if (!front_scales_ok(d) || (reinterpret_cast<uintptr_t>(d->brdf_weights) & 15) ||
+        ((reinterpret_cast<uintptr_t>(d->normal_weights) | reinterpret_cast<uintptr_t>(d->normal_biases)) & 3) || !(d->normal_in_mul > 0.0f) ||
+        !std::isfinite(d->normal_in_mul)) {
         set_error("curved_light_infer: the MLP weight vectors must be 16-byte aligned, the normal net's block 4-byte aligned, and the gathers' input scales "
                   "positive and finite");
         return NERFTEX_ERR_INVALID;
     }
     hipStream_t st = as_stream(stream);
-    char* sc = static_cast<char*>(d->scratch);
-    int32_t* idx = reinterpret_cast<int32_t*>(sc + at.idx);
-    float* dist = reinterpret_cast<float*>(sc + at.dist);
-    float* p_sur = reinterpret_cast<float*>(sc + at.p_sur);
-    float* normal = reinterpret_cast<float*>(sc + at.normal);
-    float* tbn = reinterpret_cast<float*>(sc + at.tbn);
-    uint8_t* mask = reinterpret_cast<uint8_t*>(sc + at.mask);
-    half_t* x_lbc = reinterpret_cast<half_t*>(sc + at.x_lbc);
-    half_t* n_lbc = reinterpret_cast<half_t*>(sc + at.n_lbc);
-    half_t* xin = reinterpret_cast<half_t*>(sc + at.xin);
-    half_t* h = reinterpret_cast<half_t*>(sc + at.h);
-    float* sigma_raw = reinterpret_cast<float*>(sc + at.sigma_raw);
-    half_t* brdf_in = reinterpret_cast<half_t*>(sc + at.brdf_in);
-    half_t* brdf = reinterpret_cast<half_t*>(sc + at.brdf);
-    float* shading = d->shading_normal ? d->shading_normal : reinterpret_cast<float*>(sc + at.shading);
+    float* shading = d->shading_normal ? d->shading_normal : sc.shading;
     const uint32_t B = d->B, rpu = d->rows_per_unit;
     const int32_t* units = d->units_dev;
     const dim3 grid(div_up(B, 256u)), block(256);
 
-    int rc = knn_query_rows(d->knn, d->xyz, d->dirs, B, d->K, idx, dist, units, rpu, st);
+    int rc = curved_front_gather(d, sc.f, sc.tbn, stream);
     if (rc != NERFTEX_OK) return rc;
-    rc = curved_project_rows(d->tracer, d->xyz, d->dirs, idx, dist, B, d->K, d->mesh_vertices, d->vertex_normals, d->n_verts, d->dir_vec_wdist, d->h_threshold,
-                             p_sur, mask, normal, xin, units, rpu, st, d->tbn, tbn);
-    if (rc != NERFTEX_OK) return rc;
-    // (exported entries of this library: they clear the error text, which holds nothing at this point, and check the gathers' own arguments)
-    rc = nerftex_grid_encode_forward_rows(p_sur, d->table, d->offsets, x_lbc, B, d->D, d->C, d->L, d->S, d->H, d->gridtype, d->align_corners, NERFTEX_F16,
-                                          NERFTEX_LAYOUT_LBC, d->in_add, d->in_mul, units, rpu, stream);
-    if (rc != NERFTEX_OK) return rc;
-    rc = nerftex_grid_encode_forward_rows(p_sur, d->normal_table, d->normal_offsets, n_lbc, B, d->D, d->normal_C, d->normal_L, d->normal_S, d->normal_H,
+    // (the normal table's gather, in front of the pack kernel: an exported entry, as the texture table's)
+    rc = nerftex_grid_encode_forward_rows(sc.f.p_sur, d->normal_table, d->normal_offsets, sc.n_lbc, B, d->D, d->normal_C, d->normal_L, d->normal_S, d->normal_H,
                                           d->normal_gridtype, d->normal_align_corners, NERFTEX_F16, NERFTEX_LAYOUT_LBC, d->normal_in_add, d->normal_in_mul, units,
                                           rpu, stream);
     if (rc != NERFTEX_OK) return rc;
-    {
-        KernelTimer kt("curved_pack_features_rows_kernel", st);
-        hipLaunchKernelGGL(curved_pack_features_rows_kernel, grid, block, 0, st, x_lbc, B, xin, units, rpu);
-    }
-    if ((rc = check_launch("curved_light_infer(pack)")) != NERFTEX_OK) return rc;
-    rc = ffmlp_inference_rows(xin, d->sigma_weights, B, 48, 32, 2, h, units, rpu, st);
-    if (rc != NERFTEX_OK) return rc;
+    if ((rc = curved_front_sigma(d, sc.f, "curved_light_infer(pack)", stream)) != NERFTEX_OK) return rc;
     {
         KernelTimer kt("curved_light_mid_rows_kernel", st);
-        hipLaunchKernelGGL(curved_light_mid_rows_kernel, grid, block, 0, st, h, xin, n_lbc, normal, tbn, d->dirs, static_cast<const half_t*>(d->normal_weights),
-                           d->normal_biases, B, d->fc_weight, d->eval, sigma_raw, brdf_in, shading, units, rpu);
+        hipLaunchKernelGGL(curved_light_mid_rows_kernel, grid, block, 0, st, sc.f.h, sc.f.xin, sc.n_lbc, sc.f.normal, sc.tbn, d->dirs,
+                           static_cast<const half_t*>(d->normal_weights), d->normal_biases, B, d->fc_weight, d->eval, sc.sigma_raw, sc.brdf_in, shading, units, rpu);
     }
     if ((rc = check_launch("curved_light_infer(mid)")) != NERFTEX_OK) return rc;
-    rc = ffmlp_inference_rows(brdf_in, d->brdf_weights, B, 16, 64, 3, brdf, units, rpu, st);
+    rc = ffmlp_inference_rows(sc.brdf_in, d->brdf_weights, B, 16, 64, 3, sc.brdf, units, rpu, st);
     if (rc != NERFTEX_OK) return rc;
     {
         const float inv_gamma = (float)(1.0 / (double)d->gamma);
         const bool spec = (d->flags & NERFTEX_SH_LIGHT_SPECULAR) != 0;
         KernelTimer kt("curved_light_out_rows_kernel", st);
         if (d->n_color == 3)
-            hipLaunchKernelGGL(curved_light_out_rows_kernel<3>, grid, block, 0, st, brdf, shading, d->dirs, d->env_shs, mask, sigma_raw, B, inv_gamma, spec,
+            hipLaunchKernelGGL(curved_light_out_rows_kernel<3>, grid, block, 0, st, sc.brdf, shading, d->dirs, d->env_shs, sc.f.mask, sc.sigma_raw, B, inv_gamma, spec,
                                (int)d->visual_mode, d->sigma, d->rgbs, units, rpu);
         else
-            hipLaunchKernelGGL(curved_light_out_rows_kernel<1>, grid, block, 0, st, brdf, shading, d->dirs, d->env_shs, mask, sigma_raw, B, inv_gamma, spec,
+            hipLaunchKernelGGL(curved_light_out_rows_kernel<1>, grid, block, 0, st, sc.brdf, shading, d->dirs, d->env_shs, sc.f.mask, sc.sigma_raw, B, inv_gamma, spec,
                                (int)d->visual_mode, d->sigma, d->rgbs, units, rpu);
     }
     return check_launch("curved_light_infer(out)");

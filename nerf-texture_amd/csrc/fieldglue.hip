@@ -390,30 +390,108 @@ __global__ __launch_bounds__(256) void curved_light_mid_rows_kernel(const half_t
     curved_light_mid_row(b, B, h, xin, n_lbc, normal, tbn, w_s, b_s, fc, eval, sigma_raw, brdf_in, shading);
 }
 
-// the scratch of one nerftex_curved_field_infer call: every buffer starts on a 256-byte boundary
-struct CurvedScratch {
-    size_t idx, dist, p_sur, normal, mask, x_lbc, xin, h, sigma_raw, cin, hc, total;
-    explicit CurvedScratch(size_t B) {
-        size_t at = 0;
-        auto take = [&](size_t bytes_per_row) {
-            const size_t here = at;
-            at += (B * bytes_per_row + 255) / 256 * 256;
-            return here;
-        };
-        idx = take(16 * sizeof(int32_t));  // (sized for the largest K)
-        dist = take(16 * sizeof(float));
-        p_sur = take(3 * sizeof(float));
-        normal = take(3 * sizeof(float));
-        mask = take(1);
-        x_lbc = take(16 * sizeof(half_t));
-        xin = take(48 * sizeof(half_t));
-        h = take(16 * sizeof(half_t));
-        sigma_raw = take(sizeof(half_t));
-        cin = take(32 * sizeof(half_t));
-        hc = take(16 * sizeof(half_t));
-        total = at;
+// ---- the front half nerftex_curved_field_infer and nerftex_curved_light_infer (curved_light.inc) share: neighbour search to sigma net ------------------
+
+// carves the caller's scratch into per-row buffers, each starting on a 256-byte boundary (base 0: the offsets alone, `at` ends as the size)
+struct ScratchCarver {
+    uintptr_t base;
+    size_t B, at = 0;
+    template <typename T>
+    T* take(size_t values_per_row) {
+        T* here = reinterpret_cast<T*>(base + at);
+        at += (B * values_per_row * sizeof(T) + 255) / 256 * 256;
+        return here;
     }
 };
+
+// the buffers of the front half; each entry's scratch carves them first and its own behind them
+struct CurvedFront {
+    int32_t* idx;
+    float *dist, *p_sur, *normal;
+    uint8_t* mask;
+    half_t *x_lbc, *xin, *h;
+    explicit CurvedFront(ScratchCarver& c)
+        : idx(c.take<int32_t>(16)), dist(c.take<float>(16)),  // (sized for the largest K)
+          p_sur(c.take<float>(3)), normal(c.take<float>(3)), mask(c.take<uint8_t>(1)), x_lbc(c.take<half_t>(16)), xin(c.take<half_t>(48)), h(c.take<half_t>(16)) {}
+};
+
+// the scratch of one nerftex_curved_field_infer call
+struct CurvedScratch {
+    ScratchCarver carve;
+    CurvedFront f;
+    half_t *sigma_raw, *cin, *hc;
+    CurvedScratch(void* scratch, size_t B)
+        : carve{reinterpret_cast<uintptr_t>(scratch), B}, f(carve), sigma_raw(carve.take<half_t>(1)), cin(carve.take<half_t>(32)), hc(carve.take<half_t>(16)) {}
+};
+
+// The refusals over the descriptors' shared members (knn .. in_mul, the sigma net, scratch), in the order include/nerftex_hip.h documents: each
+// entry calls them one after the other and puts its own conditions beside them.  `who`: the entry's name in the messages.
+template <typename Desc>
+bool front_batch_ok(const Desc* d, const char* who) {
+    if (!d) {
+        set_error("%s: NULL descriptor", who);
+        return false;
+    }
+    if (d->B % 128 != 0) {
+        set_error("%s: the batch must be a multiple of 128 rows, but got %u", who, d->B);
+        return false;
+    }
+    if (d->B != 0 && (d->n_verts == 0 || d->n_verts > 0x7fffffffu)) {
+        set_error("%s: the mesh needs between 1 and 2^31 - 1 vertices, but got %u", who, d->n_verts);
+        return false;
+    }
+    if (d->K == 0 || d->K > 16) {
+        set_error("%s: 1 <= K <= 16 neighbours per point, but got %u", who, d->K);
+        return false;
+    }
+    return true;
+}
+
+// (no message: the entry names its whole set of shapes in one refusal)
+template <typename Desc>
+bool front_shapes_ok(const Desc* d) {
+    return d->n_freqs == 12 && d->D == 3 && d->C == 2 && d->L == 8 && d->sigma_in == 48 && d->sigma_hidden == 32 && d->sigma_layers == 2 && d->sigma_out == 16;
+}
+
+// (tbn is the light entry's to ask for: the static light model does not read the frames)
+template <typename Desc>
+bool front_pointers_ok(const Desc* d, size_t scratch_bytes) {
+    return d->knn && d->tracer && d->xyz && d->dirs && d->mesh_vertices && d->vertex_normals && d->table && d->offsets && d->sigma_weights && d->sigma && d->rgbs &&
+           d->scratch && !(reinterpret_cast<uintptr_t>(d->scratch) & 255) && d->scratch_bytes >= scratch_bytes;
+}
+
+template <typename Desc>
+bool front_scales_ok(const Desc* d) {
+    return !(reinterpret_cast<uintptr_t>(d->sigma_weights) & 15) && d->in_mul > 0.0f && std::isfinite(d->in_mul);
+}
+
+// The launches of the front half, in two parts: the light entry gathers its normal table between them.
+// neighbour search -> projector (tbn_out: the hit face's frame, or NULL: no frame is read or written) -> gather of the texture table
+template <typename Desc>
+int curved_front_gather(const Desc* d, const CurvedFront& f, float* tbn_out, void* stream) {
+    int rc = knn_query_rows(d->knn, d->xyz, d->dirs, d->B, d->K, f.idx, f.dist, d->units_dev, d->rows_per_unit, as_stream(stream));
+    if (rc != NERFTEX_OK) return rc;
+    rc = curved_project_rows(d->tracer, d->xyz, d->dirs, f.idx, f.dist, d->B, d->K, d->mesh_vertices, d->vertex_normals, d->n_verts, d->dir_vec_wdist,
+                             d->h_threshold, f.p_sur, f.mask, f.normal, f.xin, d->units_dev, d->rows_per_unit, as_stream(stream), tbn_out ? d->tbn : nullptr,
+                             tbn_out);
+    if (rc != NERFTEX_OK) return rc;
+    // (an exported entry of this library: it clears the error text, which holds nothing at this point, and checks the gather's own arguments)
+    return nerftex_grid_encode_forward_rows(f.p_sur, d->table, d->offsets, f.x_lbc, d->B, d->D, d->C, d->L, d->S, d->H, d->gridtype, d->align_corners, NERFTEX_F16,
+                                            NERFTEX_LAYOUT_LBC, d->in_add, d->in_mul, d->units_dev, d->rows_per_unit, stream);
+}
+
+// pack -> sigma net 48 -> 32 x 2 -> 16;  pack_label: the entry's check_launch label of the pack kernel
+template <typename Desc>
+int curved_front_sigma(const Desc* d, const CurvedFront& f, const char* pack_label, void* stream) {
+    hipStream_t st = as_stream(stream);
+    {
+        KernelTimer kt("curved_pack_features_rows_kernel", st);
+        hipLaunchKernelGGL(curved_pack_features_rows_kernel, dim3(div_up(d->B, 256u)), dim3(256), 0, st, f.x_lbc, d->B, f.xin, d->units_dev, d->rows_per_unit);
+    }
+    const int rc = check_launch(pack_label);
+    if (rc != NERFTEX_OK) return rc;
+    return ffmlp_inference_rows(f.xin, d->sigma_weights, d->B, 48, 32, 2, f.h, d->units_dev, d->rows_per_unit, st);
+}
 
 }  // namespace
 }  // namespace nerftex
@@ -461,87 +539,45 @@ extern "C" int nerftex_curved_out_forward(const void* hc, uint32_t row_stride, c
     return check_launch("curved_out_forward");
 }
 
-extern "C" size_t nerftex_curved_field_infer_scratch_bytes(uint32_t B) { return CurvedScratch(B).total; }
+extern "C" size_t nerftex_curved_field_infer_scratch_bytes(uint32_t B) { return CurvedScratch(nullptr, B).carve.at; }
 
 extern "C" int nerftex_curved_field_infer(const nerftex_curved_infer_desc* d, void* stream) {
     clear_error();
-    if (!d) {
-        set_error("curved_field_infer: NULL descriptor");
-        return NERFTEX_ERR_INVALID;
-    }
-    if (d->B % 128 != 0) {
-        set_error("curved_field_infer: the batch must be a multiple of 128 rows, but got %u", d->B);
-        return NERFTEX_ERR_INVALID;
-    }
-    if (d->B != 0 && (d->n_verts == 0 || d->n_verts > 0x7fffffffu)) {
-        set_error("curved_field_infer: the mesh needs between 1 and 2^31 - 1 vertices, but got %u", d->n_verts);
-        return NERFTEX_ERR_INVALID;
-    }
-    if (d->K == 0 || d->K > 16) {
-        set_error("curved_field_infer: 1 <= K <= 16 neighbours per point, but got %u", d->K);
-        return NERFTEX_ERR_INVALID;
-    }
-    if (d->n_freqs != 12 || d->D != 3 || d->C != 2 || d->L != 8 || d->sigma_in != 48 || d->sigma_hidden != 32 || d->sigma_layers != 2 || d->sigma_out != 16 ||
-        d->color_in != 32 || d->color_hidden != 64 || d->color_layers != 3 || d->color_out != 3) {
+    if (!front_batch_ok(d, "curved_field_infer")) return NERFTEX_ERR_INVALID;
+    if (!front_shapes_ok(d) || d->color_in != 32 || d->color_hidden != 64 || d->color_layers != 3 || d->color_out != 3) {
         set_error("curved_field_infer: the kernels serve the default curved field only (12 height bands, a 3-D table of 8 levels x 2 features, "
                   "sigma net 48 -> 32 x 2 -> 16, colour net 32 -> 64 x 3 -> 3)");
         return NERFTEX_ERR_INVALID;
     }
     if (d->B == 0) return NERFTEX_OK;
-    const CurvedScratch at(d->B);
-    if (!d->knn || !d->tracer || !d->xyz || !d->dirs || !d->mesh_vertices || !d->vertex_normals || !d->table || !d->offsets || !d->sigma_weights ||
-        !d->color_weights || !d->sigma || !d->rgbs || !d->scratch || (reinterpret_cast<uintptr_t>(d->scratch) & 255) || d->scratch_bytes < at.total) {
+    const CurvedScratch sc(d->scratch, d->B);
+    if (!front_pointers_ok(d, sc.carve.at) || !d->color_weights) {
         set_error("curved_field_infer: handles, inputs, table, weights and outputs must not be NULL, and scratch must be 256-byte aligned and hold %zu bytes",
-                  at.total);
+                  sc.carve.at);
         return NERFTEX_ERR_INVALID;
     }
-    if (((reinterpret_cast<uintptr_t>(d->sigma_weights) | reinterpret_cast<uintptr_t>(d->color_weights)) & 15) || !(d->in_mul > 0.0f) || !std::isfinite(d->in_mul)) {
+    if (!front_scales_ok(d) || (reinterpret_cast<uintptr_t>(d->color_weights) & 15)) {
         set_error("curved_field_infer: the weight vectors must be 16-byte aligned and the gather's input scale positive and finite");
         return NERFTEX_ERR_INVALID;
     }
     hipStream_t st = as_stream(stream);
-    char* sc = static_cast<char*>(d->scratch);
-    int32_t* idx = reinterpret_cast<int32_t*>(sc + at.idx);
-    float* dist = reinterpret_cast<float*>(sc + at.dist);
-    float* p_sur = reinterpret_cast<float*>(sc + at.p_sur);
-    float* normal = reinterpret_cast<float*>(sc + at.normal);
-    uint8_t* mask = reinterpret_cast<uint8_t*>(sc + at.mask);
-    half_t* x_lbc = reinterpret_cast<half_t*>(sc + at.x_lbc);
-    half_t* xin = reinterpret_cast<half_t*>(sc + at.xin);
-    half_t* h = reinterpret_cast<half_t*>(sc + at.h);
-    half_t* sigma_raw = reinterpret_cast<half_t*>(sc + at.sigma_raw);
-    half_t* cin = reinterpret_cast<half_t*>(sc + at.cin);
-    half_t* hc = reinterpret_cast<half_t*>(sc + at.hc);
     const uint32_t B = d->B, rpu = d->rows_per_unit;
     const int32_t* units = d->units_dev;
     const dim3 grid(div_up(B, 256u)), block(256);
 
-    int rc = knn_query_rows(d->knn, d->xyz, d->dirs, B, d->K, idx, dist, units, rpu, st);
+    int rc = curved_front_gather(d, sc.f, nullptr, stream);
     if (rc != NERFTEX_OK) return rc;
-    rc = curved_project_rows(d->tracer, d->xyz, d->dirs, idx, dist, B, d->K, d->mesh_vertices, d->vertex_normals, d->n_verts, d->dir_vec_wdist, d->h_threshold,
-                             p_sur, mask, normal, xin, units, rpu, st);
-    if (rc != NERFTEX_OK) return rc;
-    // (an exported entry of this library: it clears the error text, which holds nothing at this point, and checks the gather's own arguments)
-    rc = nerftex_grid_encode_forward_rows(p_sur, d->table, d->offsets, x_lbc, B, d->D, d->C, d->L, d->S, d->H, d->gridtype, d->align_corners, NERFTEX_F16,
-                                          NERFTEX_LAYOUT_LBC, d->in_add, d->in_mul, units, rpu, stream);
-    if (rc != NERFTEX_OK) return rc;
-    {
-        KernelTimer kt("curved_pack_features_rows_kernel", st);
-        hipLaunchKernelGGL(curved_pack_features_rows_kernel, grid, block, 0, st, x_lbc, B, xin, units, rpu);
-    }
-    if ((rc = check_launch("curved_field_infer(pack)")) != NERFTEX_OK) return rc;
-    rc = ffmlp_inference_rows(xin, d->sigma_weights, B, 48, 32, 2, h, units, rpu, st);
-    if (rc != NERFTEX_OK) return rc;
+    if ((rc = curved_front_sigma(d, sc.f, "curved_field_infer(pack)", stream)) != NERFTEX_OK) return rc;
     {
         KernelTimer kt("curved_mid_rows_kernel", st);
-        hipLaunchKernelGGL(curved_mid_rows_kernel, grid, block, 0, st, h, normal, d->dirs, B, d->fc_weight, d->eval, sigma_raw, cin, units, rpu);
+        hipLaunchKernelGGL(curved_mid_rows_kernel, grid, block, 0, st, sc.f.h, sc.f.normal, d->dirs, B, d->fc_weight, d->eval, sc.sigma_raw, sc.cin, units, rpu);
     }
     if ((rc = check_launch("curved_field_infer(mid)")) != NERFTEX_OK) return rc;
-    rc = ffmlp_inference_rows(cin, d->color_weights, B, 32, 64, 3, hc, units, rpu, st);
+    rc = ffmlp_inference_rows(sc.cin, d->color_weights, B, 32, 64, 3, sc.hc, units, rpu, st);
     if (rc != NERFTEX_OK) return rc;
     {
         KernelTimer kt("curved_out_rows_kernel", st);
-        hipLaunchKernelGGL(curved_out_rows_kernel, grid, block, 0, st, hc, sigma_raw, mask, d->dirs, B, d->sigma, d->rgbs, units, rpu);
+        hipLaunchKernelGGL(curved_out_rows_kernel, grid, block, 0, st, sc.hc, sc.sigma_raw, sc.f.mask, d->dirs, B, d->sigma, d->rgbs, units, rpu);
     }
     return check_launch("curved_field_infer(out)");
 }

@@ -202,12 +202,13 @@ class StepPixelsDesc(C.Structure):
 
 class CurvedInferDesc(C.Structure):
     """nerftex_curved_infer_desc of include/nerftex_hip.h, field for field: the curved field's no-grad forward as one device-count call."""
-    _fields_ = [("knn", _vp), ("tracer", _vp), ("xyz", _vp), ("dirs", _vp), ("B", _u32), ("n_verts", _u32), ("mesh_vertices", _vp), ("vertex_normals", _vp),
-                ("tbn", _vp), ("K", _u32), ("n_freqs", _u32), ("dir_vec_wdist", _f32), ("h_threshold", _f32), ("table", _vp), ("offsets", _vp), ("D", _u32),
-                ("C", _u32), ("L", _u32), ("S", _f32), ("H", _u32), ("gridtype", _u32), ("align_corners", _i), ("in_add", _f32), ("in_mul", _f32),
-                ("sigma_weights", _vp), ("sigma_in", _u32), ("sigma_hidden", _u32), ("sigma_layers", _u32), ("sigma_out", _u32), ("color_weights", _vp),
-                ("color_in", _u32), ("color_hidden", _u32), ("color_layers", _u32), ("color_out", _u32), ("fc_weight", _f32), ("eval", _i), ("sigma", _vp),
-                ("rgbs", _vp), ("units_dev", _vp), ("rows_per_unit", _u32), ("scratch", _vp), ("scratch_bytes", _sz)]
+    # (knn down to in_mul: the members nerftex_curved_light_infer_desc begins with, too)
+    _prefix = [("knn", _vp), ("tracer", _vp), ("xyz", _vp), ("dirs", _vp), ("B", _u32), ("n_verts", _u32), ("mesh_vertices", _vp), ("vertex_normals", _vp),
+               ("tbn", _vp), ("K", _u32), ("n_freqs", _u32), ("dir_vec_wdist", _f32), ("h_threshold", _f32), ("table", _vp), ("offsets", _vp), ("D", _u32),
+               ("C", _u32), ("L", _u32), ("S", _f32), ("H", _u32), ("gridtype", _u32), ("align_corners", _i), ("in_add", _f32), ("in_mul", _f32)]
+    _fields_ = _prefix + [("sigma_weights", _vp), ("sigma_in", _u32), ("sigma_hidden", _u32), ("sigma_layers", _u32), ("sigma_out", _u32),
+                ("color_weights", _vp), ("color_in", _u32), ("color_hidden", _u32), ("color_layers", _u32), ("color_out", _u32), ("fc_weight", _f32),
+                ("eval", _i), ("sigma", _vp), ("rgbs", _vp), ("units_dev", _vp), ("rows_per_unit", _u32), ("scratch", _vp), ("scratch_bytes", _sz)]
 
 
 LIGHT_VISUAL = {"Full": 0, "Specular": 1, "Diffuse": 2, "Albedo": 3}  # NERFTEX_LIGHT_VISUAL_*
@@ -216,16 +217,13 @@ NORMAL_NET_WEIGHTS, NORMAL_NET_BIASES = 1312, 66  # NERFTEX_NORMAL_NET_*
 
 class CurvedLightInferDesc(C.Structure):
     """nerftex_curved_light_infer_desc of include/nerftex_hip.h, field for field: the SH-lit curved field's no-grad forward as one device-count call."""
-    _fields_ = [("knn", _vp), ("tracer", _vp), ("xyz", _vp), ("dirs", _vp), ("B", _u32), ("n_verts", _u32), ("mesh_vertices", _vp), ("vertex_normals", _vp),
-                ("tbn", _vp), ("K", _u32), ("n_freqs", _u32), ("dir_vec_wdist", _f32), ("h_threshold", _f32), ("table", _vp), ("offsets", _vp), ("D", _u32),
-                ("C", _u32), ("L", _u32), ("S", _f32), ("H", _u32), ("gridtype", _u32), ("align_corners", _i), ("in_add", _f32), ("in_mul", _f32),
-                ("normal_table", _vp), ("normal_offsets", _vp), ("normal_C", _u32), ("normal_L", _u32), ("normal_S", _f32), ("normal_H", _u32),
-                ("normal_gridtype", _u32), ("normal_align_corners", _i), ("normal_in_add", _f32), ("normal_in_mul", _f32), ("sigma_weights", _vp),
-                ("sigma_in", _u32), ("sigma_hidden", _u32), ("sigma_layers", _u32), ("sigma_out", _u32), ("normal_weights", _vp), ("normal_biases", _vp),
-                ("normal_hidden", _u32), ("normal_layers", _u32), ("brdf_weights", _vp), ("brdf_in", _u32), ("brdf_hidden", _u32), ("brdf_layers", _u32),
-                ("brdf_out", _u32), ("env_shs", _vp), ("n_sh", _u32), ("n_color", _u32), ("gamma", _f32), ("flags", _u32), ("visual_mode", _u32),
-                ("fc_weight", _f32), ("eval", _i), ("sigma", _vp), ("rgbs", _vp), ("shading_normal", _vp), ("units_dev", _vp), ("rows_per_unit", _u32),
-                ("scratch", _vp), ("scratch_bytes", _sz)]
+    _fields_ = CurvedInferDesc._prefix + [("normal_table", _vp), ("normal_offsets", _vp), ("normal_C", _u32), ("normal_L", _u32), ("normal_S", _f32),
+                ("normal_H", _u32), ("normal_gridtype", _u32), ("normal_align_corners", _i), ("normal_in_add", _f32), ("normal_in_mul", _f32),
+                ("sigma_weights", _vp), ("sigma_in", _u32), ("sigma_hidden", _u32), ("sigma_layers", _u32), ("sigma_out", _u32), ("normal_weights", _vp),
+                ("normal_biases", _vp), ("normal_hidden", _u32), ("normal_layers", _u32), ("brdf_weights", _vp), ("brdf_in", _u32), ("brdf_hidden", _u32),
+                ("brdf_layers", _u32), ("brdf_out", _u32), ("env_shs", _vp), ("n_sh", _u32), ("n_color", _u32), ("gamma", _f32), ("flags", _u32),
+                ("visual_mode", _u32), ("fc_weight", _f32), ("eval", _i), ("sigma", _vp), ("rgbs", _vp), ("shading_normal", _vp), ("units_dev", _vp),
+                ("rows_per_unit", _u32), ("scratch", _vp), ("scratch_bytes", _sz)]
 
 
 SH_LIGHT_SPECULAR = 1  # nerftex_sh_light_desc.flags

@@ -640,41 +640,63 @@ class CurvedField(torch.nn.Module):
     def _infer_fused(self, x, d):
         """Whether nerftex_curved_field_infer serves this call: _glue_fused(), the shapes the entry's kernels are built for (it refuses every
         other one), an fp16 table, and what the entry asks of its buffers.  Everything else goes through forward()."""
+        c = self.color_net
+        return (self._glue_fused() and c.dtype == torch.float16 and (c.input_dim, c.hidden_dim, c.num_layers, c.output_dim) == (32, 64, 3, 3)
+                and self._infer_front_fused(x, d))
+
+    def _infer_front_fused(self, x, d):
+        """What the two fused chains ask alike (their front half, csrc/fieldglue.hip): fp16 autocast, no probabilistic table, the default texture
+        table and sigma net, a batch of whole 128-row workgroups, contiguous fp32 inputs, an fp16 table."""
         B = x.shape[0]
-        enc, s, c = self.encoder, self.sigma_net, self.color_net
-        return (self._glue_fused() and B % 128 == 0 and B > 0 and x.dtype == torch.float32 and d.dtype == torch.float32 and x.is_contiguous()
-                and d.is_contiguous() and s.dtype == torch.float16 and c.dtype == torch.float16
+        enc, s = self.encoder, self.sigma_net
+        return (torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.float16 and self.encoder_var is None
+                and self.in_dim == 41 and self.in_pad == 48 and self.geo_feat_dim == 15 and B % 128 == 0 and B > 0
+                and x.dtype == torch.float32 and d.dtype == torch.float32 and x.is_contiguous() and d.is_contiguous() and s.dtype == torch.float16
                 and (s.input_dim, s.hidden_dim, s.num_layers, s.padded_output_dim) == (48, 32, 2, 16)
-                and (c.input_dim, c.hidden_dim, c.num_layers, c.output_dim) == (32, 64, 3, 3)
                 and (enc.input_dim, enc.level_dim, enc.num_levels, self.multires) == (3, 2, 8, 12) and 1 <= self.projector.K <= 16
                 and enc._table().dtype == torch.float16)
 
-    def _infer_desc(self, x, d, live, sigma, rgbs, scratch):
-        """The nerftex_curved_infer_desc of one call (and the tensors it points into, to be kept until the call is enqueued).  The 16-bit table
-        and weights are kept between calls and re-made when a parameter changes, as GridEncoder._table() and fused.ngp_field_infer keep theirs."""
+    def _infer_weights(self, attr, net2, more_stamp=(), more=None):
+        """The 16-bit copies of the sigma net's and the entry's second network's weights, and what `more()` makes beside them: kept in the attribute
+        `attr` between calls and re-made when a stamped version or address changes, as GridEncoder._table() and fused.ngp_field_infer keep theirs."""
         from gridencoder.grid import register_offsets
-        from nerftex_hip import CurvedInferDesc, ptr
 
-        enc, p, s, c = self.encoder, self.projector, self.sigma_net, self.color_net
-        table = enc._table()
-        ws, wc = s._weights(), c._weights()
-        stamp = (ws._version, ws.data_ptr(), wc._version, wc.data_ptr())
-        cache = getattr(self, "_infer_cache", None)
+        ws, w2 = self.sigma_net._weights(), net2._weights()
+        stamp = (ws._version, ws.data_ptr(), w2._version, w2.data_ptr()) + more_stamp
+        cache = getattr(self, attr, None)
         if cache is None or cache[0] != stamp:
-            register_offsets(enc.offsets, enc.num_levels)
-            cache = self._infer_cache = (stamp, ws.detach().to(torch.float16), wc.detach().to(torch.float16))
-        _, ws_h, wc_h = cache
+            register_offsets(self.encoder.offsets, self.encoder.num_levels)
+            cache = (stamp, ws.detach().to(torch.float16), w2.detach().to(torch.float16)) + (more() if more else ())
+            setattr(self, attr, cache)
+        return cache[1:]
+
+    def _infer_front_desc(self, x, d, live, sigma, rgbs, scratch, ws_h):
+        """What both descriptors are built from -- the shared members knn .. in_mul, the sigma net, fc_weight, the outputs, the device count, the
+        scratch -- as keyword arguments, and the 16-bit texture table they point into."""
+        from nerftex_hip import ptr
+
+        enc, p, s = self.encoder, self.projector, self.sigma_net
+        table = enc._table()
         units, rows_per_unit = (ptr(live[0]), int(live[1])) if live is not None else (None, 0)
-        desc = CurvedInferDesc(
+        return dict(
             knn=p._knn.value, tracer=p.tracer._handle.value, xyz=ptr(x), dirs=ptr(d), B=x.shape[0], n_verts=p.mesh_vertices.shape[0],
             mesh_vertices=ptr(p.mesh_vertices), vertex_normals=ptr(p.vertex_normals), tbn=ptr(p.tbn), K=int(p.K), n_freqs=int(self.multires),
             dir_vec_wdist=0.05, h_threshold=p._height_limit(...), table=ptr(table), offsets=ptr(enc.offsets), D=int(enc.input_dim), C=int(enc.level_dim),
             L=int(enc.num_levels), S=float(np.log2(enc.per_level_scale)), H=int(enc.base_resolution), gridtype=int(enc.gridtype_id),
             align_corners=int(bool(enc.align_corners)), in_add=float(self.bound), in_mul=float(np.float32(1.0) / np.float32(2 * self.bound)),
             sigma_weights=ptr(ws_h), sigma_in=s.input_dim, sigma_hidden=s.hidden_dim, sigma_layers=s.num_layers, sigma_out=s.padded_output_dim,
-            color_weights=ptr(wc_h), color_in=c.input_dim, color_hidden=c.hidden_dim, color_layers=c.num_layers, color_out=c.output_dim,
-            fc_weight=float(self.fc_weight), eval=2 | int(not self.training), sigma=ptr(sigma), rgbs=ptr(rgbs), units_dev=units,
-            rows_per_unit=rows_per_unit, scratch=ptr(scratch), scratch_bytes=scratch.numel())
+            fc_weight=float(self.fc_weight), sigma=ptr(sigma), rgbs=ptr(rgbs), units_dev=units, rows_per_unit=rows_per_unit, scratch=ptr(scratch),
+            scratch_bytes=scratch.numel()), table
+
+    def _infer_desc(self, x, d, live, sigma, rgbs, scratch):
+        """The nerftex_curved_infer_desc of one call (and the tensors it points into, to be kept until the call is enqueued)."""
+        from nerftex_hip import CurvedInferDesc, ptr
+
+        c = self.color_net
+        ws_h, wc_h = self._infer_weights("_infer_cache", c)
+        front, table = self._infer_front_desc(x, d, live, sigma, rgbs, scratch, ws_h)
+        desc = CurvedInferDesc(color_weights=ptr(wc_h), color_in=c.input_dim, color_hidden=c.hidden_dim, color_layers=c.num_layers, color_out=c.output_dim,
+                               eval=2 | int(not self.training), **front)
         return desc, (table, ws_h, wc_h)
 
     def _infer_light_fused(self, x, d):
@@ -685,23 +707,16 @@ class CurvedField(torch.nn.Module):
             return False
         from nerftex_hip import LIGHT_VISUAL
 
-        B = x.shape[0]
-        enc, s, nn, net = self.encoder, self.sigma_net, self.normal_net, self.light_net
+        nn, net = self.normal_net, self.light_net
         br = net.brdf_layer
-        return (torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.float16 and bool(net.fused) and self.encoder_var is None
-                and nn is not None and not nn.bound_output and (self.training or self.light_visual_mode in LIGHT_VISUAL)
-                and self.in_dim == 41 and self.in_pad == 48 and self.geo_feat_dim == 15 and B % 128 == 0 and B > 0
-                and x.is_cuda and x.dtype == torch.float32 and d.dtype == torch.float32 and x.is_contiguous() and d.is_contiguous()
-                and s.dtype == torch.float16 and br.dtype == torch.float16
-                and (s.input_dim, s.hidden_dim, s.num_layers, s.padded_output_dim) == (48, 32, 2, 16)
-                and (br.input_dim, br.hidden_dim, br.num_layers, br.output_dim) == (16, 64, 3, 5)
-                and (enc.input_dim, enc.level_dim, enc.num_levels, self.multires) == (3, 2, 8, 12) and 1 <= self.projector.K <= 16
+        return (bool(net.fused) and nn is not None and not nn.bound_output and (self.training or self.light_visual_mode in LIGHT_VISUAL)
+                and x.is_cuda and br.dtype == torch.float16 and (br.input_dim, br.hidden_dim, br.num_layers, br.output_dim) == (16, 64, 3, 5)
                 and (nn.encoder.input_dim, nn.encoder.level_dim, nn.encoder.num_levels) == (3, 2, 4)
                 and (nn.low_freq_band_len_x, nn.low_freq_band_len_z) == (16, 12)
                 and [tuple(l.W.shape) for l in nn.phi_net.layers] == [(16, 20), (16, 16), (1, 16)]
                 and [tuple(l.W.shape) for l in nn.theta_net.layers] == [(16, 28), (16, 16), (1, 16)]
                 and net.envSHs.shape[0] >= 9 and net.envSHs.shape[1] in (1, 3) and net.envSHs.dtype == torch.float32
-                and enc._table().dtype == torch.float16 and nn.encoder._table().dtype == torch.float16)
+                and self._infer_front_fused(x, d) and nn.encoder._table().dtype == torch.float16)
 
     def _infer_light_desc(self, x, d, live, sigma, rgbs, scratch, shading_normal=None):
         """The nerftex_curved_light_infer_desc of one call (and the tensors it points into).  Kept between calls and re-made when a parameter
@@ -710,70 +725,65 @@ class CurvedField(torch.nn.Module):
         from gridencoder.grid import register_offsets
         from nerftex_hip import LIGHT_VISUAL, SH_LIGHT_SPECULAR, CurvedLightInferDesc, ptr
 
-        enc, p, s, nn, net = self.encoder, self.projector, self.sigma_net, self.normal_net, self.light_net
+        nn, net = self.normal_net, self.light_net
         nenc, br = nn.encoder, net.brdf_layer
-        table, ntable = enc._table(), nenc._table()
-        ws, wb = s._weights(), br._weights()
+        ntable = nenc._table()
         layers = list(nn.phi_net.layers) + list(nn.theta_net.layers)
-        stamp = (ws._version, ws.data_ptr(), wb._version, wb.data_ptr(), tuple((q.data_ptr(), q._version) for l in layers for q in (l.W, l.b, l.c)))
-        cache = getattr(self, "_infer_light_cache", None)
-        if cache is None or cache[0] != stamp:
-            register_offsets(enc.offsets, enc.num_levels)
+
+        def normal_block():
             register_offsets(nenc.offsets, nenc.num_levels)
             with torch.autocast("cuda", enabled=False):
                 nw = torch.cat([l.normalization().detach().float().half().reshape(-1) for l in layers]).contiguous()
                 nb = torch.cat([l.b.detach().float().reshape(-1) for l in layers]).contiguous()
-            cache = self._infer_light_cache = (stamp, ws.detach().to(torch.float16), wb.detach().to(torch.float16), nw, nb)
-        _, ws_h, wb_h, nw, nb = cache
+            return nw, nb
+
+        ws_h, wb_h, nw, nb = self._infer_weights("_infer_light_cache", br, (tuple((q.data_ptr(), q._version) for l in layers for q in (l.W, l.b, l.c)),),
+                                                 normal_block)
+        front, table = self._infer_front_desc(x, d, live, sigma, rgbs, scratch, ws_h)
         env = net.envSHs.detach()
-        units, rows_per_unit = (ptr(live[0]), int(live[1])) if live is not None else (None, 0)
         mode = "Full" if self.training else self.light_visual_mode
         desc = CurvedLightInferDesc(
-            knn=p._knn.value, tracer=p.tracer._handle.value, xyz=ptr(x), dirs=ptr(d), B=x.shape[0], n_verts=p.mesh_vertices.shape[0],
-            mesh_vertices=ptr(p.mesh_vertices), vertex_normals=ptr(p.vertex_normals), tbn=ptr(p.tbn), K=int(p.K), n_freqs=int(self.multires),
-            dir_vec_wdist=0.05, h_threshold=p._height_limit(...), table=ptr(table), offsets=ptr(enc.offsets), D=int(enc.input_dim), C=int(enc.level_dim),
-            L=int(enc.num_levels), S=float(np.log2(enc.per_level_scale)), H=int(enc.base_resolution), gridtype=int(enc.gridtype_id),
-            align_corners=int(bool(enc.align_corners)), in_add=float(self.bound), in_mul=float(np.float32(1.0) / np.float32(2 * self.bound)),
             normal_table=ptr(ntable), normal_offsets=ptr(nenc.offsets), normal_C=int(nenc.level_dim), normal_L=int(nenc.num_levels),
             normal_S=float(np.log2(nenc.per_level_scale)), normal_H=int(nenc.base_resolution), normal_gridtype=int(nenc.gridtype_id),
             normal_align_corners=int(bool(nenc.align_corners)), normal_in_add=1.0, normal_in_mul=float(np.float32(1.0) / np.float32(2)),  # (encoder(p_sur): bound 1)
-            sigma_weights=ptr(ws_h), sigma_in=s.input_dim, sigma_hidden=s.hidden_dim, sigma_layers=s.num_layers, sigma_out=s.padded_output_dim,
             normal_weights=ptr(nw), normal_biases=ptr(nb), normal_hidden=16, normal_layers=2,
             brdf_weights=ptr(wb_h), brdf_in=br.input_dim, brdf_hidden=br.hidden_dim, brdf_layers=br.num_layers, brdf_out=br.output_dim,
             env_shs=ptr(env), n_sh=env.shape[0], n_color=env.shape[1], gamma=float(net.gamma), flags=SH_LIGHT_SPECULAR if net.use_specular else 0,
-            visual_mode=LIGHT_VISUAL[mode], fc_weight=float(self.fc_weight), eval=int(not self.training), sigma=ptr(sigma), rgbs=ptr(rgbs),
-            shading_normal=ptr(shading_normal), units_dev=units, rows_per_unit=rows_per_unit, scratch=ptr(scratch), scratch_bytes=scratch.numel())
+            visual_mode=LIGHT_VISUAL[mode], eval=int(not self.training), shading_normal=ptr(shading_normal), **front)
         return desc, (table, ntable, ws_h, wb_h, nw, nb, env)
 
-    def _light_scratch(self, nbytes, device, st):
-        """One scratch buffer per stream (the ray ranges of a pipelined frame run side by side), grown to the largest batch seen: the loop's
-        batch size changes with nearly every iteration.  A buffer that is replaced goes back to the allocator, which hands it out again only
-        behind the work this stream still has queued on it.  Under a graph capture: a fresh one (the graph's pool keeps it)."""
-        if torch.cuda.is_current_stream_capturing():
-            return torch.empty(nbytes, dtype=torch.uint8, device=device)
-        held = getattr(self, "_infer_light_scratch", None)
-        if held is None:
-            held = self._infer_light_scratch = {}
-        scratch = held.get((device, st))
-        if scratch is None or scratch.numel() < nbytes:
-            scratch = held[(device, st)] = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        return scratch
-
-    @torch.no_grad()
-    def infer_light(self, x, d, live=None, shading_normal=None):
-        """infer() of the SH-lit field through nerftex_curved_light_infer (see `_infer_light_fused`, which the caller has checked);
-        shading_normal: an fp32 [B,3] tensor that receives the normal the head shades with."""
+    def _infer_call(self, entry, make_desc, x, d, live, *more):
+        """One call of the library entry `entry` (its scratch query is `entry`_scratch_bytes) over the descriptor make_desc builds: -> (sigma [B],
+        rgbs [B,3]), fp32 views of one allocation.  The scratch is one buffer per stream (the ray ranges of a pipelined frame run side by side),
+        grown to the largest batch seen: the loop's batch size changes with nearly every iteration.  A buffer that is replaced goes back to the
+        allocator, which hands it out again only behind the work this stream still has queued on it.  Under a graph capture: a fresh one (the
+        graph's pool keeps it)."""
         import ctypes
 
         from nerftex_hip import check, lib, stream
 
         B, st = x.shape[0], stream()
-        scratch = self._light_scratch(lib.nerftex_curved_light_infer_scratch_bytes(B), x.device, st)
+        nbytes = getattr(lib, entry + "_scratch_bytes")(B)
+        if torch.cuda.is_current_stream_capturing():
+            scratch = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+        else:
+            held = getattr(self, "_infer_scratch", None)
+            if held is None:
+                held = self._infer_scratch = {}
+            scratch = held.get((x.device, st))
+            if scratch is None or scratch.numel() < nbytes:
+                scratch = held[(x.device, st)] = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
         out = torch.empty(4 * B, dtype=torch.float32, device=x.device)  # [sigma | rgb] in one allocation
         sigma, rgbs = out[:B], out[B:].view(B, 3)
-        desc, _keep = self._infer_light_desc(x, d, live, sigma, rgbs, scratch, shading_normal)
-        check(lib.nerftex_curved_light_infer(ctypes.byref(desc), st))
+        desc, _keep = make_desc(x, d, live, sigma, rgbs, scratch, *more)
+        check(getattr(lib, entry)(ctypes.byref(desc), st))
         return sigma, rgbs
+
+    @torch.no_grad()
+    def infer_light(self, x, d, live=None, shading_normal=None):
+        """infer() of the SH-lit field through nerftex_curved_light_infer (see `_infer_light_fused`, which the caller has checked);
+        shading_normal: an fp32 [B,3] tensor that receives the normal the head shades with."""
+        return self._infer_call("nerftex_curved_light_infer", self._infer_light_desc, x, d, live, shading_normal)
 
     @torch.no_grad()
     def infer_padded(self, x, d):
@@ -805,32 +815,10 @@ class CurvedField(torch.nn.Module):
         colour follow forward()'s arithmetic at its rounding points."""
         if self._infer_light_fused(x, d):  # (opt-in: `fused_light_infer`; the SH light model's own chain, the same rows contract)
             return self.infer_light(x, d, live)
-        if not self._infer_fused(x, d):
-            sigma, rgbs, _ = self.forward(x, d)
-            return sigma.float(), rgbs.float()
-        import ctypes
-
-        from nerftex_hip import check, lib, stream
-
-        B, st = x.shape[0], stream()
-        nbytes = lib.nerftex_curved_field_infer_scratch_bytes(B)
-        if torch.cuda.is_current_stream_capturing():
-            scratch = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-        else:
-            # one buffer per stream (the ray ranges of a pipelined frame run side by side), grown to the largest batch seen: the loop's batch
-            # size changes with nearly every iteration.  A buffer that is replaced goes back to the allocator, which hands it out again only
-            # behind the work this stream still has queued on it
-            held = getattr(self, "_infer_scratch", None)
-            if held is None:
-                held = self._infer_scratch = {}
-            scratch = held.get((x.device, st))
-            if scratch is None or scratch.numel() < nbytes:
-                scratch = held[(x.device, st)] = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-        out = torch.empty(4 * B, dtype=torch.float32, device=x.device)  # [sigma | rgb] in one allocation
-        sigma, rgbs = out[:B], out[B:].view(B, 3)
-        desc, _keep = self._infer_desc(x, d, live, sigma, rgbs, scratch)
-        check(lib.nerftex_curved_field_infer(ctypes.byref(desc), st))
-        return sigma, rgbs
+        if self._infer_fused(x, d):
+            return self._infer_call("nerftex_curved_field_infer", self._infer_desc, x, d, live)
+        sigma, rgbs, _ = self.forward(x, d)
+        return sigma.float(), rgbs.float()
 
     @torch.no_grad()
     def forward_graphed(self, x, d):

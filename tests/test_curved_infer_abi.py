@@ -89,6 +89,8 @@ REFUSED = [
     (dict(n_freqs=10), "default curved field"),
     (dict(L=16), "default curved field"),
     (dict(), "must not be NULL"),  # default shapes, no handles and no buffers
+    (dict(B=64, sigma_in=32), "multiple of 128"),  # the batch is looked at before the shapes
+    (dict(B=0, L=16), "default curved field"),  # the shapes are looked at before the empty batch returns
 ]
 
 
@@ -112,3 +114,43 @@ def test_empty_batch_is_ok_and_launches_nothing():
     from nerftex_hip import lib
 
     assert lib.nerftex_curved_field_infer(ctypes.byref(_default_desc(B=0)), None) == 0
+    assert lib.nerftex_curved_field_infer(ctypes.byref(_default_desc(B=0, n_verts=0)), None) == 0  # the mesh is looked at for a batch with rows only
+
+
+POINTERS = ("knn", "tracer", "xyz", "dirs", "mesh_vertices", "vertex_normals", "table", "offsets", "sigma_weights", "color_weights", "sigma", "rgbs",
+            "scratch")
+FAKE = 0x10000  # a non-NULL, 256-byte aligned address that is never dereferenced: every case below is refused before anything is launched
+
+
+def _pointed_desc(**over):
+    """_default_desc with every required pointer set and a scratch that is large enough: one step short of a launch."""
+    kw = dict({name: FAKE for name in POINTERS}, scratch_bytes=1 << 40)
+    kw.update(over)
+    return _default_desc(**kw)
+
+
+def _refused_at_the_pointers():
+    cases = [({name: None}, "must not be NULL") for name in POINTERS]  # (tbn is not among them: the static light model does not read the frames)
+    cases += [(dict(scratch=FAKE + 0x80), "256-byte aligned"),
+              (dict(sigma_weights=FAKE + 8), "16-byte aligned"),
+              (dict(color_weights=FAKE + 8), "16-byte aligned"),
+              (dict(in_mul=0.0), "positive and finite"),
+              (dict(in_mul=float("inf")), "positive and finite")]
+    return cases
+
+
+@pytest.mark.parametrize("over,text", _refused_at_the_pointers(), ids=lambda v: "-".join(map(str, v)) if isinstance(v, dict) else None)
+def test_pointers_alignment_and_scales_are_refused_before_any_launch(over, text):
+    from nerftex_hip import lib
+
+    assert lib.nerftex_curved_field_infer(ctypes.byref(_pointed_desc(**over)), None) == NERFTEX_ERR_INVALID
+    assert text in lib.nerftex_last_error().decode(), lib.nerftex_last_error().decode()
+
+
+def test_a_scratch_one_byte_short_is_refused_with_the_size_it_needs():
+    from nerftex_hip import lib
+
+    need = lib.nerftex_curved_field_infer_scratch_bytes(128)
+    assert lib.nerftex_curved_field_infer(ctypes.byref(_pointed_desc(scratch_bytes=need - 1)), None) == NERFTEX_ERR_INVALID
+    text = lib.nerftex_last_error().decode()
+    assert "must not be NULL" in text and str(need) in text, text

@@ -138,3 +138,45 @@ def test_empty_batch_is_ok_and_launches_nothing():
     from nerftex_hip import lib
 
     assert lib.nerftex_curved_light_infer(ctypes.byref(_default_desc(B=0)), None) == 0
+    assert lib.nerftex_curved_light_infer(ctypes.byref(_default_desc(B=0, n_verts=0)), None) == 0  # the mesh is looked at for a batch with rows only
+
+
+POINTERS = ("knn", "tracer", "xyz", "dirs", "mesh_vertices", "vertex_normals", "tbn", "table", "offsets", "normal_table", "normal_offsets",
+            "sigma_weights", "normal_weights", "normal_biases", "brdf_weights", "env_shs", "sigma", "rgbs", "scratch")
+FAKE = 0x10000  # a non-NULL, 256-byte aligned address that is never dereferenced: every case below is refused before anything is launched
+
+
+def _pointed_desc(**over):
+    """_default_desc with every required pointer set and a scratch that is large enough: one step short of a launch."""
+    kw = dict({name: FAKE for name in POINTERS}, scratch_bytes=1 << 40)
+    kw.update(over)
+    return _default_desc(**kw)
+
+
+def _refused_at_the_pointers():
+    cases = [({name: None}, "must not be NULL") for name in POINTERS]  # (shading_normal is not among them: an optional output)
+    cases += [(dict(scratch=FAKE + 0x80), "256-byte aligned"),
+              (dict(sigma_weights=FAKE + 8), "16-byte aligned"),
+              (dict(brdf_weights=FAKE + 8), "16-byte aligned"),
+              (dict(normal_weights=FAKE + 2), "4-byte aligned"),
+              (dict(in_mul=0.0), "positive and finite"),
+              (dict(in_mul=float("inf")), "positive and finite"),
+              (dict(normal_in_mul=0.0), "positive and finite")]
+    return cases
+
+
+@pytest.mark.parametrize("over,text", _refused_at_the_pointers(), ids=lambda v: "-".join(map(str, v)) if isinstance(v, dict) else None)
+def test_pointers_alignment_and_scales_are_refused_before_any_launch(over, text):
+    from nerftex_hip import lib
+
+    assert lib.nerftex_curved_light_infer(ctypes.byref(_pointed_desc(**over)), None) == NERFTEX_ERR_INVALID
+    assert text in lib.nerftex_last_error().decode(), lib.nerftex_last_error().decode()
+
+
+def test_a_scratch_one_byte_short_is_refused_with_the_size_it_needs():
+    from nerftex_hip import lib
+
+    need = lib.nerftex_curved_light_infer_scratch_bytes(128)
+    assert lib.nerftex_curved_light_infer(ctypes.byref(_pointed_desc(scratch_bytes=need - 1)), None) == NERFTEX_ERR_INVALID
+    text = lib.nerftex_last_error().decode()
+    assert "must not be NULL" in text and str(need) in text, text

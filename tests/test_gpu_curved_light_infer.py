@@ -419,6 +419,23 @@ def test_switch_off_is_forward_on_all_rows(dev, setup, monkeypatch):
         field.fused_light_infer = False
 
 
+def test_eager_scratch_is_one_buffer_per_stream(dev, setup):
+    """As tests/test_gpu_curved_infer.py's test of the same name, for the light chain: infer() keeps ONE scratch buffer per stream in
+    `_infer_scratch`, grown to the largest batch seen (a field of its own: the shared one has rendered frames on several streams)."""
+    from nerftex_hip import lib
+
+    field, _ = _sh_field(dev)
+    field.fused_light_infer = True
+    with torch.no_grad(), torch.autocast("cuda", dtype=torch.float16):
+        for n in (384, 128):
+            x, d = setup["xm"][:n].contiguous(), setup["dm"][:n].contiguous()
+            assert field._infer_light_fused(x, d)
+            sigma, rgbs = field.infer(x, d)
+            assert sigma.shape == (n,) and rgbs.shape == (n, 3) and float(sigma.max()) > 0
+    held = field._infer_scratch
+    assert len(held) == 1 and next(iter(held.values())).numel() == lib.nerftex_curved_light_infer_scratch_bytes(384)
+
+
 @pytest.mark.parametrize("kw", (dict(hidden_dim=64), dict(prob_model=True), dict(bound_output=True)), ids=("sigma64", "prob_model", "bound_output"))
 def test_other_shapes_go_through_forward(dev, setup, monkeypatch, kw):
     """A 64-wide sigma net, the probabilistic table and bounded angles are not the entry's: with the switch on, infer() still serves them by
