@@ -784,6 +784,72 @@ size_t nerftex_curved_field_infer_scratch_bytes(uint32_t B);
 int nerftex_curved_field_infer(const nerftex_curved_infer_desc* d, void* stream);
 
 /* -------------------------------------------------------------------------
+ * Extension: an IMPORTED planar feature texture under the curved field -- the `imported_type == 'field'` branch of MeshFeatureField.forward
+ * (tools/map.py:646-668): where the mesh chain searches neighbours, traces twice and gathers a hash table, an O(1) bilinear read of a
+ * [map_h, map_w, 16] fp32 image (channel-last, in the axis order MeshFeatureField.import_field receives) on the xy plane.  Per sample x, all
+ * fp32, every operation rounded on its own:
+ *   mode NERFTEX_PLANAR_MULTIPLY (the reference's `rescale`):  u = x0 * plane_scale0,  v = x1 * plane_scale1
+ *   mode NERFTEX_PLANAR_DIVIDE:                                u = x0 / plane_scale0,  v = x1 / plane_scale1   (true divisions)
+ *   sdf  = (x2 * height_scale0) * height_scale1 - sdf_offset
+ *   mask = |sdf| < h_threshold (strict; no 9.5 cap here) and -1 <= u <= 1 and -1 <= v <= 1 (inclusive)
+ *   features = grid_sample(bilinear, align_corners, zero padding) at (u, v), u along the map's FIRST axis: iu = ((u + 1) / 2) (map_h - 1),
+ *              iv likewise, i0 = floor(iu), j0 = floor(iv); the weights (i0+1-iu)(j0+1-iv), (iu-i0)(j0+1-iv), (i0+1-iu)(iv-j0), (iu-i0)(iv-j0)
+ *              on the texels (i0,j0), (i0+1,j0), (i0,j0+1), (i0+1,j0+1), four products added in that order; a corner outside the map adds nothing
+ *              and is not read.  Evaluated for every row, whatever its mask (as the reference does).
+ *   xin [B,48] fp16 = [half(features) | half(FreqEncoder(sdf)), 25 values: the projector's ladder | 1 x 7]   (the sigma net's padded input)
+ * nerftex_planar_lookup is the plain form: any B, every row; p_uv [B,2] = (u, v), sdf [B], mask [B] bytes, xin.  NERFTEX_ERR_INVALID before
+ * anything is launched, in this order: n_freqs other than 12; map_h or map_w outside 1..16384; (B == 0 returns NERFTEX_OK here;) a NULL
+ * pointer, a map or xin that is not 16-byte aligned; a mode other than the two; a scale or h_threshold that is not positive and finite, an
+ * sdf_offset that is not finite.
+ *
+ * nerftex_curved_import_infer: the whole no-grad forward over such a map as ONE call under the rows contract of nerftex_curved_field_infer --
+ *   lookup -> sigma net 48 -> 32 -> 16 -> trunc_exp / reflected view direction / SH -> colour net 32 -> 64 -> 64 -> 3 -> sigmoid + mask,
+ * five launches (the last four are nerftex_curved_field_infer's own), nothing allocated, capturable.  The coarse normal is (0, 0, 1), which
+ * the mid kernel normalises as MeshFeatureField does (eval bit 1).
+ *   rows >= live                      no work; sigma / rgbs keep what they held.
+ *   live rows the march marked unused no texel read; sigma = 0, rgbs = 0.
+ *   every other live row              bit for bit what nerftex_planar_lookup, nerftex_ffmlp_inference, nerftex_curved_mid_forward,
+ *                                     nerftex_ffmlp_inference and nerftex_curved_out_forward give one after the other, widened to fp32.
+ * NERFTEX_ERR_INVALID with a message, before anything is launched, in this order: a NULL descriptor; B % 128 != 0; n_features other than 16,
+ * n_freqs other than 12 or other network shapes than sigma net 48 / 32 / 2 / 16, colour net 32 / 64 / 3 / 3; map_h or map_w outside
+ * 1..16384; (B == 0 returns NERFTEX_OK here;) a NULL pointer, a scratch that is not 256-byte aligned or smaller than
+ * nerftex_curved_import_infer_scratch_bytes(B); a map or weight vector that is not 16-byte aligned; a mode other than the two; a scale or
+ * h_threshold that is not positive and finite, an sdf_offset that is not finite.
+ * ------------------------------------------------------------------------- */
+#define NERFTEX_PLANAR_MULTIPLY 0
+#define NERFTEX_PLANAR_DIVIDE 1
+int nerftex_planar_lookup(const float* xyz, const float* map, uint32_t map_h, uint32_t map_w, uint32_t mode, float plane_scale0, float plane_scale1,
+                          float height_scale0, float height_scale1, float sdf_offset, float h_threshold, uint32_t n_freqs, uint32_t B, float* p_uv,
+                          float* sdf, uint8_t* mask, void* xin, void* stream);
+typedef struct nerftex_curved_import_infer_desc {
+    const float* xyz;                  /* [B,3] sample positions                                                                  */
+    const float* dirs;                 /* [B,3] view directions; dirs[row][0] > 1e29 marks an unused slot                         */
+    uint32_t B;
+    const float* map;                  /* [map_h, map_w, n_features] fp32, 16-byte aligned                                        */
+    uint32_t map_h, map_w, n_features;
+    uint32_t mode;                     /* NERFTEX_PLANAR_MULTIPLY / NERFTEX_PLANAR_DIVIDE                                          */
+    float plane_scale0, plane_scale1;
+    float height_scale0, height_scale1;
+    float sdf_offset;
+    float h_threshold;
+    uint32_t n_freqs;                  /* FreqEncoder(height) bands (multires)                                                    */
+    const void* sigma_weights;         /* fp16, 16-byte aligned                                                                   */
+    uint32_t sigma_in, sigma_hidden, sigma_layers, sigma_out;
+    const void* color_weights;         /* fp16, 16-byte aligned                                                                   */
+    uint32_t color_in, color_hidden, color_layers, color_out;
+    float fc_weight;
+    int eval;                          /* the eval bits of nerftex_curved_mid_forward                                             */
+    float* sigma;                      /* [B] fp32                                                                                */
+    float* rgbs;                       /* [B,3] fp32                                                                              */
+    const int32_t* units_dev;
+    uint32_t rows_per_unit;
+    void* scratch;                     /* caller-owned, 256-byte aligned, >= nerftex_curved_import_infer_scratch_bytes(B) bytes   */
+    size_t scratch_bytes;
+} nerftex_curved_import_infer_desc;
+size_t nerftex_curved_import_infer_scratch_bytes(uint32_t B);
+int nerftex_curved_import_infer(const nerftex_curved_import_infer_desc* d, void* stream);
+
+/* -------------------------------------------------------------------------
  * Extension: the same ONE call for the curved field with the SH light model (CurvedField(light_model="SH")), under the same rows contract:
  *   neighbour search -> projector (+ the hit face's frame) -> hash-grid gather of the texture table -> gather of the normal net's table ->
  *   sigma net 48 -> 32 -> 16 -> light mid: exp / BRDF input / the factorized fine-normal net (two 16-wide LipMLPs, toCoor, the frame's

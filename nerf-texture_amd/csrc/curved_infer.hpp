@@ -14,7 +14,8 @@ int knn_query_rows(const nerftex_knn* kn, const float* xyz, const float* dirs, u
                    const int32_t* units_dev, uint32_t rows_per_unit, hipStream_t st);
 
 // nerftex_curved_project with n_freqs = 12 for unmarked live rows: p_sur [N,3], h_mask [N], normal [N,3], and half(z_embed) followed by the
-// seven padding ones straight into columns 16..47 of the sigma net's input xin [N,48] (what nerftex_curved_pack_inputs builds from z_embed).
+// seven padding ones straight into columns 16..47 of the sigma net's input xin [N,48] (what nerftex_curved_pack_inputs builds from z_embed;
+// height_ladder.hpp: the one ladder the planar lookup of an imported map, planar.inc, writes too).
 // A marked live row: p_sur = 1e30 (the gather answers zeros without a table read), h_mask = 0, normal = 0, z = 0 | ones.
 // tbn_out [N,9] (optional, with the per-face frames tbn [F,9]): the hit face's frame as nerftex_curved_project writes it, zeros for a marked
 // row; NULL: no frame is read or written (the static light model's chain).

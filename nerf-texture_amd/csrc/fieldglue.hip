@@ -9,6 +9,7 @@
 // narrowed to half; sigmoid in fp32 narrowed to half and widened again; gradients narrowed to half where autograd would).
 #include "common.hpp"
 #include "curved_infer.hpp"
+#include "height_ladder.hpp"
 #include "sh_common.hpp"
 
 #include <cmath>
@@ -415,13 +416,18 @@ struct CurvedFront {
           p_sur(c.take<float>(3)), normal(c.take<float>(3)), mask(c.take<uint8_t>(1)), x_lbc(c.take<half_t>(16)), xin(c.take<half_t>(48)), h(c.take<half_t>(16)) {}
 };
 
+// the buffers of the back half nerftex_curved_field_infer and nerftex_curved_import_infer (planar.inc) share: mid kernel to the closing kernel
+struct CurvedBack {
+    half_t *sigma_raw, *cin, *hc;
+    explicit CurvedBack(ScratchCarver& c) : sigma_raw(c.take<half_t>(1)), cin(c.take<half_t>(32)), hc(c.take<half_t>(16)) {}
+};
+
 // the scratch of one nerftex_curved_field_infer call
 struct CurvedScratch {
     ScratchCarver carve;
     CurvedFront f;
-    half_t *sigma_raw, *cin, *hc;
-    CurvedScratch(void* scratch, size_t B)
-        : carve{reinterpret_cast<uintptr_t>(scratch), B}, f(carve), sigma_raw(carve.take<half_t>(1)), cin(carve.take<half_t>(32)), hc(carve.take<half_t>(16)) {}
+    CurvedBack back;
+    CurvedScratch(void* scratch, size_t B) : carve{reinterpret_cast<uintptr_t>(scratch), B}, f(carve), back(carve) {}
 };
 
 // The refusals over the descriptors' shared members (knn .. in_mul, the sigma net, scratch), in the order include/nerftex_hip.h documents: each
@@ -493,6 +499,35 @@ int curved_front_sigma(const Desc* d, const CurvedFront& f, const char* pack_lab
     return ffmlp_inference_rows(f.xin, d->sigma_weights, d->B, 48, 32, 2, f.h, d->units_dev, d->rows_per_unit, st);
 }
 
+// (no message, as front_shapes_ok)
+template <typename Desc>
+bool back_shapes_ok(const Desc* d) {
+    return d->color_in == 32 && d->color_hidden == 64 && d->color_layers == 3 && d->color_out == 3;
+}
+
+// The launches of the back half: mid (trunc_exp, the reflected view direction, SH) -> colour net 32 -> 64 x 3 -> 3 -> sigmoid + mask as fp32.
+// h [B,16]: the sigma net's output, normal [B,3]: the raw coarse normal, mask [B]; labels: the entry's check_launch labels of the two kernels.
+template <typename Desc>
+int curved_back_half(const Desc* d, const half_t* h, const float* normal, const uint8_t* mask, const CurvedBack& k, const char* const (&labels)[2], void* stream) {
+    hipStream_t st = as_stream(stream);
+    const uint32_t B = d->B, rpu = d->rows_per_unit;
+    const int32_t* units = d->units_dev;
+    const dim3 grid(div_up(B, 256u)), block(256);
+    {
+        KernelTimer kt("curved_mid_rows_kernel", st);
+        hipLaunchKernelGGL(curved_mid_rows_kernel, grid, block, 0, st, h, normal, d->dirs, B, d->fc_weight, d->eval, k.sigma_raw, k.cin, units, rpu);
+    }
+    int rc = check_launch(labels[0]);
+    if (rc != NERFTEX_OK) return rc;
+    rc = ffmlp_inference_rows(k.cin, d->color_weights, B, 32, 64, 3, k.hc, units, rpu, st);
+    if (rc != NERFTEX_OK) return rc;
+    {
+        KernelTimer kt("curved_out_rows_kernel", st);
+        hipLaunchKernelGGL(curved_out_rows_kernel, grid, block, 0, st, k.hc, k.sigma_raw, mask, d->dirs, B, d->sigma, d->rgbs, units, rpu);
+    }
+    return check_launch(labels[1]);
+}
+
 }  // namespace
 }  // namespace nerftex
 
@@ -544,7 +579,7 @@ extern "C" size_t nerftex_curved_field_infer_scratch_bytes(uint32_t B) { return 
 extern "C" int nerftex_curved_field_infer(const nerftex_curved_infer_desc* d, void* stream) {
     clear_error();
     if (!front_batch_ok(d, "curved_field_infer")) return NERFTEX_ERR_INVALID;
-    if (!front_shapes_ok(d) || d->color_in != 32 || d->color_hidden != 64 || d->color_layers != 3 || d->color_out != 3) {
+    if (!front_shapes_ok(d) || !back_shapes_ok(d)) {
         set_error("curved_field_infer: the kernels serve the default curved field only (12 height bands, a 3-D table of 8 levels x 2 features, "
                   "sigma net 48 -> 32 x 2 -> 16, colour net 32 -> 64 x 3 -> 3)");
         return NERFTEX_ERR_INVALID;
@@ -560,26 +595,11 @@ extern "C" int nerftex_curved_field_infer(const nerftex_curved_infer_desc* d, vo
         set_error("curved_field_infer: the weight vectors must be 16-byte aligned and the gather's input scale positive and finite");
         return NERFTEX_ERR_INVALID;
     }
-    hipStream_t st = as_stream(stream);
-    const uint32_t B = d->B, rpu = d->rows_per_unit;
-    const int32_t* units = d->units_dev;
-    const dim3 grid(div_up(B, 256u)), block(256);
-
     int rc = curved_front_gather(d, sc.f, nullptr, stream);
     if (rc != NERFTEX_OK) return rc;
     if ((rc = curved_front_sigma(d, sc.f, "curved_field_infer(pack)", stream)) != NERFTEX_OK) return rc;
-    {
-        KernelTimer kt("curved_mid_rows_kernel", st);
-        hipLaunchKernelGGL(curved_mid_rows_kernel, grid, block, 0, st, sc.f.h, sc.f.normal, d->dirs, B, d->fc_weight, d->eval, sc.sigma_raw, sc.cin, units, rpu);
-    }
-    if ((rc = check_launch("curved_field_infer(mid)")) != NERFTEX_OK) return rc;
-    rc = ffmlp_inference_rows(sc.cin, d->color_weights, B, 32, 64, 3, sc.hc, units, rpu, st);
-    if (rc != NERFTEX_OK) return rc;
-    {
-        KernelTimer kt("curved_out_rows_kernel", st);
-        hipLaunchKernelGGL(curved_out_rows_kernel, grid, block, 0, st, sc.hc, sc.sigma_raw, sc.f.mask, d->dirs, B, d->sigma, d->rgbs, units, rpu);
-    }
-    return check_launch("curved_field_infer(out)");
+    static const char* const labels[2] = {"curved_field_infer(mid)", "curved_field_infer(out)"};
+    return curved_back_half(d, sc.f.h, sc.f.normal, sc.f.mask, sc.back, labels, stream);
 }
 
 extern "C" int nerftex_field_mid_forward(const void* h, const float* dirs, uint32_t B, float* sigma, void* cin, void* stream) {
@@ -627,6 +647,9 @@ extern "C" int nerftex_field_out_backward(const float* grad_rgbs, const float* r
     }
     return check_launch("field_out_backward");
 }
+
+// ---- the planar lookup of an imported feature map and its chain (nerftex_planar_lookup, nerftex_curved_import_infer): in front of shlight.inc ------------
+#include "planar.inc"
 
 // ---- the SH light head of the curved field (nerftex_sh_light_forward / _backward) ----------------------------------------------------------------------
 #include "shlight.inc"

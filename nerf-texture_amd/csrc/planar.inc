@@ -1,0 +1,212 @@
+// The planar lookup of an imported feature map (nerftex_planar_lookup) and the curved field's no-grad forward over it as one device-count call
+// (nerftex_curved_import_infer): MeshFeatureField.forward's `imported_type == 'field'` branch (tools/map.py:646-668) -- an O(1) bilinear read of a
+// [H, W, 16] fp32 image on the xy plane where the mesh chain searches neighbours, traces twice and gathers a hash table.  Included by fieldglue.hip
+// in FRONT of shlight.inc (whose file-scope pragma holds for everything behind it); the kernel switches contraction off itself.
+
+namespace nerftex {
+namespace {
+
+struct PlanarArgs {
+    const float* map;  // [H, W, 16] fp32, channel-last, 16-byte aligned
+    uint32_t H, W;
+    int divide;          // 0: u = x0 * plane0, v = x1 * plane1;  1: u = x0 / plane0, v = x1 / plane1 (true divisions)
+    float plane0, plane1;
+    float height0, height1;  // sdf = (x2 * height0) * height1 - offset
+    float offset, h_threshold;
+};
+
+// LANES = 1: one thread per row -- the four corners' 64 bytes each as four 16-byte loads, 16 independent loads in flight, two 16-byte stores of features.
+// LANES = 4: four adjacent lanes per row -- lane q loads quarter q of each corner (the four lanes read one texel's 64 contiguous bytes with one
+// instruction) and stores its 8 bytes; lane 0 also writes the row's scalars and the ladder.  Which one runs: the knob `planar_lanes`; the measured
+// choice is DESIGN.md 4.15's.  The arithmetic is the same expression tree per element in both: the same bits.
+// ROWS: the rows contract of nerftex_curved_field_infer's kernels (writes the raw normal (0, 0, 1) for the mid kernel); otherwise the plain form
+// (every row, writes p_uv and sdf).  Both write mask [B] and the sigma net's input row xin [B,48] = [half(features) | half(ladder) | ones].
+template <bool ROWS, int LANES>
+__global__ __launch_bounds__(256) void planar_lookup_rows_kernel(const float* __restrict__ xyz, const float* __restrict__ dirs, const uint32_t B, const PlanarArgs a,
+                                                                 float* __restrict__ p_uv, float* __restrict__ sdf_out, uint8_t* __restrict__ mask,
+                                                                 float* __restrict__ normal, half_t* __restrict__ xin, const int32_t* __restrict__ units_dev,
+                                                                 const uint32_t rows_per_unit) {
+#pragma clang fp contract(off)  // every framework op rounds on its own
+    static_assert(LANES == 1 || LANES == 4, "one thread or four lanes per row");
+    const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t b = tid / LANES, q = tid % LANES;
+    const bool first = q == 0;  // the lane that writes what a row has once
+    if (b >= (ROWS ? live_rows(B, units_dev, rows_per_unit) : B)) return;
+    half_t* row = xin + (size_t)b * 48;
+    if (ROWS && slot_unused(dirs, b)) {  // no texel is read
+        if (!first) return;
+        mask[b] = 0;
+#pragma unroll
+        for (int c = 0; c < 3; c++) normal[(size_t)b * 3 + c] = 0.0f;
+        const half8_t zero = {0, 0, 0, 0, 0, 0, 0, 0};
+        reinterpret_cast<half8_t*>(row)[0] = zero;
+        reinterpret_cast<half8_t*>(row)[1] = zero;
+        write_unused_ladder(row);
+        return;
+    }
+    const float x0 = xyz[(size_t)b * 3], x1 = xyz[(size_t)b * 3 + 1], x2 = xyz[(size_t)b * 3 + 2];
+    const float u = a.divide ? x0 / a.plane0 : x0 * a.plane0;
+    const float v = a.divide ? x1 / a.plane1 : x1 * a.plane1;
+    const float sdf = (x2 * a.height0) * a.height1 - a.offset;
+    if (first) {
+        mask[b] = (fabsf(sdf) < a.h_threshold && u >= -1.0f && u <= 1.0f && v >= -1.0f && v <= 1.0f) ? 1 : 0;
+        if (ROWS) {
+            normal[(size_t)b * 3] = 0.0f; normal[(size_t)b * 3 + 1] = 0.0f; normal[(size_t)b * 3 + 2] = 1.0f;
+        } else {
+            p_uv[(size_t)b * 2] = u; p_uv[(size_t)b * 2 + 1] = v;
+            sdf_out[b] = sdf;
+        }
+    }
+    // grid_sample(bilinear, align_corners=True, padding zeros); u runs along the map's first axis
+    const float iu = ((u + 1.0f) / 2.0f) * (float)(a.H - 1), iv = ((v + 1.0f) / 2.0f) * (float)(a.W - 1);
+    const float i0 = floorf(iu), j0 = floorf(iv);
+    const float wu1 = iu - i0, wu0 = (i0 + 1.0f) - iu, wv1 = iv - j0, wv0 = (j0 + 1.0f) - iv;
+    const float w[4] = {wu0 * wv0, wu1 * wv0, wu0 * wv1, wu1 * wv1};  // texels (i0,j0), (i0+1,j0), (i0,j0+1), (i0+1,j0+1), added in this order
+    // a corner outside [0,H) x [0,W) contributes nothing and is not read; the comparisons are on the floats (a NaN or a huge coordinate fails
+    // them all) and the index is converted only inside the range
+    const float hi_i = (float)(a.H - 1), hi_j = (float)(a.W - 1);
+    const bool in_i[2] = {i0 >= 0.0f && i0 <= hi_i, i0 + 1.0f >= 0.0f && i0 + 1.0f <= hi_i};
+    const bool in_j[2] = {j0 >= 0.0f && j0 <= hi_j, j0 + 1.0f >= 0.0f && j0 + 1.0f <= hi_j};
+    constexpr int Q = 4 / LANES;  // 16-byte quarters of a texel this lane reads: all four, or quarter q
+    float4_t t[4][Q];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int di = k & 1, dj = k >> 1;
+        if (in_i[di] && in_j[dj]) {
+            const size_t i = (size_t)(int)(i0 + (float)di), j = (size_t)(int)(j0 + (float)dj);
+            const float4_t* src = reinterpret_cast<const float4_t*>(a.map + (i * (size_t)a.W + j) * 16);
+#pragma unroll
+            for (int qq = 0; qq < Q; qq++) t[k][qq] = src[LANES == 1 ? (uint32_t)qq : q];
+        } else {
+#pragma unroll
+            for (int qq = 0; qq < Q; qq++) t[k][qq] = float4_t{0.0f, 0.0f, 0.0f, 0.0f};
+        }
+    }
+    // four products and three sums; an absent corner's texel is 0 and its weight finite whenever another corner is present (iu, iv then lie within one
+    // texel of the map), so its product adds nothing; with no corner present the weights may be anything and the answer is 0
+    const bool any = (in_i[0] || in_i[1]) && (in_j[0] || in_j[1]);
+    half4_t o[Q];
+#pragma unroll
+    for (int c = 0; c < 4 * Q; c++) {
+        const float acc = ((t[0][c / 4][c % 4] * w[0] + t[1][c / 4][c % 4] * w[1]) + t[2][c / 4][c % 4] * w[2]) + t[3][c / 4][c % 4] * w[3];
+        o[c / 4][c % 4] = narrow(any ? acc : 0.0f);
+    }
+    if constexpr (LANES == 1) {
+        half8_t o8[2];
+#pragma unroll
+        for (int c = 0; c < 16; c++) o8[c / 8][c % 8] = o[c / 4][c % 4];
+        reinterpret_cast<half8_t*>(row)[0] = o8[0];
+        reinterpret_cast<half8_t*>(row)[1] = o8[1];
+    } else {
+        reinterpret_cast<half4_t*>(row)[q] = o[0];
+    }
+    if (first) write_height_ladder(sdf, row);
+}
+
+// one launch of the lookup in the lane mapping the knob `planar_lanes` names (4: four lanes per row; anything else: one thread per row)
+template <bool ROWS>
+void launch_planar_lookup(hipStream_t st, const float* xyz, const float* dirs, uint32_t B, const PlanarArgs& a, float* p_uv, float* sdf, uint8_t* mask,
+                          float* normal, half_t* xin, const int32_t* units_dev, uint32_t rows_per_unit) {
+    KernelTimer kt("planar_lookup_rows_kernel", st);
+    if (knob(kKnobPlanarLanes) == 4 && B < (1u << 30))  // (4 B thread indices stay 32-bit)
+        hipLaunchKernelGGL((planar_lookup_rows_kernel<ROWS, 4>), dim3(div_up(4u * B, 256u)), dim3(256), 0, st, xyz, dirs, B, a, p_uv, sdf, mask, normal, xin, units_dev,
+                           rows_per_unit);
+    else
+        hipLaunchKernelGGL((planar_lookup_rows_kernel<ROWS, 1>), dim3(div_up(B, 256u)), dim3(256), 0, st, xyz, dirs, B, a, p_uv, sdf, mask, normal, xin, units_dev,
+                           rows_per_unit);
+}
+
+// (no message: each entry names what it refuses)
+inline bool planar_scales_ok(uint32_t mode, float p0, float p1, float h0, float h1, float offset, float h_threshold) {
+    auto pos = [](float v) { return v > 0.0f && std::isfinite(v); };
+    return mode <= 1u && pos(p0) && pos(p1) && pos(h0) && pos(h1) && pos(h_threshold) && std::isfinite(offset);
+}
+
+// the scratch of one nerftex_curved_import_infer call
+struct ImportScratch {
+    ScratchCarver carve;
+    uint8_t* mask;
+    float* normal;
+    half_t *xin, *h;
+    CurvedBack back;
+    ImportScratch(void* scratch, size_t B)
+        : carve{reinterpret_cast<uintptr_t>(scratch), B}, mask(carve.take<uint8_t>(1)), normal(carve.take<float>(3)), xin(carve.take<half_t>(48)),
+          h(carve.take<half_t>(16)), back(carve) {}
+};
+
+}  // namespace
+}  // namespace nerftex
+
+extern "C" int nerftex_planar_lookup(const float* xyz, const float* map, uint32_t map_h, uint32_t map_w, uint32_t mode, float plane_scale0, float plane_scale1,
+                                     float height_scale0, float height_scale1, float sdf_offset, float h_threshold, uint32_t n_freqs, uint32_t B, float* p_uv,
+                                     float* sdf, uint8_t* mask, void* xin, void* stream) {
+    clear_error();
+    if (n_freqs != kInferFreqs) {
+        set_error("planar_lookup: the kernel writes the curved field's 12 height bands, but got n_freqs = %u", n_freqs);
+        return NERFTEX_ERR_INVALID;
+    }
+    if (map_h == 0 || map_h > 16384u || map_w == 0 || map_w > 16384u) {
+        set_error("planar_lookup: the map needs between 1 and 16384 texels along each axis, but got %u x %u", map_h, map_w);
+        return NERFTEX_ERR_INVALID;
+    }
+    if (B == 0) return NERFTEX_OK;
+    if (!xyz || !map || !p_uv || !sdf || !mask || !xin || (reinterpret_cast<uintptr_t>(map) & 15) || (reinterpret_cast<uintptr_t>(xin) & 15)) {
+        set_error("planar_lookup: inputs, map and outputs must not be NULL, and the map and xin must be 16-byte aligned");
+        return NERFTEX_ERR_INVALID;
+    }
+    if (!planar_scales_ok(mode, plane_scale0, plane_scale1, height_scale0, height_scale1, sdf_offset, h_threshold)) {
+        set_error("planar_lookup: mode is NERFTEX_PLANAR_MULTIPLY or NERFTEX_PLANAR_DIVIDE, the scales and h_threshold positive and finite, sdf_offset finite");
+        return NERFTEX_ERR_INVALID;
+    }
+    hipStream_t st = as_stream(stream);
+    const PlanarArgs a{map, map_h, map_w, (int)mode, plane_scale0, plane_scale1, height_scale0, height_scale1, sdf_offset, h_threshold};
+    launch_planar_lookup<false>(st, xyz, nullptr, B, a, p_uv, sdf, mask, nullptr, static_cast<half_t*>(xin), nullptr, 0u);
+    return check_launch("planar_lookup");
+}
+
+extern "C" size_t nerftex_curved_import_infer_scratch_bytes(uint32_t B) { return ImportScratch(nullptr, B).carve.at; }
+
+extern "C" int nerftex_curved_import_infer(const nerftex_curved_import_infer_desc* d, void* stream) {
+    clear_error();
+    if (!d) {
+        set_error("curved_import_infer: NULL descriptor");
+        return NERFTEX_ERR_INVALID;
+    }
+    if (d->B % 128 != 0) {
+        set_error("curved_import_infer: the batch must be a multiple of 128 rows, but got %u", d->B);
+        return NERFTEX_ERR_INVALID;
+    }
+    if (d->n_features != 16 || d->n_freqs != kInferFreqs || d->sigma_in != 48 || d->sigma_hidden != 32 || d->sigma_layers != 2 || d->sigma_out != 16 ||
+        !back_shapes_ok(d)) {
+        set_error("curved_import_infer: the kernels serve the default curved field only (a map of 16 features, 12 height bands, "
+                  "sigma net 48 -> 32 x 2 -> 16, colour net 32 -> 64 x 3 -> 3)");
+        return NERFTEX_ERR_INVALID;
+    }
+    if (d->map_h == 0 || d->map_h > 16384u || d->map_w == 0 || d->map_w > 16384u) {
+        set_error("curved_import_infer: the map needs between 1 and 16384 texels along each axis, but got %u x %u", d->map_h, d->map_w);
+        return NERFTEX_ERR_INVALID;
+    }
+    if (d->B == 0) return NERFTEX_OK;
+    const ImportScratch sc(d->scratch, d->B);
+    if (!d->xyz || !d->dirs || !d->map || !d->sigma_weights || !d->color_weights || !d->sigma || !d->rgbs || !d->scratch ||
+        (reinterpret_cast<uintptr_t>(d->scratch) & 255) || d->scratch_bytes < sc.carve.at) {
+        set_error("curved_import_infer: inputs, map, weights and outputs must not be NULL, and scratch must be 256-byte aligned and hold %zu bytes", sc.carve.at);
+        return NERFTEX_ERR_INVALID;
+    }
+    if ((reinterpret_cast<uintptr_t>(d->map) & 15) || (reinterpret_cast<uintptr_t>(d->sigma_weights) & 15) || (reinterpret_cast<uintptr_t>(d->color_weights) & 15)) {
+        set_error("curved_import_infer: the map and the weight vectors must be 16-byte aligned");
+        return NERFTEX_ERR_INVALID;
+    }
+    if (!planar_scales_ok(d->mode, d->plane_scale0, d->plane_scale1, d->height_scale0, d->height_scale1, d->sdf_offset, d->h_threshold)) {
+        set_error("curved_import_infer: mode is NERFTEX_PLANAR_MULTIPLY or NERFTEX_PLANAR_DIVIDE, the scales and h_threshold positive and finite, sdf_offset finite");
+        return NERFTEX_ERR_INVALID;
+    }
+    hipStream_t st = as_stream(stream);
+    const PlanarArgs a{d->map, d->map_h, d->map_w, (int)d->mode, d->plane_scale0, d->plane_scale1, d->height_scale0, d->height_scale1, d->sdf_offset, d->h_threshold};
+    launch_planar_lookup<true>(st, d->xyz, d->dirs, d->B, a, nullptr, nullptr, sc.mask, sc.normal, sc.xin, d->units_dev, d->rows_per_unit);
+    int rc = check_launch("curved_import_infer(lookup)");
+    if (rc != NERFTEX_OK) return rc;
+    if ((rc = ffmlp_inference_rows(sc.xin, d->sigma_weights, d->B, 48, 32, 2, sc.h, d->units_dev, d->rows_per_unit, st)) != NERFTEX_OK) return rc;
+    static const char* const labels[2] = {"curved_import_infer(mid)", "curved_import_infer(out)"};
+    return curved_back_half(d, sc.h, sc.normal, sc.mask, sc.back, labels, stream);
+}

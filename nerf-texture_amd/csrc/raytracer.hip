@@ -14,6 +14,7 @@
 // Arithmetic follows oracle/src/orc_raytracer.c expression by expression (explicit fmaf, no other contraction).
 #include "common.hpp"
 #include "curved_infer.hpp"
+#include "height_ladder.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -243,7 +244,6 @@ __global__ __launch_bounds__(64) void raytrace_kernel(uint32_t N, const float* r
 //   tools/encoding.py:5-43).  The reference runs this as ~35 framework launches + two trace launches and materialises every
 //   intermediate ([N,K,3] gathers, two full hit records); the neighbour search itself (frnn, un-vendored) stays outside.
 constexpr int kMaxK = 16;
-constexpr uint32_t kInferFreqs = 12;  // multires of the curved field: z_embed has 1 + 2 * 12 = 25 columns
 // One point of the projector, run by the TWO lanes of a pair (side 0: the trace along +normal, which also writes; side 1: along -normal) -- both
 // lanes must arrive here together: the traces meet in an __shfl_xor.
 // INFER (nerftex_curved_field_infer): no height, face or frame output, and FreqEncoder(height) leaves as the 16-bit values the sigma net reads --
@@ -311,25 +311,7 @@ __device__ __forceinline__ void curved_project_point(const uint32_t i, const uin
     h_mask[i] = fabsf(sdf) < h_limit ? 1 : 0;
     normal_out[3 * (size_t)i] = nrm.x; normal_out[3 * (size_t)i + 1] = nrm.y; normal_out[3 * (size_t)i + 2] = nrm.z;
     if constexpr (INFER) {
-        // the fp32 value the plain form stores is narrowed as nerftex_curved_pack_inputs narrows it after reading it back (the empty asm keeps
-        // the conversion from being folded into the operation that produces the value)
-        auto narrow = [](float v) {
-            asm volatile("" : "+v"(v));
-            return (half_t)v;
-        };
-        half8_t o[4];
-        o[0][0] = narrow(sdf);
-        float f = 1.0f;
-#pragma unroll
-        for (uint32_t k = 0; k < kInferFreqs; k++, f *= 2.0f) {
-            o[(1 + 2 * k) / 8][(1 + 2 * k) % 8] = narrow(sinf(sdf * f));
-            o[(2 + 2 * k) / 8][(2 + 2 * k) % 8] = narrow(cosf(sdf * f));
-        }
-#pragma unroll
-        for (int c = 1 + 2 * (int)kInferFreqs; c < 32; c++) o[c / 8][c % 8] = (half_t)1.0f;
-        half8_t* dst = reinterpret_cast<half8_t*>(static_cast<half_t*>(z_embed) + (size_t)i * 48 + 16);
-#pragma unroll
-        for (int q = 0; q < 4; q++) dst[q] = o[q];
+        write_height_ladder(sdf, static_cast<half_t*>(z_embed) + (size_t)i * 48);  // (height_ladder.hpp: the planar lookup's ladder, too)
         if (tbn_out) {  // (the light-model chain: the hit face's frame, as the plain form below)
             const int64_t hit = best >= 0 ? tris[best].id : (int64_t)0;
 #pragma unroll
@@ -391,14 +373,7 @@ __global__ __launch_bounds__(64) void curved_project_rows_kernel(uint32_t N, con
             normal_out[3 * (size_t)i + c] = 0.0f;
         }
         h_mask[i] = 0;
-        half8_t z8, tail;
-#pragma unroll
-        for (int c = 0; c < 8; c++) {
-            z8[c] = (half_t)0.0f;
-            tail[c] = c == 0 ? (half_t)0.0f : (half_t)1.0f;  // column 40 is z's last, 41..47 the padding ones
-        }
-        half8_t* dst = reinterpret_cast<half8_t*>(xin + (size_t)i * 48 + 16);
-        dst[0] = z8; dst[1] = z8; dst[2] = z8; dst[3] = tail;
+        write_unused_ladder(xin + (size_t)i * 48);
         if (tbn_out) {
 #pragma unroll
             for (int k = 0; k < 9; k++) tbn_out[9 * (size_t)i + k] = 0.0f;

@@ -652,6 +652,9 @@ class CurvedTrainer(AcceleratedTrainer):
 
         field = renderer.field
         assert isinstance(field, CurvedField), "CurvedTrainer trains a curved.CurvedField"
+        if getattr(field, "imported", False):
+            raise NotImplementedError("CurvedTrainer: the field renders an imported feature map (CurvedField.import_field); import mode is for rendering -- "
+                                      "switch_import() back to the mesh field to train")
         assert field.encoder_var is None, "accelerate(): prob_model=True (the log-variance table) is not on the graphed path (main.py:86 trains without it)"
         assert not normal_loss or getattr(field, "light_model", None) == "SH", "accelerate(normal_loss=True) supervises the fine normal of CurvedField(light_model='SH')"
         self.use_normal_loss = bool(normal_loss)

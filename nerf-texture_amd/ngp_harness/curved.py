@@ -459,6 +459,7 @@ class CurvedField(torch.nn.Module):
 
         self.bound, self.h_threshold, self.geo_feat_dim, self.multires, self.fc_weight = bound, h_threshold, geo_feat_dim, 12, 1.0
         self.projector = MeshProjector(vertices, faces, h_threshold=h_threshold, K=K, vertex_normals=vertex_normals, tbn=tbn)
+        self._init_import_state()
         kw = dict(input_dim=3, num_levels=num_level, level_dim=2, base_resolution=512, log2_hashmap_size=19, desired_resolution=1024, gridtype="hash",
                   align_corners=True)
         self.encoder = GridEncoder_clustering(**kw)  # tools/map.py:563
@@ -487,6 +488,118 @@ class CurvedField(torch.nn.Module):
         self.color_pad = (self.color_in + 15) // 16 * 16
         self.color_net = FFMLP(input_dim=self.color_pad, output_dim=3, hidden_dim=hidden_dim_color, num_layers=num_layers_color)
 
+    # ---- an imported planar feature texture (MeshFeatureField.import_field, tools/map.py:912-927; the 'field' branch of its forward, :646-668) ----
+
+    def _init_import_state(self):
+        """The import state of MeshFeatureField as its constructor leaves it (tools/map.py:604-618): nothing imported."""
+        self.imported, self.rescale, self.features_imported, self.bounds = False, False, None, None
+        self.uv_utilize_rate, self.sdf_offset, self._import_version = 1.0, 0.0, 0
+
+    def import_field(self, features, grid_gap, rescale=None):
+        """NeRFNetwork.import_field -> MeshFeatureField.import_field for a planar map (`mesh is None`, network_curvedfield.py:457-475):
+        features [H, W, 16] (numpy or tensor, the array the reference receives, in its axis order) is kept channel-last in fp32 on the field's
+        device, bounds = [grid_gap H / 2, grid_gap W / 2], `imported` is set and `rescale` TOGGLES as the reference's does (False at
+        construction, so True after the first import: u, v = x, y scaled by uv_utilize_rate; False: x, y divided by the bounds); rescale=
+        sets it instead.  From here on embed() / density() / forward() / infer() read the map and touch neither the projector nor the hash
+        table, until switch_import().  The caller re-estimates the occupancy grid (Renderer.initialize_states), as the reference does."""
+        if self.normal_net is not None or getattr(self, "light_model", None) is not None:
+            raise NotImplementedError("CurvedField.import_field: a field with the fine-normal net or a light model would also need the imported phi_embed, "
+                                      "local_tbn and sample_tbn maps (tools/map.py:670-675); only the static light model without a normal net imports here")
+        f = torch.as_tensor(np.asarray(features) if not torch.is_tensor(features) else features).detach()
+        if f.dim() != 3 or f.shape[-1] != self.encoder.output_dim or f.shape[0] < 1 or f.shape[1] < 1:
+            raise ValueError(f"CurvedField.import_field: features are [H, W, {self.encoder.output_dim}], but got {tuple(f.shape)}")
+        dev = self.sigma_net.weights.device
+        self.features_imported = f.to(device=dev, dtype=torch.float32).contiguous()
+        H, W = int(f.shape[0]), int(f.shape[1])
+        self.bounds = [0.5 * float(grid_gap) * H, 0.5 * float(grid_gap) * W]
+        self.imported = True
+        self.rescale = (not self.rescale) if rescale is None else bool(rescale)
+        self._import_version += 1
+
+    def switch_import(self):
+        """network_curvedfield.py:519-521: between the imported map and the field's own mesh and table (the map is kept)."""
+        if self.features_imported is None:
+            raise RuntimeError("CurvedField.switch_import: nothing has been imported")
+        self.imported = not self.imported
+        self._import_version += 1
+
+    def set_uv_utilize_rate(self, rate=1.0):
+        self.uv_utilize_rate = float(rate)
+        self._import_version += 1
+
+    def set_sdf_offset(self, sdf_offset=0.0):
+        self.sdf_offset = float(sdf_offset)
+        self._import_version += 1
+
+    def set_h_threshold(self, h_threshold=0.03):
+        """network_curvedfield.py:539-541: the one threshold the mesh projector and the imported map's mask read."""
+        self.h_threshold = self.projector.h_threshold = float(h_threshold)
+        self._import_version += 1
+
+    def _import_scalars(self):
+        """(mode, plane scales, height scales, sdf_offset, h_threshold) of nerftex_planar_lookup for the state as it is: `rescale` multiplies,
+        u, v = x, y rate and sdf = (z b0) rate - offset; otherwise u, v = x / b0, y / b1 and sdf = z - offset (the two ones multiply exactly)."""
+        from nerftex_hip import PLANAR_DIVIDE, PLANAR_MULTIPLY
+
+        b0, b1, rate = float(self.bounds[0]), float(self.bounds[1]), float(self.uv_utilize_rate)
+        if self.rescale:
+            return (PLANAR_MULTIPLY, rate, rate, b0, rate, float(self.sdf_offset), float(self.h_threshold))
+        return (PLANAR_DIVIDE, b0, b1, 1.0, 1.0, float(self.sdf_offset), float(self.h_threshold))
+
+    def _import_stamp(self):
+        """graph_stamp()'s share of the import state: nothing unless a map is in use (the stamp of a field that never imported is unchanged)."""
+        if not getattr(self, "imported", False):
+            return ()
+        f = self.features_imported
+        return ("import", f.data_ptr(), tuple(f.shape)) + self._import_scalars() + (self._import_version,)
+
+    @torch.no_grad()
+    def _import_lookup(self, x):
+        """nerftex_planar_lookup: -> p_uv [N,2], sdf [N], h_mask [N] bool, xin [N,48] half (the sigma net's padded input)."""
+        from nerftex_hip import check, lib, ptr, stream
+
+        x = x.detach().float().contiguous()
+        N, dev, f = x.shape[0], x.device, self.features_imported
+        p_uv = torch.empty(N, 2, device=dev)
+        sdf = torch.empty(N, device=dev)
+        mask = torch.empty(N, dtype=torch.uint8, device=dev)
+        xin = torch.empty(N, 48, dtype=torch.float16, device=dev)
+        mode, p0, p1, h0, h1, off, h = self._import_scalars()
+        check(lib.nerftex_planar_lookup(ptr(x), ptr(f), f.shape[0], f.shape[1], mode, p0, p1, h0, h1, off, h, int(self.multires), N, ptr(p_uv), ptr(sdf),
+                                        ptr(mask), ptr(xin), stream()))
+        return p_uv, sdf, mask.bool(), xin
+
+    def _import_normal(self, x, normalised):
+        """normal_coarse of the import branch (:667-668): (0, 0, 1), divided by |n| + 1e-5 as tools/map.py:720 does when `normalised`."""
+        n = torch.zeros(x.shape[0], 3, dtype=torch.float32, device=x.device)
+        n[:, 2] = 1.0
+        return n / (n.norm(dim=-1, keepdim=True) + 1e-5) if normalised else n
+
+    def _import_embed_reference(self, x):
+        """The import branch op by op, the reference's expressions (tools/map.py:649-668): -> embed [N,41] fp32, normal_coarse, h_mask.
+        The divisors are tensors: a device division by a Python scalar is a multiplication by its reciprocal, the reference's (as executed) is
+        a true division."""
+        x = x.float()
+        b0, b1 = (torch.tensor(b, dtype=torch.float32, device=x.device) for b in self.bounds)
+        if self.rescale:
+            p_sur = x[..., :2] * self.uv_utilize_rate
+            sdf = x[..., -1:] * self.bounds[0] * self.uv_utilize_rate
+        else:
+            p_sur = torch.stack([x[..., 0] / b0, x[..., 1] / b1], dim=-1)
+            sdf = x[..., -1:]
+        sdf = sdf - self.sdf_offset
+        h_mask = sdf[..., 0].abs() < self.h_threshold
+        h_mask = torch.logical_and(h_mask, (p_sur >= -1.0).all(dim=-1))
+        h_mask = torch.logical_and(h_mask, (p_sur <= 1.0).all(dim=-1))
+        # [H, W, C] -> [1, C, W, H]: the grid's first coordinate indexes the last axis, so u runs along the map's first axis (:915-919)
+        image = self.features_imported.to(x.device).permute(2, 1, 0).unsqueeze(0)
+        x_embed = torch.nn.functional.grid_sample(image, p_sur[None, None], align_corners=True, padding_mode="zeros")[0, :, 0].permute(1, 0)
+        embed = torch.cat([x_embed, freq_encode(sdf, self.multires)], dim=-1)
+        return embed, self._import_normal(x, True), h_mask
+
+    def _import_fused(self, x):
+        return x.is_cuda and self._glue_fused() and self.multires == 12 and self.sigma_net.dtype == torch.float16
+
     def fine_normal(self, x, no_noise=False, requires_grad_xyz=False):
         """normal_fine of MeshFeatureField.forward (tools/map.py:637-641, 726-735): the factorized net's local normal rotated into the world by the
         hit face's frame, normalised.  -> (normal_fine [N,3], normal_coarse [N,3], h_mask [N])."""
@@ -501,6 +614,13 @@ class CurvedField(torch.nn.Module):
         requires_grad_xyz (network_curvedfield.py:236-259, the branch that differentiates sigma with respect to the sample position): the
         projection carries `diff_project_layer`'s gradient, the hash table is looked up with input gradients (dy_dx) and the height ladder
         is evaluated by framework ops on the differentiable height -- dL/dembed reaches x."""
+        if getattr(self, "imported", False):  # the import branch (:646-668): the map instead of the mesh and the table
+            if requires_grad_xyz or with_fine_normal:
+                raise NotImplementedError("CurvedField.embed: an imported map is rendered without gradients to the sample position and without a fine normal")
+            if self._import_fused(x):
+                _, _, h_mask, xin = self._import_lookup(x)
+                return xin[:, :self.in_dim], self._import_normal(x, True), h_mask
+            return self._import_embed_reference(x)
         if requires_grad_xyz:
             p_sur, sdf, h_mask, normal, local_tbn = self.projector.project(x, K=self.projector.K, h_threshold=self.h_threshold, requires_grad_xyz=True)
             z_embed = freq_encode(sdf, self.multires)
@@ -526,6 +646,11 @@ class CurvedField(torch.nn.Module):
         return _TruncExp.apply(h[..., 0]), h[..., 1:]
 
     def density(self, x, requires_grad_xyz=False):
+        if getattr(self, "imported", False) and not requires_grad_xyz and self._import_fused(x):
+            _, _, h_mask, xin = self._import_lookup(x)
+            h = self.sigma_net(xin)
+            sigma = _TruncExp.apply(h[..., 0])
+            return {"sigma": torch.where(h_mask, sigma, torch.zeros_like(sigma)), "geo_feat": h[..., 1:]}
         embed, _, h_mask = self.embed(x, requires_grad_xyz=requires_grad_xyz)
         sigma, geo = self._sigma(embed)
         return {"sigma": torch.where(h_mask, sigma, torch.zeros_like(sigma)), "geo_feat": geo}
@@ -593,7 +718,13 @@ class CurvedField(torch.nn.Module):
     def forward(self, x, d, **kwargs):
         if getattr(self, "light_model", None) == "SH":
             return self._forward_light(x, d, normal_supervision=bool(kwargs.get("normal_supervision", False)))
-        if self._glue_fused():
+        if getattr(self, "imported", False) and self._import_fused(x):
+            _, _, h_mask, xin = self._import_lookup(x)
+            h = self.sigma_net(xin)
+            sigma_raw, cin = _CurvedMid.apply(h, self._import_normal(x, False), d, self.fc_weight, 2 | int(not self.training))  # (bit 1: tools/map.py:720 in the kernel)
+            sigma, color = _CurvedOut.apply(self.color_net(cin), sigma_raw, h_mask)
+            return sigma, color, {}
+        if self._glue_fused() and not getattr(self, "imported", False):
             p_sur, sdf, h_mask, normal, local_tbn, _, z_embed = self.projector.project_fused(x, multires=self.multires)
             x_embed = self.encoder(p_sur, bound=self.bound)
             if x_embed.dtype == torch.float16 and z_embed.dtype == torch.float32:
@@ -622,7 +753,7 @@ class CurvedField(torch.nn.Module):
         grid's and the tracer's handles, the mesh buffers' storage, the projector's and the field's scalars, train / eval, the fused switch."""
         p = self.projector
         return (p._knn.value, p.tracer._handle.value, p.mesh_vertices.data_ptr(), p.vertex_normals.data_ptr(), p.tbn.data_ptr(), int(p.K),
-                p._height_limit(...), float(self.fc_weight), float(self.bound), bool(self.training), bool(getattr(self, "fused_glue", True))) + self._light_stamp()
+                p._height_limit(...), float(self.fc_weight), float(self.bound), bool(self.training), bool(getattr(self, "fused_glue", True))) + self._light_stamp() + self._import_stamp()
 
     def _light_stamp(self):
         """graph_stamp()'s share of the light model: nothing without one (the stamp of today's field is unchanged)."""
@@ -698,6 +829,31 @@ class CurvedField(torch.nn.Module):
         desc = CurvedInferDesc(color_weights=ptr(wc_h), color_in=c.input_dim, color_hidden=c.hidden_dim, color_layers=c.num_layers, color_out=c.output_dim,
                                eval=2 | int(not self.training), **front)
         return desc, (table, ws_h, wc_h)
+
+    def _infer_import_fused(self, x, d):
+        """Whether nerftex_curved_import_infer serves this call: _infer_fused()'s conditions without the neighbour search's and the table's."""
+        c, s, B = self.color_net, self.sigma_net, x.shape[0]
+        return (self._import_fused(x) and c.dtype == torch.float16 and (c.input_dim, c.hidden_dim, c.num_layers, c.output_dim) == (32, 64, 3, 3)
+                and (s.input_dim, s.hidden_dim, s.num_layers, s.padded_output_dim) == (48, 32, 2, 16) and B % 128 == 0 and B > 0
+                and x.dtype == torch.float32 and d.dtype == torch.float32 and x.is_contiguous() and d.is_contiguous()
+                and self.features_imported.device == x.device)
+
+    def _infer_import_desc(self, x, d, live, sigma, rgbs, scratch):
+        """The nerftex_curved_import_infer_desc of one call (and the tensors it points into, to be kept until the call is enqueued)."""
+        from nerftex_hip import CurvedImportInferDesc, ptr
+
+        c, s, f = self.color_net, self.sigma_net, self.features_imported
+        ws_h, wc_h = self._infer_weights("_infer_cache", c)
+        mode, p0, p1, h0, h1, off, h = self._import_scalars()
+        units, rows_per_unit = (ptr(live[0]), int(live[1])) if live is not None else (None, 0)
+        desc = CurvedImportInferDesc(
+            xyz=ptr(x), dirs=ptr(d), B=x.shape[0], map=ptr(f), map_h=f.shape[0], map_w=f.shape[1], n_features=f.shape[2], mode=mode, plane_scale0=p0,
+            plane_scale1=p1, height_scale0=h0, height_scale1=h1, sdf_offset=off, h_threshold=h, n_freqs=int(self.multires), sigma_weights=ptr(ws_h),
+            sigma_in=s.input_dim, sigma_hidden=s.hidden_dim, sigma_layers=s.num_layers, sigma_out=s.padded_output_dim, color_weights=ptr(wc_h),
+            color_in=c.input_dim, color_hidden=c.hidden_dim, color_layers=c.num_layers, color_out=c.output_dim, fc_weight=float(self.fc_weight),
+            eval=2 | int(not self.training), sigma=ptr(sigma), rgbs=ptr(rgbs), units_dev=units, rows_per_unit=rows_per_unit, scratch=ptr(scratch),
+            scratch_bytes=scratch.numel())
+        return desc, (f, ws_h, wc_h)
 
     def _infer_light_fused(self, x, d):
         """Whether nerftex_curved_light_infer serves this call: the SH light model with the switch `fused_light_infer` set (default: not), fp16
@@ -813,6 +969,11 @@ class CurvedField(torch.nn.Module):
         light_model="SH": forward(x, d) on all rows unless `fused_light_infer` is set (default False) -- then the light model's own chain,
         nerftex_curved_light_infer, under the same rows contract: sigma and the mask are forward()'s bit for bit, the shading normal and the
         colour follow forward()'s arithmetic at its rounding points."""
+        if getattr(self, "imported", False):  # an imported map: its own chain under the same rows contract, or forward() on all rows
+            if self._infer_import_fused(x, d):
+                return self._infer_call("nerftex_curved_import_infer", self._infer_import_desc, x, d, live)
+            sigma, rgbs, _ = self.forward(x, d)
+            return sigma.float(), rgbs.float()
         if self._infer_light_fused(x, d):  # (opt-in: `fused_light_infer`; the SH light model's own chain, the same rows contract)
             return self.infer_light(x, d, live)
         if self._infer_fused(x, d):

@@ -385,6 +385,13 @@ class Renderer(nn.Module):
         self.iter_density += 1
         self.update_mean_count()
 
+    def initialize_states(self, n=50, fp16=True):
+        """nerf/network_curvedfield.py:543-546: the occupancy grid re-estimated from scratch after the field changed under it (an imported map, a
+        switch, a new threshold) -- n full sweeps that overwrite every cell, under fp16 autocast unless fp16=False."""
+        with torch.autocast("cuda", dtype=torch.float16, enabled=bool(fp16)):
+            for _ in range(int(n)):
+                self.update_extra_state_device(decay=1.0, force_full_update=True, force_full_grid=True)
+
     def commit_counter(self, counter):
         """Ring bookkeeping for a step that ran with a caller-owned counter (graph replay)."""
         self.step_counter[self.local_step % 16].copy_(counter)

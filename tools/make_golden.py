@@ -499,6 +499,9 @@ def reference_python_goldens():
 
 def main():
     os.makedirs(OUT, exist_ok=True)
+    if "--import-field-only" in sys.argv:
+        import_field_goldens()
+        return
     if "--sh-light-only" in sys.argv:
         sh_light_goldens()
         sh_field_goldens()
@@ -1129,6 +1132,84 @@ def sh_field_goldens():
     np.savez_compressed(os.path.join(OUT, "ref_python_curvedfield_sh.npz"), **out)
     print("ref_python_curvedfield_sh.npz: eval colour", float(out["eval_color_full"].min()), float(out["eval_color_full"].max()), "inside", float(out["eval_h_mask"].mean()),
           "train rows shaded", float(out["train_h_mask"].mean()), "normal_grad not a number on", int(np.isnan(out["train_normal_grad"]).any(-1).sum()), "rows")
+
+
+def import_field_goldens():
+    """ref_python_import_field.npz: MeshFeatureField.import_field (tools/map.py:912-927) and the `imported_type == 'field'` branch of its forward
+    (:646-668, 719-720) executed, with network_curvedfield.NeRFNetwork.forward / density behind it (static light model, the sigma and colour nets
+    of ref_python_curvedfield.npz), on the CPU: a seeded 24 x 20 x 16 feature map, grid_gap 1/32, h_threshold 0.0625, 512 points uniform in
+    [-1.1, 1.1]^2 x [-0.22, 0.22], seeded directions.  Mode A (`rescale` True: the state after the first import) and mode B (after a second
+    import), each with (uv_utilize_rate, sdf_offset) = (1, 0) and (0.8, 0.01).  The embedding is kept for A (1, 0) and B (0.8, 0.01); mask,
+    sigma and colour for all four.  Inputs and outputs only: the weights are the other fixture's.  Reads one fixture; writes this one file."""
+    import time
+
+    import torch
+
+    started = time.time()
+
+    _install_map_imports()
+    for name, cls in (("sg_light_model", "SG_EnvmapMaterialNet"), ("sh_light_model", "SH_EnvmapMaterialNet"), ("envmap_light_model", "Envmap_EnvmapMaterialNet")):
+        if "nerf." + name not in sys.modules:
+            _stub("nerf." + name, **{cls: None})
+    import nerf.network_curvedfield as ref_cf
+    import tools.map as ref_map
+    from tools.encoding import get_encoder
+
+    c = np.load(os.path.join(OUT, "ref_python_curvedfield.npz"))
+    H, W, grid_gap, h_threshold = 24, 20, 1.0 / 32, 0.0625
+    rng = np.random.default_rng(151)
+    features = rng.uniform(-0.5, 0.5, (H, W, 16)).astype(np.float32)
+    pts = rng.uniform(-1.0, 1.0, (512, 3)).astype(np.float32) * np.array([1.1, 1.1, 0.22], np.float32)
+    dirs = rng.normal(size=(512, 3))
+    dirs = (dirs / np.linalg.norm(dirs, axis=-1, keepdims=True)).astype(np.float32)
+
+    mff = object.__new__(ref_map.MeshFeatureField)
+    torch.nn.Module.__init__(mff)
+    mff.device, mff.h_threshold, mff.K, mff.bound, mff.hash, mff.prob_model, mff.pred_normal, mff.clustering = "cpu", h_threshold, 8, 1, True, False, False, True
+    mff.imported, mff.imported_type, mff.normal_net, mff.rescale = False, None, None, False  # (the constructor's values, :604-618)
+    mff.sdf_scale_factor, mff.sdf_offset, mff.uv_utilize_rate, mff.K_for_uv = 1.0, 0.0, 1.0, 5
+    mff.encoder_f_out_dim = 16
+    mff.encoder_z, mff.encoder_z_outdim = get_encoder("frequency", input_dim=1, multires=12)
+    net = object.__new__(ref_cf.NeRFNetwork)
+    torch.nn.Module.__init__(net)
+    net.visual_mode, net.render_light_model, net.use_grad_normal, net.fc_weight, net.dir_degree = "RGB", False, False, 1.0, 4
+    net.optimize_gamma, net.meshfea_field = False, mff
+    tcnn = sys.modules["tinycudann"]
+    torch.manual_seed(42)
+    net.sigma_net = tcnn.Network(n_input_dims=mff.encoder_z_outdim + mff.encoder_f_out_dim, n_output_dims=16,
+                                 network_config={"otype": "FullyFusedMLP", "activation": "ReLU", "output_activation": "None", "n_neurons": 32, "n_hidden_layers": 1})
+    net.encoder_dir = tcnn.Encoding(n_input_dims=3, encoding_config={"otype": "SphericalHarmonics", "degree": 4})
+    net.color_net = tcnn.Network(n_input_dims=net.encoder_dir.n_output_dims + 15, n_output_dims=3,
+                                 network_config={"otype": "FullyFusedMLP", "activation": "ReLU", "output_activation": "None", "n_neurons": 64, "n_hidden_layers": 2})
+    assert np.array_equal(net.sigma_net.net.weights.detach().numpy(), c["w_sigma"]) and np.array_equal(net.color_net.net.weights.detach().numpy(), c["w_color"])
+    net.eval()
+
+    def do_import():  # (the maps only a normal net reads: placeholders of the right rank)
+        mff.import_field(features, bounds=[0.5 * grid_gap * H, 0.5 * grid_gap * W], sample_tbn=np.eye(3, dtype=np.float32)[None], sample_tbn_ids=np.zeros((H, W), np.float32),
+                         local_tbn=np.zeros((H, W, 9), np.float32), phi_embed=np.zeros((H, W, 8), np.float32))
+
+    x, d = torch.from_numpy(pts), torch.from_numpy(dirs)
+    out = dict(features=features, grid_gap=grid_gap, h_threshold=h_threshold, xyz=pts, dirs=dirs, weights_of="ref_python_curvedfield.npz")
+    for mode in ("A", "B"):
+        do_import()
+        assert mff.rescale == (mode == "A") and tuple(mff.features_imported.shape) == (1, 16, W, H)
+        for k, (rate, off) in enumerate(((1.0, 0.0), (0.8, 0.01))):
+            mff.uv_utilize_rate, mff.sdf_offset = rate, off
+            with torch.no_grad(), emulated_autocast():
+                embed, nc, _, hm = mff(x)
+                sigma, color, _ = net(x, d)
+                dens = net.density(x)
+            assert torch.equal(dens["sigma"], sigma) and torch.equal(color.half().float(), color.float())
+            key = f"{mode}{k}"
+            out.update({key + "_rate": rate, key + "_offset": off, key + "_h_mask": hm.numpy(), key + "_sigma": sigma.float().numpy(),
+                        key + "_color": color.half().numpy()})
+            if key in ("A0", "B1"):
+                out.update({key + "_embed": embed.float().numpy()})
+                assert torch.equal(nc, torch.tensor([0.0, 0.0, 1.0]).expand_as(nc) / (1 + 1e-5))
+            print("ref_python_import_field.npz:", key, "inside the mask", float(hm.float().mean()), "sigma max", float(sigma.max()))
+    np.savez_compressed(os.path.join(OUT, "ref_python_import_field.npz"), **out)
+    new = [os.path.join(r, n) for r, _, names in os.walk(REF) for n in names if os.lstat(os.path.join(r, n)).st_mtime >= started]
+    assert not new, "files appeared under the reference tree:\n" + "\n".join(new[:20])
 
 
 if __name__ == "__main__":
