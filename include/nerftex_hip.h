@@ -850,6 +850,80 @@ size_t nerftex_curved_import_infer_scratch_bytes(uint32_t B);
 int nerftex_curved_import_infer(const nerftex_curved_import_infer_desc* d, void* stream);
 
 /* -------------------------------------------------------------------------
+ * Extension: the imported map on a NEW UV-MAPPED MESH -- the `imported_type == 'shape'` branch of MeshFeatureField.forward (tools/map.py:693-700)
+ * over MeshProjector.uvh / barycentric_mapping (:503-543) and knn(use_dir_vec=False, weighting='DualD', nn_consis_check=True) (:454-501).  One
+ * launch behind the neighbour search (nerftex_knn_query over the new mesh's vertices).  Per sample x, all fp32, every operation rounded on its
+ * own (no fused multiply-add but the tracer's own o + t d):
+ *   dir_k  = (x - v_k) / (|x - v_k| + 1e-5);  dis_k = dir_k . dir_0 > 0 ? knn_dist_k : 1e5;  dk = max dis, d1 = min dis
+ *   w_k    = (dk - dis_k) / (dk - d1 + 1e-5) * (dk + d1) / (dk + dis_k),  w_k /= sum w  (no epsilon)
+ *   normal = n / (|n| + 1e-5),  n = sum_k w_k n_k / (|n_k| + 1e-5)          knn_idx: -1 is the last vertex, anything else is clamped
+ *   d1, d2 = the closest hits along +normal and -normal (10 on a miss); inner = d1 < d2; the nearer hit's face (-1 when both miss) and point
+ *   sdf    = (inner ? -d1 : d2) / sdf_scale - sdf_offset                     (a true division; the caller clamps sdf_scale to >= 1e-5)
+ *   mask   = |sdf| < min(9.5, h_threshold) and face != -1
+ *   b      = (|p1 x p2|, |p2 x p0|, |p0 x p1|) / (their sum + 1e-5),  p_k = corner_k - p_sur        (face -1 reads face 0)
+ *   (u, v) = (sum_k b_k face_uv[face][k]) * uv_rate
+ *   features = nerftex_planar_lookup's bilinear read of the map at (u, v) (no box test in the mask; a corner outside the map adds nothing)
+ *   xin [N,48] fp16 = [half(features) | half(FreqEncoder(sdf)) | 1 x 7]
+ * A row whose normal is not finite (every kept distance ties, K == 1, x on its nearest vertex: the reference's 0 / 0) reads no face, UV or
+ * texel: mask = 0, normal = 0, p_uv = 0, sdf = 0, face = -1, features 0, ladder 0 | ones.
+ * nerftex_shape_lookup is the plain form: any N, every row.  face_uv [n_faces,6]: the three corners' (u, v) per face.  NERFTEX_ERR_INVALID
+ * before anything is launched, in this order: a NULL pointer; K outside 1..16 or n_verts outside 1..2^31-1; n_faces other than the raytracer's
+ * triangle count; map_h or map_w outside 1..16384; n_freqs other than 12; a map or xin that is not 16-byte aligned; sdf_scale, uv_rate or
+ * h_threshold not positive and finite; sdf_offset not finite.  (N == 0 returns NERFTEX_OK behind these; N above 2^31 - 1 -- two lanes per
+ * point -- is refused last.)
+ *
+ * nerftex_curved_shape_infer: the whole no-grad forward as ONE call under the rows contract of nerftex_curved_field_infer --
+ *   neighbour search (K) -> shape lookup -> sigma net -> trunc_exp / reflected view direction / SH -> colour net -> sigmoid + mask,
+ * six launches (the last four are nerftex_curved_field_infer's own), nothing allocated, capturable.  The mid kernel normalises the coarse
+ * normal (eval bit 1).
+ *   rows >= live                      no work; sigma / rgbs keep what they held.
+ *   live rows the march marked unused no search, no traversal, no texel read; sigma = 0, rgbs = 0.
+ *   every other live row              bit for bit what nerftex_knn_query, nerftex_shape_lookup, nerftex_ffmlp_inference,
+ *                                     nerftex_curved_mid_forward, nerftex_ffmlp_inference and nerftex_curved_out_forward give one after
+ *                                     the other, widened to fp32 (a row with a non-finite normal: sigma = 0, rgbs = 0 through its mask).
+ * NERFTEX_ERR_INVALID before anything is launched, in this order: a NULL descriptor; B % 128 != 0; n_verts outside 1..2^31-1; K outside 1..16;
+ * n_features other than 16 or other network shapes than sigma net 48 / 32 / 2 / 16, colour net 32 / 64 / 3 / 3; a NULL raytracer or n_faces
+ * other than its triangle count; the map extents, n_freqs, map alignment, scales and offset as above; (B == 0 returns NERFTEX_OK here;) a NULL
+ * pointer, a scratch that is not 256-byte aligned or smaller than nerftex_curved_shape_infer_scratch_bytes(B); a weight vector that is not
+ * 16-byte aligned.
+ * ------------------------------------------------------------------------- */
+int nerftex_shape_lookup(const nerftex_raytracer* rt, const float* xyz, const int32_t* knn_idx, const float* knn_dist, uint32_t N, uint32_t K,
+                         const float* mesh_vertices, const float* vertex_normals, uint32_t n_verts, const float* face_uv, uint32_t n_faces,
+                         const float* map, uint32_t map_h, uint32_t map_w, float sdf_scale, float sdf_offset, float uv_rate, float h_threshold,
+                         uint32_t n_freqs, float* p_uv, float* sdf, uint8_t* mask, float* normal, int64_t* face_idx, void* xin, void* stream);
+typedef struct nerftex_curved_shape_infer_desc {
+    const nerftex_knn* knn;            /* the NEW mesh's neighbour grid                                                           */
+    const nerftex_raytracer* tracer;   /* the NEW mesh's BVH                                                                      */
+    const float* xyz;                  /* [B,3] sample positions                                                                  */
+    const float* dirs;                 /* [B,3] view directions; dirs[row][0] > 1e29 marks an unused slot                         */
+    uint32_t B;
+    uint32_t n_verts;
+    const float* mesh_vertices;        /* [n_verts,3]                                                                             */
+    const float* vertex_normals;       /* [n_verts,3]                                                                             */
+    const float* face_uv;              /* [n_faces,6]                                                                             */
+    uint32_t n_faces;
+    uint32_t K;                        /* neighbours per point (K_for_uv)                                                         */
+    const float* map;                  /* [map_h, map_w, n_features] fp32, 16-byte aligned                                        */
+    uint32_t map_h, map_w, n_features;
+    float sdf_scale, sdf_offset, uv_rate, h_threshold;
+    uint32_t n_freqs;                  /* FreqEncoder(height) bands (multires)                                                    */
+    const void* sigma_weights;         /* fp16, 16-byte aligned                                                                   */
+    uint32_t sigma_in, sigma_hidden, sigma_layers, sigma_out;
+    const void* color_weights;         /* fp16, 16-byte aligned                                                                   */
+    uint32_t color_in, color_hidden, color_layers, color_out;
+    float fc_weight;
+    int eval;                          /* the eval bits of nerftex_curved_mid_forward                                             */
+    float* sigma;                      /* [B] fp32                                                                                */
+    float* rgbs;                       /* [B,3] fp32                                                                              */
+    const int32_t* units_dev;
+    uint32_t rows_per_unit;
+    void* scratch;                     /* caller-owned, 256-byte aligned, >= nerftex_curved_shape_infer_scratch_bytes(B) bytes    */
+    size_t scratch_bytes;
+} nerftex_curved_shape_infer_desc;
+size_t nerftex_curved_shape_infer_scratch_bytes(uint32_t B);
+int nerftex_curved_shape_infer(const nerftex_curved_shape_infer_desc* d, void* stream);
+
+/* -------------------------------------------------------------------------
  * Extension: the same ONE call for the curved field with the SH light model (CurvedField(light_model="SH")), under the same rows contract:
  *   neighbour search -> projector (+ the hit face's frame) -> hash-grid gather of the texture table -> gather of the normal net's table ->
  *   sigma net 48 -> 32 -> 16 -> light mid: exp / BRDF input / the factorized fine-normal net (two 16-wide LipMLPs, toCoor, the frame's

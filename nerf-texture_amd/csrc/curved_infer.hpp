@@ -24,6 +24,26 @@ int curved_project_rows(const nerftex_raytracer* rt, const float* xyz, const flo
                         float* p_sur, uint8_t* h_mask, float* normal, void* xin, const int32_t* units_dev, uint32_t rows_per_unit, hipStream_t st,
                         const float* tbn = nullptr, float* tbn_out = nullptr);
 
+// The shape lookup (raytracer.hip: an imported map on a new UV-mapped mesh) -- what nerftex_shape_lookup and nerftex_curved_shape_infer hand it alike.
+struct ShapeLookup {
+    const float* face_uv;  // [F,6]
+    const float* map;      // [map_h, map_w, 16] fp32
+    uint32_t map_h, map_w;
+    float sdf_scale, sdf_offset, uv_rate, h_threshold;
+    uint32_t n_freqs;
+    void* xin;             // [N,48] half
+};
+uint32_t raytracer_triangles(const nerftex_raytracer* rt);
+// NULL, or why the two entries refuse these values -- in the order include/nerftex_hip.h documents: map extents, n_freqs, alignment of the map and
+// of xin, scales and threshold, offset
+const char* shape_lookup_refusal(const ShapeLookup& s);
+// nerftex_shape_lookup's rows for unmarked live rows: mask [N], the raw coarse normal [N,3], and the whole sigma-net input row xin [N,48] =
+// [half(features) | half(ladder) | ones].  A marked live row, or one whose normal is not finite: mask = 0, normal = 0, features 0, z = 0 | ones;
+// nothing is traced and no texel read.  The caller has validated (front_batch_ok's K and n_verts, n_faces, shape_lookup_refusal).
+int curved_shape_rows(const nerftex_raytracer* rt, const float* xyz, const float* dirs, const int32_t* knn_idx, const float* knn_dist, uint32_t N, uint32_t K,
+                      const float* mesh_vertices, const float* vertex_normals, uint32_t n_verts, const ShapeLookup& s, uint8_t* mask, float* normal,
+                      const int32_t* units_dev, uint32_t rows_per_unit, hipStream_t st);
+
 // nerftex_ffmlp_inference (fp16, ReLU, no output activation) of the curved field's networks -- (IN, H, NL) = (48, 32, 2), (32, 64, 3) or the SH
 // light head's BRDF net (16, 64, 3) -- over the 128-row workgroups that hold a live row; a workgroup wholly past the live rows exits before it
 // stages its weights.

@@ -7,6 +7,7 @@
 // that is ~25 launches and ~0.2 ms per training step of pure memory traffic.  Here it is two streaming kernels per direction,
 // with the arithmetic of the framework ops reproduced step by step (same roundings: fp32 exp of the half logit; SH in fp32
 // narrowed to half; sigmoid in fp32 narrowed to half and widened again; gradients narrowed to half where autograd would).
+#include "bilinear_read.hpp"
 #include "common.hpp"
 #include "curved_infer.hpp"
 #include "height_ladder.hpp"

@@ -57,46 +57,12 @@ __global__ __launch_bounds__(256) void planar_lookup_rows_kernel(const float* __
             sdf_out[b] = sdf;
         }
     }
-    // grid_sample(bilinear, align_corners=True, padding zeros); u runs along the map's first axis
-    const float iu = ((u + 1.0f) / 2.0f) * (float)(a.H - 1), iv = ((v + 1.0f) / 2.0f) * (float)(a.W - 1);
-    const float i0 = floorf(iu), j0 = floorf(iv);
-    const float wu1 = iu - i0, wu0 = (i0 + 1.0f) - iu, wv1 = iv - j0, wv0 = (j0 + 1.0f) - iv;
-    const float w[4] = {wu0 * wv0, wu1 * wv0, wu0 * wv1, wu1 * wv1};  // texels (i0,j0), (i0+1,j0), (i0,j0+1), (i0+1,j0+1), added in this order
-    // a corner outside [0,H) x [0,W) contributes nothing and is not read; the comparisons are on the floats (a NaN or a huge coordinate fails
-    // them all) and the index is converted only inside the range
-    const float hi_i = (float)(a.H - 1), hi_j = (float)(a.W - 1);
-    const bool in_i[2] = {i0 >= 0.0f && i0 <= hi_i, i0 + 1.0f >= 0.0f && i0 + 1.0f <= hi_i};
-    const bool in_j[2] = {j0 >= 0.0f && j0 <= hi_j, j0 + 1.0f >= 0.0f && j0 + 1.0f <= hi_j};
+    // grid_sample(bilinear, align_corners=True, padding zeros); u runs along the map's first axis (bilinear_read.hpp: the shape lookup's read, too)
     constexpr int Q = 4 / LANES;  // 16-byte quarters of a texel this lane reads: all four, or quarter q
-    float4_t t[4][Q];
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const int di = k & 1, dj = k >> 1;
-        if (in_i[di] && in_j[dj]) {
-            const size_t i = (size_t)(int)(i0 + (float)di), j = (size_t)(int)(j0 + (float)dj);
-            const float4_t* src = reinterpret_cast<const float4_t*>(a.map + (i * (size_t)a.W + j) * 16);
-#pragma unroll
-            for (int qq = 0; qq < Q; qq++) t[k][qq] = src[LANES == 1 ? (uint32_t)qq : q];
-        } else {
-#pragma unroll
-            for (int qq = 0; qq < Q; qq++) t[k][qq] = float4_t{0.0f, 0.0f, 0.0f, 0.0f};
-        }
-    }
-    // four products and three sums; an absent corner's texel is 0 and its weight finite whenever another corner is present (iu, iv then lie within one
-    // texel of the map), so its product adds nothing; with no corner present the weights may be anything and the answer is 0
-    const bool any = (in_i[0] || in_i[1]) && (in_j[0] || in_j[1]);
     half4_t o[Q];
-#pragma unroll
-    for (int c = 0; c < 4 * Q; c++) {
-        const float acc = ((t[0][c / 4][c % 4] * w[0] + t[1][c / 4][c % 4] * w[1]) + t[2][c / 4][c % 4] * w[2]) + t[3][c / 4][c % 4] * w[3];
-        o[c / 4][c % 4] = narrow(any ? acc : 0.0f);
-    }
+    bilinear_read<LANES>(a.map, a.H, a.W, u, v, q, o);
     if constexpr (LANES == 1) {
-        half8_t o8[2];
-#pragma unroll
-        for (int c = 0; c < 16; c++) o8[c / 8][c % 8] = o[c / 4][c % 4];
-        reinterpret_cast<half8_t*>(row)[0] = o8[0];
-        reinterpret_cast<half8_t*>(row)[1] = o8[1];
+        store_features(o, row);
     } else {
         reinterpret_cast<half4_t*>(row)[q] = o[0];
     }
@@ -208,5 +174,69 @@ extern "C" int nerftex_curved_import_infer(const nerftex_curved_import_infer_des
     if (rc != NERFTEX_OK) return rc;
     if ((rc = ffmlp_inference_rows(sc.xin, d->sigma_weights, d->B, 48, 32, 2, sc.h, d->units_dev, d->rows_per_unit, st)) != NERFTEX_OK) return rc;
     static const char* const labels[2] = {"curved_import_infer(mid)", "curved_import_infer(out)"};
+    return curved_back_half(d, sc.h, sc.normal, sc.mask, sc.back, labels, stream);
+}
+
+
+// ---- the same map on a new UV-mapped mesh (nerftex_curved_shape_infer): neighbour search -> shape lookup (raytracer.hip) -> the shared back half --------
+namespace nerftex {
+namespace {
+
+// the scratch of one nerftex_curved_shape_infer call
+struct ShapeScratch {
+    ScratchCarver carve;
+    int32_t* idx;
+    float* dist;
+    uint8_t* mask;
+    float* normal;
+    half_t *xin, *h;
+    CurvedBack back;
+    ShapeScratch(void* scratch, size_t B)
+        : carve{reinterpret_cast<uintptr_t>(scratch), B}, idx(carve.take<int32_t>(16)), dist(carve.take<float>(16)),  // (sized for the largest K)
+          mask(carve.take<uint8_t>(1)), normal(carve.take<float>(3)), xin(carve.take<half_t>(48)), h(carve.take<half_t>(16)), back(carve) {}
+};
+
+}  // namespace
+}  // namespace nerftex
+
+extern "C" size_t nerftex_curved_shape_infer_scratch_bytes(uint32_t B) { return ShapeScratch(nullptr, B).carve.at; }
+
+extern "C" int nerftex_curved_shape_infer(const nerftex_curved_shape_infer_desc* d, void* stream) {
+    clear_error();
+    if (!front_batch_ok(d, "curved_shape_infer")) return NERFTEX_ERR_INVALID;  // NULL descriptor, B % 128, n_verts, K
+    if (d->n_features != 16 || d->sigma_in != 48 || d->sigma_hidden != 32 || d->sigma_layers != 2 || d->sigma_out != 16 || !back_shapes_ok(d)) {
+        set_error("curved_shape_infer: the kernels serve the default curved field only (a map of 16 features, sigma net 48 -> 32 x 2 -> 16, "
+                  "colour net 32 -> 64 x 3 -> 3)");
+        return NERFTEX_ERR_INVALID;
+    }
+    if (!d->tracer || d->n_faces != raytracer_triangles(d->tracer)) {
+        set_error("curved_shape_infer: a raytracer is required and face_uv must hold its %u faces, but got %u", raytracer_triangles(d->tracer), d->n_faces);
+        return NERFTEX_ERR_INVALID;
+    }
+    const ShapeScratch sc(d->scratch, d->B);
+    const ShapeLookup s{d->face_uv, d->map, d->map_h, d->map_w, d->sdf_scale, d->sdf_offset, d->uv_rate, d->h_threshold, d->n_freqs, sc.xin};
+    if (const char* why = shape_lookup_refusal(s)) {
+        set_error("curved_shape_infer: %s", why);
+        return NERFTEX_ERR_INVALID;
+    }
+    if (d->B == 0) return NERFTEX_OK;
+    if (!d->knn || !d->xyz || !d->dirs || !d->mesh_vertices || !d->vertex_normals || !d->face_uv || !d->map || !d->sigma_weights || !d->color_weights || !d->sigma ||
+        !d->rgbs || !d->scratch || (reinterpret_cast<uintptr_t>(d->scratch) & 255) || d->scratch_bytes < sc.carve.at) {
+        set_error("curved_shape_infer: handles, inputs, mesh arrays, face_uv, map, weights and outputs must not be NULL, and scratch must be 256-byte aligned and "
+                  "hold %zu bytes", sc.carve.at);
+        return NERFTEX_ERR_INVALID;
+    }
+    if ((reinterpret_cast<uintptr_t>(d->sigma_weights) & 15) || (reinterpret_cast<uintptr_t>(d->color_weights) & 15)) {
+        set_error("curved_shape_infer: the weight vectors must be 16-byte aligned");
+        return NERFTEX_ERR_INVALID;
+    }
+    hipStream_t st = as_stream(stream);
+    int rc = knn_query_rows(d->knn, d->xyz, d->dirs, d->B, d->K, sc.idx, sc.dist, d->units_dev, d->rows_per_unit, st);
+    if (rc != NERFTEX_OK) return rc;
+    if ((rc = curved_shape_rows(d->tracer, d->xyz, d->dirs, sc.idx, sc.dist, d->B, d->K, d->mesh_vertices, d->vertex_normals, d->n_verts, s, sc.mask, sc.normal,
+                                d->units_dev, d->rows_per_unit, st)) != NERFTEX_OK)
+        return rc;
+    if ((rc = ffmlp_inference_rows(sc.xin, d->sigma_weights, d->B, 48, 32, 2, sc.h, d->units_dev, d->rows_per_unit, st)) != NERFTEX_OK) return rc;
+    static const char* const labels[2] = {"curved_shape_infer(mid)", "curved_shape_infer(out)"};
     return curved_back_half(d, sc.h, sc.normal, sc.mask, sc.back, labels, stream);
 }

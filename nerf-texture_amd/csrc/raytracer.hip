@@ -12,6 +12,7 @@
 //     incoherent (origin = sample point, direction = +-local normal), so the kernel is latency-bound on the
 //     ~1 MiB of L2-resident nodes + triangles; one-wave workgroups spread small batches over the CUs.
 // Arithmetic follows oracle/src/orc_raytracer.c expression by expression (explicit fmaf, no other contraction).
+#include "bilinear_read.hpp"
 #include "common.hpp"
 #include "curved_infer.hpp"
 #include "height_ladder.hpp"
@@ -27,6 +28,7 @@ struct nerftex_raytracer {
     void* nodes = nullptr;      // device, Node[n_nodes]
     void* triangles = nullptr;  // device, Tri[n_triangles] (reordered; .id = original face)
     uint32_t n_nodes = 0, n_triangles = 0;
+    uint32_t face0 = 0;  // where original face 0 sits in the reordered array (the shape lookup reads it for a point both traces miss)
     int device = 0;
 };
 
@@ -384,6 +386,153 @@ __global__ __launch_bounds__(64) void curved_project_rows_kernel(uint32_t N, con
                                nullptr, h_mask, normal_out, nullptr, tbn_out, xin);
 }
 
+// ---------------------------------------------------------------- shape lookup: an imported map on a new UV-mapped mesh
+// The `imported_type == 'shape'` branch of MeshFeatureField.forward (tools/map.py:693-700) for one sample point per PAIR of lanes, in one kernel
+// behind the neighbour search: MeshProjector.uvh (:536-543) = knn(use_dir_vec=False, weighting='DualD', nn_consis_check=True) (:454-501) ->
+// barycentric_mapping (:503-528: the two traces, the scaled and offset height, the mask that also wants a hit, the hit's barycentric coordinates,
+// :85-93) -> per-vertex UVs interpolated, times uv_rate -> the bilinear read of the imported map (bilinear_read.hpp) and FreqEncoder(height).
+// Every operation rounds on its own, as a framework op does: plain products and sums, no fused multiply-add -- except the surface point, which
+// is the tracer's own o + t d (raytrace_kernel's fmaf).
+struct ShapeArgs {
+    const float* map;      // [H, W, 16] fp32, 16-byte aligned
+    uint32_t H, W;
+    const float* face_uv;  // [F, 6]: the three corners' (u, v) of every face
+    float sdf_scale, sdf_offset, uv_rate, h_limit;
+    uint32_t face0;        // nerftex_raytracer::face0
+};
+
+__device__ __forceinline__ float dot_plain(const V3& a, const V3& b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
+__device__ __forceinline__ float norm_plain(const V3& a) { return sqrtf(dot_plain(a, a)); }
+__device__ __forceinline__ V3 cross_plain(const V3& a, const V3& b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
+
+// ROWS: the rows contract of nerftex_curved_field_infer's kernels (no p_uv, sdf or face output); otherwise the plain form (every row).
+// Lane mapping: the projector's -- lanes 2 i and 2 i + 1 compute the point's normal alike (the same loads, served once), trace along +normal and
+// -normal and meet in an __shfl_xor; every exit in front of it is decided by the point, so a pair leaves or stays TOGETHER.  Behind it both lanes
+// hold d1, d2 and the tail is split: lane 0 does barycentrics, UV, the four texels and every per-point store, lane 1 the height ladder.
+template <bool ROWS>
+__global__ __launch_bounds__(64) void shape_lookup_kernel(const uint32_t N, const float* __restrict__ xyz, const float* __restrict__ dirs,
+                                                          const int32_t* __restrict__ knn_idx, const float* __restrict__ knn_dist, const uint32_t K,
+                                                          const float* __restrict__ verts, const float* __restrict__ vnormals, const int n_verts,
+                                                          const Node* __restrict__ nodes, const Tri* __restrict__ tris, const ShapeArgs a,
+                                                          float* __restrict__ p_uv, float* __restrict__ sdf_out, uint8_t* __restrict__ mask,
+                                                          float* __restrict__ normal_out, int64_t* __restrict__ face_idx, half_t* __restrict__ xin,
+                                                          const int32_t* __restrict__ units_dev, const uint32_t rows_per_unit) {
+    const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t i = tid >> 1, side = tid & 1u;
+    if (i >= (ROWS ? live_rows(N, units_dev, rows_per_unit) : N)) return;
+    half_t* row = xin + (size_t)i * 48;
+    // a marked slot, or a point whose normal is not finite: mask 0 and the constants that make the rest of the chain answer zeros
+    auto answer_nothing = [&]() {
+        mask[i] = 0;
+#pragma unroll
+        for (int c = 0; c < 3; c++) normal_out[3 * (size_t)i + c] = 0.0f;
+        const half8_t zero = {0, 0, 0, 0, 0, 0, 0, 0};
+        reinterpret_cast<half8_t*>(row)[0] = zero;
+        reinterpret_cast<half8_t*>(row)[1] = zero;
+        write_unused_ladder(row);
+        if constexpr (!ROWS) {
+            p_uv[2 * (size_t)i] = 0.0f; p_uv[2 * (size_t)i + 1] = 0.0f;
+            sdf_out[i] = 0.0f;
+            face_idx[i] = -1;
+        }
+    };
+    if (ROWS && slot_unused(dirs, i)) {  // no neighbour list to read, no tree to walk, no texel
+        if (!side) answer_nothing();
+        return;
+    }
+    const V3 x = load3(xyz + 3 * (size_t)i);
+    // ---- knn(use_dir_vec=False, weighting='DualD', nn_consis_check=True): a neighbour on the other side of the point than the nearest one
+    // (cos <= 0 between the two directions) is pushed out to 1e5; the index rules are curved_project_point's
+    auto vertex_of = [&](uint32_t k) {
+        int v = knn_idx[(size_t)i * K + k];
+        v = v < 0 ? v + n_verts : v;
+        return min(max(v, 0), n_verts - 1);
+    };
+    float dis[kMaxK];
+    V3 dir0{0, 0, 0};
+    float dk = -3.402823466e+38f, d1n = 3.402823466e+38f;
+#pragma unroll
+    for (uint32_t k = 0; k < (uint32_t)kMaxK; k++) {
+        dis[k] = 0.0f;
+        if (k < K) {
+            const V3 d = sub(x, load3(verts + 3 * (size_t)vertex_of(k)));
+            const float dl = norm_plain(d) + 1e-5f;
+            const V3 dir{d.x / dl, d.y / dl, d.z / dl};
+            if (k == 0) dir0 = dir;
+            dis[k] = dot_plain(dir, dir0) > 0.0f ? knn_dist[(size_t)i * K + k] : 1e5f;
+            dk = fmaxf(dk, dis[k]);
+            d1n = fminf(d1n, dis[k]);
+        }
+    }
+    float w[kMaxK];
+    float wsum = 0.0f;
+#pragma unroll
+    for (uint32_t k = 0; k < (uint32_t)kMaxK; k++) {
+        w[k] = 0.0f;
+        if (k < K) {
+            w[k] = (dk - dis[k]) / (dk - d1n + 1e-5f) * (dk + d1n) / (dk + dis[k]);
+            wsum = k == 0 ? w[k] : wsum + w[k];
+        }
+    }
+    V3 nrm{0, 0, 0};
+#pragma unroll
+    for (uint32_t k = 0; k < (uint32_t)kMaxK; k++) {
+        if (k < K) {
+            const V3 n = load3(vnormals + 3 * (size_t)vertex_of(k));
+            const float nl = norm_plain(n) + 1e-5f;
+            const float wk = w[k] / wsum;  // (no epsilon: 0 / 0 when every kept distance ties, K == 1, or the point sits on its nearest vertex)
+            const V3 t{(n.x / nl) * wk, (n.y / nl) * wk, (n.z / nl) * wk};
+            nrm = k == 0 ? t : V3{nrm.x + t.x, nrm.y + t.y, nrm.z + t.z};
+        }
+    }
+    {
+        const float l = norm_plain(nrm) + 1e-5f;
+        nrm = {nrm.x / l, nrm.y / l, nrm.z / l};
+    }
+    if (!(isfinite(nrm.x) && isfinite(nrm.y) && isfinite(nrm.z))) {  // (the reference carries the NaN into its traces, which miss: here a defined answer)
+        if (!side) answer_nothing();
+        return;
+    }
+    // ---- barycentric_mapping(): two closest hits, the nearer wins
+    const V3 neg{-nrm.x, -nrm.y, -nrm.z};
+    int b_mine;
+    const float d_mine = closest_hit(x, side ? neg : nrm, nodes, tris, b_mine);
+    const float d_other = __shfl_xor(d_mine, 1, kWave);
+    const int b_other = __shfl_xor(b_mine, 1, kWave);
+    const float d1 = side ? d_other : d_mine, d2 = side ? d_mine : d_other;
+    const bool inner = d1 < d2;
+    const float sdf = (inner ? -d1 : d2) / a.sdf_scale - a.sdf_offset;  // (a true division)
+    if (side) {  // lane 1: the ladder, columns 16..47
+        write_height_ladder(sdf, row);
+        return;
+    }
+    const int best = inner ? b_mine : b_other;
+    const Tri tr = tris[best >= 0 ? (uint32_t)best : a.face0];  // face -1 reads face 0, as the reference does; the mask covers it
+    const int64_t face = best >= 0 ? tr.id : (int64_t)-1;
+    const float2_t* fuv = reinterpret_cast<const float2_t*>(a.face_uv + 6 * (size_t)(best >= 0 ? tr.id : (int64_t)0));
+    const float2_t uv0 = fuv[0], uv1 = fuv[1], uv2 = fuv[2];
+    const float d = inner ? d1 : d2;
+    const V3 dir = inner ? nrm : neg;
+    const V3 p_sur{fmaf(d, dir.x, x.x), fmaf(d, dir.y, x.y), fmaf(d, dir.z, x.z)};
+    // points_to_barycentric (tools/map.py:85-93)
+    const V3 p0 = sub(load3(tr.a), p_sur), p1 = sub(load3(tr.b), p_sur), p2 = sub(load3(tr.c), p_sur);
+    const float s0 = norm_plain(cross_plain(p1, p2)), s1 = norm_plain(cross_plain(p2, p0)), s2 = norm_plain(cross_plain(p0, p1));
+    const float den = ((s0 + s1) + s2) + 1e-5f;
+    const float b0 = s0 / den, b1 = s1 / den, b2 = s2 / den;
+    const float u = ((uv0.x * b0 + uv1.x * b1) + uv2.x * b2) * a.uv_rate;
+    const float v = ((uv0.y * b0 + uv1.y * b1) + uv2.y * b2) * a.uv_rate;
+    half4_t o[4];
+    bilinear_read<1>(a.map, a.H, a.W, u, v, 0u, o);
+    store_features(o, row);
+    mask[i] = (fabsf(sdf) < a.h_limit && best >= 0) ? 1 : 0;
+    normal_out[3 * (size_t)i] = nrm.x; normal_out[3 * (size_t)i + 1] = nrm.y; normal_out[3 * (size_t)i + 2] = nrm.z;
+    if constexpr (!ROWS) {
+        p_uv[2 * (size_t)i] = u; p_uv[2 * (size_t)i + 1] = v;
+        sdf_out[i] = sdf;
+        face_idx[i] = face;
+    }
+}
+
 // depth of the BVH-4 (root = 1)
 int bvh_depth(const std::vector<Node>& nodes) {
     int deepest = 1;
@@ -435,6 +584,8 @@ extern "C" int nerftex_create_raytracer(const float* host_vertices, uint32_t n_v
     nerftex_raytracer* rt = new nerftex_raytracer();
     rt->n_nodes = (uint32_t)nodes.size();
     rt->n_triangles = n_triangles;
+    for (uint32_t k = 0; k < n_triangles; k++)
+        if (tris[k].id == 0) rt->face0 = k;
     if (hipGetDevice(&rt->device) != hipSuccess || hipMalloc(&rt->nodes, sizeof(Node) * nodes.size()) != hipSuccess ||
         hipMalloc(&rt->triangles, sizeof(Tri) * tris.size()) != hipSuccess ||
         hipMemcpy(rt->nodes, nodes.data(), sizeof(Node) * nodes.size(), hipMemcpyHostToDevice) != hipSuccess ||
@@ -511,4 +662,74 @@ extern "C" int nerftex_curved_project(const nerftex_raytracer* rt, const float* 
                            normal, face_idx, tbn_out, z_embed);
     }
     return check_launch("curved_project");
+}
+
+// ---- the shape lookup's launches (nerftex_shape_lookup below; nerftex_curved_shape_infer, planar.inc, through curved_shape_rows)
+namespace nerftex {
+namespace {
+
+template <bool ROWS>
+void launch_shape_lookup(hipStream_t st, const nerftex_raytracer* rt, const float* xyz, const float* dirs, const int32_t* knn_idx, const float* knn_dist, uint32_t N,
+                         uint32_t K, const float* verts, const float* vnormals, uint32_t n_verts, const ShapeLookup& s, float* p_uv, float* sdf, uint8_t* mask,
+                         float* normal, int64_t* face_idx, half_t* xin, const int32_t* units_dev, uint32_t rows_per_unit) {
+    const ShapeArgs a{s.map, s.map_h, s.map_w, s.face_uv, s.sdf_scale, s.sdf_offset, s.uv_rate, fminf(9.5f, s.h_threshold), rt->face0};  // depth_threshold of tools/map.py:407
+    KernelTimer kt("shape_lookup_kernel", st);
+    hipLaunchKernelGGL((shape_lookup_kernel<ROWS>), dim3(div_up(2 * N, 64u)), dim3(64), 0, st, N, xyz, dirs, knn_idx, knn_dist, K, verts, vnormals, (int)n_verts,
+                       static_cast<const Node*>(rt->nodes), static_cast<const Tri*>(rt->triangles), a, p_uv, sdf, mask, normal, face_idx, xin, units_dev, rows_per_unit);
+}
+
+}  // namespace
+}  // namespace nerftex
+
+uint32_t nerftex::raytracer_triangles(const nerftex_raytracer* rt) { return rt ? rt->n_triangles : 0u; }
+
+const char* nerftex::shape_lookup_refusal(const ShapeLookup& s) {
+    auto pos = [](float v) { return v > 0.0f && std::isfinite(v); };
+    if (s.map_h == 0 || s.map_h > 16384u || s.map_w == 0 || s.map_w > 16384u) return "the map needs between 1 and 16384 texels along each axis";
+    if (s.n_freqs != kInferFreqs) return "the kernel writes the curved field's 12 height bands";
+    if ((reinterpret_cast<uintptr_t>(s.map) & 15) || (reinterpret_cast<uintptr_t>(s.xin) & 15)) return "the map and xin must be 16-byte aligned";
+    if (!pos(s.sdf_scale) || !pos(s.uv_rate) || !pos(s.h_threshold)) return "sdf_scale, uv_rate and h_threshold must be positive and finite";
+    if (!std::isfinite(s.sdf_offset)) return "sdf_offset must be finite";
+    return nullptr;
+}
+
+int nerftex::curved_shape_rows(const nerftex_raytracer* rt, const float* xyz, const float* dirs, const int32_t* knn_idx, const float* knn_dist, uint32_t N, uint32_t K,
+                               const float* mesh_vertices, const float* vertex_normals, uint32_t n_verts, const ShapeLookup& s, uint8_t* mask, float* normal,
+                               const int32_t* units_dev, uint32_t rows_per_unit, hipStream_t st) {
+    if (N == 0) return NERFTEX_OK;
+    launch_shape_lookup<true>(st, rt, xyz, dirs, knn_idx, knn_dist, N, K, mesh_vertices, vertex_normals, n_verts, s, nullptr, nullptr, mask, normal, nullptr,
+                              static_cast<half_t*>(s.xin), units_dev, rows_per_unit);
+    return check_launch("curved_shape_infer(lookup)");
+}
+
+extern "C" int nerftex_shape_lookup(const nerftex_raytracer* rt, const float* xyz, const int32_t* knn_idx, const float* knn_dist, uint32_t N, uint32_t K,
+                                    const float* mesh_vertices, const float* vertex_normals, uint32_t n_verts, const float* face_uv, uint32_t n_faces, const float* map,
+                                    uint32_t map_h, uint32_t map_w, float sdf_scale, float sdf_offset, float uv_rate, float h_threshold, uint32_t n_freqs, float* p_uv,
+                                    float* sdf, uint8_t* mask, float* normal, int64_t* face_idx, void* xin, void* stream) {
+    clear_error();
+    if (!rt || !xyz || !knn_idx || !knn_dist || !mesh_vertices || !vertex_normals || !face_uv || !map || !p_uv || !sdf || !mask || !normal || !face_idx || !xin) {
+        set_error("shape_lookup: the raytracer, inputs, mesh arrays, face_uv, map and outputs must not be NULL");
+        return NERFTEX_ERR_INVALID;
+    }
+    if (K == 0 || K > (uint32_t)kMaxK || n_verts == 0 || n_verts > 0x7fffffffu) {
+        set_error("shape_lookup: 1 <= K <= %d neighbours per point and between 1 and 2^31 - 1 vertices, but got K = %u, n_verts = %u", kMaxK, K, n_verts);
+        return NERFTEX_ERR_INVALID;
+    }
+    if (n_faces != rt->n_triangles) {
+        set_error("shape_lookup: face_uv holds %u faces, but the raytracer was built over %u", n_faces, rt->n_triangles);
+        return NERFTEX_ERR_INVALID;
+    }
+    const ShapeLookup s{face_uv, map, map_h, map_w, sdf_scale, sdf_offset, uv_rate, h_threshold, n_freqs, xin};
+    if (const char* why = shape_lookup_refusal(s)) {
+        set_error("shape_lookup: %s", why);
+        return NERFTEX_ERR_INVALID;
+    }
+    if (N == 0) return NERFTEX_OK;
+    if (N > 0x7fffffffu) {
+        set_error("shape_lookup: at most 2^31 - 1 points per call (two lanes each), but got %u", N);
+        return NERFTEX_ERR_INVALID;
+    }
+    launch_shape_lookup<false>(as_stream(stream), rt, xyz, nullptr, knn_idx, knn_dist, N, K, mesh_vertices, vertex_normals, n_verts, s, p_uv, sdf, mask, normal, face_idx,
+                               static_cast<half_t*>(xin), nullptr, 0u);
+    return check_launch("shape_lookup");
 }

@@ -13,7 +13,8 @@ xatlas, open3d, trimesh).
                      transplant of the same fully-fused kernel): tests/golden/ref_python_curvedfield.npz pins the chain against the
                      reference's modules executed with exactly that substitution.  light_model="SH" (main.py's model, :272-349):
                      no direction encoding and no colour MLP; the SH light head (light.SHLightNet) shades with the fine normal of the
-                     factorized normal net;
+                     factorized normal net.  import_field / import_shape: an imported planar feature map rendered on its own plane or
+                     on a new UV-mapped mesh (the 'field' and 'shape' branches of MeshFeatureField.forward, tools/map.py:646-700);
   CurvedFieldLookup  round 1's minimal chain (analytic normals -> traces -> hash lookup), kept for its test.
 """
 import numpy as np
@@ -95,6 +96,56 @@ def freq_encode(x, multires=12):
     for f in bands:
         out += [torch.sin(x * f), torch.cos(x * f)]
     return torch.cat(out, dim=-1)
+
+
+def shape_preprocess(vertices, faces, uvs, normalize=True):
+    """What NeRFNetwork.import_shape and MeshProjector's constructor make of a loaded mesh before anything touches a device:
+    -> (vertices [V,3] fp32, uvs [V,2] fp32 in [-1,1], face_uv [F,6] fp32 = uvs[faces], recommended_sdf_factor).
+    normalize (network_curvedfield.py:496-498, float64): centre by the vertex mean, divide by max|v| + 1e-5, then by 1.2.
+    uvs (tools/map.py:361, fp32): mapped to [-1,1] by their single global minimum and maximum.
+    recommended_sdf_factor (:373-386): the mean 3-D length (float64) over the mean UV length (fp32) of the unique edges."""
+    v = np.array(vertices, dtype=np.float64)
+    if normalize:
+        v -= np.mean(v, axis=0)
+        v /= (np.absolute(v).max() + 1e-5)
+        v /= 1.2
+    f = np.asarray(faces).astype(np.int64)
+    uv = torch.FloatTensor(np.asarray(uvs, dtype=np.float32))
+    uv = ((uv - uv.min()) / (uv.max() - uv.min()) * 2 - 1.).numpy()
+    edges = np.sort(f[:, [0, 1, 1, 2, 2, 0]].reshape(-1, 2), axis=1)
+    edges = np.unique(edges, axis=0)
+    e3 = v[edges]
+    mean_edge_length = np.linalg.norm(e3[:, 0] - e3[:, 1], axis=-1).mean()
+    e2 = uv[edges]
+    mean_edges_uv = np.linalg.norm(e2[:, 0] - e2[:, 1], axis=-1).mean()
+    return v.astype(np.float32), uv, np.ascontiguousarray(uv[f].reshape(-1, 6)), float(mean_edge_length / mean_edges_uv)
+
+
+def shape_knn_normal(xyz, idx, dis, mesh_vertices, vertex_normals):
+    """knn(use_dir_vec=False, weighting='DualD', nn_consis_check=True) of tools/map.py:454-501, op for op: dual-distance weights over the
+    neighbours on the nearest one's side of the point.  0 / 0 = NaN where every kept distance ties (as in the reference)."""
+    normals = vertex_normals[idx.long()]
+    dir_vec_ori = xyz.unsqueeze(-2) - mesh_vertices[idx.long()]
+    dir_vec = dir_vec_ori / (dir_vec_ori.norm(dim=-1, keepdim=True) + 1e-5)
+    dir_vec_cosine = (dir_vec * dir_vec[..., :1, :]).sum(-1)
+    dis = torch.where(dir_vec_cosine > 0, dis, 1e5 * torch.ones_like(dis))
+    dk = dis.max(dim=-1, keepdim=True)[0]
+    d1 = dis.min(dim=-1, keepdim=True)[0]
+    weights = (dk - dis) / (dk - d1 + 1e-5) * (dk + d1) / (dk + dis)
+    weights = weights / torch.sum(weights, dim=-1, keepdims=True)
+    normals = normals / (normals.norm(dim=-1, keepdim=True) + 1e-5)
+    normal = (normals * weights.unsqueeze(-1)).sum(-2)
+    return normal / (normal.norm(dim=-1, keepdim=True) + 1e-5)
+
+
+def points_to_barycentric(triangles, points):
+    """tools/map.py:85-93: area coordinates of `points` [N,3] in `triangles` [N,3,3] (sub-triangle areas over their sum + 1e-5)."""
+    p2v = triangles - points.unsqueeze(-2)
+    s0 = torch.cross(p2v[..., 1, :], p2v[..., 2, :], dim=-1).norm(dim=-1)
+    s1 = torch.cross(p2v[..., 2, :], p2v[..., 0, :], dim=-1).norm(dim=-1)
+    s2 = torch.cross(p2v[..., 0, :], p2v[..., 1, :], dim=-1).norm(dim=-1)
+    barycentric = torch.stack([s0, s1, s2], dim=-1)
+    return barycentric / (barycentric.sum(dim=-1, keepdim=True) + 1e-5)
 
 
 class MeshProjector(torch.nn.Module):
@@ -494,6 +545,9 @@ class CurvedField(torch.nn.Module):
         """The import state of MeshFeatureField as its constructor leaves it (tools/map.py:604-618): nothing imported."""
         self.imported, self.rescale, self.features_imported, self.bounds = False, False, None, None
         self.uv_utilize_rate, self.sdf_offset, self._import_version = 1.0, 0.0, 0
+        # ... and of the 'shape' branch (:615-618): no second mesh, sdf_scale_factor 1, K_for_uv 5
+        self.imported_type, self.shape_projector, self.shape_faces, self.shape_uvs, self.shape_face_uv = None, None, None, None, None
+        self.sdf_scale_factor, self.K_for_uv, self.recommended_sdf_factor = 1.0, 5, None
 
     def import_field(self, features, grid_gap, rescale=None):
         """NeRFNetwork.import_field -> MeshFeatureField.import_field for a planar map (`mesh is None`, network_curvedfield.py:457-475):
@@ -512,9 +566,118 @@ class CurvedField(torch.nn.Module):
         self.features_imported = f.to(device=dev, dtype=torch.float32).contiguous()
         H, W = int(f.shape[0]), int(f.shape[1])
         self.bounds = [0.5 * float(grid_gap) * H, 0.5 * float(grid_gap) * W]
-        self.imported = True
+        self.imported, self.imported_type = True, "field"
         self.rescale = (not self.rescale) if rescale is None else bool(rescale)
         self._import_version += 1
+
+    # ---- the imported map on a new UV-mapped mesh (NeRFNetwork.import_shape, network_curvedfield.py:494-501; the 'shape' branch, tools/map.py:693-700) ----
+
+    def import_shape(self, vertices, faces, uvs, vertex_normals=None, normalize=True):
+        """NeRFNetwork.import_shape -> MeshFeatureField.import_shape (tools/map.py:939-949) for a mesh given as arrays: vertices [V,3], faces
+        [F,3], per-vertex uvs [V,2] (what `mesh.visual.uv` holds; the xatlas parametrisation of a mesh without UVs is not built here),
+        vertex_normals [V,3] (default: area-weighted, the role of open3d's).  normalize: the reference's centring and scaling of the loaded mesh
+        (`shape_preprocess`).  A second MeshProjector over the mesh, the per-face UV table, sdf_scale_factor = recommended_sdf_factor /
+        bounds[0]; from here on embed() / density() / forward() / infer() project onto THIS mesh and read the imported map at the hit's
+        interpolated UV, until switch_shape_feature() or switch_import().  The reference prints a message and returns when no map was
+        imported; here that is a RuntimeError.  The caller re-estimates the occupancy grid (Renderer.initialize_states)."""
+        if self.features_imported is None or self.imported_type not in ("field", "shape"):
+            raise RuntimeError("CurvedField.import_shape: a feature map has to be imported first (import_field)")
+        if self.normal_net is not None or getattr(self, "light_model", None) is not None:
+            raise NotImplementedError("CurvedField.import_shape: a field with the fine-normal net or a light model would also need the imported phi_embed, "
+                                      "local_tbn and sample_tbn maps and the new mesh's frames (tools/map.py:702-707, :728-729); only the static light model "
+                                      "without a normal net imports here")
+        v, uv, face_uv, factor = shape_preprocess(vertices, faces, uvs, normalize=normalize)
+        dev = self.sigma_net.weights.device
+        self.shape_projector = MeshProjector(v, np.asarray(faces), h_threshold=self.h_threshold, K=self.K_for_uv, vertex_normals=vertex_normals).to(dev)
+        self.shape_faces = torch.as_tensor(np.asarray(faces).astype(np.int64)).to(dev)
+        self.shape_uvs = torch.from_numpy(uv).to(dev)
+        if len(face_uv) <= 8:  # (RayTracer pads so small a mesh with 8 far-away faces: the table follows the tracer's face count, the rows are never hit)
+            face_uv = np.concatenate([face_uv, np.zeros((8, 6), np.float32)], 0)
+        self.shape_face_uv = torch.from_numpy(face_uv).to(dev).contiguous()
+        self.recommended_sdf_factor = factor
+        self.sdf_scale_factor = factor / self.bounds[0]
+        self.imported, self.imported_type = True, "shape"
+        self._import_version += 1
+
+    def switch_shape_feature(self):
+        """network_curvedfield.py:508-517: between the planar map ('field') and the map on the imported mesh ('shape')."""
+        if self.imported_type == "field" and self.shape_projector is not None:
+            self.imported_type = "shape"
+        elif self.imported_type == "shape":
+            self.imported_type = "field"
+        else:
+            raise RuntimeError("CurvedField.switch_shape_feature: no shape has been imported")
+        self._import_version += 1
+
+    def set_k_for_uv(self, k_for_uv=5):
+        self.K_for_uv = int(k_for_uv)
+        self._import_version += 1
+
+    def set_sdf_factor(self, sdf_factor=1.0):
+        self.sdf_scale_factor = float(sdf_factor)
+        self._import_version += 1
+
+    def _shape_active(self):
+        return bool(getattr(self, "imported", False)) and getattr(self, "imported_type", None) == "shape"
+
+    def _shape_scalars(self):
+        """(K, sdf_scale, sdf_offset, uv_rate, h_threshold) of nerftex_shape_lookup for the state as it is.  The scale is the reference's
+        max(1e-5, sdf_scale_factor / uv_utilize_rate) in Python double, rounded to fp32: what its CPU division of a tensor by a Python float does."""
+        scale = float(np.float32(max(1e-5, float(self.sdf_scale_factor) / float(self.uv_utilize_rate))))
+        K = max(1, min(int(self.K_for_uv), int(self.shape_projector.mesh_vertices.shape[0])))
+        return K, scale, float(self.sdf_offset), float(self.uv_utilize_rate), float(self.h_threshold)
+
+    @torch.no_grad()
+    def _shape_lookup(self, x, neighbours=None):
+        """nerftex_knn_query + nerftex_shape_lookup: -> p_uv [N,2], sdf [N], h_mask [N] bool, normal [N,3] (raw), face [N], xin [N,48] half."""
+        from nerftex_hip import check, lib, ptr, stream
+
+        x = x.detach().float().contiguous()
+        N, dev, f, p = x.shape[0], x.device, self.features_imported, self.shape_projector
+        K, scale, off, rate, h = self._shape_scalars()
+        idx, dis = p.knn(x, K) if neighbours is None else neighbours
+        idx, dis = idx.int().contiguous(), dis.float().contiguous()
+        p_uv = torch.empty(N, 2, device=dev)
+        sdf = torch.empty(N, device=dev)
+        mask = torch.empty(N, dtype=torch.uint8, device=dev)
+        normal = torch.empty(N, 3, device=dev)
+        face = torch.empty(N, dtype=torch.int64, device=dev)
+        xin = torch.empty(N, 48, dtype=torch.float16, device=dev)
+        check(lib.nerftex_shape_lookup(p.tracer._handle, ptr(x), ptr(idx), ptr(dis), N, idx.shape[1], ptr(p.mesh_vertices), ptr(p.vertex_normals),
+                                       p.mesh_vertices.shape[0], ptr(self.shape_face_uv), self.shape_face_uv.shape[0], ptr(f), f.shape[0], f.shape[1], scale, off,
+                                       rate, h, int(self.multires), ptr(p_uv), ptr(sdf), ptr(mask), ptr(normal), ptr(face), ptr(xin), stream()))
+        return p_uv, sdf, mask.bool(), normal, face, xin
+
+    def _shape_embed_reference(self, x, neighbours=None, details=False):
+        """The 'shape' branch op by op, the reference's expressions (tools/map.py:695-700 over :454-543 and :85-93) over RayTracer.trace:
+        -> embed [N,41] fp32, normal_coarse, h_mask (details: + p_uv, sdf, the raw normal, face).  The divisor is a 0-d tensor, as in
+        `_import_embed_reference`.  neighbours: a neighbour list from elsewhere (default: the library's search over the imported mesh)."""
+        x = x.float()
+        p = self.shape_projector
+        K, scale, off, rate, h = self._shape_scalars()
+        idx, dis = p.knn(x, K) if neighbours is None else neighbours
+        normal = shape_knn_normal(x, idx, dis, p.mesh_vertices, p.vertex_normals)
+        p1, _, d1, f1 = p.tracer.trace(x, normal)
+        p2, _, d2, f2 = p.tracer.trace(x, -normal)
+        cond = d1 < d2
+        sdf = torch.where(cond, -d1, d2).unsqueeze(-1) / torch.tensor(scale, dtype=torch.float32, device=x.device) - off
+        p_sur = torch.where(cond.unsqueeze(-1), p1, p2)
+        face = torch.where(cond, f1, f2)
+        h_mask = (sdf.abs() < min(9.5, h)).squeeze(-1)
+        face_mask = face == -1
+        h_mask = torch.logical_and(h_mask, torch.logical_not(face_mask))
+        face0 = torch.where(face_mask, torch.zeros_like(face), face)
+        vertex_idx = self.shape_faces[face0]
+        bary = points_to_barycentric(p.mesh_vertices[vertex_idx], p_sur)
+        uv = (self.shape_uvs[vertex_idx] * bary.unsqueeze(-1)).sum(-2)
+        p_uv = uv * rate
+        image = self.features_imported.to(x.device).permute(2, 1, 0).unsqueeze(0)
+        x_embed = torch.nn.functional.grid_sample(image, p_uv[None, None], align_corners=True, padding_mode="zeros")[0, :, 0].permute(1, 0)
+        embed = torch.cat([x_embed, freq_encode(sdf, self.multires)], dim=-1)
+        normal_coarse = normal / (normal.norm(dim=-1, keepdim=True) + 1e-5)
+        if details:
+            return embed, normal_coarse, h_mask, p_uv, sdf[..., 0], normal, face
+        return embed, normal_coarse, h_mask
 
     def switch_import(self):
         """network_curvedfield.py:519-521: between the imported map and the field's own mesh and table (the map is kept)."""
@@ -551,6 +714,10 @@ class CurvedField(torch.nn.Module):
         if not getattr(self, "imported", False):
             return ()
         f = self.features_imported
+        if self._shape_active():
+            p = self.shape_projector
+            return (("import-shape", f.data_ptr(), tuple(f.shape), p._knn.value, p.tracer._handle.value, p.mesh_vertices.data_ptr(), p.vertex_normals.data_ptr(),
+                     self.shape_face_uv.data_ptr()) + self._shape_scalars() + (self._import_version,))
         return ("import", f.data_ptr(), tuple(f.shape)) + self._import_scalars() + (self._import_version,)
 
     @torch.no_grad()
@@ -617,6 +784,11 @@ class CurvedField(torch.nn.Module):
         if getattr(self, "imported", False):  # the import branch (:646-668): the map instead of the mesh and the table
             if requires_grad_xyz or with_fine_normal:
                 raise NotImplementedError("CurvedField.embed: an imported map is rendered without gradients to the sample position and without a fine normal")
+            if self._shape_active():  # the 'shape' branch (:693-700): the map at the UV of the hit on the imported mesh
+                if self._import_fused(x):
+                    _, _, h_mask, normal, _, xin = self._shape_lookup(x)
+                    return xin[:, :self.in_dim], normal / (normal.norm(dim=-1, keepdim=True) + 1e-5), h_mask
+                return self._shape_embed_reference(x)
             if self._import_fused(x):
                 _, _, h_mask, xin = self._import_lookup(x)
                 return xin[:, :self.in_dim], self._import_normal(x, True), h_mask
@@ -647,7 +819,7 @@ class CurvedField(torch.nn.Module):
 
     def density(self, x, requires_grad_xyz=False):
         if getattr(self, "imported", False) and not requires_grad_xyz and self._import_fused(x):
-            _, _, h_mask, xin = self._import_lookup(x)
+            h_mask, xin = (self._shape_lookup(x)[i] for i in (2, 5)) if self._shape_active() else self._import_lookup(x)[2:]
             h = self.sigma_net(xin)
             sigma = _TruncExp.apply(h[..., 0])
             return {"sigma": torch.where(h_mask, sigma, torch.zeros_like(sigma)), "geo_feat": h[..., 1:]}
@@ -719,9 +891,13 @@ class CurvedField(torch.nn.Module):
         if getattr(self, "light_model", None) == "SH":
             return self._forward_light(x, d, normal_supervision=bool(kwargs.get("normal_supervision", False)))
         if getattr(self, "imported", False) and self._import_fused(x):
-            _, _, h_mask, xin = self._import_lookup(x)
+            if self._shape_active():
+                _, _, h_mask, normal, _, xin = self._shape_lookup(x)
+            else:
+                _, _, h_mask, xin = self._import_lookup(x)
+                normal = self._import_normal(x, False)
             h = self.sigma_net(xin)
-            sigma_raw, cin = _CurvedMid.apply(h, self._import_normal(x, False), d, self.fc_weight, 2 | int(not self.training))  # (bit 1: tools/map.py:720 in the kernel)
+            sigma_raw, cin = _CurvedMid.apply(h, normal, d, self.fc_weight, 2 | int(not self.training))  # (bit 1: tools/map.py:720 in the kernel)
             sigma, color = _CurvedOut.apply(self.color_net(cin), sigma_raw, h_mask)
             return sigma, color, {}
         if self._glue_fused() and not getattr(self, "imported", False):
@@ -855,6 +1031,24 @@ class CurvedField(torch.nn.Module):
             scratch_bytes=scratch.numel())
         return desc, (f, ws_h, wc_h)
 
+    def _infer_shape_desc(self, x, d, live, sigma, rgbs, scratch):
+        """The nerftex_curved_shape_infer_desc of one call (and the tensors it points into, to be kept until the call is enqueued)."""
+        from nerftex_hip import CurvedShapeInferDesc, ptr
+
+        c, s, f, p = self.color_net, self.sigma_net, self.features_imported, self.shape_projector
+        ws_h, wc_h = self._infer_weights("_infer_cache", c)
+        K, scale, off, rate, h = self._shape_scalars()
+        units, rows_per_unit = (ptr(live[0]), int(live[1])) if live is not None else (None, 0)
+        desc = CurvedShapeInferDesc(
+            knn=p._knn.value, tracer=p.tracer._handle.value, xyz=ptr(x), dirs=ptr(d), B=x.shape[0], n_verts=p.mesh_vertices.shape[0],
+            mesh_vertices=ptr(p.mesh_vertices), vertex_normals=ptr(p.vertex_normals), face_uv=ptr(self.shape_face_uv), n_faces=self.shape_face_uv.shape[0], K=K,
+            map=ptr(f), map_h=f.shape[0], map_w=f.shape[1], n_features=f.shape[2], sdf_scale=scale, sdf_offset=off, uv_rate=rate, h_threshold=h,
+            n_freqs=int(self.multires), sigma_weights=ptr(ws_h), sigma_in=s.input_dim, sigma_hidden=s.hidden_dim, sigma_layers=s.num_layers,
+            sigma_out=s.padded_output_dim, color_weights=ptr(wc_h), color_in=c.input_dim, color_hidden=c.hidden_dim, color_layers=c.num_layers,
+            color_out=c.output_dim, fc_weight=float(self.fc_weight), eval=2 | int(not self.training), sigma=ptr(sigma), rgbs=ptr(rgbs), units_dev=units,
+            rows_per_unit=rows_per_unit, scratch=ptr(scratch), scratch_bytes=scratch.numel())
+        return desc, (f, ws_h, wc_h)
+
     def _infer_light_fused(self, x, d):
         """Whether nerftex_curved_light_infer serves this call: the SH light model with the switch `fused_light_infer` set (default: not), fp16
         autocast, the fused head (`light_net.fused`), no probabilistic table, the default shapes (the entry refuses every other one), no bounded
@@ -970,7 +1164,9 @@ class CurvedField(torch.nn.Module):
         nerftex_curved_light_infer, under the same rows contract: sigma and the mask are forward()'s bit for bit, the shading normal and the
         colour follow forward()'s arithmetic at its rounding points."""
         if getattr(self, "imported", False):  # an imported map: its own chain under the same rows contract, or forward() on all rows
-            if self._infer_import_fused(x, d):
+            if self._shape_active() and self._infer_import_fused(x, d):
+                return self._infer_call("nerftex_curved_shape_infer", self._infer_shape_desc, x, d, live)
+            if not self._shape_active() and self._infer_import_fused(x, d):
                 return self._infer_call("nerftex_curved_import_infer", self._infer_import_desc, x, d, live)
             sigma, rgbs, _ = self.forward(x, d)
             return sigma.float(), rgbs.float()

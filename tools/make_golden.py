@@ -502,6 +502,9 @@ def main():
     if "--import-field-only" in sys.argv:
         import_field_goldens()
         return
+    if "--import-shape-only" in sys.argv:
+        import_shape_goldens()
+        return
     if "--sh-light-only" in sys.argv:
         sh_light_goldens()
         sh_field_goldens()
@@ -1208,6 +1211,143 @@ def import_field_goldens():
                 assert torch.equal(nc, torch.tensor([0.0, 0.0, 1.0]).expand_as(nc) / (1 + 1e-5))
             print("ref_python_import_field.npz:", key, "inside the mask", float(hm.float().mean()), "sigma max", float(sigma.max()))
     np.savez_compressed(os.path.join(OUT, "ref_python_import_field.npz"), **out)
+    new = [os.path.join(r, n) for r, _, names in os.walk(REF) for n in names if os.lstat(os.path.join(r, n)).st_mtime >= started]
+    assert not new, "files appeared under the reference tree:\n" + "\n".join(new[:20])
+
+
+def import_shape_goldens():
+    """ref_python_import_shape.npz: MeshFeatureField.import_shape (tools/map.py:939-949) and the `imported_type == 'shape'` branch of its forward
+    (:693-700, 719-720) over MeshProjector.uvh / barycentric_mapping / knn (:454-543) executed on the CPU, with NeRFNetwork.forward / density
+    behind it (the nets of ref_python_curvedfield.npz, the 24 x 20 x 16 map of ref_python_import_field.npz's recipe).  The new mesh: a seeded
+    height field of 24 x 24 vertices over [-0.8, 0.8]^2 (no duplicated vertex: the reference produces no NaN row), per-vertex UVs an affine
+    image of (x, y) plus a seeded perturbation of a tenth of the mean UV edge.  The MeshProjector is made past its trimesh / xatlas / open3d
+    constructor: the three lines of it that matter (the UV mapping :361, the edge means :374-386) and NeRFNetwork.import_shape's
+    normalisation (:496-498, behind trimesh.load_mesh) are restated here on the arrays.  frnn -> exact brute force, tracer -> the oracle.
+    512 points within +-0.1 of the surface, a tenth pushed beyond the footprint (both traces miss).  Three states of (K_for_uv,
+    uv_utilize_rate, sdf_scale_factor, sdf_offset): (5, 1, recommended, 0), (5, 0.8, recommended, 0.01), (3, 1.3, 2.0, 0).  Inputs and outputs
+    only (uvh, mask, the coarse normal raw and normalised, the hit face, sigma, colour); the embedding is kept for the first and the last state."""
+    import time
+
+    import torch
+
+    started = time.time()
+    _install_map_imports()
+    for name, cls in (("sg_light_model", "SG_EnvmapMaterialNet"), ("sh_light_model", "SH_EnvmapMaterialNet"), ("envmap_light_model", "Envmap_EnvmapMaterialNet")):
+        if "nerf." + name not in sys.modules:
+            _stub("nerf." + name, **{cls: None})
+    import nerf.network_curvedfield as ref_cf
+    import tools.map as ref_map
+    from RayTracer import RayTracer as RefRayTracer
+    from tools.encoding import get_encoder
+
+    c = np.load(os.path.join(OUT, "ref_python_curvedfield.npz"))
+    H, W, grid_gap, h_threshold = 24, 20, 1.0 / 32, 0.0625
+    features = np.random.default_rng(151).uniform(-0.5, 0.5, (H, W, 16)).astype(np.float32)  # (ref_python_import_field.npz's map)
+    rng = np.random.default_rng(163)
+    n = 24
+    gx, gy = np.meshgrid(np.linspace(-0.8, 0.8, n), np.linspace(-0.8, 0.8, n), indexing="ij")
+    cell = 1.6 / (n - 1)
+    gx, gy = gx + rng.uniform(-0.2, 0.2, gx.shape) * cell, gy + rng.uniform(-0.2, 0.2, gy.shape) * cell
+    gz = 0.06 * np.sin(3.0 * gx) * np.cos(2.5 * gy) + rng.uniform(-0.01, 0.01, gx.shape)
+    vertices_raw = np.stack([gx, gy, gz], -1).reshape(-1, 3)
+    faces = []
+    for a in range(n - 1):
+        for b in range(n - 1):
+            p, q, r, s = a * n + b, a * n + b + 1, (a + 1) * n + b, (a + 1) * n + b + 1
+            faces += [(p, r, q), (q, r, s)]
+    faces = np.asarray(faces, np.int64)
+    uv_affine = np.stack([0.55 * vertices_raw[:, 0] + 0.1 * vertices_raw[:, 1] + 0.5, -0.08 * vertices_raw[:, 0] + 0.5 * vertices_raw[:, 1] + 0.5], -1)
+    uvs_raw = (uv_affine + rng.uniform(-1, 1, uv_affine.shape) * 0.1 * 0.55 * cell).astype(np.float32)
+
+    # NeRFNetwork.import_shape (:496-498) on the arrays
+    vertices = vertices_raw.copy()
+    vertices -= np.mean(vertices, axis=0)
+    vertices /= (np.absolute(vertices).max() + 1e-5)
+    vertices /= 1.2
+    v32 = vertices.astype(np.float32)
+    fn = np.cross(vertices[faces[:, 1]] - vertices[faces[:, 0]], vertices[faces[:, 2]] - vertices[faces[:, 0]])
+    vn = np.zeros_like(vertices)
+    for k in range(3):
+        np.add.at(vn, faces[:, k], fn)
+    vn = (vn / (np.linalg.norm(vn, axis=-1, keepdims=True) + 1e-12)).astype(np.float32)  # (the role of open3d's compute_vertex_normals)
+
+    mp = object.__new__(ref_map.MeshProjector)
+    uvs = torch.FloatTensor(uvs_raw)
+    mp.uvs = (uvs - uvs.min()) / (uvs.max() - uvs.min()) * 2 - 1.  # :361
+    edges_unique = np.unique(np.sort(faces[:, [0, 1, 1, 2, 2, 0]].reshape(-1, 2), axis=1), axis=0)  # (trimesh's edges_unique as a set)
+    edges = vertices[edges_unique]
+    mp.mean_edge_length = np.linalg.norm(edges[:, 0] - edges[:, 1], axis=-1).mean()  # :374-376
+    edges_uv = mp.uvs.numpy()[edges_unique]
+    mp.recommended_sdf_factor = mp.mean_edge_length / np.linalg.norm(edges_uv[:, 0] - edges_uv[:, 1], axis=-1).mean()  # :382-386
+    mp.mesh_vertices, mp.vertex_normals, mp.tbn = torch.FloatTensor(vertices), torch.from_numpy(vn), None
+    mp.grid, mp.radius, mp.max_K, mp.depth_threshold = None, 100.0, v32.shape[0], 9.5
+    mp.raytracer = RefRayTracer(v32, faces.astype(np.uint32))
+    mp.faces = torch.from_numpy(faces).long()
+    assert np.unique(v32, axis=0).shape[0] == v32.shape[0]
+
+    # points: on the surface +- 0.1 along z, a tenth beyond the footprint
+    pick, bary = rng.integers(0, len(faces), 512), rng.dirichlet([1, 1, 1], 512)
+    pts = (vertices[faces[pick]] * bary[..., None]).sum(1)
+    pts[:, 2] += rng.uniform(-0.1, 0.1, 512)
+    out_rows = rng.choice(512, 51, replace=False)
+    pts[out_rows, :2] = np.sign(pts[out_rows, :2] + 1e-9) * rng.uniform(1.0, 1.3, (51, 2))
+    pts = pts.astype(np.float32)
+    dirs = rng.normal(size=(512, 3))
+    dirs = (dirs / np.linalg.norm(dirs, axis=-1, keepdims=True)).astype(np.float32)
+
+    mff = object.__new__(ref_map.MeshFeatureField)
+    torch.nn.Module.__init__(mff)
+    mff.device, mff.h_threshold, mff.K, mff.bound, mff.hash, mff.prob_model, mff.pred_normal, mff.clustering = "cpu", h_threshold, 8, 1, True, False, False, True
+    mff.imported, mff.imported_type, mff.normal_net, mff.rescale = False, None, None, False
+    mff.sdf_scale_factor, mff.sdf_offset, mff.uv_utilize_rate, mff.K_for_uv = 1.0, 0.0, 1.0, 5
+    mff.encoder_f_out_dim = 16
+    mff.encoder_z, mff.encoder_z_outdim = get_encoder("frequency", input_dim=1, multires=12)
+    net = object.__new__(ref_cf.NeRFNetwork)
+    torch.nn.Module.__init__(net)
+    net.visual_mode, net.render_light_model, net.use_grad_normal, net.fc_weight, net.dir_degree = "RGB", False, False, 1.0, 4
+    net.optimize_gamma, net.meshfea_field = False, mff
+    tcnn = sys.modules["tinycudann"]
+    torch.manual_seed(42)
+    net.sigma_net = tcnn.Network(n_input_dims=mff.encoder_z_outdim + mff.encoder_f_out_dim, n_output_dims=16,
+                                 network_config={"otype": "FullyFusedMLP", "activation": "ReLU", "output_activation": "None", "n_neurons": 32, "n_hidden_layers": 1})
+    net.encoder_dir = tcnn.Encoding(n_input_dims=3, encoding_config={"otype": "SphericalHarmonics", "degree": 4})
+    net.color_net = tcnn.Network(n_input_dims=net.encoder_dir.n_output_dims + 15, n_output_dims=3,
+                                 network_config={"otype": "FullyFusedMLP", "activation": "ReLU", "output_activation": "None", "n_neurons": 64, "n_hidden_layers": 2})
+    assert np.array_equal(net.sigma_net.net.weights.detach().numpy(), c["w_sigma"]) and np.array_equal(net.color_net.net.weights.detach().numpy(), c["w_color"])
+    net.eval()
+    mff.import_field(features, bounds=[0.5 * grid_gap * H, 0.5 * grid_gap * W], sample_tbn=np.eye(3, dtype=np.float32)[None], sample_tbn_ids=np.zeros((H, W), np.float32),
+                     local_tbn=np.zeros((H, W, 9), np.float32), phi_embed=np.zeros((H, W, 8), np.float32))
+    # MeshFeatureField.import_shape (:939-949) behind its MeshProjector(...) call
+    assert mff.imported_type == "field"
+    mff.meshprojector_imported = mp
+    mff.sdf_scale_factor = mp.recommended_sdf_factor / mff.bounds[0]
+    mff.imported, mff.imported_type = True, "shape"
+
+    x, d = torch.from_numpy(pts), torch.from_numpy(dirs)
+    out = dict(features=features, grid_gap=grid_gap, h_threshold=h_threshold, xyz=pts, dirs=dirs, weights_of="ref_python_curvedfield.npz",
+               vertices_raw=vertices_raw, faces=faces.astype(np.int32), uvs_raw=uvs_raw, vertices=v32, uvs=mp.uvs.numpy(), vertex_normals=vn,
+               recommended_sdf_factor=float(mp.recommended_sdf_factor), sdf_scale_factor=float(mff.sdf_scale_factor))
+    recommended = float(mff.sdf_scale_factor)
+    for k, (K, rate, factor, off) in enumerate(((5, 1.0, recommended, 0.0), (5, 0.8, recommended, 0.01), (3, 1.3, 2.0, 0.0))):
+        mff.K_for_uv, mff.uv_utilize_rate, mff.sdf_scale_factor, mff.sdf_offset = K, rate, factor, off
+        with torch.no_grad(), emulated_autocast():
+            uvh, hm_u, normal, _ = mp.uvh(x, K=K, h_threshold=h_threshold, sdf_scale=factor / rate, sdf_offset=off)
+            embed, nc, _, hm = mff(x)
+            sigma, color, _ = net(x, d)
+            dens = net.density(x)
+            _, _, d1, f1 = mp.raytracer.trace(x, normal)
+            _, _, d2, f2 = mp.raytracer.trace(x, -normal)
+        face = torch.where(d1 < d2, f1, f2)  # (barycentric_mapping overwrites its -1 with 0: kept here as the tracer gives it)
+        assert torch.equal(hm, hm_u) and torch.equal(dens["sigma"], sigma) and not torch.isnan(normal).any()
+        key = f"S{k}"
+        out.update({key + "_normal_raw": normal.float().numpy(), key + "_face": face.numpy().astype(np.int32)})
+        out.update({key + "_K": K, key + "_rate": rate, key + "_sdf_factor": factor, key + "_offset": off, key + "_uvh": uvh.float().numpy(),
+                    key + "_h_mask": hm.numpy(), key + "_normal": nc.float().numpy(), key + "_sigma": sigma.float().numpy(), key + "_color": color.half().numpy()})
+        if k in (0, 2):
+            out[key + "_embed"] = embed.float().numpy()
+        print("ref_python_import_shape.npz:", key, "inside the mask", float(hm.float().mean()), "sigma max", float(sigma.max()),
+              "|uv| max", float(uvh[:, :2].abs().max() * rate))
+    np.savez_compressed(os.path.join(OUT, "ref_python_import_shape.npz"), **out)
     new = [os.path.join(r, n) for r, _, names in os.walk(REF) for n in names if os.lstat(os.path.join(r, n)).st_mtime >= started]
     assert not new, "files appeared under the reference tree:\n" + "\n".join(new[:20])
 
