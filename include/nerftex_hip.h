@@ -231,7 +231,19 @@ int nerftex_packbits(const float* grid, uint32_t N, float density_thresh, uint8_
  *            counter[1] += N  (same end state as the reference's atomics)
  *   perturb  0/1; the RNG is pcg32 seeded 42, advanced by the ray id.
  * Unlike the reference (two global atomics per ray, arbitrary order) the ray
- * records are emitted in ray order with prefix-sum offsets: deterministic.   */
+ * records are emitted in ray order with prefix-sum offsets: deterministic.
+ * H must be a power of two (the Morton index of any other grid runs past
+ * C*H^3 bits, in the reference as well).  Dispatch, the same bits on every
+ * path (tests/test_gpu_march_paths.py):
+ *   H <= 256  the data-parallel count pass + the expanding pass (knob
+ *             march_lean = 1: the count pass compiled for fewer registers;
+ *             march_serial = 1: the serial count pass, as for H > 256);
+ *   H > 256   the serial count pass (one ray per lane, logging the accepted
+ *             parameters) + the expanding pass: the data-parallel pass packs
+ *             voxel coordinates into 8 bits each;
+ *   replay    knob march = 1, or a log N * max_steps * 4 bytes above 1 GiB:
+ *             the serial count pass without a log, then a second serial walk
+ *             per ray that writes the samples.                               */
 int nerftex_march_rays_train(const float* rays_o, const float* rays_d, const uint8_t* grid,
                              float bound, float dt_gamma, uint32_t max_steps, uint32_t N,
                              uint32_t C, uint32_t H, uint32_t M, const float* nears,
@@ -246,15 +258,23 @@ int nerftex_march_rays_train(const float* rays_o, const float* rays_d, const uin
  * (counter[0] = total points, counter[1] = N); xyzs | dirs | deltas may arrive
  * uninitialised (they must be consecutive parts of ONE buffer of 8 M floats):
  * the rows no ray writes are zeroed by the second launch.  Same samples, ray
- * records and counter as the four-step sequence, bit for bit.                 */
+ * records and counter as the four-step sequence, bit for bit.
+ * H a power of two; the two-launch form is that of the data-parallel count
+ * pass (H <= 256, march_serial and march unset, and a log N * max_steps * 4
+ * bytes of at most 1 GiB).  On the serial and replay paths, chosen by a knob,
+ * by H > 256 or by a log above 1 GiB (see nerftex_march_rays_train), the call
+ * makes the steps it stands for
+ * -- a near / far launch and ONE fill of the 8 M floats and the counter --
+ * and then the plain march: four launches, the same bits.                    */
 int nerftex_march_rays_train_fresh(const float* rays_o, const float* rays_d, const uint8_t* grid,
                                    float bound, float dt_gamma, uint32_t max_steps, uint32_t N,
                                    uint32_t C, uint32_t H, uint32_t M, const float* aabb,
                                    float min_near, float* nears, float* fars, float* xyzs,
                                    float* dirs, float* deltas, int32_t* rays, int32_t* counter,
                                    uint32_t perturb, void* stream);
-/* raymarching.cu:671-678 (kernel :506-669): as above + rays_ts [M] = t after
- * each emitted step.                                                         */
+/* raymarching.cu:671-678 (kernel :506-669): as nerftex_march_rays_train
+ * (H a power of two, the same dispatch by H and by the knobs, the same bits
+ * on every path) + rays_ts [M] = t after each emitted step.                  */
 int nerftex_march_rays_train_differentiable(const float* rays_o, const float* rays_d,
                                             const uint8_t* grid, float bound, float dt_gamma,
                                             uint32_t max_steps, uint32_t N, uint32_t C, uint32_t H,
