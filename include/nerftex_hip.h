@@ -1027,6 +1027,80 @@ size_t nerftex_curved_light_infer_scratch_bytes(uint32_t B);
 int nerftex_curved_light_infer(const nerftex_curved_light_infer_desc* d, void* stream);
 
 /* -------------------------------------------------------------------------
+ * Extension: the IMPORTED planar map under the SH light model -- the `pred_normal` part of the 'field' branch of MeshFeatureField.forward
+ * (tools/map.py:670-675, :722-730).  Beside the [map_h, map_w, 16] feature map of nerftex_planar_lookup, three more device arrays:
+ *   phi_map        [map_h, map_w, 8] fp32: the normal net's own table features per texel, read BILINEARLY with the feature read's expression.
+ *   frame_map      [map_h, map_w, 12] fp32: per texel three 16-byte words -- the 9 floats of its frame (`local_tbn`, row-major 3 x 3), its patch
+ *                  id as a float (`sample_tbn_ids`), two zeros.  Read NEAREST: ix = ((u + 1) / 2) (map_h - 1) in fp32, rounded half to even
+ *                  (nearbyintf), iy likewise; a texel index outside the map gives zeros (frame 0, id 0); the id is the float truncated.
+ *   sample_tbn_inv [n_patches, 12] fp32: the 9 floats of each patch's INVERTED frame, three zeros; row `id` is read.  An id outside
+ *                  [0, n_patches) -- the caller rules it out -- reads nothing: zeros, and patch_id = -1 in the plain form.
+ * All four maps in the axis order MeshFeatureField.import_field receives: u runs along the first axis.
+ * nerftex_planar_light_lookup is the plain form (any B, every row): p_uv, sdf, mask, xin bit for bit nerftex_planar_lookup's; phi [B,8] fp32 (the
+ * rows form narrows exactly these values to half); patch_id [B] int32; local_tbn [B,9] and sample_tbn [B,9] fp32.  Refusals, in this order:
+ * n_freqs other than 12; map_h or map_w outside 1..16384; n_patches outside 1..2^24; (B == 0 returns NERFTEX_OK here;) a NULL pointer, a map,
+ * the patch frames, xin or phi not 16-byte aligned; mode, scales, h_threshold, sdf_offset as nerftex_planar_lookup.
+ *
+ * nerftex_curved_light_import_infer: the lit field's whole no-grad forward over these maps as ONE call under the rows contract of
+ * nerftex_curved_light_infer, five launches, nothing allocated, capturable --
+ *   lit lookup -> sigma net 48 -> 32 -> 16 -> light mid (the normal net fed from phi_map; the local normal rotated by the texel's frame and
+ *   then by the patch's inverted frame, two half products one after the other, each result rounded to half -- the frames are NOT multiplied
+ *   together; the two normalisations; in eval the fc_weight blend with the coarse normal (0, 0, 1)) -> BRDF net 16 -> 64 x 3 -> 16 -> light out.
+ *   rows >= live                      no work; sigma / rgbs / shading_normal keep what they held.
+ *   live rows the march marked unused no texel of any map is read; sigma = 0, rgbs = 0, shading_normal = 0.
+ *   every other live row              sigma and the mask bit for bit the field's forward(); rgbs, shading_normal as nerftex_curved_light_infer.
+ * NERFTEX_ERR_INVALID with a message, before anything is launched, in this order: a NULL descriptor; B % 128 != 0; n_features other than 16,
+ * n_phi other than 8, n_freqs other than 12 or other network shapes than the default SH field's; n_sh, n_color, gamma, flags, visual_mode, eval
+ * as nerftex_curved_light_infer; map_h or map_w outside 1..16384; n_patches outside 1..2^24; (B == 0 returns NERFTEX_OK here;) a NULL pointer,
+ * a scratch that is not 256-byte aligned or smaller than nerftex_curved_light_import_infer_scratch_bytes(B); a map, the patch frames or an MLP
+ * weight vector not 16-byte aligned, the normal net's block not 4-byte aligned; mode, scales, h_threshold, sdf_offset as nerftex_planar_lookup.
+ * ------------------------------------------------------------------------- */
+#define NERFTEX_FRAME_MAP_STRIDE 12 /* floats per texel of frame_map and per row of sample_tbn_inv */
+int nerftex_planar_light_lookup(const float* xyz, const float* map, const float* phi_map, const float* frame_map, const float* sample_tbn_inv,
+                                uint32_t map_h, uint32_t map_w, uint32_t n_patches, uint32_t mode, float plane_scale0, float plane_scale1,
+                                float height_scale0, float height_scale1, float sdf_offset, float h_threshold, uint32_t n_freqs, uint32_t B, float* p_uv,
+                                float* sdf, uint8_t* mask, void* xin, float* phi, int32_t* patch_id, float* local_tbn, float* sample_tbn, void* stream);
+typedef struct nerftex_curved_light_import_infer_desc {
+    const float* xyz;                  /* [B,3] sample positions                                                                  */
+    const float* dirs;                 /* [B,3] view directions; dirs[row][0] > 1e29 marks an unused slot                         */
+    uint32_t B;
+    const float* map;                  /* [map_h, map_w, n_features] fp32, 16-byte aligned                                        */
+    const float* phi_map;              /* [map_h, map_w, n_phi] fp32, 16-byte aligned                                             */
+    const float* frame_map;            /* [map_h, map_w, NERFTEX_FRAME_MAP_STRIDE] fp32, 16-byte aligned: see above               */
+    const float* sample_tbn_inv;       /* [n_patches, NERFTEX_FRAME_MAP_STRIDE] fp32, 16-byte aligned: see above                  */
+    uint32_t map_h, map_w, n_features, n_phi, n_patches;
+    uint32_t mode;                     /* NERFTEX_PLANAR_MULTIPLY / NERFTEX_PLANAR_DIVIDE                                          */
+    float plane_scale0, plane_scale1;
+    float height_scale0, height_scale1;
+    float sdf_offset;
+    float h_threshold;
+    uint32_t n_freqs;                  /* FreqEncoder(height) bands (multires)                                                    */
+    const void* sigma_weights;         /* fp16, 16-byte aligned                                                                   */
+    uint32_t sigma_in, sigma_hidden, sigma_layers, sigma_out;
+    const void* normal_weights;        /* fp16 [NERFTEX_NORMAL_NET_WEIGHTS], 4-byte aligned: as nerftex_curved_light_infer_desc   */
+    const float* normal_biases;        /* fp32 [NERFTEX_NORMAL_NET_BIASES]                                                        */
+    uint32_t normal_hidden, normal_layers; /* 16, 2                                                                               */
+    const void* brdf_weights;          /* fp16, 16-byte aligned                                                                   */
+    uint32_t brdf_in, brdf_hidden, brdf_layers, brdf_out;
+    const float* env_shs;              /* [n_sh, n_color] fp32, as nerftex_sh_light_desc                                          */
+    uint32_t n_sh, n_color;
+    float gamma;
+    uint32_t flags;                    /* NERFTEX_SH_LIGHT_SPECULAR                                                               */
+    uint32_t visual_mode;              /* NERFTEX_LIGHT_VISUAL_*                                                                  */
+    float fc_weight;
+    int eval;                          /* as nerftex_curved_light_infer_desc                                                      */
+    float* sigma;                      /* [B] fp32                                                                                */
+    float* rgbs;                       /* [B,3] fp32                                                                              */
+    float* shading_normal;             /* [B,3] fp32 or NULL (not written)                                                        */
+    const int32_t* units_dev;
+    uint32_t rows_per_unit;
+    void* scratch;                     /* caller-owned, 256-byte aligned, >= nerftex_curved_light_import_infer_scratch_bytes(B)   */
+    size_t scratch_bytes;
+} nerftex_curved_light_import_infer_desc;
+size_t nerftex_curved_light_import_infer_scratch_bytes(uint32_t B);
+int nerftex_curved_light_import_infer(const nerftex_curved_light_import_infer_desc* d, void* stream);
+
+/* -------------------------------------------------------------------------
  * Extension: the SH light head of the curved field -- SH_EnvmapMaterialNet.forward behind its BRDF MLP (nerf/sh_light_model.py:554-616) -- as one
  * streaming kernel per direction instead of ~40 framework ops per sample batch, the framework's arithmetic at its rounding points:
  *   albedo = half(sigmoid(brdf[:, :3])), spec_w = half(sigmoid(brdf[:, 3]))              (fp32 sigmoid narrowed to half)

@@ -1,24 +1,29 @@
-// grid_sample(bilinear, align_corners=True, padding zeros) of an imported [H, W, 16] fp32 feature map at (u, v), narrowed to the 16-bit values
-// the sigma net reads: the one read of the planar lookup (planar.inc, the 'field' branch of MeshFeatureField.forward) and of the shape lookup
-// (raytracer.hip, the 'shape' branch).  u runs along the map's FIRST axis.
+// grid_sample(bilinear, align_corners=True, padding zeros) of an imported [H, W, C] fp32 map at (u, v), narrowed to the 16-bit values the
+// networks read: the one read of the planar lookup (planar.inc, the 'field' branch of MeshFeatureField.forward), of the shape lookup
+// (raytracer.hip, the 'shape' branch) and of the lit lookup's phi map (planar_light.inc, C = 8).  u runs along the map's FIRST axis.
 #pragma once
 
 #include "common.hpp"
 
 namespace nerftex {
 
-// LANES = 1: the calling thread reads the four corners' 64 bytes each as four 16-byte loads (16 independent loads in flight) and gets all 16
-// features, o[0..3]; LANES = 4: lane q of four reads quarter q of each corner and gets its four features, o[0].
+// LANES = 1: the calling thread reads the four corners' 4 C bytes each as C / 4 16-byte loads (all of them independent, in flight together) and gets
+// all C features, o[0 .. C / 4 - 1]; LANES = 4 (C = 16): lane q of four reads quarter q of each corner and gets its four features, o[0].
+// V = half4_t: the values narrowed to half; V = float4_t: the fp32 values those are the narrowing of.
 // Every framework op rounds on its own (no contraction); a corner outside [0,H) x [0,W) contributes nothing and is not read; the comparisons are on
 // the floats (a NaN or a huge coordinate fails them all) and the index is converted only inside the range, then widened to size_t.
-template <int LANES>
+template <int LANES, int C = 16, typename V = half4_t>
 __device__ __forceinline__ void bilinear_read(const float* __restrict__ map, const uint32_t H, const uint32_t W, const float u, const float v, const uint32_t q,
-                                              half4_t (&o)[4 / LANES]) {
+                                              V (&o)[C / 4 / LANES]) {
 #pragma clang fp contract(off)
-    static_assert(LANES == 1 || LANES == 4, "one thread or four lanes per row");
-    auto narrow = [](float x) {  // (fieldglue.hip's narrow: the value rounded to fp32 first, then to half)
+    static_assert(LANES == 1 || (LANES == 4 && C == 16), "one thread per row, or four lanes per row of 16 features");
+    static_assert(C % 4 == 0 && C >= 4, "whole 16-byte words per texel");
+    auto narrow = [](float x) {  // (fieldglue.hip's narrow: the value rounded to fp32 first, then to half; fp32 out: the value as it is)
         asm volatile("" : "+v"(x));
-        return (half_t)x;
+        if constexpr (sizeof(V) == sizeof(half4_t))
+            return (half_t)x;
+        else
+            return x;
     };
     const float iu = ((u + 1.0f) / 2.0f) * (float)(H - 1), iv = ((v + 1.0f) / 2.0f) * (float)(W - 1);
     const float i0 = floorf(iu), j0 = floorf(iv);
@@ -27,14 +32,14 @@ __device__ __forceinline__ void bilinear_read(const float* __restrict__ map, con
     const float hi_i = (float)(H - 1), hi_j = (float)(W - 1);
     const bool in_i[2] = {i0 >= 0.0f && i0 <= hi_i, i0 + 1.0f >= 0.0f && i0 + 1.0f <= hi_i};
     const bool in_j[2] = {j0 >= 0.0f && j0 <= hi_j, j0 + 1.0f >= 0.0f && j0 + 1.0f <= hi_j};
-    constexpr int Q = 4 / LANES;  // 16-byte quarters of a texel this lane reads: all four, or quarter q
+    constexpr int Q = C / 4 / LANES;  // 16-byte words of a texel this lane reads: all of them, or quarter q
     float4_t t[4][Q];
 #pragma unroll
     for (int k = 0; k < 4; k++) {
         const int di = k & 1, dj = k >> 1;
         if (in_i[di] && in_j[dj]) {
             const size_t i = (size_t)(int)(i0 + (float)di), j = (size_t)(int)(j0 + (float)dj);
-            const float4_t* src = reinterpret_cast<const float4_t*>(map + (i * (size_t)W + j) * 16);
+            const float4_t* src = reinterpret_cast<const float4_t*>(map + (i * (size_t)W + j) * C);
 #pragma unroll
             for (int qq = 0; qq < Q; qq++) t[k][qq] = src[LANES == 1 ? (uint32_t)qq : q];
         } else {

@@ -50,6 +50,37 @@ struct CurvedLightScratch {
           brdf_in(carve.take<half_t>(16)), brdf(carve.take<half_t>(16)), shading(carve.take<float>(3)) {}
 };
 
+// The refusals over the light head's members (n_sh .. eval), which the two lit chains' descriptors share; `who`: the entry's name in the messages.
+template <typename Desc>
+bool light_head_ok(const Desc* d, const char* who) {
+    if (d->n_sh < 9 || (d->n_color != 1 && d->n_color != 3)) {
+        set_error("%s: the lighting holds at least 9 SH rows of 1 or 3 colours, but got [%u, %u]", who, d->n_sh, d->n_color);
+        return false;
+    }
+    if (!(d->gamma > 0.0f) || !std::isfinite(d->gamma) || (d->flags & ~(uint32_t)NERFTEX_SH_LIGHT_SPECULAR) || d->visual_mode > NERFTEX_LIGHT_VISUAL_ALBEDO ||
+        (d->eval != 0 && d->eval != 1)) {
+        set_error("%s: gamma is positive and finite, flags holds NERFTEX_SH_LIGHT_SPECULAR or nothing (got 0x%x), visual_mode is one of "
+                  "NERFTEX_LIGHT_VISUAL_* (got %u) and eval is 0 or 1 (got %d)", who, d->flags, d->visual_mode, d->eval);
+        return false;
+    }
+    return true;
+}
+
+// the closing launch of the two lit chains
+template <typename Desc>
+void launch_light_out(const Desc* d, const half_t* brdf, const float* shading, const uint8_t* mask, const float* sigma_raw, hipStream_t st) {
+    const dim3 grid(div_up(d->B, 256u)), block(256);
+    const float inv_gamma = (float)(1.0 / (double)d->gamma);
+    const bool spec = (d->flags & NERFTEX_SH_LIGHT_SPECULAR) != 0;
+    KernelTimer kt("curved_light_out_rows_kernel", st);
+    if (d->n_color == 3)
+        hipLaunchKernelGGL(curved_light_out_rows_kernel<3>, grid, block, 0, st, brdf, shading, d->dirs, d->env_shs, mask, sigma_raw, d->B, inv_gamma, spec,
+                           (int)d->visual_mode, d->sigma, d->rgbs, d->units_dev, d->rows_per_unit);
+    else
+        hipLaunchKernelGGL(curved_light_out_rows_kernel<1>, grid, block, 0, st, brdf, shading, d->dirs, d->env_shs, mask, sigma_raw, d->B, inv_gamma, spec,
+                           (int)d->visual_mode, d->sigma, d->rgbs, d->units_dev, d->rows_per_unit);
+}
+
 }  // namespace
 }  // namespace nerftex
 
@@ -64,16 +95,7 @@ extern "C" int nerftex_curved_light_infer(const nerftex_curved_light_infer_desc*
                   "table of 4 levels x 2 features, sigma net 48 -> 32 x 2 -> 16, normal nets 16 wide with 2 hidden layers, BRDF net 16 -> 64 x 3 -> 5)");
         return NERFTEX_ERR_INVALID;
     }
-    if (d->n_sh < 9 || (d->n_color != 1 && d->n_color != 3)) {
-        set_error("curved_light_infer: the lighting holds at least 9 SH rows of 1 or 3 colours, but got [%u, %u]", d->n_sh, d->n_color);
-        return NERFTEX_ERR_INVALID;
-    }
-    if (!(d->gamma > 0.0f) || !std::isfinite(d->gamma) || (d->flags & ~(uint32_t)NERFTEX_SH_LIGHT_SPECULAR) || d->visual_mode > NERFTEX_LIGHT_VISUAL_ALBEDO ||
-        (d->eval != 0 && d->eval != 1)) {
-        set_error("curved_light_infer: gamma is positive and finite, flags holds NERFTEX_SH_LIGHT_SPECULAR or nothing (got 0x%x), visual_mode is one of "
-                  "NERFTEX_LIGHT_VISUAL_* (got %u) and eval is 0 or 1 (got %d)", d->flags, d->visual_mode, d->eval);
-        return NERFTEX_ERR_INVALID;
-    }
+    if (!light_head_ok(d, "curved_light_infer")) return NERFTEX_ERR_INVALID;
     if (d->B == 0) return NERFTEX_OK;
     const CurvedLightScratch sc(d->scratch, d->B);
     if (!front_pointers_ok(d, sc.carve.at) || !d->tbn || !d->normal_table || !d->normal_offsets || !d->normal_weights || !d->normal_biases || !d->brdf_weights ||
@@ -105,22 +127,12 @@ extern "C" int nerftex_curved_light_infer(const nerftex_curved_light_infer_desc*
     if ((rc = curved_front_sigma(d, sc.f, "curved_light_infer(pack)", stream)) != NERFTEX_OK) return rc;
     {
         KernelTimer kt("curved_light_mid_rows_kernel", st);
-        hipLaunchKernelGGL(curved_light_mid_rows_kernel, grid, block, 0, st, sc.f.h, sc.f.xin, sc.n_lbc, sc.f.normal, sc.tbn, d->dirs,
+        hipLaunchKernelGGL(curved_light_mid_rows_kernel<false>, grid, block, 0, st, sc.f.h, sc.f.xin, sc.n_lbc, sc.f.normal, sc.tbn, nullptr, d->dirs,
                            static_cast<const half_t*>(d->normal_weights), d->normal_biases, B, d->fc_weight, d->eval, sc.sigma_raw, sc.brdf_in, shading, units, rpu);
     }
     if ((rc = check_launch("curved_light_infer(mid)")) != NERFTEX_OK) return rc;
     rc = ffmlp_inference_rows(sc.brdf_in, d->brdf_weights, B, 16, 64, 3, sc.brdf, units, rpu, st);
     if (rc != NERFTEX_OK) return rc;
-    {
-        const float inv_gamma = (float)(1.0 / (double)d->gamma);
-        const bool spec = (d->flags & NERFTEX_SH_LIGHT_SPECULAR) != 0;
-        KernelTimer kt("curved_light_out_rows_kernel", st);
-        if (d->n_color == 3)
-            hipLaunchKernelGGL(curved_light_out_rows_kernel<3>, grid, block, 0, st, sc.brdf, shading, d->dirs, d->env_shs, sc.f.mask, sc.sigma_raw, B, inv_gamma, spec,
-                               (int)d->visual_mode, d->sigma, d->rgbs, units, rpu);
-        else
-            hipLaunchKernelGGL(curved_light_out_rows_kernel<1>, grid, block, 0, st, sc.brdf, shading, d->dirs, d->env_shs, sc.f.mask, sc.sigma_raw, B, inv_gamma, spec,
-                               (int)d->visual_mode, d->sigma, d->rgbs, units, rpu);
-    }
+    launch_light_out(d, sc.brdf, shading, sc.f.mask, sc.sigma_raw, st);
     return check_launch("curved_light_infer(out)");
 }

@@ -294,9 +294,14 @@ __device__ __forceinline__ float lip_mlp_row(const float (&x)[IN], const float* 
 //      brdf_in [B,16] half = [h[:,1:16] | 1]
 //      shading [B,3] fp32: toCoor(phi, theta) rotated by the frame (a half product), normalised twice (tools/map.py:732, network_curvedfield.py:285);
 //      eval: fc x fine + (1 - fc) x coarse, renormalised (:293-301), coarse = the raw normal normalised twice (tools/map.py:720, :285)
+// TWO (the imported map's chain, planar_light.inc): tbn2 [B,9] is a second frame the rotated normal is rotated by once more (tools/map.py:726-727, the
+// sampled patch's inverted frame), the same half product on the first one's half result -- the reference rounds between the two, so the frames are
+// not multiplied together.  Without it (the mesh chain) tbn2 is not read.
+template <bool TWO>
 __device__ __forceinline__ void curved_light_mid_row(const uint32_t b, const uint32_t B, const half_t* __restrict__ h, const half_t* __restrict__ xin,
                                                      const half_t* __restrict__ n_lbc, const float* __restrict__ normal, const float* __restrict__ tbn,
-                                                     const float* __restrict__ w, const float* __restrict__ bias, const float fc, const int eval,
+                                                     const float* __restrict__ tbn2, const float* __restrict__ w, const float* __restrict__ bias, const float fc,
+                                                     const int eval,
                                                      float* __restrict__ sigma_raw, half_t* __restrict__ brdf_in, float* __restrict__ shading) {
 #pragma clang fp contract(off)  // every framework op rounds on its own
     const half8_t h0 = *reinterpret_cast<const half8_t*>(h + (size_t)b * 16);
@@ -346,6 +351,14 @@ __device__ __forceinline__ void curved_light_mid_row(const uint32_t b, const uin
     for (int k = 0; k < 9; k++) th[k] = (float)(half_t)tbn[(size_t)b * 9 + k];
 #pragma unroll
     for (int a = 0; a < 3; a++) n[a] = (float)narrow((th[a] * lh[0] + th[3 + a] * lh[1]) + th[6 + a] * lh[2]);
+    if constexpr (TWO) {
+#pragma unroll
+        for (int k = 0; k < 3; k++) lh[k] = n[k];  // (half values already)
+#pragma unroll
+        for (int k = 0; k < 9; k++) th[k] = (float)(half_t)tbn2[(size_t)b * 9 + k];
+#pragma unroll
+        for (int a = 0; a < 3; a++) n[a] = (float)narrow((th[a] * lh[0] + th[3 + a] * lh[1]) + th[6 + a] * lh[2]);
+    }
     auto unit = [](float (&v)[3]) {  // v / (|v| + 1e-5)
         const float len = sqrtf((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]) + 1e-5f;
 #pragma unroll
@@ -369,9 +382,11 @@ __device__ __forceinline__ void curved_light_mid_row(const uint32_t b, const uin
 
 // One thread per row.  The net's weights (1312 half values, 66 biases: 5.4 KiB as fp32) are staged once per workgroup in LDS -- every lane of a wave
 // reads the same word at the same time (a broadcast, no bank conflict), and 1.3 k words per row would not stay in scalar registers.  A workgroup wholly
-// past the live rows leaves before it stages anything.
+// past the live rows leaves before it stages anything.  TWO: curved_light_mid_row's second frame.
+template <bool TWO>
 __global__ __launch_bounds__(256) void curved_light_mid_rows_kernel(const half_t* __restrict__ h, const half_t* __restrict__ xin, const half_t* __restrict__ n_lbc,
-                                                                   const float* __restrict__ normal, const float* __restrict__ tbn, const float* __restrict__ dirs,
+                                                                   const float* __restrict__ normal, const float* __restrict__ tbn, const float* __restrict__ tbn2,
+                                                                   const float* __restrict__ dirs,
                                                                    const half_t* __restrict__ nn_weights, const float* __restrict__ nn_biases, uint32_t B,
                                                                    const float fc, const int eval, float* __restrict__ sigma_raw, half_t* __restrict__ brdf_in,
                                                                    float* __restrict__ shading, const int32_t* __restrict__ units_dev, uint32_t rows_per_unit) {
@@ -389,7 +404,7 @@ __global__ __launch_bounds__(256) void curved_light_mid_rows_kernel(const half_t
         for (int c = 0; c < 3; c++) shading[(size_t)b * 3 + c] = 0.0f;
         return;
     }
-    curved_light_mid_row(b, B, h, xin, n_lbc, normal, tbn, w_s, b_s, fc, eval, sigma_raw, brdf_in, shading);
+    curved_light_mid_row<TWO>(b, B, h, xin, n_lbc, normal, tbn, tbn2, w_s, b_s, fc, eval, sigma_raw, brdf_in, shading);
 }
 
 // ---- the front half nerftex_curved_field_infer and nerftex_curved_light_infer (curved_light.inc) share: neighbour search to sigma net ------------------
@@ -657,3 +672,6 @@ extern "C" int nerftex_field_out_backward(const float* grad_rgbs, const float* r
 
 // ---- the SH light model's inference chain (nerftex_curved_light_infer): its closing kernel shares the head's row function above ----------------------------
 #include "curved_light.inc"
+
+// ---- the imported map under the SH light model (nerftex_planar_light_lookup, nerftex_curved_light_import_infer): behind both -----------------------------
+#include "planar_light.inc"

@@ -21,20 +21,23 @@ struct PlanarArgs {
 // choice is DESIGN.md 4.15's.  The arithmetic is the same expression tree per element in both: the same bits.
 // ROWS: the rows contract of nerftex_curved_field_infer's kernels (writes the raw normal (0, 0, 1) for the mid kernel); otherwise the plain form
 // (every row, writes p_uv and sdf).  Both write mask [B] and the sigma net's input row xin [B,48] = [half(features) | half(ladder) | ones].
+// One row of the lookup (lane q of its LANES): everything the two kernels below and the lit lookup (planar_light.inc) write alike -- one expression
+// tree, so the same bits wherever it is called.  -> false: this thread is done (past the live rows, or a marked slot whose zeros are written);
+// true: b, q, u, v are the row, the lane and the map coordinates of a row that reads its texels.
 template <bool ROWS, int LANES>
-__global__ __launch_bounds__(256) void planar_lookup_rows_kernel(const float* __restrict__ xyz, const float* __restrict__ dirs, const uint32_t B, const PlanarArgs a,
-                                                                 float* __restrict__ p_uv, float* __restrict__ sdf_out, uint8_t* __restrict__ mask,
-                                                                 float* __restrict__ normal, half_t* __restrict__ xin, const int32_t* __restrict__ units_dev,
-                                                                 const uint32_t rows_per_unit) {
+__device__ __forceinline__ bool planar_lookup_row(const float* __restrict__ xyz, const float* __restrict__ dirs, const uint32_t B, const PlanarArgs& a,
+                                                  float* __restrict__ p_uv, float* __restrict__ sdf_out, uint8_t* __restrict__ mask, float* __restrict__ normal,
+                                                  half_t* __restrict__ xin, const int32_t* __restrict__ units_dev, const uint32_t rows_per_unit, uint32_t& b,
+                                                  uint32_t& q, float& u, float& v) {
 #pragma clang fp contract(off)  // every framework op rounds on its own
     static_assert(LANES == 1 || LANES == 4, "one thread or four lanes per row");
     const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t b = tid / LANES, q = tid % LANES;
+    b = tid / LANES, q = tid % LANES;
     const bool first = q == 0;  // the lane that writes what a row has once
-    if (b >= (ROWS ? live_rows(B, units_dev, rows_per_unit) : B)) return;
+    if (b >= (ROWS ? live_rows(B, units_dev, rows_per_unit) : B)) return false;
     half_t* row = xin + (size_t)b * 48;
     if (ROWS && slot_unused(dirs, b)) {  // no texel is read
-        if (!first) return;
+        if (!first) return false;
         mask[b] = 0;
 #pragma unroll
         for (int c = 0; c < 3; c++) normal[(size_t)b * 3 + c] = 0.0f;
@@ -42,11 +45,11 @@ __global__ __launch_bounds__(256) void planar_lookup_rows_kernel(const float* __
         reinterpret_cast<half8_t*>(row)[0] = zero;
         reinterpret_cast<half8_t*>(row)[1] = zero;
         write_unused_ladder(row);
-        return;
+        return false;
     }
     const float x0 = xyz[(size_t)b * 3], x1 = xyz[(size_t)b * 3 + 1], x2 = xyz[(size_t)b * 3 + 2];
-    const float u = a.divide ? x0 / a.plane0 : x0 * a.plane0;
-    const float v = a.divide ? x1 / a.plane1 : x1 * a.plane1;
+    u = a.divide ? x0 / a.plane0 : x0 * a.plane0;
+    v = a.divide ? x1 / a.plane1 : x1 * a.plane1;
     const float sdf = (x2 * a.height0) * a.height1 - a.offset;
     if (first) {
         mask[b] = (fabsf(sdf) < a.h_threshold && u >= -1.0f && u <= 1.0f && v >= -1.0f && v <= 1.0f) ? 1 : 0;
@@ -67,6 +70,17 @@ __global__ __launch_bounds__(256) void planar_lookup_rows_kernel(const float* __
         reinterpret_cast<half4_t*>(row)[q] = o[0];
     }
     if (first) write_height_ladder(sdf, row);
+    return true;
+}
+
+template <bool ROWS, int LANES>
+__global__ __launch_bounds__(256) void planar_lookup_rows_kernel(const float* __restrict__ xyz, const float* __restrict__ dirs, const uint32_t B, const PlanarArgs a,
+                                                                 float* __restrict__ p_uv, float* __restrict__ sdf_out, uint8_t* __restrict__ mask,
+                                                                 float* __restrict__ normal, half_t* __restrict__ xin, const int32_t* __restrict__ units_dev,
+                                                                 const uint32_t rows_per_unit) {
+    uint32_t b, q;
+    float u, v;
+    planar_lookup_row<ROWS, LANES>(xyz, dirs, B, a, p_uv, sdf_out, mask, normal, xin, units_dev, rows_per_unit, b, q, u, v);
 }
 
 // one launch of the lookup in the lane mapping the knob `planar_lanes` names (4: four lanes per row; anything else: one thread per row)

@@ -1,0 +1,219 @@
+// The imported planar map under the SH light model: the `pred_normal` part of the 'field' branch of MeshFeatureField.forward (tools/map.py:670-675,
+// :722-730) -- beside the feature read of planar.inc, a bilinear read of the [H, W, 8] phi map (the normal net's own table features), a nearest read
+// of the per-texel frame and patch id, and the patch's inverted frame -- as one launch (nerftex_planar_light_lookup), and the lit field's no-grad
+// forward over it as one device-count call (nerftex_curved_light_import_infer).  Included at the end of fieldglue.hip behind curved_light.inc: the
+// row function of the lookup is planar.inc's, the mid kernel fieldglue.hip's (its second frame), the closing kernel curved_light.inc's.
+//
+// Lane mapping: one thread per row (planar.inc's LANES = 1; DESIGN.md 4.15 measured the four-lane mapping no faster for the feature read, and the
+// 6 + 3 + 3 sixteen-byte words a row reads here beside the features do not split over four lanes evenly).  DESIGN.md 4.17.
+
+namespace nerftex {
+namespace {
+
+struct PlanarLightArgs {
+    const float* phi_map;     // [H, W, 8] fp32, channel-last, 16-byte aligned
+    const float* frame_map;   // [H, W, 12] fp32, 16-byte aligned: a texel is three 16-byte words -- the 9 floats of its frame, its patch id, two zeros
+    const float* sample_inv;  // [P, 12] fp32, 16-byte aligned: the 9 floats of patch p's inverted frame, three zeros
+    uint32_t P;
+};
+
+// grid_sample(mode='nearest', align_corners=True, padding zeros)'s texel of a map whose FIRST axis u runs along: ix = ((u + 1) / 2) (size - 1) in
+// fp32, rounded half to even; -> false outside the map (zeros; a NaN fails the comparisons).  The index is converted only inside the range.
+__device__ __forceinline__ bool nearest_texel(const uint32_t H, const uint32_t W, const float u, const float v, size_t& texel) {
+#pragma clang fp contract(off)
+    const float iu = ((u + 1.0f) / 2.0f) * (float)(H - 1), iv = ((v + 1.0f) / 2.0f) * (float)(W - 1);
+    const float ri = nearbyintf(iu), rj = nearbyintf(iv);
+    if (!(ri >= 0.0f && ri <= (float)(H - 1) && rj >= 0.0f && rj <= (float)(W - 1))) return false;
+    texel = (size_t)(int)ri * (size_t)W + (size_t)(int)rj;
+    return true;
+}
+
+// ROWS: the rows contract; phi goes out as half, level-major [4, B, 2] (what curved_light_mid_row reads as n_lbc); id_out is not written.
+// Otherwise the plain form: every row, phi as fp32 [B, 8] (the values the half ones are the narrowing of), the sampled id [B].
+// Both: local_tbn [B, 9] the texel's frame, sample_tbn [B, 9] row `id` of the inverted patch frames; an id outside [0, P) (the caller's to
+// rule out) reads nothing and gives zeros.  A marked slot reads no texel of any map and writes planar_lookup_row's zeros only.
+template <bool ROWS>
+__global__ __launch_bounds__(256) void planar_light_lookup_rows_kernel(const float* __restrict__ xyz, const float* __restrict__ dirs, const uint32_t B,
+                                                                       const PlanarArgs a, const PlanarLightArgs l, float* __restrict__ p_uv,
+                                                                       float* __restrict__ sdf_out, uint8_t* __restrict__ mask, float* __restrict__ normal,
+                                                                       half_t* __restrict__ xin, void* __restrict__ phi_out, int32_t* __restrict__ id_out,
+                                                                       float* __restrict__ local_tbn, float* __restrict__ sample_tbn,
+                                                                       const int32_t* __restrict__ units_dev, const uint32_t rows_per_unit) {
+    uint32_t b, q;
+    float u, v;
+    if (!planar_lookup_row<ROWS, 1>(xyz, dirs, B, a, p_uv, sdf_out, mask, normal, xin, units_dev, rows_per_unit, b, q, u, v)) return;
+    // the nearest reads first: the patch's frame hangs on the texel's id, the longest chain of dependent loads in the row
+    const float4_t zero = {0.0f, 0.0f, 0.0f, 0.0f};
+    float4_t f[3] = {zero, zero, zero}, s[3] = {zero, zero, zero};
+    size_t texel;
+    if (nearest_texel(a.H, a.W, u, v, texel)) {
+        const float4_t* src = reinterpret_cast<const float4_t*>(l.frame_map + texel * 12);
+#pragma unroll
+        for (int k = 0; k < 3; k++) f[k] = src[k];
+    }
+    const float idf = f[2][1];
+    const int32_t id = (idf > -1.0f && idf < (float)l.P) ? (int32_t)idf : -1;  // (.long() truncates towards zero)
+    if (id >= 0) {
+        const float4_t* src = reinterpret_cast<const float4_t*>(l.sample_inv + (size_t)id * 12);
+#pragma unroll
+        for (int k = 0; k < 3; k++) s[k] = src[k];
+    }
+    if constexpr (ROWS) {
+        half4_t o[2];
+        bilinear_read<1, 8>(l.phi_map, a.H, a.W, u, v, 0u, o);
+        half_t* n_lbc = static_cast<half_t*>(phi_out);
+#pragma unroll
+        for (int lv = 0; lv < 4; lv++) {
+            const half2_t pair = {o[lv / 2][2 * (lv % 2)], o[lv / 2][2 * (lv % 2) + 1]};
+            *reinterpret_cast<half2_t*>(n_lbc + ((size_t)lv * B + b) * 2) = pair;
+        }
+    } else {
+        float4_t o[2];
+        bilinear_read<1, 8, float4_t>(l.phi_map, a.H, a.W, u, v, 0u, o);
+        float4_t* dst = reinterpret_cast<float4_t*>(static_cast<float*>(phi_out) + (size_t)b * 8);
+        dst[0] = o[0]; dst[1] = o[1];
+        id_out[b] = id;  // (-1: a texel whose id is not in [0, P))
+    }
+#pragma unroll
+    for (int k = 0; k < 9; k++) {
+        local_tbn[(size_t)b * 9 + k] = f[k / 4][k % 4];
+        sample_tbn[(size_t)b * 9 + k] = s[k / 4][k % 4];
+    }
+}
+
+template <bool ROWS>
+void launch_planar_light_lookup(hipStream_t st, const float* xyz, const float* dirs, uint32_t B, const PlanarArgs& a, const PlanarLightArgs& l, float* p_uv,
+                                float* sdf, uint8_t* mask, float* normal, half_t* xin, void* phi, int32_t* id, float* local_tbn, float* sample_tbn,
+                                const int32_t* units_dev, uint32_t rows_per_unit) {
+    KernelTimer kt("planar_light_lookup_rows_kernel", st);
+    hipLaunchKernelGGL(planar_light_lookup_rows_kernel<ROWS>, dim3(div_up(B, 256u)), dim3(256), 0, st, xyz, dirs, B, a, l, p_uv, sdf, mask, normal, xin, phi, id,
+                       local_tbn, sample_tbn, units_dev, rows_per_unit);
+}
+
+// the scratch of one nerftex_curved_light_import_infer call
+struct LightImportScratch {
+    ScratchCarver carve;
+    uint8_t* mask;
+    float* normal;
+    half_t *xin, *h, *n_lbc;
+    float *local_tbn, *sample_tbn, *sigma_raw;
+    half_t *brdf_in, *brdf;
+    float* shading;  // (used when the caller does not ask for the shading normal)
+    LightImportScratch(void* scratch, size_t B)
+        : carve{reinterpret_cast<uintptr_t>(scratch), B}, mask(carve.take<uint8_t>(1)), normal(carve.take<float>(3)), xin(carve.take<half_t>(48)),
+          h(carve.take<half_t>(16)), n_lbc(carve.take<half_t>(8)), local_tbn(carve.take<float>(9)), sample_tbn(carve.take<float>(9)),
+          sigma_raw(carve.take<float>(1)), brdf_in(carve.take<half_t>(16)), brdf(carve.take<half_t>(16)), shading(carve.take<float>(3)) {}
+};
+
+inline bool aligned16(const void* p) { return !(reinterpret_cast<uintptr_t>(p) & 15); }
+
+}  // namespace
+}  // namespace nerftex
+
+extern "C" int nerftex_planar_light_lookup(const float* xyz, const float* map, const float* phi_map, const float* frame_map, const float* sample_tbn_inv,
+                                           uint32_t map_h, uint32_t map_w, uint32_t n_patches, uint32_t mode, float plane_scale0, float plane_scale1,
+                                           float height_scale0, float height_scale1, float sdf_offset, float h_threshold, uint32_t n_freqs, uint32_t B, float* p_uv,
+                                           float* sdf, uint8_t* mask, void* xin, float* phi, int32_t* patch_id, float* local_tbn, float* sample_tbn,
+                                           void* stream) {
+    clear_error();
+    if (n_freqs != kInferFreqs) {
+        set_error("planar_light_lookup: the kernel writes the curved field's 12 height bands, but got n_freqs = %u", n_freqs);
+        return NERFTEX_ERR_INVALID;
+    }
+    if (map_h == 0 || map_h > 16384u || map_w == 0 || map_w > 16384u) {
+        set_error("planar_light_lookup: the maps need between 1 and 16384 texels along each axis, but got %u x %u", map_h, map_w);
+        return NERFTEX_ERR_INVALID;
+    }
+    if (n_patches == 0 || n_patches > (1u << 24)) {
+        set_error("planar_light_lookup: between 1 and 2^24 patch frames (an id is read from an fp32 texel), but got %u", n_patches);
+        return NERFTEX_ERR_INVALID;
+    }
+    if (B == 0) return NERFTEX_OK;
+    if (!xyz || !map || !phi_map || !frame_map || !sample_tbn_inv || !p_uv || !sdf || !mask || !xin || !phi || !patch_id || !local_tbn || !sample_tbn ||
+        !aligned16(map) || !aligned16(phi_map) || !aligned16(frame_map) || !aligned16(sample_tbn_inv) || !aligned16(xin) || !aligned16(phi)) {
+        set_error("planar_light_lookup: inputs, maps and outputs must not be NULL, and the maps, the patch frames, xin and phi must be 16-byte aligned");
+        return NERFTEX_ERR_INVALID;
+    }
+    if (!planar_scales_ok(mode, plane_scale0, plane_scale1, height_scale0, height_scale1, sdf_offset, h_threshold)) {
+        set_error("planar_light_lookup: mode is NERFTEX_PLANAR_MULTIPLY or NERFTEX_PLANAR_DIVIDE, the scales and h_threshold positive and finite, sdf_offset "
+                  "finite");
+        return NERFTEX_ERR_INVALID;
+    }
+    hipStream_t st = as_stream(stream);
+    const PlanarArgs a{map, map_h, map_w, (int)mode, plane_scale0, plane_scale1, height_scale0, height_scale1, sdf_offset, h_threshold};
+    const PlanarLightArgs l{phi_map, frame_map, sample_tbn_inv, n_patches};
+    launch_planar_light_lookup<false>(st, xyz, nullptr, B, a, l, p_uv, sdf, mask, nullptr, static_cast<half_t*>(xin), phi, patch_id, local_tbn, sample_tbn, nullptr,
+                                      0u);
+    return check_launch("planar_light_lookup");
+}
+
+extern "C" size_t nerftex_curved_light_import_infer_scratch_bytes(uint32_t B) { return LightImportScratch(nullptr, B).carve.at; }
+
+extern "C" int nerftex_curved_light_import_infer(const nerftex_curved_light_import_infer_desc* d, void* stream) {
+    clear_error();
+    if (!d) {
+        set_error("curved_light_import_infer: NULL descriptor");
+        return NERFTEX_ERR_INVALID;
+    }
+    if (d->B % 128 != 0) {
+        set_error("curved_light_import_infer: the batch must be a multiple of 128 rows, but got %u", d->B);
+        return NERFTEX_ERR_INVALID;
+    }
+    if (d->n_features != 16 || d->n_phi != 8 || d->n_freqs != kInferFreqs || d->sigma_in != 48 || d->sigma_hidden != 32 || d->sigma_layers != 2 ||
+        d->sigma_out != 16 || d->normal_hidden != 16 || d->normal_layers != 2 || d->brdf_in != 16 || d->brdf_hidden != 64 || d->brdf_layers != 3 ||
+        d->brdf_out != 5) {
+        set_error("curved_light_import_infer: the kernels serve the default SH-lit curved field only (a map of 16 features, a phi map of 8, 12 height bands, "
+                  "sigma net 48 -> 32 x 2 -> 16, normal nets 16 wide with 2 hidden layers, BRDF net 16 -> 64 x 3 -> 5)");
+        return NERFTEX_ERR_INVALID;
+    }
+    if (!light_head_ok(d, "curved_light_import_infer")) return NERFTEX_ERR_INVALID;
+    if (d->map_h == 0 || d->map_h > 16384u || d->map_w == 0 || d->map_w > 16384u) {
+        set_error("curved_light_import_infer: the maps need between 1 and 16384 texels along each axis, but got %u x %u", d->map_h, d->map_w);
+        return NERFTEX_ERR_INVALID;
+    }
+    if (d->n_patches == 0 || d->n_patches > (1u << 24)) {
+        set_error("curved_light_import_infer: between 1 and 2^24 patch frames (an id is read from an fp32 texel), but got %u", d->n_patches);
+        return NERFTEX_ERR_INVALID;
+    }
+    if (d->B == 0) return NERFTEX_OK;
+    const LightImportScratch sc(d->scratch, d->B);
+    if (!d->xyz || !d->dirs || !d->map || !d->phi_map || !d->frame_map || !d->sample_tbn_inv || !d->sigma_weights || !d->normal_weights || !d->normal_biases ||
+        !d->brdf_weights || !d->env_shs || !d->sigma || !d->rgbs || !d->scratch || (reinterpret_cast<uintptr_t>(d->scratch) & 255) ||
+        d->scratch_bytes < sc.carve.at) {
+        set_error("curved_light_import_infer: inputs, maps, patch frames, weights, lighting and outputs must not be NULL, and scratch must be 256-byte aligned "
+                  "and hold %zu bytes", sc.carve.at);
+        return NERFTEX_ERR_INVALID;
+    }
+    if (!aligned16(d->map) || !aligned16(d->phi_map) || !aligned16(d->frame_map) || !aligned16(d->sample_tbn_inv) || !aligned16(d->sigma_weights) ||
+        !aligned16(d->brdf_weights) || ((reinterpret_cast<uintptr_t>(d->normal_weights) | reinterpret_cast<uintptr_t>(d->normal_biases)) & 3)) {
+        set_error("curved_light_import_infer: the maps, the patch frames and the MLP weight vectors must be 16-byte aligned, the normal net's block 4-byte "
+                  "aligned");
+        return NERFTEX_ERR_INVALID;
+    }
+    if (!planar_scales_ok(d->mode, d->plane_scale0, d->plane_scale1, d->height_scale0, d->height_scale1, d->sdf_offset, d->h_threshold)) {
+        set_error("curved_light_import_infer: mode is NERFTEX_PLANAR_MULTIPLY or NERFTEX_PLANAR_DIVIDE, the scales and h_threshold positive and finite, "
+                  "sdf_offset finite");
+        return NERFTEX_ERR_INVALID;
+    }
+    hipStream_t st = as_stream(stream);
+    float* shading = d->shading_normal ? d->shading_normal : sc.shading;
+    const uint32_t B = d->B, rpu = d->rows_per_unit;
+    const int32_t* units = d->units_dev;
+    const PlanarArgs a{d->map, d->map_h, d->map_w, (int)d->mode, d->plane_scale0, d->plane_scale1, d->height_scale0, d->height_scale1, d->sdf_offset, d->h_threshold};
+    const PlanarLightArgs l{d->phi_map, d->frame_map, d->sample_tbn_inv, d->n_patches};
+    launch_planar_light_lookup<true>(st, d->xyz, d->dirs, B, a, l, nullptr, nullptr, sc.mask, sc.normal, sc.xin, sc.n_lbc, nullptr, sc.local_tbn, sc.sample_tbn, units,
+                                     rpu);
+    int rc = check_launch("curved_light_import_infer(lookup)");
+    if (rc != NERFTEX_OK) return rc;
+    if ((rc = ffmlp_inference_rows(sc.xin, d->sigma_weights, B, 48, 32, 2, sc.h, units, rpu, st)) != NERFTEX_OK) return rc;
+    {
+        KernelTimer kt("curved_light_mid_rows_kernel", st);
+        hipLaunchKernelGGL(curved_light_mid_rows_kernel<true>, dim3(div_up(B, 256u)), dim3(256), 0, st, sc.h, sc.xin, sc.n_lbc, sc.normal, sc.local_tbn, sc.sample_tbn,
+                           d->dirs, static_cast<const half_t*>(d->normal_weights), d->normal_biases, B, d->fc_weight, d->eval, sc.sigma_raw, sc.brdf_in, shading, units,
+                           rpu);
+    }
+    if ((rc = check_launch("curved_light_import_infer(mid)")) != NERFTEX_OK) return rc;
+    if ((rc = ffmlp_inference_rows(sc.brdf_in, d->brdf_weights, B, 16, 64, 3, sc.brdf, units, rpu, st)) != NERFTEX_OK) return rc;
+    launch_light_out(d, sc.brdf, shading, sc.mask, sc.sigma_raw, st);
+    return check_launch("curved_light_import_infer(out)");
+}

@@ -14,7 +14,8 @@ xatlas, open3d, trimesh).
                      reference's modules executed with exactly that substitution.  light_model="SH" (main.py's model, :272-349):
                      no direction encoding and no colour MLP; the SH light head (light.SHLightNet) shades with the fine normal of the
                      factorized normal net.  import_field / import_shape: an imported planar feature map rendered on its own plane or
-                     on a new UV-mapped mesh (the 'field' and 'shape' branches of MeshFeatureField.forward, tools/map.py:646-700);
+                     on a new UV-mapped mesh (the 'field' and 'shape' branches of MeshFeatureField.forward, tools/map.py:646-700); with the
+                     normal net or the light model, the planar map comes with its phi_embed, local_tbn and sample_tbn maps (:670-675);
   CurvedFieldLookup  round 1's minimal chain (analytic normals -> traces -> hash lookup), kept for its test.
 """
 import numpy as np
@@ -548,23 +549,73 @@ class CurvedField(torch.nn.Module):
         # ... and of the 'shape' branch (:615-618): no second mesh, sdf_scale_factor 1, K_for_uv 5
         self.imported_type, self.shape_projector, self.shape_faces, self.shape_uvs, self.shape_face_uv = None, None, None, None, None
         self.sdf_scale_factor, self.K_for_uv, self.recommended_sdf_factor = 1.0, 5, None
+        # ... and the maps of the `pred_normal` part (:920-923): none
+        self.phi_embed_imported = self.local_tbn_imported = self.sample_tbn_ids_imported = self.sample_tbn_inv_imported = None
+        self.frame_map_imported = self.sample_inv_rows_imported = None
 
-    def import_field(self, features, grid_gap, rescale=None):
+    def _lit(self):
+        """A field whose forward reads a fine normal: the normal net, or a light model (which shades with it)."""
+        return self.normal_net is not None or getattr(self, "light_model", None) is not None
+
+    def _import_light_maps(self, H, W, phi_embed, local_tbn, sample_tbn, sample_tbn_ids, dev):
+        """The four maps of MeshFeatureField.import_field's `pred_normal` part (tools/map.py:916-923), checked and brought to the device:
+        phi_embed [H,W,8], local_tbn [H,W,9] or [H,W,3,3], sample_tbn [P,3,3] or [P,9] (inverted once, in fp32 on the host: :921),
+        sample_tbn_ids [H,W] with every id in [0, P).  Beside them the two arrays the kernels read (include/nerftex_hip.h): the frame map
+        [H,W,12] = [frame | id | 0 0] and the inverted patch frames padded to [P,12]."""
+        def arr(a):
+            return torch.as_tensor(np.asarray(a) if not torch.is_tensor(a) else a).detach().cpu()
+
+        phi, loc, smp, ids = arr(phi_embed), arr(local_tbn), arr(sample_tbn), arr(sample_tbn_ids)
+        if tuple(phi.shape) != (H, W, 8):
+            raise ValueError(f"CurvedField.import_field: phi_embed is [H, W, 8] = {(H, W, 8)}, but got {tuple(phi.shape)}")
+        if tuple(loc.shape) not in ((H, W, 9), (H, W, 3, 3)):
+            raise ValueError(f"CurvedField.import_field: local_tbn is [H, W, 9] or [H, W, 3, 3] with H, W = {(H, W)}, but got {tuple(loc.shape)}")
+        if not ((smp.dim() == 3 and tuple(smp.shape[1:]) == (3, 3)) or (smp.dim() == 2 and smp.shape[1] == 9)) or smp.shape[0] < 1:
+            raise ValueError(f"CurvedField.import_field: sample_tbn is [P, 3, 3] or [P, 9] with P >= 1, but got {tuple(smp.shape)}")
+        if tuple(ids.shape) != (H, W):
+            raise ValueError(f"CurvedField.import_field: sample_tbn_ids is [H, W] = {(H, W)}, but got {tuple(ids.shape)}")
+        P = int(smp.shape[0])
+        ids = ids.to(torch.float32)
+        whole = ids.long()  # (what the reference's `.long()` of the sampled float makes of it)
+        if not bool(torch.isfinite(ids).all()) or int(whole.min()) < 0 or int(whole.max()) >= P or P > (1 << 24):
+            raise ValueError(f"CurvedField.import_field: every id of sample_tbn_ids must lie in [0, P) = [0, {P}), P at most 2^24")
+        loc = loc.to(torch.float32).reshape(H, W, 9)
+        inv = torch.linalg.inv(smp.to(torch.float32).reshape(P, 3, 3))
+        frame = torch.zeros(H, W, 12, dtype=torch.float32)
+        frame[..., :9], frame[..., 9] = loc, ids
+        rows = torch.zeros(P, 12, dtype=torch.float32)
+        rows[:, :9] = inv.reshape(P, 9)
+        self.phi_embed_imported = phi.to(device=dev, dtype=torch.float32).contiguous()
+        self.local_tbn_imported, self.sample_tbn_ids_imported = loc.to(dev).contiguous(), ids.to(dev).contiguous()
+        self.sample_tbn_inv_imported = inv.to(dev).contiguous()
+        self.frame_map_imported, self.sample_inv_rows_imported = frame.to(dev).contiguous(), rows.to(dev).contiguous()
+
+    def import_field(self, features, grid_gap, rescale=None, *, phi_embed=None, local_tbn=None, sample_tbn=None, sample_tbn_ids=None):
         """NeRFNetwork.import_field -> MeshFeatureField.import_field for a planar map (`mesh is None`, network_curvedfield.py:457-475):
         features [H, W, 16] (numpy or tensor, the array the reference receives, in its axis order) is kept channel-last in fp32 on the field's
         device, bounds = [grid_gap H / 2, grid_gap W / 2], `imported` is set and `rescale` TOGGLES as the reference's does (False at
         construction, so True after the first import: u, v = x, y scaled by uv_utilize_rate; False: x, y divided by the bounds); rescale=
         sets it instead.  From here on embed() / density() / forward() / infer() read the map and touch neither the projector nor the hash
-        table, until switch_import().  The caller re-estimates the occupancy grid (Renderer.initialize_states), as the reference does."""
-        if self.normal_net is not None or getattr(self, "light_model", None) is not None:
+        table, until switch_import().  The caller re-estimates the occupancy grid (Renderer.initialize_states), as the reference does.
+        A field with the fine-normal net or a light model needs the four maps of the reference's `pred_normal` part as well (`_import_light_maps`,
+        tools/map.py:670-675): phi_embed, local_tbn, sample_tbn, sample_tbn_ids; a field without a normal net takes none of them."""
+        maps = (phi_embed, local_tbn, sample_tbn, sample_tbn_ids)
+        if not self._lit() and any(m is not None for m in maps):
+            raise ValueError("CurvedField.import_field: phi_embed, local_tbn, sample_tbn and sample_tbn_ids are read by the fine-normal net only; this field "
+                             "has none and would ignore them")
+        if self._lit() and any(m is not None for m in maps) and any(m is None for m in maps):
+            raise ValueError("CurvedField.import_field: phi_embed, local_tbn, sample_tbn and sample_tbn_ids come together, all four or none")
+        if self._lit() and phi_embed is None:
             raise NotImplementedError("CurvedField.import_field: a field with the fine-normal net or a light model would also need the imported phi_embed, "
                                       "local_tbn and sample_tbn maps (tools/map.py:670-675); only the static light model without a normal net imports here")
         f = torch.as_tensor(np.asarray(features) if not torch.is_tensor(features) else features).detach()
         if f.dim() != 3 or f.shape[-1] != self.encoder.output_dim or f.shape[0] < 1 or f.shape[1] < 1:
             raise ValueError(f"CurvedField.import_field: features are [H, W, {self.encoder.output_dim}], but got {tuple(f.shape)}")
         dev = self.sigma_net.weights.device
-        self.features_imported = f.to(device=dev, dtype=torch.float32).contiguous()
         H, W = int(f.shape[0]), int(f.shape[1])
+        if self._lit():  # (before anything of the state changes: a refused import leaves the field as it was)
+            self._import_light_maps(H, W, phi_embed, local_tbn, sample_tbn, sample_tbn_ids, dev)
+        self.features_imported = f.to(device=dev, dtype=torch.float32).contiguous()
         self.bounds = [0.5 * float(grid_gap) * H, 0.5 * float(grid_gap) * W]
         self.imported, self.imported_type = True, "field"
         self.rescale = (not self.rescale) if rescale is None else bool(rescale)
@@ -718,7 +769,11 @@ class CurvedField(torch.nn.Module):
             p = self.shape_projector
             return (("import-shape", f.data_ptr(), tuple(f.shape), p._knn.value, p.tracer._handle.value, p.mesh_vertices.data_ptr(), p.vertex_normals.data_ptr(),
                      self.shape_face_uv.data_ptr()) + self._shape_scalars() + (self._import_version,))
-        return ("import", f.data_ptr(), tuple(f.shape)) + self._import_scalars() + (self._import_version,)
+        stamp = ("import", f.data_ptr(), tuple(f.shape)) + self._import_scalars() + (self._import_version,)
+        if self._lit() and self.phi_embed_imported is not None:  # the lit field's maps: their storage and shapes
+            stamp += tuple((m.data_ptr(), tuple(m.shape)) for m in (self.phi_embed_imported, self.local_tbn_imported, self.sample_tbn_inv_imported,
+                                                                    self.sample_tbn_ids_imported, self.frame_map_imported, self.sample_inv_rows_imported))
+        return stamp
 
     @torch.no_grad()
     def _import_lookup(self, x):
@@ -767,6 +822,65 @@ class CurvedField(torch.nn.Module):
     def _import_fused(self, x):
         return x.is_cuda and self._glue_fused() and self.multires == 12 and self.sigma_net.dtype == torch.float16
 
+    def _import_light_fused(self, x):
+        """_import_fused() for the lit field (which has no colour net for _glue_fused() to ask about): the planar lookups serve the default
+        shapes under fp16 autocast without the probabilistic table, once the four maps are there."""
+        return (x.is_cuda and self._lit() and self.phi_embed_imported is not None and not self._shape_active() and self.encoder_var is None
+                and self.in_dim == 41 and self.in_pad == 48 and self.geo_feat_dim == 15 and self.multires == 12 and self.sigma_net.dtype == torch.float16
+                and torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.float16)
+
+    @torch.no_grad()
+    def _import_light_lookup(self, x):
+        """nerftex_planar_light_lookup: -> p_uv [N,2], sdf [N], h_mask [N] bool, xin [N,48] half, phi [N,8] fp32, id [N] int32, local_tbn [N,3,3],
+        sample_tbn_inv [N,3,3] (row `id` of the inverted patch frames)."""
+        from nerftex_hip import check, lib, ptr, stream
+
+        x = x.detach().float().contiguous()
+        N, dev, f = x.shape[0], x.device, self.features_imported
+        p_uv = torch.empty(N, 2, device=dev)
+        sdf = torch.empty(N, device=dev)
+        mask = torch.empty(N, dtype=torch.uint8, device=dev)
+        xin = torch.empty(N, 48, dtype=torch.float16, device=dev)
+        phi = torch.empty(N, 8, device=dev)
+        ids = torch.empty(N, dtype=torch.int32, device=dev)
+        local, sample = torch.empty(N, 9, device=dev), torch.empty(N, 9, device=dev)
+        mode, p0, p1, h0, h1, off, h = self._import_scalars()
+        check(lib.nerftex_planar_light_lookup(ptr(x), ptr(f), ptr(self.phi_embed_imported), ptr(self.frame_map_imported), ptr(self.sample_inv_rows_imported),
+                                              f.shape[0], f.shape[1], self.sample_inv_rows_imported.shape[0], mode, p0, p1, h0, h1, off, h, int(self.multires), N,
+                                              ptr(p_uv), ptr(sdf), ptr(mask), ptr(xin), ptr(phi), ptr(ids), ptr(local), ptr(sample), stream()))
+        return p_uv, sdf, mask.bool(), xin, phi, ids, local.view(N, 3, 3), sample.view(N, 3, 3)
+
+    @staticmethod
+    def _rotate_fine(local, local_tbn, sample_tbn_inv):
+        """tools/map.py:724-730: the local normal rotated by the texel's frame, then by the patch's inverted frame, normalised."""
+        fine = torch.einsum("nba,nb->na", local_tbn, local)
+        fine = torch.einsum("nba,nb->na", sample_tbn_inv, fine)
+        return fine / (fine.norm(dim=-1, keepdim=True) + 1e-5)
+
+    def _import_light_embed_reference(self, x, details=False):
+        """The import branch with `pred_normal` op by op, the reference's expressions (tools/map.py:649-675, :722-730) over grid_sample:
+        -> embed [N,41] fp32, normal_coarse, h_mask, normal_fine (details: + the sampled phi_embed, local_tbn, id and sample_tbn_inv rows)."""
+        embed, normal_coarse, h_mask = self._import_embed_reference(x)
+        x = x.float()
+        b0, b1 = (torch.tensor(b, dtype=torch.float32, device=x.device) for b in self.bounds)
+        p_sur = x[..., :2] * self.uv_utilize_rate if self.rescale else torch.stack([x[..., 0] / b0, x[..., 1] / b1], dim=-1)
+        grid = p_sur[None, None]
+
+        def image(m):  # [H, W, C] -> [1, C, W, H], as `_import_embed_reference`
+            return m.to(x.device).permute(2, 1, 0).unsqueeze(0)
+
+        gs = torch.nn.functional.grid_sample
+        ids = gs(image(self.sample_tbn_ids_imported[..., None]), grid, mode="nearest", align_corners=True, padding_mode="zeros")[0, 0, 0].long()
+        sample_tbn_inv = self.sample_tbn_inv_imported.to(x.device)[ids]
+        local_tbn = gs(image(self.local_tbn_imported), grid, mode="nearest", align_corners=True, padding_mode="zeros")[0, :, 0].permute(1, 0).reshape(-1, 3, 3)
+        phi = gs(image(self.phi_embed_imported), grid, align_corners=True, padding_mode="zeros")[0, :, 0].permute(1, 0)
+        x_embed, z_embed = embed[:, :self.encoder.output_dim], embed[:, self.encoder.output_dim:]
+        local = self.normal_net(phi_embed=phi, z_embed=z_embed, x_embed=x_embed)
+        fine = self._rotate_fine(local, local_tbn, sample_tbn_inv)
+        if details:
+            return embed, normal_coarse, h_mask, fine, phi, local_tbn, ids, sample_tbn_inv
+        return embed, normal_coarse, h_mask, fine
+
     def fine_normal(self, x, no_noise=False, requires_grad_xyz=False):
         """normal_fine of MeshFeatureField.forward (tools/map.py:637-641, 726-735): the factorized net's local normal rotated into the world by the
         hit face's frame, normalised.  -> (normal_fine [N,3], normal_coarse [N,3], h_mask [N])."""
@@ -782,14 +896,21 @@ class CurvedField(torch.nn.Module):
         projection carries `diff_project_layer`'s gradient, the hash table is looked up with input gradients (dy_dx) and the height ladder
         is evaluated by framework ops on the differentiable height -- dL/dembed reaches x."""
         if getattr(self, "imported", False):  # the import branch (:646-668): the map instead of the mesh and the table
-            if requires_grad_xyz or with_fine_normal:
+            lit_maps = self._lit() and self.phi_embed_imported is not None and not self._shape_active()
+            if requires_grad_xyz or (with_fine_normal and not lit_maps):
                 raise NotImplementedError("CurvedField.embed: an imported map is rendered without gradients to the sample position and without a fine normal")
+            if with_fine_normal:  # the `pred_normal` part (:670-675, :722-730): the normal net fed from the phi map, two rotations
+                if self._import_light_fused(x):
+                    _, _, h_mask, xin, phi, _, local_tbn, sample_tbn_inv = self._import_light_lookup(x)
+                    local = self.normal_net(phi_embed=phi, z_embed=xin[:, 16:self.in_dim], x_embed=xin[:, :16])
+                    return xin[:, :self.in_dim], self._import_normal(x, True), h_mask, self._rotate_fine(local, local_tbn, sample_tbn_inv)
+                return self._import_light_embed_reference(x)
             if self._shape_active():  # the 'shape' branch (:693-700): the map at the UV of the hit on the imported mesh
                 if self._import_fused(x):
                     _, _, h_mask, normal, _, xin = self._shape_lookup(x)
                     return xin[:, :self.in_dim], normal / (normal.norm(dim=-1, keepdim=True) + 1e-5), h_mask
                 return self._shape_embed_reference(x)
-            if self._import_fused(x):
+            if self._import_fused(x) or self._import_light_fused(x):
                 _, _, h_mask, xin = self._import_lookup(x)
                 return xin[:, :self.in_dim], self._import_normal(x, True), h_mask
             return self._import_embed_reference(x)
@@ -818,7 +939,7 @@ class CurvedField(torch.nn.Module):
         return _TruncExp.apply(h[..., 0]), h[..., 1:]
 
     def density(self, x, requires_grad_xyz=False):
-        if getattr(self, "imported", False) and not requires_grad_xyz and self._import_fused(x):
+        if getattr(self, "imported", False) and not requires_grad_xyz and (self._import_fused(x) or self._import_light_fused(x)):
             h_mask, xin = (self._shape_lookup(x)[i] for i in (2, 5)) if self._shape_active() else self._import_lookup(x)[2:]
             h = self.sigma_net(xin)
             sigma = _TruncExp.apply(h[..., 0])
@@ -1053,6 +1174,13 @@ class CurvedField(torch.nn.Module):
         """Whether nerftex_curved_light_infer serves this call: the SH light model with the switch `fused_light_infer` set (default: not), fp16
         autocast, the fused head (`light_net.fused`), no probabilistic table, the default shapes (the entry refuses every other one), no bounded
         angles, a visual mode the head has, fp16 tables, and what the entry asks of its buffers.  Everything else goes through forward()."""
+        nn = self.normal_net
+        return (self._infer_light_back_fused(x) and (nn.encoder.input_dim, nn.encoder.level_dim, nn.encoder.num_levels) == (3, 2, 4)
+                and self._infer_front_fused(x, d) and nn.encoder._table().dtype == torch.float16)
+
+    def _infer_light_back_fused(self, x):
+        """What the two lit chains ask alike (the light mid, the BRDF net, the head): the switch, the fused head, the normal nets' and the BRDF
+        net's default shapes, no bounded angles, a visual mode the head has, fp32 lighting of 1 or 3 colours."""
         if not (getattr(self, "light_model", None) == "SH" and getattr(self, "fused_light_infer", False)):
             return False
         from nerftex_hip import LIGHT_VISUAL
@@ -1061,34 +1189,30 @@ class CurvedField(torch.nn.Module):
         br = net.brdf_layer
         return (bool(net.fused) and nn is not None and not nn.bound_output and (self.training or self.light_visual_mode in LIGHT_VISUAL)
                 and x.is_cuda and br.dtype == torch.float16 and (br.input_dim, br.hidden_dim, br.num_layers, br.output_dim) == (16, 64, 3, 5)
-                and (nn.encoder.input_dim, nn.encoder.level_dim, nn.encoder.num_levels) == (3, 2, 4)
                 and (nn.low_freq_band_len_x, nn.low_freq_band_len_z) == (16, 12)
                 and [tuple(l.W.shape) for l in nn.phi_net.layers] == [(16, 20), (16, 16), (1, 16)]
                 and [tuple(l.W.shape) for l in nn.theta_net.layers] == [(16, 28), (16, 16), (1, 16)]
-                and net.envSHs.shape[0] >= 9 and net.envSHs.shape[1] in (1, 3) and net.envSHs.dtype == torch.float32
-                and self._infer_front_fused(x, d) and nn.encoder._table().dtype == torch.float16)
+                and net.envSHs.shape[0] >= 9 and net.envSHs.shape[1] in (1, 3) and net.envSHs.dtype == torch.float32)
+
+    def _infer_light_import_fused(self, x, d):
+        """Whether nerftex_curved_light_import_infer serves this call: _infer_light_fused()'s conditions without the neighbour search's and the
+        two tables', with the imported maps on x's device instead."""
+        s, B = self.sigma_net, x.shape[0]
+        return (getattr(self, "imported", False) and self._infer_light_back_fused(x) and self._import_light_fused(x)
+                and (s.input_dim, s.hidden_dim, s.num_layers, s.padded_output_dim) == (48, 32, 2, 16) and B % 128 == 0 and B > 0
+                and x.dtype == torch.float32 and d.dtype == torch.float32 and x.is_contiguous() and d.is_contiguous()
+                and all(m.device == x.device for m in (self.features_imported, self.phi_embed_imported, self.frame_map_imported, self.sample_inv_rows_imported)))
 
     def _infer_light_desc(self, x, d, live, sigma, rgbs, scratch, shading_normal=None):
         """The nerftex_curved_light_infer_desc of one call (and the tensors it points into).  Kept between calls and re-made when a parameter
         changes: the 16-bit MLP weights, and the normal net's packed block -- every LipLayer's normalization().half(), which is what the
         framework's half GEMM multiplies with under autocast, and its fp32 biases, in the order include/nerftex_hip.h gives."""
-        from gridencoder.grid import register_offsets
         from nerftex_hip import LIGHT_VISUAL, SH_LIGHT_SPECULAR, CurvedLightInferDesc, ptr
 
         nn, net = self.normal_net, self.light_net
         nenc, br = nn.encoder, net.brdf_layer
         ntable = nenc._table()
-        layers = list(nn.phi_net.layers) + list(nn.theta_net.layers)
-
-        def normal_block():
-            register_offsets(nenc.offsets, nenc.num_levels)
-            with torch.autocast("cuda", enabled=False):
-                nw = torch.cat([l.normalization().detach().float().half().reshape(-1) for l in layers]).contiguous()
-                nb = torch.cat([l.b.detach().float().reshape(-1) for l in layers]).contiguous()
-            return nw, nb
-
-        ws_h, wb_h, nw, nb = self._infer_weights("_infer_light_cache", br, (tuple((q.data_ptr(), q._version) for l in layers for q in (l.W, l.b, l.c)),),
-                                                 normal_block)
+        ws_h, wb_h, nw, nb = self._infer_light_weights()
         front, table = self._infer_front_desc(x, d, live, sigma, rgbs, scratch, ws_h)
         env = net.envSHs.detach()
         mode = "Full" if self.training else self.light_visual_mode
@@ -1101,6 +1225,49 @@ class CurvedField(torch.nn.Module):
             env_shs=ptr(env), n_sh=env.shape[0], n_color=env.shape[1], gamma=float(net.gamma), flags=SH_LIGHT_SPECULAR if net.use_specular else 0,
             visual_mode=LIGHT_VISUAL[mode], eval=int(not self.training), shading_normal=ptr(shading_normal), **front)
         return desc, (table, ntable, ws_h, wb_h, nw, nb, env)
+
+    def _infer_light_weights(self):
+        """-> (sigma net, BRDF net: 16-bit weights; the normal net's packed block: half weights, fp32 biases) of the two lit chains, kept between
+        calls (`_infer_weights`)."""
+        from gridencoder.grid import register_offsets
+
+        nn = self.normal_net
+        nenc = nn.encoder
+        layers = list(nn.phi_net.layers) + list(nn.theta_net.layers)
+
+        def normal_block():
+            register_offsets(nenc.offsets, nenc.num_levels)
+            with torch.autocast("cuda", enabled=False):
+                nw = torch.cat([l.normalization().detach().float().half().reshape(-1) for l in layers]).contiguous()
+                nb = torch.cat([l.b.detach().float().reshape(-1) for l in layers]).contiguous()
+            return nw, nb
+
+        return self._infer_weights("_infer_light_cache", self.light_net.brdf_layer, (tuple((q.data_ptr(), q._version) for l in layers for q in (l.W, l.b, l.c)),),
+                                   normal_block)
+
+    def _infer_light_import_desc(self, x, d, live, sigma, rgbs, scratch, shading_normal=None):
+        """The nerftex_curved_light_import_infer_desc of one call (and the tensors it points into, to be kept until the call is enqueued)."""
+        from nerftex_hip import LIGHT_VISUAL, SH_LIGHT_SPECULAR, CurvedLightImportInferDesc, ptr
+
+        net, s, f = self.light_net, self.sigma_net, self.features_imported
+        br = net.brdf_layer
+        phi, frame, rows = self.phi_embed_imported, self.frame_map_imported, self.sample_inv_rows_imported
+        ws_h, wb_h, nw, nb = self._infer_light_weights()
+        mode, p0, p1, h0, h1, off, h = self._import_scalars()
+        units, rows_per_unit = (ptr(live[0]), int(live[1])) if live is not None else (None, 0)
+        env = net.envSHs.detach()
+        visual = "Full" if self.training else self.light_visual_mode
+        desc = CurvedLightImportInferDesc(
+            xyz=ptr(x), dirs=ptr(d), B=x.shape[0], map=ptr(f), phi_map=ptr(phi), frame_map=ptr(frame), sample_tbn_inv=ptr(rows), map_h=f.shape[0],
+            map_w=f.shape[1], n_features=f.shape[2], n_phi=phi.shape[2], n_patches=rows.shape[0], mode=mode, plane_scale0=p0, plane_scale1=p1,
+            height_scale0=h0, height_scale1=h1, sdf_offset=off, h_threshold=h, n_freqs=int(self.multires), sigma_weights=ptr(ws_h), sigma_in=s.input_dim,
+            sigma_hidden=s.hidden_dim, sigma_layers=s.num_layers, sigma_out=s.padded_output_dim, normal_weights=ptr(nw), normal_biases=ptr(nb),
+            normal_hidden=16, normal_layers=2, brdf_weights=ptr(wb_h), brdf_in=br.input_dim, brdf_hidden=br.hidden_dim, brdf_layers=br.num_layers,
+            brdf_out=br.output_dim, env_shs=ptr(env), n_sh=env.shape[0], n_color=env.shape[1], gamma=float(net.gamma),
+            flags=SH_LIGHT_SPECULAR if net.use_specular else 0, visual_mode=LIGHT_VISUAL[visual], fc_weight=float(self.fc_weight), eval=int(not self.training),
+            sigma=ptr(sigma), rgbs=ptr(rgbs), shading_normal=ptr(shading_normal), units_dev=units, rows_per_unit=rows_per_unit, scratch=ptr(scratch),
+            scratch_bytes=scratch.numel())
+        return desc, (f, phi, frame, rows, ws_h, wb_h, nw, nb, env)
 
     def _infer_call(self, entry, make_desc, x, d, live, *more):
         """One call of the library entry `entry` (its scratch query is `entry`_scratch_bytes) over the descriptor make_desc builds: -> (sigma [B],
@@ -1136,6 +1303,12 @@ class CurvedField(torch.nn.Module):
         return self._infer_call("nerftex_curved_light_infer", self._infer_light_desc, x, d, live, shading_normal)
 
     @torch.no_grad()
+    def infer_light_import(self, x, d, live=None, shading_normal=None):
+        """infer() of the SH-lit field over its imported maps through nerftex_curved_light_import_infer (see `_infer_light_import_fused`, which
+        the caller has checked)."""
+        return self._infer_call("nerftex_curved_light_import_infer", self._infer_light_import_desc, x, d, live, shading_normal)
+
+    @torch.no_grad()
     def infer_padded(self, x, d):
         """infer(x, d) for a batch of ANY size (the reference loop's iterations, Renderer.render_infer): where the light model's fused chain
         applies but for the batch's size, the batch is padded to the next multiple of 128 with marked slots (which cost nothing) -- every
@@ -1146,7 +1319,11 @@ class CurvedField(torch.nn.Module):
             xp = torch.full((B + pad, 3), 1e30, dtype=x.dtype, device=x.device)
             dp = torch.full((B + pad, 3), 1e30, dtype=d.dtype, device=d.device)
             xp[:B], dp[:B] = x, d
-            if self._infer_light_fused(xp, dp):
+            if getattr(self, "imported", False):
+                if self._infer_light_import_fused(xp, dp):
+                    sigma, rgbs = self.infer_light_import(xp, dp)
+                    return sigma[:B], rgbs[:B]
+            elif self._infer_light_fused(xp, dp):
                 sigma, rgbs = self.infer_light(xp, dp)
                 return sigma[:B], rgbs[:B]
         return self.infer(x, d)
@@ -1162,8 +1339,11 @@ class CurvedField(torch.nn.Module):
         128) this is forward(x, d) on all rows, cast to fp32: slower, the same image.
         light_model="SH": forward(x, d) on all rows unless `fused_light_infer` is set (default False) -- then the light model's own chain,
         nerftex_curved_light_infer, under the same rows contract: sigma and the mask are forward()'s bit for bit, the shading normal and the
-        colour follow forward()'s arithmetic at its rounding points."""
+        colour follow forward()'s arithmetic at its rounding points; over imported maps, nerftex_curved_light_import_infer
+        (DESIGN.md 4.17)."""
         if getattr(self, "imported", False):  # an imported map: its own chain under the same rows contract, or forward() on all rows
+            if self._infer_light_import_fused(x, d):  # (opt-in, as the mesh field's lit chain: `fused_light_infer`)
+                return self.infer_light_import(x, d, live)
             if self._shape_active() and self._infer_import_fused(x, d):
                 return self._infer_call("nerftex_curved_shape_infer", self._infer_shape_desc, x, d, live)
             if not self._shape_active() and self._infer_import_fused(x, d):

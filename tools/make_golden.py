@@ -502,6 +502,9 @@ def main():
     if "--import-field-only" in sys.argv:
         import_field_goldens()
         return
+    if "--import-field-sh-only" in sys.argv:
+        import_field_sh_goldens()
+        return
     if "--import-shape-only" in sys.argv:
         import_shape_goldens()
         return
@@ -1211,6 +1214,134 @@ def import_field_goldens():
                 assert torch.equal(nc, torch.tensor([0.0, 0.0, 1.0]).expand_as(nc) / (1 + 1e-5))
             print("ref_python_import_field.npz:", key, "inside the mask", float(hm.float().mean()), "sigma max", float(sigma.max()))
     np.savez_compressed(os.path.join(OUT, "ref_python_import_field.npz"), **out)
+    new = [os.path.join(r, n) for r, _, names in os.walk(REF) for n in names if os.lstat(os.path.join(r, n)).st_mtime >= started]
+    assert not new, "files appeared under the reference tree:\n" + "\n".join(new[:20])
+
+
+def import_field_sh_goldens():
+    """ref_python_import_field_sh.npz: MeshFeatureField.import_field (tools/map.py:912-927) with all six arguments and the `pred_normal` part of
+    the `imported_type == 'field'` branch (:646-675, :722-730) executed, with network_curvedfield.NeRFNetwork.forward behind it in eval with
+    the real SH_EnvmapMaterialNet (light_model 'SH', white light), on the CPU under emulated_autocast.  A seeded 24 x 20 map set (16
+    features, 8 phi features, a frame and a patch id per texel), P = 5 patch frames; the frames are NOT orthonormal (inverse != transpose)
+    and differ per texel and per patch.  512 points: the first half uniform in [-1.1, 1.1]^2 x [-0.22, 0.22] (both sides of every edge with
+    `rescale`), the second in [-0.42, 0.42] x [-0.35, 0.35] x [-0.09, 0.09] (likewise without).  Mode A (`rescale` True: after the first
+    import) and mode B (after a second import), fc_weight 1.0 and 0.7, the four light_visual_modes.  Recorded: inputs, weights, h_mask, what
+    the four grid_sample calls and the table of inverted frames returned (a recorder around grid_sample and a hook on the normal net), the
+    fine normal, the shading normal handed to the head (a hook on the head), sigma and the four colours.  The normal net's weights are
+    scaled up so that its angles are of order 1.  Values only.  Reads one fixture (the sigma net's weights, as a check); writes this one."""
+    import time
+
+    import torch
+
+    started = time.time()
+    _install_map_imports()
+    _stub("imageio")
+    for name in ("nerf.sh_light_model", "nerf.network_curvedfield", "tools.shape_tools"):
+        sys.modules.pop(name, None)
+    for name, cls in (("sg_light_model", "SG_EnvmapMaterialNet"), ("envmap_light_model", "Envmap_EnvmapMaterialNet")):
+        _stub("nerf." + name, **{cls: None})
+    import nerf.network_curvedfield as ref_cf
+    import nerf.sh_light_model as ref_sh
+    import tools.map as ref_map
+    from tools.encoding import get_encoder
+
+    c = np.load(os.path.join(OUT, "ref_python_curvedfield.npz"))
+    H, W, P, grid_gap, h_threshold = 24, 20, 5, 1.0 / 32, 0.0625
+    rng = np.random.default_rng(171)
+    features = rng.uniform(-0.5, 0.5, (H, W, 16)).astype(np.float32)
+    phi_embed = rng.uniform(-0.5, 0.5, (H, W, 8)).astype(np.float32)
+    local_tbn = (np.eye(3, dtype=np.float32).reshape(9) + rng.normal(0, 0.35, (H, W, 9))).astype(np.float32)
+    sample_tbn = (np.eye(3, dtype=np.float32) + rng.normal(0, 0.3, (P, 3, 3))).astype(np.float32)
+    assert np.linalg.cond(sample_tbn.astype(np.float64)).max() < 50
+    assert np.abs(np.linalg.inv(sample_tbn.astype(np.float64)) - np.swapaxes(sample_tbn, 1, 2)).max() > 0.1, "inverse != transpose"
+    sample_tbn_ids = rng.integers(0, P, (H, W)).astype(np.float32)
+    pts = rng.uniform(-1.0, 1.0, (512, 3)).astype(np.float32)
+    pts[:256] *= np.array([1.1, 1.1, 0.22], np.float32)
+    pts[256:] *= np.array([0.42, 0.35, 0.09], np.float32)
+    dirs = rng.normal(size=(512, 3))
+    dirs = (dirs / np.linalg.norm(dirs, axis=-1, keepdims=True)).astype(np.float32)
+
+    mff = object.__new__(ref_map.MeshFeatureField)
+    torch.nn.Module.__init__(mff)
+    mff.device, mff.h_threshold, mff.K, mff.bound, mff.hash, mff.prob_model, mff.pred_normal, mff.clustering = "cpu", h_threshold, 8, 1, True, False, True, True
+    mff.imported, mff.imported_type, mff.rescale = False, None, False  # (the constructor's values, :604-618)
+    mff.sdf_scale_factor, mff.sdf_offset, mff.uv_utilize_rate, mff.K_for_uv = 1.0, 0.0, 1.0, 5
+    mff.encoder_f_out_dim = 16
+    mff.encoder_z, mff.encoder_z_outdim = get_encoder("frequency", input_dim=1, multires=12)
+    torch.manual_seed(11)
+    mff.normal_net = ref_map.Factorized_Normal_Net(x_dim=mff.encoder_f_out_dim, z_dim=mff.encoder_z_outdim, lip=True, direct_pred_coor=False, bound_output=False)
+    gen = torch.Generator().manual_seed(13)
+    with torch.no_grad():
+        for mlp in (mff.normal_net.phi_net, mff.normal_net.theta_net):
+            for layer in mlp.layers:
+                layer.W.mul_(6.0)
+                layer.b.copy_(torch.randn(layer.b.shape, generator=gen) * 0.3)
+                layer.c.fill_(2.0)
+    net = object.__new__(ref_cf.NeRFNetwork)
+    torch.nn.Module.__init__(net)
+    net.visual_mode, net.render_light_model, net.use_grad_normal, net.fc_weight, net.dir_degree = "RGB", True, False, 1.0, 4
+    net.optimize_gamma, net.meshfea_field, net.light_model, net.smooth_grad_weight = False, mff, "SH", 1e-1
+    net.use_coarse_normal, net.coarse_as_primary, net.no_visibility, net.shade_visibility, net.light_visual_mode = False, False, False, True, "Full"
+    tcnn = sys.modules["tinycudann"]
+    torch.manual_seed(42)
+    net.sigma_net = tcnn.Network(n_input_dims=mff.encoder_z_outdim + mff.encoder_f_out_dim, n_output_dims=16,
+                                 network_config={"otype": "FullyFusedMLP", "activation": "ReLU", "output_activation": "None", "n_neurons": 32, "n_hidden_layers": 1})
+    assert np.array_equal(net.sigma_net.net.weights.detach().numpy(), c["w_sigma"]), "the sigma net of ref_python_curvedfield.npz"
+    net.color_net = None
+    net.light_net = ref_sh.SH_EnvmapMaterialNet(input_dim=15, sh_order=3, white_light=True, use_specular=True)
+    with torch.no_grad():
+        net.light_net.envSHs[1:] = torch.from_numpy(np.random.default_rng(91).normal(0, 1.5, (15, 1)).astype(np.float32))
+    out = dict(features=features, phi_embed=phi_embed, local_tbn=local_tbn, sample_tbn=sample_tbn, sample_tbn_ids=sample_tbn_ids, grid_gap=grid_gap,
+               h_threshold=h_threshold, xyz=pts, dirs=dirs, w_sigma=c["w_sigma"], w_brdf=net.light_net.brdf_layer.net.weights.detach().numpy().copy(),
+               env_shs=net.light_net.envSHs.detach().numpy().copy())
+    for name, mlp in (("phi", mff.normal_net.phi_net), ("theta", mff.normal_net.theta_net)):
+        for i, layer in enumerate(mlp.layers):
+            out[f"{name}_W{i}"], out[f"{name}_b{i}"], out[f"{name}_c{i}"] = layer.W.detach().numpy().copy(), layer.b.detach().numpy().copy(), float(layer.c)
+    handed, sampled = {}, []
+    net.light_net.register_forward_pre_hook(lambda m, a: handed.update(normal=a[1].detach().float().numpy().copy()))
+    mff.normal_net.register_forward_pre_hook(lambda m, a, k: handed.update(phi=k["phi_embed"].detach().float().numpy().copy()), with_kwargs=True)
+    real_grid_sample = torch.nn.functional.grid_sample
+
+    def recording_grid_sample(*a, **k):
+        r = real_grid_sample(*a, **k)
+        sampled.append((k.get("mode", "bilinear"), r))
+        return r
+
+    x, d = torch.from_numpy(pts), torch.from_numpy(dirs)
+    net.eval()
+    torch.nn.functional.grid_sample = recording_grid_sample
+    try:
+        for mode in ("A", "B"):
+            mff.import_field(features, bounds=[0.5 * grid_gap * H, 0.5 * grid_gap * W], sample_tbn=sample_tbn, sample_tbn_ids=sample_tbn_ids, local_tbn=local_tbn,
+                             phi_embed=phi_embed)
+            assert mff.rescale == (mode == "A") and tuple(mff.phi_embed_imported.shape) == (1, 8, W, H)
+            with torch.no_grad(), emulated_autocast():
+                del sampled[:]
+                embed, nc, nf, hm = mff(x)
+                assert [m for m, _ in sampled] == ["bilinear", "nearest", "nearest", "bilinear"]  # features, ids, local_tbn, phi_embed (:663-674)
+                ids = sampled[1][1].squeeze().long()
+                s_local = sampled[2][1].squeeze().permute(1, 0).reshape(-1, 3, 3)
+                s_phi = sampled[3][1].squeeze().permute(1, 0)
+                assert np.array_equal(s_phi.numpy(), handed["phi"])
+                assert torch.equal(nc, torch.tensor([0.0, 0.0, 1.0]).expand_as(nc) / (1 + 1e-5))
+                out.update({mode + "_h_mask": hm.numpy(), mode + "_embed": embed.float().numpy(), mode + "_phi": s_phi.numpy(), mode + "_local_tbn": s_local.numpy(),
+                            mode + "_id": ids.numpy().astype(np.int32), mode + "_sample_tbn_inv": mff.sample_tbn_inv_imported[ids].numpy(),
+                            mode + "_normal_fine": nf.float().numpy()})
+                for fc in (1.0, 0.7):
+                    net.fc_weight = fc
+                    key = f"{mode}_fc{fc}"
+                    for visual in ("Full", "Specular", "Diffuse", "Albedo"):
+                        net.light_visual_mode = visual
+                        sigma, color, ret = net(x, d, is_gui_mode=False)
+                        assert ret == {}
+                        out[f"{key}_color_{visual.lower()}"] = color.float().numpy()
+                    out[mode + "_sigma"], out[key + "_shading_normal"] = sigma.float().numpy(), handed["normal"]
+                print("ref_python_import_field_sh.npz:", mode, "inside the mask", float(hm.float().mean()), "sigma max", float(sigma.max()),
+                      "fine normal away from the texel frame's third row by (median)", float(np.median(np.abs(nf.numpy() - s_local.numpy()[:, 2]).max(-1)[hm.numpy()])))
+    finally:
+        torch.nn.functional.grid_sample = real_grid_sample
+    out["sample_tbn_inv"] = mff.sample_tbn_inv_imported.numpy().copy()
+    np.savez_compressed(os.path.join(OUT, "ref_python_import_field_sh.npz"), **out)
     new = [os.path.join(r, n) for r, _, names in os.walk(REF) for n in names if os.lstat(os.path.join(r, n)).st_mtime >= started]
     assert not new, "files appeared under the reference tree:\n" + "\n".join(new[:20])
 
