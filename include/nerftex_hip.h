@@ -1101,6 +1101,93 @@ size_t nerftex_curved_light_import_infer_scratch_bytes(uint32_t B);
 int nerftex_curved_light_import_infer(const nerftex_curved_light_import_infer_desc* d, void* stream);
 
 /* -------------------------------------------------------------------------
+ * Extension: the imported maps on a NEW UV-MAPPED MESH under the SH light model -- the `pred_normal` part of the 'shape' branch of
+ * MeshFeatureField.forward (tools/map.py:693-707, :722-730): nerftex_shape_lookup's work for one sample, plus, at the row's own (u, v), the lit
+ * reads of nerftex_planar_light_lookup (the nearest frame texel, the patch frame that hangs on its id, the bilinear phi read), plus the hit
+ * face's frame new_tbn = face_tbn[face] (:542; face -1, a double miss, reads face 0 as the reference does -- its mask is 0).
+ *   face_tbn [n_tbn_faces, NERFTEX_FRAME_MAP_STRIDE] fp32, 16-byte aligned, indexed by the ORIGINAL face id (not the BVH's order): the 9 floats
+ *   of the face's frame (rows t, b, n of calculate_tbn, :119-138, over the normalised mesh and the [-1, 1] UVs), three zeros.
+ * One launch behind the neighbour search, two lanes per point as nerftex_shape_lookup: the (u, v)-dependent reads sit on the lane that reads the
+ * features, the face frame on the lane that writes the height ladder.  No rounding point is new: the values are the two lookups' own.
+ * A row whose normal is not finite reads no face, UV, frame or texel of any map: nerftex_shape_lookup's constants, and zeros for phi and all
+ * three frames, patch_id = -1.
+ * nerftex_shape_light_lookup is the plain form (any N, every row): p_uv, sdf, mask, normal, face_idx, xin bit for bit nerftex_shape_lookup's;
+ * phi [N,8] fp32 (the rows form narrows exactly these values to half); patch_id [N] int32; local_tbn, sample_tbn, new_tbn [N,9] fp32.
+ * NERFTEX_ERR_INVALID before anything is launched, in this order: nerftex_shape_lookup's refusals over the arguments the two share (a NULL
+ * pointer; K or n_verts; n_faces other than the raytracer's triangle count; map extents; n_freqs; alignment of the map and of xin; scales,
+ * threshold; offset); then nerftex_planar_light_lookup's over what this entry adds (n_patches outside 1..2^24; a NULL lit map, patch frames,
+ * face_tbn or lit output; a lit map, the patch frames, face_tbn or phi not 16-byte aligned); then n_tbn_faces other than the raytracer's
+ * triangle count.  (N == 0 returns NERFTEX_OK behind these; N above 2^31 - 1 is refused last.)
+ *
+ * nerftex_curved_light_shape_infer: the lit field's whole no-grad forward over the maps on the new mesh as ONE call under the rows contract of
+ * nerftex_curved_light_infer, six launches, nothing allocated, capturable --
+ *   neighbour search (K) -> lit shape lookup -> sigma net 48 -> 32 -> 16 -> light mid (the normal net fed from phi_map; the local normal rotated
+ *   by the texel's frame, then by the patch's inverted frame, then by the new mesh's face frame: three half products one after the other, each
+ *   result rounded to half -- the frames are NEVER multiplied together; the two normalisations; in eval the fc_weight blend with the coarse
+ *   normal of the new mesh) -> BRDF net 16 -> 64 x 3 -> 16 -> light out.
+ *   rows >= live                      no work; sigma / rgbs / shading_normal keep what they held.
+ *   live rows the march marked unused no search, no traversal, no texel of any map; sigma = 0, rgbs = 0, shading_normal = 0.
+ *   every other live row              sigma and the mask bit for bit the field's forward(); rgbs, shading_normal as nerftex_curved_light_infer.
+ * NERFTEX_ERR_INVALID with a message, before anything is launched, in this order: a NULL descriptor; B % 128 != 0; n_verts outside 1..2^31-1;
+ * K outside 1..16; n_features other than 16, n_phi other than 8 or other network shapes than the default SH field's; n_sh, n_color, gamma,
+ * flags, visual_mode, eval as nerftex_curved_light_infer; a NULL raytracer or n_faces other than its triangle count; the map extents, n_freqs,
+ * map alignment, scales and offset as nerftex_shape_lookup; n_patches outside 1..2^24; n_tbn_faces other than n_faces; (B == 0 returns
+ * NERFTEX_OK here;) a NULL pointer, a scratch that is not 256-byte aligned or smaller than nerftex_curved_light_shape_infer_scratch_bytes(B);
+ * a lit map, the patch frames, face_tbn or an MLP weight vector not 16-byte aligned, the normal net's block not 4-byte aligned.
+ * ------------------------------------------------------------------------- */
+int nerftex_shape_light_lookup(const nerftex_raytracer* rt, const float* xyz, const int32_t* knn_idx, const float* knn_dist, uint32_t N, uint32_t K,
+                               const float* mesh_vertices, const float* vertex_normals, uint32_t n_verts, const float* face_uv, uint32_t n_faces,
+                               const float* face_tbn, uint32_t n_tbn_faces, const float* map, const float* phi_map, const float* frame_map,
+                               const float* sample_tbn_inv, uint32_t map_h, uint32_t map_w, uint32_t n_patches, float sdf_scale, float sdf_offset,
+                               float uv_rate, float h_threshold, uint32_t n_freqs, float* p_uv, float* sdf, uint8_t* mask, float* normal,
+                               int64_t* face_idx, void* xin, float* phi, int32_t* patch_id, float* local_tbn, float* sample_tbn, float* new_tbn,
+                               void* stream);
+typedef struct nerftex_curved_light_shape_infer_desc {
+    const nerftex_knn* knn;            /* the NEW mesh's neighbour grid                                                           */
+    const nerftex_raytracer* tracer;   /* the NEW mesh's BVH                                                                      */
+    const float* xyz;                  /* [B,3] sample positions                                                                  */
+    const float* dirs;                 /* [B,3] view directions; dirs[row][0] > 1e29 marks an unused slot                         */
+    uint32_t B;
+    uint32_t n_verts;
+    const float* mesh_vertices;        /* [n_verts,3]                                                                             */
+    const float* vertex_normals;       /* [n_verts,3]                                                                             */
+    const float* face_uv;              /* [n_faces,6]                                                                             */
+    const float* face_tbn;             /* [n_tbn_faces, NERFTEX_FRAME_MAP_STRIDE] fp32, 16-byte aligned: see above                */
+    uint32_t n_faces, n_tbn_faces;
+    uint32_t K;                        /* neighbours per point (K_for_uv)                                                         */
+    const float* map;                  /* [map_h, map_w, n_features] fp32, 16-byte aligned                                        */
+    const float* phi_map;              /* [map_h, map_w, n_phi] fp32, 16-byte aligned                                             */
+    const float* frame_map;            /* [map_h, map_w, NERFTEX_FRAME_MAP_STRIDE] fp32, 16-byte aligned                          */
+    const float* sample_tbn_inv;       /* [n_patches, NERFTEX_FRAME_MAP_STRIDE] fp32, 16-byte aligned                             */
+    uint32_t map_h, map_w, n_features, n_phi, n_patches;
+    float sdf_scale, sdf_offset, uv_rate, h_threshold;
+    uint32_t n_freqs;                  /* FreqEncoder(height) bands (multires)                                                    */
+    const void* sigma_weights;         /* fp16, 16-byte aligned                                                                   */
+    uint32_t sigma_in, sigma_hidden, sigma_layers, sigma_out;
+    const void* normal_weights;        /* fp16 [NERFTEX_NORMAL_NET_WEIGHTS], 4-byte aligned: as nerftex_curved_light_infer_desc   */
+    const float* normal_biases;        /* fp32 [NERFTEX_NORMAL_NET_BIASES]                                                        */
+    uint32_t normal_hidden, normal_layers; /* 16, 2                                                                               */
+    const void* brdf_weights;          /* fp16, 16-byte aligned                                                                   */
+    uint32_t brdf_in, brdf_hidden, brdf_layers, brdf_out;
+    const float* env_shs;              /* [n_sh, n_color] fp32, as nerftex_sh_light_desc                                          */
+    uint32_t n_sh, n_color;
+    float gamma;
+    uint32_t flags;                    /* NERFTEX_SH_LIGHT_SPECULAR                                                               */
+    uint32_t visual_mode;              /* NERFTEX_LIGHT_VISUAL_*                                                                  */
+    float fc_weight;
+    int eval;                          /* as nerftex_curved_light_infer_desc                                                      */
+    float* sigma;                      /* [B] fp32                                                                                */
+    float* rgbs;                       /* [B,3] fp32                                                                              */
+    float* shading_normal;             /* [B,3] fp32 or NULL (not written)                                                        */
+    const int32_t* units_dev;
+    uint32_t rows_per_unit;
+    void* scratch;                     /* caller-owned, 256-byte aligned, >= nerftex_curved_light_shape_infer_scratch_bytes(B)    */
+    size_t scratch_bytes;
+} nerftex_curved_light_shape_infer_desc;
+size_t nerftex_curved_light_shape_infer_scratch_bytes(uint32_t B);
+int nerftex_curved_light_shape_infer(const nerftex_curved_light_shape_infer_desc* d, void* stream);
+
+/* -------------------------------------------------------------------------
  * Extension: the SH light head of the curved field -- SH_EnvmapMaterialNet.forward behind its BRDF MLP (nerf/sh_light_model.py:554-616) -- as one
  * streaming kernel per direction instead of ~40 framework ops per sample batch, the framework's arithmetic at its rounding points:
  *   albedo = half(sigmoid(brdf[:, :3])), spec_w = half(sigmoid(brdf[:, 3]))              (fp32 sigmoid narrowed to half)

@@ -44,6 +44,27 @@ int curved_shape_rows(const nerftex_raytracer* rt, const float* xyz, const float
                       const float* mesh_vertices, const float* vertex_normals, uint32_t n_verts, const ShapeLookup& s, uint8_t* mask, float* normal,
                       const int32_t* units_dev, uint32_t rows_per_unit, hipStream_t st);
 
+// The lit shape lookup (raytracer.hip: the same lookup under the SH light model) -- what nerftex_shape_light_lookup and
+// nerftex_curved_light_shape_infer hand it beside a ShapeLookup.
+struct ShapeLight {
+    const float* phi_map;         // [map_h, map_w, 8] fp32
+    const float* frame_map;       // [map_h, map_w, 12] fp32
+    const float* sample_tbn_inv;  // [n_patches, 12] fp32
+    uint32_t n_patches;
+    const float* face_tbn;        // [n_tbn_faces, 12] fp32, by original face id
+    uint32_t n_tbn_faces;
+    void* phi;                    // rows form: half [4,N,2]; plain form: fp32 [N,8]
+    float *local_tbn, *sample_tbn, *new_tbn;  // [N,9] each
+};
+// NULL, or why the two entries refuse these values -- in the order include/nerftex_hip.h documents: n_patches, a NULL pointer, alignment of the
+// maps, the frames and phi, then a face_tbn that does not hold the tracer's n_triangles faces
+const char* shape_light_refusal(const ShapeLight& t, uint32_t n_triangles);
+// curved_shape_rows plus the lit reads for unmarked live rows: phi (half, level-major), local_tbn, sample_tbn and new_tbn.  A marked live row,
+// or one whose normal is not finite, reads no face, UV, frame or texel and writes zeros for all four on top of curved_shape_rows' constants.
+int curved_shape_light_rows(const nerftex_raytracer* rt, const float* xyz, const float* dirs, const int32_t* knn_idx, const float* knn_dist, uint32_t N,
+                            uint32_t K, const float* mesh_vertices, const float* vertex_normals, uint32_t n_verts, const ShapeLookup& s, const ShapeLight& t,
+                            uint8_t* mask, float* normal, const int32_t* units_dev, uint32_t rows_per_unit, hipStream_t st);
+
 // nerftex_ffmlp_inference (fp16, ReLU, no output activation) of the curved field's networks -- (IN, H, NL) = (48, 32, 2), (32, 64, 3) or the SH
 // light head's BRDF net (16, 64, 3) -- over the 128-row workgroups that hold a live row; a workgroup wholly past the live rows exits before it
 // stages its weights.

@@ -127,7 +127,7 @@ extern "C" int nerftex_curved_light_infer(const nerftex_curved_light_infer_desc*
     if ((rc = curved_front_sigma(d, sc.f, "curved_light_infer(pack)", stream)) != NERFTEX_OK) return rc;
     {
         KernelTimer kt("curved_light_mid_rows_kernel", st);
-        hipLaunchKernelGGL(curved_light_mid_rows_kernel<false>, grid, block, 0, st, sc.f.h, sc.f.xin, sc.n_lbc, sc.f.normal, sc.tbn, nullptr, d->dirs,
+        hipLaunchKernelGGL(curved_light_mid_rows_kernel<1>, grid, block, 0, st, sc.f.h, sc.f.xin, sc.n_lbc, sc.f.normal, sc.tbn, nullptr, nullptr, d->dirs,
                            static_cast<const half_t*>(d->normal_weights), d->normal_biases, B, d->fc_weight, d->eval, sc.sigma_raw, sc.brdf_in, shading, units, rpu);
     }
     if ((rc = check_launch("curved_light_infer(mid)")) != NERFTEX_OK) return rc;

@@ -11,6 +11,7 @@
 #include "common.hpp"
 #include "curved_infer.hpp"
 #include "height_ladder.hpp"
+#include "lit_reads.hpp"
 #include "sh_common.hpp"
 
 #include <cmath>
@@ -297,11 +298,13 @@ __device__ __forceinline__ float lip_mlp_row(const float (&x)[IN], const float* 
 // TWO (the imported map's chain, planar_light.inc): tbn2 [B,9] is a second frame the rotated normal is rotated by once more (tools/map.py:726-727, the
 // sampled patch's inverted frame), the same half product on the first one's half result -- the reference rounds between the two, so the frames are
 // not multiplied together.  Without it (the mesh chain) tbn2 is not read.
-template <bool TWO>
+// FRAMES = 3 (the imported map on a new mesh, shape_light.inc): tbn3 [B,9], the new mesh's hit face's frame, rotates the second rotation's half
+// result once more (tools/map.py:728-729) -- the same half product again.  FRAMES counts the rotations: 1 the mesh chain, 2 the planar maps.
+template <int FRAMES>
 __device__ __forceinline__ void curved_light_mid_row(const uint32_t b, const uint32_t B, const half_t* __restrict__ h, const half_t* __restrict__ xin,
                                                      const half_t* __restrict__ n_lbc, const float* __restrict__ normal, const float* __restrict__ tbn,
-                                                     const float* __restrict__ tbn2, const float* __restrict__ w, const float* __restrict__ bias, const float fc,
-                                                     const int eval,
+                                                     const float* __restrict__ tbn2, const float* __restrict__ tbn3, const float* __restrict__ w,
+                                                     const float* __restrict__ bias, const float fc, const int eval,
                                                      float* __restrict__ sigma_raw, half_t* __restrict__ brdf_in, float* __restrict__ shading) {
 #pragma clang fp contract(off)  // every framework op rounds on its own
     const half8_t h0 = *reinterpret_cast<const half8_t*>(h + (size_t)b * 16);
@@ -351,11 +354,19 @@ __device__ __forceinline__ void curved_light_mid_row(const uint32_t b, const uin
     for (int k = 0; k < 9; k++) th[k] = (float)(half_t)tbn[(size_t)b * 9 + k];
 #pragma unroll
     for (int a = 0; a < 3; a++) n[a] = (float)narrow((th[a] * lh[0] + th[3 + a] * lh[1]) + th[6 + a] * lh[2]);
-    if constexpr (TWO) {
+    if constexpr (FRAMES >= 2) {
 #pragma unroll
         for (int k = 0; k < 3; k++) lh[k] = n[k];  // (half values already)
 #pragma unroll
         for (int k = 0; k < 9; k++) th[k] = (float)(half_t)tbn2[(size_t)b * 9 + k];
+#pragma unroll
+        for (int a = 0; a < 3; a++) n[a] = (float)narrow((th[a] * lh[0] + th[3 + a] * lh[1]) + th[6 + a] * lh[2]);
+    }
+    if constexpr (FRAMES >= 3) {
+#pragma unroll
+        for (int k = 0; k < 3; k++) lh[k] = n[k];  // (the second rotation's half result as it is)
+#pragma unroll
+        for (int k = 0; k < 9; k++) th[k] = (float)(half_t)tbn3[(size_t)b * 9 + k];
 #pragma unroll
         for (int a = 0; a < 3; a++) n[a] = (float)narrow((th[a] * lh[0] + th[3 + a] * lh[1]) + th[6 + a] * lh[2]);
     }
@@ -382,11 +393,11 @@ __device__ __forceinline__ void curved_light_mid_row(const uint32_t b, const uin
 
 // One thread per row.  The net's weights (1312 half values, 66 biases: 5.4 KiB as fp32) are staged once per workgroup in LDS -- every lane of a wave
 // reads the same word at the same time (a broadcast, no bank conflict), and 1.3 k words per row would not stay in scalar registers.  A workgroup wholly
-// past the live rows leaves before it stages anything.  TWO: curved_light_mid_row's second frame.
-template <bool TWO>
+// past the live rows leaves before it stages anything.  FRAMES: curved_light_mid_row's count of rotations (tbn, then tbn2, then tbn3).
+template <int FRAMES>
 __global__ __launch_bounds__(256) void curved_light_mid_rows_kernel(const half_t* __restrict__ h, const half_t* __restrict__ xin, const half_t* __restrict__ n_lbc,
                                                                    const float* __restrict__ normal, const float* __restrict__ tbn, const float* __restrict__ tbn2,
-                                                                   const float* __restrict__ dirs,
+                                                                   const float* __restrict__ tbn3, const float* __restrict__ dirs,
                                                                    const half_t* __restrict__ nn_weights, const float* __restrict__ nn_biases, uint32_t B,
                                                                    const float fc, const int eval, float* __restrict__ sigma_raw, half_t* __restrict__ brdf_in,
                                                                    float* __restrict__ shading, const int32_t* __restrict__ units_dev, uint32_t rows_per_unit) {
@@ -404,7 +415,7 @@ __global__ __launch_bounds__(256) void curved_light_mid_rows_kernel(const half_t
         for (int c = 0; c < 3; c++) shading[(size_t)b * 3 + c] = 0.0f;
         return;
     }
-    curved_light_mid_row<TWO>(b, B, h, xin, n_lbc, normal, tbn, tbn2, w_s, b_s, fc, eval, sigma_raw, brdf_in, shading);
+    curved_light_mid_row<FRAMES>(b, B, h, xin, n_lbc, normal, tbn, tbn2, tbn3, w_s, b_s, fc, eval, sigma_raw, brdf_in, shading);
 }
 
 // ---- the front half nerftex_curved_field_infer and nerftex_curved_light_infer (curved_light.inc) share: neighbour search to sigma net ------------------
@@ -675,3 +686,6 @@ extern "C" int nerftex_field_out_backward(const float* grad_rgbs, const float* r
 
 // ---- the imported map under the SH light model (nerftex_planar_light_lookup, nerftex_curved_light_import_infer): behind both -----------------------------
 #include "planar_light.inc"
+
+// ---- the imported map on a new mesh under the SH light model (nerftex_curved_light_shape_infer): the lit shape lookup (raytracer.hip) in front ----------
+#include "shape_light.inc"

@@ -2,31 +2,14 @@
 // :722-730) -- beside the feature read of planar.inc, a bilinear read of the [H, W, 8] phi map (the normal net's own table features), a nearest read
 // of the per-texel frame and patch id, and the patch's inverted frame -- as one launch (nerftex_planar_light_lookup), and the lit field's no-grad
 // forward over it as one device-count call (nerftex_curved_light_import_infer).  Included at the end of fieldglue.hip behind curved_light.inc: the
-// row function of the lookup is planar.inc's, the mid kernel fieldglue.hip's (its second frame), the closing kernel curved_light.inc's.
+// row function of the lookup is planar.inc's, the lit reads lit_reads.hpp's, the mid kernel fieldglue.hip's (its second frame), the closing kernel
+// curved_light.inc's.
 //
 // Lane mapping: one thread per row (planar.inc's LANES = 1; DESIGN.md 4.15 measured the four-lane mapping no faster for the feature read, and the
 // 6 + 3 + 3 sixteen-byte words a row reads here beside the features do not split over four lanes evenly).  DESIGN.md 4.17.
 
 namespace nerftex {
 namespace {
-
-struct PlanarLightArgs {
-    const float* phi_map;     // [H, W, 8] fp32, channel-last, 16-byte aligned
-    const float* frame_map;   // [H, W, 12] fp32, 16-byte aligned: a texel is three 16-byte words -- the 9 floats of its frame, its patch id, two zeros
-    const float* sample_inv;  // [P, 12] fp32, 16-byte aligned: the 9 floats of patch p's inverted frame, three zeros
-    uint32_t P;
-};
-
-// grid_sample(mode='nearest', align_corners=True, padding zeros)'s texel of a map whose FIRST axis u runs along: ix = ((u + 1) / 2) (size - 1) in
-// fp32, rounded half to even; -> false outside the map (zeros; a NaN fails the comparisons).  The index is converted only inside the range.
-__device__ __forceinline__ bool nearest_texel(const uint32_t H, const uint32_t W, const float u, const float v, size_t& texel) {
-#pragma clang fp contract(off)
-    const float iu = ((u + 1.0f) / 2.0f) * (float)(H - 1), iv = ((v + 1.0f) / 2.0f) * (float)(W - 1);
-    const float ri = nearbyintf(iu), rj = nearbyintf(iv);
-    if (!(ri >= 0.0f && ri <= (float)(H - 1) && rj >= 0.0f && rj <= (float)(W - 1))) return false;
-    texel = (size_t)(int)ri * (size_t)W + (size_t)(int)rj;
-    return true;
-}
 
 // ROWS: the rows contract; phi goes out as half, level-major [4, B, 2] (what curved_light_mid_row reads as n_lbc); id_out is not written.
 // Otherwise the plain form: every row, phi as fp32 [B, 8] (the values the half ones are the narrowing of), the sampled id [B].
@@ -42,43 +25,7 @@ __global__ __launch_bounds__(256) void planar_light_lookup_rows_kernel(const flo
     uint32_t b, q;
     float u, v;
     if (!planar_lookup_row<ROWS, 1>(xyz, dirs, B, a, p_uv, sdf_out, mask, normal, xin, units_dev, rows_per_unit, b, q, u, v)) return;
-    // the nearest reads first: the patch's frame hangs on the texel's id, the longest chain of dependent loads in the row
-    const float4_t zero = {0.0f, 0.0f, 0.0f, 0.0f};
-    float4_t f[3] = {zero, zero, zero}, s[3] = {zero, zero, zero};
-    size_t texel;
-    if (nearest_texel(a.H, a.W, u, v, texel)) {
-        const float4_t* src = reinterpret_cast<const float4_t*>(l.frame_map + texel * 12);
-#pragma unroll
-        for (int k = 0; k < 3; k++) f[k] = src[k];
-    }
-    const float idf = f[2][1];
-    const int32_t id = (idf > -1.0f && idf < (float)l.P) ? (int32_t)idf : -1;  // (.long() truncates towards zero)
-    if (id >= 0) {
-        const float4_t* src = reinterpret_cast<const float4_t*>(l.sample_inv + (size_t)id * 12);
-#pragma unroll
-        for (int k = 0; k < 3; k++) s[k] = src[k];
-    }
-    if constexpr (ROWS) {
-        half4_t o[2];
-        bilinear_read<1, 8>(l.phi_map, a.H, a.W, u, v, 0u, o);
-        half_t* n_lbc = static_cast<half_t*>(phi_out);
-#pragma unroll
-        for (int lv = 0; lv < 4; lv++) {
-            const half2_t pair = {o[lv / 2][2 * (lv % 2)], o[lv / 2][2 * (lv % 2) + 1]};
-            *reinterpret_cast<half2_t*>(n_lbc + ((size_t)lv * B + b) * 2) = pair;
-        }
-    } else {
-        float4_t o[2];
-        bilinear_read<1, 8, float4_t>(l.phi_map, a.H, a.W, u, v, 0u, o);
-        float4_t* dst = reinterpret_cast<float4_t*>(static_cast<float*>(phi_out) + (size_t)b * 8);
-        dst[0] = o[0]; dst[1] = o[1];
-        id_out[b] = id;  // (-1: a texel whose id is not in [0, P))
-    }
-#pragma unroll
-    for (int k = 0; k < 9; k++) {
-        local_tbn[(size_t)b * 9 + k] = f[k / 4][k % 4];
-        sample_tbn[(size_t)b * 9 + k] = s[k / 4][k % 4];
-    }
+    lit_reads_row<ROWS>(l, a.H, a.W, u, v, b, B, phi_out, id_out, local_tbn, sample_tbn);  // (lit_reads.hpp: the reads the lit shape lookup shares)
 }
 
 template <bool ROWS>
@@ -208,8 +155,8 @@ extern "C" int nerftex_curved_light_import_infer(const nerftex_curved_light_impo
     if ((rc = ffmlp_inference_rows(sc.xin, d->sigma_weights, B, 48, 32, 2, sc.h, units, rpu, st)) != NERFTEX_OK) return rc;
     {
         KernelTimer kt("curved_light_mid_rows_kernel", st);
-        hipLaunchKernelGGL(curved_light_mid_rows_kernel<true>, dim3(div_up(B, 256u)), dim3(256), 0, st, sc.h, sc.xin, sc.n_lbc, sc.normal, sc.local_tbn, sc.sample_tbn,
-                           d->dirs, static_cast<const half_t*>(d->normal_weights), d->normal_biases, B, d->fc_weight, d->eval, sc.sigma_raw, sc.brdf_in, shading, units,
+        hipLaunchKernelGGL(curved_light_mid_rows_kernel<2>, dim3(div_up(B, 256u)), dim3(256), 0, st, sc.h, sc.xin, sc.n_lbc, sc.normal, sc.local_tbn, sc.sample_tbn,
+                           nullptr, d->dirs, static_cast<const half_t*>(d->normal_weights), d->normal_biases, B, d->fc_weight, d->eval, sc.sigma_raw, sc.brdf_in, shading, units,
                            rpu);
     }
     if ((rc = check_launch("curved_light_import_infer(mid)")) != NERFTEX_OK) return rc;

@@ -16,6 +16,7 @@
 #include "common.hpp"
 #include "curved_infer.hpp"
 #include "height_ladder.hpp"
+#include "lit_reads.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -405,18 +406,32 @@ __device__ __forceinline__ float dot_plain(const V3& a, const V3& b) { return (a
 __device__ __forceinline__ float norm_plain(const V3& a) { return sqrtf(dot_plain(a, a)); }
 __device__ __forceinline__ V3 cross_plain(const V3& a, const V3& b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
 
+// What the LIT form reads and writes beside that (nerftex_shape_light_lookup, nerftex_curved_light_shape_infer: the `pred_normal` part of the
+// branch, tools/map.py:702-707, and the hit face's frame, :542): the three maps of lit_reads.hpp at the row's own (u, v), and per-face frames.
+struct ShapeLitArgs {
+    PlanarLightArgs l;
+    const float* face_tbn;  // [F, 12] fp32, 16-byte aligned, indexed by the ORIGINAL face id: the 9 floats of the face's frame, three zeros
+    void* phi;              // ROWS: half [4, N, 2], otherwise fp32 [N, 8]
+    int32_t* patch_id;      // [N] (plain form only)
+    float *local_tbn, *sample_tbn, *new_tbn;  // [N, 9] each
+};
+
 // ROWS: the rows contract of nerftex_curved_field_infer's kernels (no p_uv, sdf or face output); otherwise the plain form (every row).
+// LIT: the lit reads too (t is not read without it).  Their placement: everything that depends on (u, v) -- the nearest frame read, the patch
+// frame that hangs on its id, the phi read -- sits on lane 0 beside the feature read, issued in that order in front of it; the face frame,
+// which depends on `best` only and both lanes hold, sits on lane 1 beside the ladder.  No second shuffle: the other placement (u, v handed to
+// lane 1 through one more __shfl_xor, the lit reads there) was not measured.
 // Lane mapping: the projector's -- lanes 2 i and 2 i + 1 compute the point's normal alike (the same loads, served once), trace along +normal and
 // -normal and meet in an __shfl_xor; every exit in front of it is decided by the point, so a pair leaves or stays TOGETHER.  Behind it both lanes
 // hold d1, d2 and the tail is split: lane 0 does barycentrics, UV, the four texels and every per-point store, lane 1 the height ladder.
-template <bool ROWS>
+template <bool ROWS, bool LIT = false>
 __global__ __launch_bounds__(64) void shape_lookup_kernel(const uint32_t N, const float* __restrict__ xyz, const float* __restrict__ dirs,
                                                           const int32_t* __restrict__ knn_idx, const float* __restrict__ knn_dist, const uint32_t K,
                                                           const float* __restrict__ verts, const float* __restrict__ vnormals, const int n_verts,
                                                           const Node* __restrict__ nodes, const Tri* __restrict__ tris, const ShapeArgs a,
                                                           float* __restrict__ p_uv, float* __restrict__ sdf_out, uint8_t* __restrict__ mask,
                                                           float* __restrict__ normal_out, int64_t* __restrict__ face_idx, half_t* __restrict__ xin,
-                                                          const int32_t* __restrict__ units_dev, const uint32_t rows_per_unit) {
+                                                          const int32_t* __restrict__ units_dev, const uint32_t rows_per_unit, const ShapeLitArgs t) {
     const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t i = tid >> 1, side = tid & 1u;
     if (i >= (ROWS ? live_rows(N, units_dev, rows_per_unit) : N)) return;
@@ -434,6 +449,11 @@ __global__ __launch_bounds__(64) void shape_lookup_kernel(const uint32_t N, cons
             p_uv[2 * (size_t)i] = 0.0f; p_uv[2 * (size_t)i + 1] = 0.0f;
             sdf_out[i] = 0.0f;
             face_idx[i] = -1;
+        }
+        if constexpr (LIT) {  // zeros for phi and all three frames (the mid kernel reads them for every unmarked row), patch_id -1 in the plain form
+            lit_reads_nothing<ROWS>(i, N, t.phi, t.patch_id, t.local_tbn, t.sample_tbn);
+#pragma unroll
+            for (int k = 0; k < 9; k++) t.new_tbn[9 * (size_t)i + k] = 0.0f;
         }
     };
     if (ROWS && slot_unused(dirs, i)) {  // no neighbour list to read, no tree to walk, no texel
@@ -503,6 +523,16 @@ __global__ __launch_bounds__(64) void shape_lookup_kernel(const uint32_t N, cons
     const bool inner = d1 < d2;
     const float sdf = (inner ? -d1 : d2) / a.sdf_scale - a.sdf_offset;  // (a true division)
     if (side) {  // lane 1: the ladder, columns 16..47
+        if constexpr (LIT) {  // ... and new_tbn = tbn[face], face -1 overwritten by 0 (tools/map.py:521, :542): three 16-byte loads, issued in front of the ladder
+            const int best1 = inner ? b_other : b_mine;  // (this lane traced -normal: the partner's face is d1's)
+            const int64_t id = best1 >= 0 ? tris[(uint32_t)best1].id : (int64_t)0;
+            const float4_t* src = reinterpret_cast<const float4_t*>(t.face_tbn + 12 * (size_t)id);
+            const float4_t f0 = src[0], f1 = src[1], f2 = src[2];
+            float* dst = t.new_tbn + 9 * (size_t)i;
+            dst[0] = f0[0]; dst[1] = f0[1]; dst[2] = f0[2]; dst[3] = f0[3];
+            dst[4] = f1[0]; dst[5] = f1[1]; dst[6] = f1[2]; dst[7] = f1[3];
+            dst[8] = f2[0];
+        }
         write_height_ladder(sdf, row);
         return;
     }
@@ -521,6 +551,7 @@ __global__ __launch_bounds__(64) void shape_lookup_kernel(const uint32_t N, cons
     const float b0 = s0 / den, b1 = s1 / den, b2 = s2 / den;
     const float u = ((uv0.x * b0 + uv1.x * b1) + uv2.x * b2) * a.uv_rate;
     const float v = ((uv0.y * b0 + uv1.y * b1) + uv2.y * b2) * a.uv_rate;
+    if constexpr (LIT) lit_reads_row<ROWS>(t.l, a.H, a.W, u, v, i, N, t.phi, t.patch_id, t.local_tbn, t.sample_tbn);
     half4_t o[4];
     bilinear_read<1>(a.map, a.H, a.W, u, v, 0u, o);
     store_features(o, row);
@@ -668,14 +699,27 @@ extern "C" int nerftex_curved_project(const nerftex_raytracer* rt, const float* 
 namespace nerftex {
 namespace {
 
+// lit: NULL for the unlit lookup; otherwise the LIT instantiation with its maps and outputs (phi: half [4,N,2] with ROWS, fp32 [N,8] without)
 template <bool ROWS>
 void launch_shape_lookup(hipStream_t st, const nerftex_raytracer* rt, const float* xyz, const float* dirs, const int32_t* knn_idx, const float* knn_dist, uint32_t N,
                          uint32_t K, const float* verts, const float* vnormals, uint32_t n_verts, const ShapeLookup& s, float* p_uv, float* sdf, uint8_t* mask,
-                         float* normal, int64_t* face_idx, half_t* xin, const int32_t* units_dev, uint32_t rows_per_unit) {
+                         float* normal, int64_t* face_idx, half_t* xin, const int32_t* units_dev, uint32_t rows_per_unit, const ShapeLight* lit = nullptr,
+                         int32_t* patch_id = nullptr) {
     const ShapeArgs a{s.map, s.map_h, s.map_w, s.face_uv, s.sdf_scale, s.sdf_offset, s.uv_rate, fminf(9.5f, s.h_threshold), rt->face0};  // depth_threshold of tools/map.py:407
+    const dim3 grid(div_up(2 * N, 64u)), block(64);
+    if (lit) {
+        const ShapeLitArgs t{{lit->phi_map, lit->frame_map, lit->sample_tbn_inv, lit->n_patches}, lit->face_tbn, lit->phi, patch_id, lit->local_tbn, lit->sample_tbn,
+                             lit->new_tbn};
+        KernelTimer kt("shape_light_lookup_kernel", st);
+        hipLaunchKernelGGL((shape_lookup_kernel<ROWS, true>), grid, block, 0, st, N, xyz, dirs, knn_idx, knn_dist, K, verts, vnormals, (int)n_verts,
+                           static_cast<const Node*>(rt->nodes), static_cast<const Tri*>(rt->triangles), a, p_uv, sdf, mask, normal, face_idx, xin, units_dev,
+                           rows_per_unit, t);
+        return;
+    }
     KernelTimer kt("shape_lookup_kernel", st);
-    hipLaunchKernelGGL((shape_lookup_kernel<ROWS>), dim3(div_up(2 * N, 64u)), dim3(64), 0, st, N, xyz, dirs, knn_idx, knn_dist, K, verts, vnormals, (int)n_verts,
-                       static_cast<const Node*>(rt->nodes), static_cast<const Tri*>(rt->triangles), a, p_uv, sdf, mask, normal, face_idx, xin, units_dev, rows_per_unit);
+    hipLaunchKernelGGL((shape_lookup_kernel<ROWS, false>), grid, block, 0, st, N, xyz, dirs, knn_idx, knn_dist, K, verts, vnormals, (int)n_verts,
+                       static_cast<const Node*>(rt->nodes), static_cast<const Tri*>(rt->triangles), a, p_uv, sdf, mask, normal, face_idx, xin, units_dev, rows_per_unit,
+                       ShapeLitArgs{});
 }
 
 }  // namespace
@@ -700,6 +744,70 @@ int nerftex::curved_shape_rows(const nerftex_raytracer* rt, const float* xyz, co
     launch_shape_lookup<true>(st, rt, xyz, dirs, knn_idx, knn_dist, N, K, mesh_vertices, vertex_normals, n_verts, s, nullptr, nullptr, mask, normal, nullptr,
                               static_cast<half_t*>(s.xin), units_dev, rows_per_unit);
     return check_launch("curved_shape_infer(lookup)");
+}
+
+const char* nerftex::shape_light_refusal(const ShapeLight& t, uint32_t n_triangles) {
+    auto aligned = [](const void* p) { return !(reinterpret_cast<uintptr_t>(p) & 15); };
+    if (t.n_patches == 0 || t.n_patches > (1u << 24)) return "between 1 and 2^24 patch frames (an id is read from an fp32 texel)";
+    if (!t.phi_map || !t.frame_map || !t.sample_tbn_inv || !t.face_tbn || !t.phi || !t.local_tbn || !t.sample_tbn || !t.new_tbn)
+        return "the lit maps, the patch frames, the face frames and the lit outputs must not be NULL";
+    if (!aligned(t.phi_map) || !aligned(t.frame_map) || !aligned(t.sample_tbn_inv) || !aligned(t.face_tbn) || !aligned(t.phi))
+        return "the lit maps, the patch frames, the face frames and phi must be 16-byte aligned";
+    if (t.n_tbn_faces != n_triangles) return "face_tbn must hold one frame per face of the raytracer";
+    return nullptr;
+}
+
+int nerftex::curved_shape_light_rows(const nerftex_raytracer* rt, const float* xyz, const float* dirs, const int32_t* knn_idx, const float* knn_dist, uint32_t N,
+                                     uint32_t K, const float* mesh_vertices, const float* vertex_normals, uint32_t n_verts, const ShapeLookup& s,
+                                     const ShapeLight& t, uint8_t* mask, float* normal, const int32_t* units_dev, uint32_t rows_per_unit, hipStream_t st) {
+    if (N == 0) return NERFTEX_OK;
+    launch_shape_lookup<true>(st, rt, xyz, dirs, knn_idx, knn_dist, N, K, mesh_vertices, vertex_normals, n_verts, s, nullptr, nullptr, mask, normal, nullptr,
+                              static_cast<half_t*>(s.xin), units_dev, rows_per_unit, &t);
+    return check_launch("curved_light_shape_infer(lookup)");
+}
+
+extern "C" int nerftex_shape_light_lookup(const nerftex_raytracer* rt, const float* xyz, const int32_t* knn_idx, const float* knn_dist, uint32_t N, uint32_t K,
+                                          const float* mesh_vertices, const float* vertex_normals, uint32_t n_verts, const float* face_uv, uint32_t n_faces,
+                                          const float* face_tbn, uint32_t n_tbn_faces, const float* map, const float* phi_map, const float* frame_map,
+                                          const float* sample_tbn_inv, uint32_t map_h, uint32_t map_w, uint32_t n_patches, float sdf_scale, float sdf_offset,
+                                          float uv_rate, float h_threshold, uint32_t n_freqs, float* p_uv, float* sdf, uint8_t* mask, float* normal,
+                                          int64_t* face_idx, void* xin, float* phi, int32_t* patch_id, float* local_tbn, float* sample_tbn, float* new_tbn,
+                                          void* stream) {
+    clear_error();
+    // nerftex_shape_lookup's refusals, in its order ...
+    if (!rt || !xyz || !knn_idx || !knn_dist || !mesh_vertices || !vertex_normals || !face_uv || !map || !p_uv || !sdf || !mask || !normal || !face_idx || !xin) {
+        set_error("shape_light_lookup: the raytracer, inputs, mesh arrays, face_uv, map and outputs must not be NULL");
+        return NERFTEX_ERR_INVALID;
+    }
+    if (K == 0 || K > (uint32_t)kMaxK || n_verts == 0 || n_verts > 0x7fffffffu) {
+        set_error("shape_light_lookup: 1 <= K <= %d neighbours per point and between 1 and 2^31 - 1 vertices, but got K = %u, n_verts = %u", kMaxK, K, n_verts);
+        return NERFTEX_ERR_INVALID;
+    }
+    if (n_faces != rt->n_triangles) {
+        set_error("shape_light_lookup: face_uv holds %u faces, but the raytracer was built over %u", n_faces, rt->n_triangles);
+        return NERFTEX_ERR_INVALID;
+    }
+    const ShapeLookup s{face_uv, map, map_h, map_w, sdf_scale, sdf_offset, uv_rate, h_threshold, n_freqs, xin};
+    if (const char* why = shape_lookup_refusal(s)) {
+        set_error("shape_light_lookup: %s", why);
+        return NERFTEX_ERR_INVALID;
+    }
+    // ... then nerftex_planar_light_lookup's over what it adds (n_patches, the lit pointers, their alignment), then the face frames' count
+    const ShapeLight t{phi_map, frame_map, sample_tbn_inv, n_patches, face_tbn, n_tbn_faces, phi, local_tbn, sample_tbn, new_tbn};
+    const char* why = shape_light_refusal(t, rt->n_triangles);
+    if (!why && !patch_id) why = "the lit maps, the patch frames, the face frames and the lit outputs must not be NULL";
+    if (why) {
+        set_error("shape_light_lookup: %s (n_patches = %u, face_tbn holds %u faces, the raytracer %u)", why, n_patches, n_tbn_faces, rt->n_triangles);
+        return NERFTEX_ERR_INVALID;
+    }
+    if (N == 0) return NERFTEX_OK;
+    if (N > 0x7fffffffu) {
+        set_error("shape_light_lookup: at most 2^31 - 1 points per call (two lanes each), but got %u", N);
+        return NERFTEX_ERR_INVALID;
+    }
+    launch_shape_lookup<false>(as_stream(stream), rt, xyz, nullptr, knn_idx, knn_dist, N, K, mesh_vertices, vertex_normals, n_verts, s, p_uv, sdf, mask, normal, face_idx,
+                               static_cast<half_t*>(xin), nullptr, 0u, &t, patch_id);
+    return check_launch("shape_light_lookup");
 }
 
 extern "C" int nerftex_shape_lookup(const nerftex_raytracer* rt, const float* xyz, const int32_t* knn_idx, const float* knn_dist, uint32_t N, uint32_t K,

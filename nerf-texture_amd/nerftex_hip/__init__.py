@@ -56,6 +56,9 @@ _SIGNATURES = {
     "nerftex_shape_lookup": [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _u32, _vp, _u32, _vp, _u32, _u32, _f32, _f32, _f32, _f32, _u32, _vp, _vp, _vp, _vp, _vp,
                              _vp, _vp],
     "nerftex_curved_shape_infer": [_vp, _vp],
+    "nerftex_shape_light_lookup": [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _u32, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _f32, _f32, _f32,
+                                   _f32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "nerftex_curved_light_shape_infer": [_vp, _vp],
     "nerftex_sh_light_forward": [_vp, _vp],
     "nerftex_sh_light_backward": [_vp, _vp],
     "nerftex_field_mid_backward": [_vp, _vp, _vp, _u32, _vp, _vp],
@@ -271,6 +274,19 @@ class CurvedLightImportInferDesc(C.Structure):
                 ("scratch", _vp), ("scratch_bytes", _sz)]
 
 
+class CurvedLightShapeInferDesc(C.Structure):
+    """nerftex_curved_light_shape_infer_desc of include/nerftex_hip.h, field for field: the SH-lit curved field's no-grad forward over imported maps on a
+    new mesh."""
+    _fields_ = [("knn", _vp), ("tracer", _vp), ("xyz", _vp), ("dirs", _vp), ("B", _u32), ("n_verts", _u32), ("mesh_vertices", _vp), ("vertex_normals", _vp),
+                ("face_uv", _vp), ("face_tbn", _vp), ("n_faces", _u32), ("n_tbn_faces", _u32), ("K", _u32), ("map", _vp), ("phi_map", _vp), ("frame_map", _vp),
+                ("sample_tbn_inv", _vp), ("map_h", _u32), ("map_w", _u32), ("n_features", _u32), ("n_phi", _u32), ("n_patches", _u32), ("sdf_scale", _f32),
+                ("sdf_offset", _f32), ("uv_rate", _f32), ("h_threshold", _f32), ("n_freqs", _u32), ("sigma_weights", _vp), ("sigma_in", _u32),
+                ("sigma_hidden", _u32), ("sigma_layers", _u32), ("sigma_out", _u32), ("normal_weights", _vp), ("normal_biases", _vp), ("normal_hidden", _u32),
+                ("normal_layers", _u32), ("brdf_weights", _vp), ("brdf_in", _u32), ("brdf_hidden", _u32), ("brdf_layers", _u32), ("brdf_out", _u32),
+                ("env_shs", _vp), ("n_sh", _u32), ("n_color", _u32), ("gamma", _f32), ("flags", _u32), ("visual_mode", _u32), ("fc_weight", _f32), ("eval", _i),
+                ("sigma", _vp), ("rgbs", _vp), ("shading_normal", _vp), ("units_dev", _vp), ("rows_per_unit", _u32), ("scratch", _vp), ("scratch_bytes", _sz)]
+
+
 SH_LIGHT_SPECULAR = 1  # nerftex_sh_light_desc.flags
 
 
@@ -283,7 +299,7 @@ class SHLightDesc(C.Structure):
 
 EXPORTS = ["nerftex_last_error", "nerftex_version", "nerftex_tune_get", "nerftex_workspace_slots_touched", "nerftex_curved_field_infer_scratch_bytes",
            "nerftex_curved_light_infer_scratch_bytes", "nerftex_curved_import_infer_scratch_bytes", "nerftex_curved_shape_infer_scratch_bytes",
-           "nerftex_curved_light_import_infer_scratch_bytes", "nerftex_sh_light_scratch_bytes"] + list(_SIGNATURES)
+           "nerftex_curved_light_import_infer_scratch_bytes", "nerftex_curved_light_shape_infer_scratch_bytes", "nerftex_sh_light_scratch_bytes"] + list(_SIGNATURES)
 
 
 def _load():
@@ -309,6 +325,8 @@ def _load():
     lib.nerftex_curved_shape_infer_scratch_bytes.restype = _sz
     lib.nerftex_curved_light_import_infer_scratch_bytes.argtypes = [_u32]
     lib.nerftex_curved_light_import_infer_scratch_bytes.restype = _sz
+    lib.nerftex_curved_light_shape_infer_scratch_bytes.argtypes = [_u32]
+    lib.nerftex_curved_light_shape_infer_scratch_bytes.restype = _sz
     lib.nerftex_sh_light_scratch_bytes.argtypes = [_u32]
     lib.nerftex_sh_light_scratch_bytes.restype = _sz
     for name, args in _SIGNATURES.items():

@@ -99,17 +99,24 @@ def freq_encode(x, multires=12):
     return torch.cat(out, dim=-1)
 
 
+def shape_vertices(vertices, normalize=True):
+    """The float64 vertices `shape_preprocess` rounds to fp32 -- what the reference's trimesh mesh holds behind NeRFNetwork.import_shape's
+    normalisation, and what its calculate_tbn reads (`uv_face_frames`)."""
+    v = np.array(vertices, dtype=np.float64)
+    if normalize:
+        v -= np.mean(v, axis=0)
+        v /= (np.absolute(v).max() + 1e-5)
+        v /= 1.2
+    return v
+
+
 def shape_preprocess(vertices, faces, uvs, normalize=True):
     """What NeRFNetwork.import_shape and MeshProjector's constructor make of a loaded mesh before anything touches a device:
     -> (vertices [V,3] fp32, uvs [V,2] fp32 in [-1,1], face_uv [F,6] fp32 = uvs[faces], recommended_sdf_factor).
     normalize (network_curvedfield.py:496-498, float64): centre by the vertex mean, divide by max|v| + 1e-5, then by 1.2.
     uvs (tools/map.py:361, fp32): mapped to [-1,1] by their single global minimum and maximum.
     recommended_sdf_factor (:373-386): the mean 3-D length (float64) over the mean UV length (fp32) of the unique edges."""
-    v = np.array(vertices, dtype=np.float64)
-    if normalize:
-        v -= np.mean(v, axis=0)
-        v /= (np.absolute(v).max() + 1e-5)
-        v /= 1.2
+    v = shape_vertices(vertices, normalize)
     f = np.asarray(faces).astype(np.int64)
     uv = torch.FloatTensor(np.asarray(uvs, dtype=np.float32))
     uv = ((uv - uv.min()) / (uv.max() - uv.min()) * 2 - 1.).numpy()
@@ -120,6 +127,33 @@ def shape_preprocess(vertices, faces, uvs, normalize=True):
     e2 = uv[edges]
     mean_edges_uv = np.linalg.norm(e2[:, 0] - e2[:, 1], axis=-1).mean()
     return v.astype(np.float32), uv, np.ascontiguousarray(uv[f].reshape(-1, 6)), float(mean_edge_length / mean_edges_uv)
+
+
+def uv_face_frames(vertices, faces, uvs):
+    """The per-face frames of a UV-mapped mesh as MeshProjector's constructor computes them (calculate_tbn, tools/map.py:119-138, called at :366
+    with the normalised mesh and the [-1, 1] UVs): -> [F, 3, 3] fp32, rows t, b, n.  Per face, in float64 over the vertices: the 2 x 2 matrix of
+    the two UV edges is inverted (a matrix of rank < 2 gets 1e-3 added to its element [1, 1] first, every such matrix when there is one) and
+    multiplied by the two 3-D edges -> t, b; n is the face normal (the normalised cross product of the first two edges, trimesh's
+    `face_normals`); b is replaced by n x t; every row is divided by its length.  The UV edges keep the dtype `uvs` comes in: the reference
+    hands over fp32 UVs, so rank and inverse are numpy's fp32 ones there, and `shape_preprocess` returns them as fp32 for that reason."""
+    v = np.asarray(vertices, dtype=np.float64)
+    f = np.asarray(faces).astype(np.int64)
+    uv = np.asarray(uvs)
+    if not np.issubdtype(uv.dtype, np.floating):
+        uv = uv.astype(np.float64)
+    fv, fuv = v[f], uv[f]
+    e3 = fv[:, 1:] - fv[:, :1]
+    e2 = fuv[:, 1:] - fuv[:, :1]
+    rank = np.linalg.matrix_rank(e2)
+    if rank.min() < 2:
+        e2[np.where(rank < 2)[0], 1, 1] += 1e-3
+    tb = np.einsum("fij,fjk->fik", np.linalg.inv(e2), e3)  # [t; b] per face
+    n = np.cross(e3[:, 0], e3[:, 1])
+    n = n / np.linalg.norm(n, axis=-1, keepdims=True)
+    tbn = np.concatenate([tb, n[:, None]], axis=1)
+    tbn[:, 1] = np.cross(tbn[:, 2], tbn[:, 0], axis=-1)
+    tbn = tbn / np.linalg.norm(tbn, axis=-1, keepdims=True)
+    return tbn.astype(np.float32)
 
 
 def shape_knn_normal(xyz, idx, dis, mesh_vertices, vertex_normals):
@@ -552,6 +586,8 @@ class CurvedField(torch.nn.Module):
         # ... and the maps of the `pred_normal` part (:920-923): none
         self.phi_embed_imported = self.local_tbn_imported = self.sample_tbn_ids_imported = self.sample_tbn_inv_imported = None
         self.frame_map_imported = self.sample_inv_rows_imported = None
+        # ... and the new mesh's per-face frames (`new_tbn`, :542): none
+        self.shape_face_tbn = None
 
     def _lit(self):
         """A field whose forward reads a fine normal: the normal net, or a light model (which shades with it)."""
@@ -623,21 +659,48 @@ class CurvedField(torch.nn.Module):
 
     # ---- the imported map on a new UV-mapped mesh (NeRFNetwork.import_shape, network_curvedfield.py:494-501; the 'shape' branch, tools/map.py:693-700) ----
 
-    def import_shape(self, vertices, faces, uvs, vertex_normals=None, normalize=True):
+    def import_shape(self, vertices, faces, uvs, vertex_normals=None, normalize=True, *, new_tbn=None):
         """NeRFNetwork.import_shape -> MeshFeatureField.import_shape (tools/map.py:939-949) for a mesh given as arrays: vertices [V,3], faces
         [F,3], per-vertex uvs [V,2] (what `mesh.visual.uv` holds; the xatlas parametrisation of a mesh without UVs is not built here),
         vertex_normals [V,3] (default: area-weighted, the role of open3d's).  normalize: the reference's centring and scaling of the loaded mesh
         (`shape_preprocess`).  A second MeshProjector over the mesh, the per-face UV table, sdf_scale_factor = recommended_sdf_factor /
         bounds[0]; from here on embed() / density() / forward() / infer() project onto THIS mesh and read the imported map at the hit's
         interpolated UV, until switch_shape_feature() or switch_import().  The reference prints a message and returns when no map was
-        imported; here that is a RuntimeError.  The caller re-estimates the occupancy grid (Renderer.initialize_states)."""
+        imported; here that is a RuntimeError.  The caller re-estimates the occupancy grid (Renderer.initialize_states).
+        new_tbn (a field with the fine-normal net or a light model needs it, and the four lit maps of import_field): the new mesh's per-face
+        frames the fine normal is rotated by last (`new_tbn = self.tbn[face_idx]`, tools/map.py:542, :728-729) -- "uv": the reference's,
+        `uv_face_frames` over the preprocessed mesh and UVs; or an array [F, 3, 3] taken as given (the role `tbn=` plays for the field's own
+        mesh).  Kept as `shape_face_tbn` [F', 12] fp32 by ORIGINAL face id: 9 floats and three zeros per face, padded where `shape_face_uv`
+        is.  A field without a normal net takes none.  A refused call changes nothing of the field's state."""
         if self.features_imported is None or self.imported_type not in ("field", "shape"):
             raise RuntimeError("CurvedField.import_shape: a feature map has to be imported first (import_field)")
-        if self.normal_net is not None or getattr(self, "light_model", None) is not None:
+        if new_tbn is not None and not self._lit():
+            raise ValueError("CurvedField.import_shape: new_tbn is read by the fine-normal net only; this field has none and would ignore it")
+        if new_tbn is not None and self.phi_embed_imported is None:
+            raise RuntimeError("CurvedField.import_shape: a field with the fine-normal net or a light model reads the imported phi_embed, local_tbn, "
+                               "sample_tbn and sample_tbn_ids maps on the new mesh too; import them first (import_field)")
+        if new_tbn is None and (self.normal_net is not None or getattr(self, "light_model", None) is not None):
             raise NotImplementedError("CurvedField.import_shape: a field with the fine-normal net or a light model would also need the imported phi_embed, "
                                       "local_tbn and sample_tbn maps and the new mesh's frames (tools/map.py:702-707, :728-729); only the static light model "
                                       "without a normal net imports here")
         v, uv, face_uv, factor = shape_preprocess(vertices, faces, uvs, normalize=normalize)
+        face_tbn = None
+        if new_tbn is not None:  # (before anything of the state changes)
+            if isinstance(new_tbn, str):
+                if new_tbn != "uv":
+                    raise ValueError(f"CurvedField.import_shape: new_tbn is \"uv\" or an array [F, 3, 3], but got {new_tbn!r}")
+                try:
+                    frames = uv_face_frames(shape_vertices(vertices, normalize), faces, uv)  # (the float64 vertices, as the reference's mesh holds them)
+                except np.linalg.LinAlgError:  # (a UV edge matrix the 1e-3 rule does not mend: the reference stops here, too)
+                    frames = np.full((len(face_uv), 3, 3), np.nan, np.float32)
+            else:
+                frames = np.asarray(new_tbn.detach().cpu() if torch.is_tensor(new_tbn) else new_tbn, dtype=np.float32)
+            if tuple(frames.shape) != (len(face_uv), 3, 3):
+                raise ValueError(f"CurvedField.import_shape: new_tbn holds one frame per face, [F, 3, 3] = {(len(face_uv), 3, 3)}, but got {tuple(frames.shape)}")
+            if not np.isfinite(frames).all():
+                raise ValueError("CurvedField.import_shape: every frame of new_tbn must be finite (a face without area, or UV corners that coincide?)")
+            face_tbn = np.zeros((len(face_uv) + (8 if len(face_uv) <= 8 else 0), 12), np.float32)  # (padded as the UV table below)
+            face_tbn[:len(face_uv), :9] = frames.reshape(-1, 9)
         dev = self.sigma_net.weights.device
         self.shape_projector = MeshProjector(v, np.asarray(faces), h_threshold=self.h_threshold, K=self.K_for_uv, vertex_normals=vertex_normals).to(dev)
         self.shape_faces = torch.as_tensor(np.asarray(faces).astype(np.int64)).to(dev)
@@ -645,6 +708,7 @@ class CurvedField(torch.nn.Module):
         if len(face_uv) <= 8:  # (RayTracer pads so small a mesh with 8 far-away faces: the table follows the tracer's face count, the rows are never hit)
             face_uv = np.concatenate([face_uv, np.zeros((8, 6), np.float32)], 0)
         self.shape_face_uv = torch.from_numpy(face_uv).to(dev).contiguous()
+        self.shape_face_tbn = None if face_tbn is None else torch.from_numpy(face_tbn).to(dev).contiguous()
         self.recommended_sdf_factor = factor
         self.sdf_scale_factor = factor / self.bounds[0]
         self.imported, self.imported_type = True, "shape"
@@ -730,6 +794,67 @@ class CurvedField(torch.nn.Module):
             return embed, normal_coarse, h_mask, p_uv, sdf[..., 0], normal, face
         return embed, normal_coarse, h_mask
 
+    def _shape_light_fused(self, x):
+        """_import_light_fused() for the maps on the imported mesh: the lit shape lookup serves the default shapes under fp16 autocast, once the
+        four lit maps and the new mesh's frames are there."""
+        return (x.is_cuda and self._lit() and self._shape_active() and self.phi_embed_imported is not None and self.shape_face_tbn is not None
+                and self.encoder_var is None and self.in_dim == 41 and self.in_pad == 48 and self.geo_feat_dim == 15 and self.multires == 12
+                and self.sigma_net.dtype == torch.float16 and torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.float16)
+
+    @torch.no_grad()
+    def _shape_light_lookup(self, x, neighbours=None):
+        """nerftex_knn_query + nerftex_shape_light_lookup: -> p_uv [N,2], sdf [N], h_mask [N] bool, normal [N,3] (raw), face [N], xin [N,48] half,
+        phi [N,8] fp32, id [N] int32, local_tbn, sample_tbn_inv, new_tbn [N,3,3]."""
+        from nerftex_hip import check, lib, ptr, stream
+
+        x = x.detach().float().contiguous()
+        N, dev, f, p = x.shape[0], x.device, self.features_imported, self.shape_projector
+        K, scale, off, rate, h = self._shape_scalars()
+        idx, dis = p.knn(x, K) if neighbours is None else neighbours
+        idx, dis = idx.int().contiguous(), dis.float().contiguous()
+        p_uv = torch.empty(N, 2, device=dev)
+        sdf = torch.empty(N, device=dev)
+        mask = torch.empty(N, dtype=torch.uint8, device=dev)
+        normal = torch.empty(N, 3, device=dev)
+        face = torch.empty(N, dtype=torch.int64, device=dev)
+        xin = torch.empty(N, 48, dtype=torch.float16, device=dev)
+        phi = torch.empty(N, 8, device=dev)
+        ids = torch.empty(N, dtype=torch.int32, device=dev)
+        local, sample, new = (torch.empty(N, 9, device=dev) for _ in range(3))
+        rows = self.sample_inv_rows_imported
+        check(lib.nerftex_shape_light_lookup(p.tracer._handle, ptr(x), ptr(idx), ptr(dis), N, idx.shape[1], ptr(p.mesh_vertices), ptr(p.vertex_normals),
+                                             p.mesh_vertices.shape[0], ptr(self.shape_face_uv), self.shape_face_uv.shape[0], ptr(self.shape_face_tbn),
+                                             self.shape_face_tbn.shape[0], ptr(f), ptr(self.phi_embed_imported), ptr(self.frame_map_imported), ptr(rows),
+                                             f.shape[0], f.shape[1], rows.shape[0], scale, off, rate, h, int(self.multires), ptr(p_uv), ptr(sdf), ptr(mask),
+                                             ptr(normal), ptr(face), ptr(xin), ptr(phi), ptr(ids), ptr(local), ptr(sample), ptr(new), stream()))
+        return p_uv, sdf, mask.bool(), normal, face, xin, phi, ids, local.view(N, 3, 3), sample.view(N, 3, 3), new.view(N, 3, 3)
+
+    def _shape_light_embed_reference(self, x, neighbours=None, details=False):
+        """The 'shape' branch with `pred_normal` op by op (tools/map.py:693-707, :722-730): `_shape_embed_reference`'s expressions, the four
+        grid_sample calls of `_import_light_embed_reference` at its p_uv, the hit face's frame (face -1 reads face 0), the normal net and the
+        three rotations.  -> embed [N,41] fp32, normal_coarse, h_mask, normal_fine (details: + p_uv, sdf, face, the sampled phi_embed,
+        local_tbn, id, sample_tbn_inv rows and new_tbn)."""
+        embed, normal_coarse, h_mask, p_uv, sdf, _, face = self._shape_embed_reference(x, neighbours=neighbours, details=True)
+        x = x.float()
+        grid = p_uv[None, None]
+
+        def image(m):  # [H, W, C] -> [1, C, W, H], as `_import_embed_reference`
+            return m.to(x.device).permute(2, 1, 0).unsqueeze(0)
+
+        gs = torch.nn.functional.grid_sample
+        ids = gs(image(self.sample_tbn_ids_imported[..., None]), grid, mode="nearest", align_corners=True, padding_mode="zeros")[0, 0, 0].long()
+        sample_tbn_inv = self.sample_tbn_inv_imported.to(x.device)[ids]
+        local_tbn = gs(image(self.local_tbn_imported), grid, mode="nearest", align_corners=True, padding_mode="zeros")[0, :, 0].permute(1, 0).reshape(-1, 3, 3)
+        phi = gs(image(self.phi_embed_imported), grid, align_corners=True, padding_mode="zeros")[0, :, 0].permute(1, 0)
+        face0 = torch.where(face == -1, torch.zeros_like(face), face)
+        new_tbn = self.shape_face_tbn.to(x.device)[face0, :9].reshape(-1, 3, 3)
+        x_embed, z_embed = embed[:, :self.encoder.output_dim], embed[:, self.encoder.output_dim:]
+        local = self.normal_net(phi_embed=phi, z_embed=z_embed, x_embed=x_embed)
+        fine = self._rotate_fine(local, local_tbn, sample_tbn_inv, new_tbn)
+        if details:
+            return embed, normal_coarse, h_mask, fine, p_uv, sdf, face, phi, local_tbn, ids, sample_tbn_inv, new_tbn
+        return embed, normal_coarse, h_mask, fine
+
     def switch_import(self):
         """network_curvedfield.py:519-521: between the imported map and the field's own mesh and table (the map is kept)."""
         if self.features_imported is None:
@@ -767,8 +892,13 @@ class CurvedField(torch.nn.Module):
         f = self.features_imported
         if self._shape_active():
             p = self.shape_projector
-            return (("import-shape", f.data_ptr(), tuple(f.shape), p._knn.value, p.tracer._handle.value, p.mesh_vertices.data_ptr(), p.vertex_normals.data_ptr(),
-                     self.shape_face_uv.data_ptr()) + self._shape_scalars() + (self._import_version,))
+            stamp = (("import-shape", f.data_ptr(), tuple(f.shape), p._knn.value, p.tracer._handle.value, p.mesh_vertices.data_ptr(), p.vertex_normals.data_ptr(),
+                      self.shape_face_uv.data_ptr()) + self._shape_scalars() + (self._import_version,))
+            if self._lit() and self.phi_embed_imported is not None and getattr(self, "shape_face_tbn", None) is not None:  # the lit field's maps and frames
+                stamp += tuple((m.data_ptr(), tuple(m.shape)) for m in (self.phi_embed_imported, self.local_tbn_imported, self.sample_tbn_inv_imported,
+                                                                        self.sample_tbn_ids_imported, self.frame_map_imported, self.sample_inv_rows_imported,
+                                                                        self.shape_face_tbn))
+            return stamp
         stamp = ("import", f.data_ptr(), tuple(f.shape)) + self._import_scalars() + (self._import_version,)
         if self._lit() and self.phi_embed_imported is not None:  # the lit field's maps: their storage and shapes
             stamp += tuple((m.data_ptr(), tuple(m.shape)) for m in (self.phi_embed_imported, self.local_tbn_imported, self.sample_tbn_inv_imported,
@@ -851,10 +981,13 @@ class CurvedField(torch.nn.Module):
         return p_uv, sdf, mask.bool(), xin, phi, ids, local.view(N, 3, 3), sample.view(N, 3, 3)
 
     @staticmethod
-    def _rotate_fine(local, local_tbn, sample_tbn_inv):
-        """tools/map.py:724-730: the local normal rotated by the texel's frame, then by the patch's inverted frame, normalised."""
+    def _rotate_fine(local, local_tbn, sample_tbn_inv, new_tbn=None):
+        """tools/map.py:724-730: the local normal rotated by the texel's frame, then by the patch's inverted frame, then (the 'shape' branch) by
+        the new mesh's face frame, normalised."""
         fine = torch.einsum("nba,nb->na", local_tbn, local)
         fine = torch.einsum("nba,nb->na", sample_tbn_inv, fine)
+        if new_tbn is not None:
+            fine = torch.einsum("nba,nb->na", new_tbn, fine)
         return fine / (fine.norm(dim=-1, keepdim=True) + 1e-5)
 
     def _import_light_embed_reference(self, x, details=False):
@@ -896,9 +1029,16 @@ class CurvedField(torch.nn.Module):
         projection carries `diff_project_layer`'s gradient, the hash table is looked up with input gradients (dy_dx) and the height ladder
         is evaluated by framework ops on the differentiable height -- dL/dembed reaches x."""
         if getattr(self, "imported", False):  # the import branch (:646-668): the map instead of the mesh and the table
-            lit_maps = self._lit() and self.phi_embed_imported is not None and not self._shape_active()
+            lit_maps = self._lit() and self.phi_embed_imported is not None and (not self._shape_active() or self.shape_face_tbn is not None)
             if requires_grad_xyz or (with_fine_normal and not lit_maps):
                 raise NotImplementedError("CurvedField.embed: an imported map is rendered without gradients to the sample position and without a fine normal")
+            if with_fine_normal and self._shape_active():  # the same on the imported mesh (:702-707): a third rotation, by the hit face's frame
+                if self._shape_light_fused(x):
+                    _, _, h_mask, normal, _, xin, phi, _, local_tbn, sample_tbn_inv, new_tbn = self._shape_light_lookup(x)
+                    local = self.normal_net(phi_embed=phi, z_embed=xin[:, 16:self.in_dim], x_embed=xin[:, :16])
+                    return (xin[:, :self.in_dim], normal / (normal.norm(dim=-1, keepdim=True) + 1e-5), h_mask,
+                            self._rotate_fine(local, local_tbn, sample_tbn_inv, new_tbn))
+                return self._shape_light_embed_reference(x)
             if with_fine_normal:  # the `pred_normal` part (:670-675, :722-730): the normal net fed from the phi map, two rotations
                 if self._import_light_fused(x):
                     _, _, h_mask, xin, phi, _, local_tbn, sample_tbn_inv = self._import_light_lookup(x)
@@ -906,7 +1046,7 @@ class CurvedField(torch.nn.Module):
                     return xin[:, :self.in_dim], self._import_normal(x, True), h_mask, self._rotate_fine(local, local_tbn, sample_tbn_inv)
                 return self._import_light_embed_reference(x)
             if self._shape_active():  # the 'shape' branch (:693-700): the map at the UV of the hit on the imported mesh
-                if self._import_fused(x):
+                if self._import_fused(x) or self._shape_light_fused(x):  # (the lit field: none of the lit reads is needed here)
                     _, _, h_mask, normal, _, xin = self._shape_lookup(x)
                     return xin[:, :self.in_dim], normal / (normal.norm(dim=-1, keepdim=True) + 1e-5), h_mask
                 return self._shape_embed_reference(x)
@@ -939,7 +1079,7 @@ class CurvedField(torch.nn.Module):
         return _TruncExp.apply(h[..., 0]), h[..., 1:]
 
     def density(self, x, requires_grad_xyz=False):
-        if getattr(self, "imported", False) and not requires_grad_xyz and (self._import_fused(x) or self._import_light_fused(x)):
+        if getattr(self, "imported", False) and not requires_grad_xyz and (self._import_fused(x) or self._import_light_fused(x) or self._shape_light_fused(x)):
             h_mask, xin = (self._shape_lookup(x)[i] for i in (2, 5)) if self._shape_active() else self._import_lookup(x)[2:]
             h = self.sigma_net(xin)
             sigma = _TruncExp.apply(h[..., 0])
@@ -1203,6 +1343,16 @@ class CurvedField(torch.nn.Module):
                 and x.dtype == torch.float32 and d.dtype == torch.float32 and x.is_contiguous() and d.is_contiguous()
                 and all(m.device == x.device for m in (self.features_imported, self.phi_embed_imported, self.frame_map_imported, self.sample_inv_rows_imported)))
 
+    def _infer_light_shape_fused(self, x, d):
+        """Whether nerftex_curved_light_shape_infer serves this call: _infer_light_import_fused()'s conditions over the maps on the imported mesh,
+        with its frames and a K the neighbour search serves."""
+        s, B = self.sigma_net, x.shape[0]
+        return (getattr(self, "imported", False) and self._infer_light_back_fused(x) and self._shape_light_fused(x)
+                and (s.input_dim, s.hidden_dim, s.num_layers, s.padded_output_dim) == (48, 32, 2, 16) and B % 128 == 0 and B > 0
+                and x.dtype == torch.float32 and d.dtype == torch.float32 and x.is_contiguous() and d.is_contiguous() and 1 <= self._shape_scalars()[0] <= 16
+                and all(m.device == x.device for m in (self.features_imported, self.phi_embed_imported, self.frame_map_imported, self.sample_inv_rows_imported,
+                                                       self.shape_face_uv, self.shape_face_tbn)))
+
     def _infer_light_desc(self, x, d, live, sigma, rgbs, scratch, shading_normal=None):
         """The nerftex_curved_light_infer_desc of one call (and the tensors it points into).  Kept between calls and re-made when a parameter
         changes: the 16-bit MLP weights, and the normal net's packed block -- every LipLayer's normalization().half(), which is what the
@@ -1269,6 +1419,31 @@ class CurvedField(torch.nn.Module):
             scratch_bytes=scratch.numel())
         return desc, (f, phi, frame, rows, ws_h, wb_h, nw, nb, env)
 
+    def _infer_light_shape_desc(self, x, d, live, sigma, rgbs, scratch, shading_normal=None):
+        """The nerftex_curved_light_shape_infer_desc of one call (and the tensors it points into, to be kept until the call is enqueued)."""
+        from nerftex_hip import LIGHT_VISUAL, SH_LIGHT_SPECULAR, CurvedLightShapeInferDesc, ptr
+
+        net, s, f, p = self.light_net, self.sigma_net, self.features_imported, self.shape_projector
+        br = net.brdf_layer
+        phi, frame, rows = self.phi_embed_imported, self.frame_map_imported, self.sample_inv_rows_imported
+        ws_h, wb_h, nw, nb = self._infer_light_weights()
+        K, scale, off, rate, h = self._shape_scalars()
+        units, rows_per_unit = (ptr(live[0]), int(live[1])) if live is not None else (None, 0)
+        env = net.envSHs.detach()
+        visual = "Full" if self.training else self.light_visual_mode
+        desc = CurvedLightShapeInferDesc(
+            knn=p._knn.value, tracer=p.tracer._handle.value, xyz=ptr(x), dirs=ptr(d), B=x.shape[0], n_verts=p.mesh_vertices.shape[0],
+            mesh_vertices=ptr(p.mesh_vertices), vertex_normals=ptr(p.vertex_normals), face_uv=ptr(self.shape_face_uv), face_tbn=ptr(self.shape_face_tbn),
+            n_faces=self.shape_face_uv.shape[0], n_tbn_faces=self.shape_face_tbn.shape[0], K=K, map=ptr(f), phi_map=ptr(phi), frame_map=ptr(frame),
+            sample_tbn_inv=ptr(rows), map_h=f.shape[0], map_w=f.shape[1], n_features=f.shape[2], n_phi=phi.shape[2], n_patches=rows.shape[0], sdf_scale=scale,
+            sdf_offset=off, uv_rate=rate, h_threshold=h, n_freqs=int(self.multires), sigma_weights=ptr(ws_h), sigma_in=s.input_dim, sigma_hidden=s.hidden_dim,
+            sigma_layers=s.num_layers, sigma_out=s.padded_output_dim, normal_weights=ptr(nw), normal_biases=ptr(nb), normal_hidden=16, normal_layers=2,
+            brdf_weights=ptr(wb_h), brdf_in=br.input_dim, brdf_hidden=br.hidden_dim, brdf_layers=br.num_layers, brdf_out=br.output_dim, env_shs=ptr(env),
+            n_sh=env.shape[0], n_color=env.shape[1], gamma=float(net.gamma), flags=SH_LIGHT_SPECULAR if net.use_specular else 0,
+            visual_mode=LIGHT_VISUAL[visual], fc_weight=float(self.fc_weight), eval=int(not self.training), sigma=ptr(sigma), rgbs=ptr(rgbs),
+            shading_normal=ptr(shading_normal), units_dev=units, rows_per_unit=rows_per_unit, scratch=ptr(scratch), scratch_bytes=scratch.numel())
+        return desc, (f, phi, frame, rows, ws_h, wb_h, nw, nb, env)
+
     def _infer_call(self, entry, make_desc, x, d, live, *more):
         """One call of the library entry `entry` (its scratch query is `entry`_scratch_bytes) over the descriptor make_desc builds: -> (sigma [B],
         rgbs [B,3]), fp32 views of one allocation.  The scratch is one buffer per stream (the ray ranges of a pipelined frame run side by side),
@@ -1309,6 +1484,12 @@ class CurvedField(torch.nn.Module):
         return self._infer_call("nerftex_curved_light_import_infer", self._infer_light_import_desc, x, d, live, shading_normal)
 
     @torch.no_grad()
+    def infer_light_shape(self, x, d, live=None, shading_normal=None):
+        """infer() of the SH-lit field over its imported maps on the imported mesh through nerftex_curved_light_shape_infer (see
+        `_infer_light_shape_fused`, which the caller has checked)."""
+        return self._infer_call("nerftex_curved_light_shape_infer", self._infer_light_shape_desc, x, d, live, shading_normal)
+
+    @torch.no_grad()
     def infer_padded(self, x, d):
         """infer(x, d) for a batch of ANY size (the reference loop's iterations, Renderer.render_infer): where the light model's fused chain
         applies but for the batch's size, the batch is padded to the next multiple of 128 with marked slots (which cost nothing) -- every
@@ -1320,6 +1501,9 @@ class CurvedField(torch.nn.Module):
             dp = torch.full((B + pad, 3), 1e30, dtype=d.dtype, device=d.device)
             xp[:B], dp[:B] = x, d
             if getattr(self, "imported", False):
+                if self._infer_light_shape_fused(xp, dp):
+                    sigma, rgbs = self.infer_light_shape(xp, dp)
+                    return sigma[:B], rgbs[:B]
                 if self._infer_light_import_fused(xp, dp):
                     sigma, rgbs = self.infer_light_import(xp, dp)
                     return sigma[:B], rgbs[:B]
@@ -1340,9 +1524,11 @@ class CurvedField(torch.nn.Module):
         light_model="SH": forward(x, d) on all rows unless `fused_light_infer` is set (default False) -- then the light model's own chain,
         nerftex_curved_light_infer, under the same rows contract: sigma and the mask are forward()'s bit for bit, the shading normal and the
         colour follow forward()'s arithmetic at its rounding points; over imported maps, nerftex_curved_light_import_infer
-        (DESIGN.md 4.17)."""
+        (DESIGN.md 4.17), and over the maps on an imported mesh nerftex_curved_light_shape_infer."""
         if getattr(self, "imported", False):  # an imported map: its own chain under the same rows contract, or forward() on all rows
-            if self._infer_light_import_fused(x, d):  # (opt-in, as the mesh field's lit chain: `fused_light_infer`)
+            if self._infer_light_shape_fused(x, d):  # (opt-in, as the mesh field's lit chain: `fused_light_infer`; DESIGN.md 4.18)
+                return self.infer_light_shape(x, d, live)
+            if self._infer_light_import_fused(x, d):
                 return self.infer_light_import(x, d, live)
             if self._shape_active() and self._infer_import_fused(x, d):
                 return self._infer_call("nerftex_curved_shape_infer", self._infer_shape_desc, x, d, live)

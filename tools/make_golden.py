@@ -508,6 +508,9 @@ def main():
     if "--import-shape-only" in sys.argv:
         import_shape_goldens()
         return
+    if "--import-shape-sh-only" in sys.argv:
+        import_shape_sh_goldens()
+        return
     if "--sh-light-only" in sys.argv:
         sh_light_goldens()
         sh_field_goldens()
@@ -1479,6 +1482,190 @@ def import_shape_goldens():
         print("ref_python_import_shape.npz:", key, "inside the mask", float(hm.float().mean()), "sigma max", float(sigma.max()),
               "|uv| max", float(uvh[:, :2].abs().max() * rate))
     np.savez_compressed(os.path.join(OUT, "ref_python_import_shape.npz"), **out)
+    new = [os.path.join(r, n) for r, _, names in os.walk(REF) for n in names if os.lstat(os.path.join(r, n)).st_mtime >= started]
+    assert not new, "files appeared under the reference tree:\n" + "\n".join(new[:20])
+
+
+def import_shape_sh_goldens():
+    """ref_python_import_shape_sh.npz: the `pred_normal` part of the `imported_type == 'shape'` branch of MeshFeatureField.forward
+    (tools/map.py:693-707, :722-730) executed on the CPU under emulated_autocast, with network_curvedfield.NeRFNetwork.forward behind it in eval
+    with the real SH_EnvmapMaterialNet.  It joins import_shape_goldens (the mesh, the UVs, the points and the directions are READ from
+    ref_python_import_shape.npz; the MeshProjector is made past its constructor as there, frnn -> exact brute force, tracer -> the oracle) with
+    import_field_sh_goldens (the real six-argument import_field; the 24 x 20 maps, the P = 5 patch frames, the normal net, the sigma and BRDF
+    nets and the lighting are its recipe, re-made from its seeds and asserted equal to ref_python_import_field_sh.npz, where they are READ from
+    by the tests).  mp.tbn is the reference's OWN calculate_tbn (:119-138) over a namespace with vertices, faces and face_normals of the
+    normalised mesh, and mp.uvs.  The three states of ref_python_import_shape.npz, fc_weight 1.0 and 0.7, the four light_visual_modes.
+    Recorded, outputs only: uvh, mask, face, the sampled id, the three sampled frames, phi, the 28 columns of the embedding the normal net
+    reads (16 features, the first 12 height bands), normal_fine, the shading normal, sigma and the colours; `tbn` [F,3,3]; per state the count of rows within the nearest read's margin of a texel edge."""
+    import time
+    import types
+
+    import torch
+
+    started = time.time()
+    _install_map_imports()
+    _stub("imageio")
+    for name in ("nerf.sh_light_model", "nerf.network_curvedfield", "tools.shape_tools"):
+        sys.modules.pop(name, None)
+    for name, cls in (("sg_light_model", "SG_EnvmapMaterialNet"), ("envmap_light_model", "Envmap_EnvmapMaterialNet")):
+        _stub("nerf." + name, **{cls: None})
+    import nerf.network_curvedfield as ref_cf
+    import nerf.sh_light_model as ref_sh
+    import tools.map as ref_map
+    from RayTracer import RayTracer as RefRayTracer
+    from tools.encoding import get_encoder
+
+    c = np.load(os.path.join(OUT, "ref_python_curvedfield.npz"))
+    gs = np.load(os.path.join(OUT, "ref_python_import_shape.npz"))
+    gl = np.load(os.path.join(OUT, "ref_python_import_field_sh.npz"))
+    H, W, P, grid_gap, h_threshold = 24, 20, 5, float(gl["grid_gap"]), float(gl["h_threshold"])
+    assert h_threshold == float(gs["h_threshold"]) and grid_gap == float(gs["grid_gap"])
+    # the maps: import_field_sh_goldens' recipe, equal to what that fixture stores
+    rng = np.random.default_rng(171)
+    features = rng.uniform(-0.5, 0.5, (H, W, 16)).astype(np.float32)
+    phi_embed = rng.uniform(-0.5, 0.5, (H, W, 8)).astype(np.float32)
+    local_tbn = (np.eye(3, dtype=np.float32).reshape(9) + rng.normal(0, 0.35, (H, W, 9))).astype(np.float32)
+    sample_tbn = (np.eye(3, dtype=np.float32) + rng.normal(0, 0.3, (P, 3, 3))).astype(np.float32)
+    sample_tbn_ids = rng.integers(0, P, (H, W)).astype(np.float32)
+    for name, a in (("features", features), ("phi_embed", phi_embed), ("local_tbn", local_tbn), ("sample_tbn", sample_tbn), ("sample_tbn_ids", sample_tbn_ids)):
+        assert np.array_equal(a, gl[name]), name
+
+    # the mesh: import_shape_goldens' construction on the arrays of its fixture
+    vertices_raw, faces, uvs_raw = gs["vertices_raw"], gs["faces"].astype(np.int64), gs["uvs_raw"]
+    vertices = vertices_raw.copy()
+    vertices -= np.mean(vertices, axis=0)
+    vertices /= (np.absolute(vertices).max() + 1e-5)
+    vertices /= 1.2
+    v32 = vertices.astype(np.float32)
+    assert np.array_equal(v32, gs["vertices"])
+    mp = object.__new__(ref_map.MeshProjector)
+    uvs = torch.FloatTensor(uvs_raw)
+    mp.uvs = (uvs - uvs.min()) / (uvs.max() - uvs.min()) * 2 - 1.  # :361
+    assert np.array_equal(mp.uvs.numpy(), gs["uvs"])
+    e1, e2 = vertices[faces[:, 1]] - vertices[faces[:, 0]], vertices[faces[:, 2]] - vertices[faces[:, 0]]
+    face_normals = np.cross(e1, e2)
+    face_normals /= np.linalg.norm(face_normals, axis=-1, keepdims=True)  # (trimesh's face_normals)
+    uv_np = mp.uvs.cpu().numpy()
+    uv_edges = uv_np[faces][:, 1:] - uv_np[faces][:, :1]
+    det = np.abs(np.linalg.det(uv_edges.astype(np.float64)))
+    assert np.linalg.matrix_rank(uv_edges).min() == 2, "every UV edge matrix has rank 2"
+    tbn = ref_map.calculate_tbn(types.SimpleNamespace(vertices=vertices, faces=faces, face_normals=face_normals), uv_np)  # :366
+    assert np.isfinite(tbn).all() and len(np.unique(tbn.round(6), axis=0)) == len(faces)
+    assert np.abs(np.einsum("fab,fcb->fac", tbn, tbn) - np.eye(3)).max() < 1e-6, "orthonormal frames"
+    print("ref_python_import_shape_sh.npz:", len(faces), "faces, smallest |det| of a UV edge matrix", float(det.min()))
+    mp.tbn = torch.from_numpy(tbn).float()
+    edges_unique = np.unique(np.sort(faces[:, [0, 1, 1, 2, 2, 0]].reshape(-1, 2), axis=1), axis=0)
+    edges = vertices[edges_unique]
+    mp.mean_edge_length = np.linalg.norm(edges[:, 0] - edges[:, 1], axis=-1).mean()
+    edges_uv = uv_np[edges_unique]
+    mp.recommended_sdf_factor = mp.mean_edge_length / np.linalg.norm(edges_uv[:, 0] - edges_uv[:, 1], axis=-1).mean()
+    assert abs(float(mp.recommended_sdf_factor) / float(gs["recommended_sdf_factor"]) - 1) < 1e-12
+    mp.mesh_vertices, mp.vertex_normals = torch.FloatTensor(vertices), torch.from_numpy(gs["vertex_normals"])
+    mp.grid, mp.radius, mp.max_K, mp.depth_threshold = None, 100.0, v32.shape[0], 9.5
+    mp.raytracer = RefRayTracer(v32, faces.astype(np.uint32))
+    mp.faces = torch.from_numpy(faces).long()
+
+    # the lit field: import_field_sh_goldens' construction, equal to what that fixture stores
+    mff = object.__new__(ref_map.MeshFeatureField)
+    torch.nn.Module.__init__(mff)
+    mff.device, mff.h_threshold, mff.K, mff.bound, mff.hash, mff.prob_model, mff.pred_normal, mff.clustering = "cpu", h_threshold, 8, 1, True, False, True, True
+    mff.imported, mff.imported_type, mff.rescale = False, None, False
+    mff.sdf_scale_factor, mff.sdf_offset, mff.uv_utilize_rate, mff.K_for_uv = 1.0, 0.0, 1.0, 5
+    mff.encoder_f_out_dim = 16
+    mff.encoder_z, mff.encoder_z_outdim = get_encoder("frequency", input_dim=1, multires=12)
+    torch.manual_seed(11)
+    mff.normal_net = ref_map.Factorized_Normal_Net(x_dim=mff.encoder_f_out_dim, z_dim=mff.encoder_z_outdim, lip=True, direct_pred_coor=False, bound_output=False)
+    gen = torch.Generator().manual_seed(13)
+    with torch.no_grad():
+        for mlp in (mff.normal_net.phi_net, mff.normal_net.theta_net):
+            for layer in mlp.layers:
+                layer.W.mul_(6.0)
+                layer.b.copy_(torch.randn(layer.b.shape, generator=gen) * 0.3)
+                layer.c.fill_(2.0)
+    for name, mlp in (("phi", mff.normal_net.phi_net), ("theta", mff.normal_net.theta_net)):
+        for i, layer in enumerate(mlp.layers):
+            assert np.array_equal(layer.W.detach().numpy(), gl[f"{name}_W{i}"]) and np.array_equal(layer.b.detach().numpy(), gl[f"{name}_b{i}"])
+    net = object.__new__(ref_cf.NeRFNetwork)
+    torch.nn.Module.__init__(net)
+    net.visual_mode, net.render_light_model, net.use_grad_normal, net.fc_weight, net.dir_degree = "RGB", True, False, 1.0, 4
+    net.optimize_gamma, net.meshfea_field, net.light_model, net.smooth_grad_weight = False, mff, "SH", 1e-1
+    net.use_coarse_normal, net.coarse_as_primary, net.no_visibility, net.shade_visibility, net.light_visual_mode = False, False, False, True, "Full"
+    tcnn = sys.modules["tinycudann"]
+    torch.manual_seed(42)
+    net.sigma_net = tcnn.Network(n_input_dims=mff.encoder_z_outdim + mff.encoder_f_out_dim, n_output_dims=16,
+                                 network_config={"otype": "FullyFusedMLP", "activation": "ReLU", "output_activation": "None", "n_neurons": 32, "n_hidden_layers": 1})
+    assert np.array_equal(net.sigma_net.net.weights.detach().numpy(), c["w_sigma"])
+    net.color_net = None
+    net.light_net = ref_sh.SH_EnvmapMaterialNet(input_dim=15, sh_order=3, white_light=True, use_specular=True)
+    with torch.no_grad():
+        net.light_net.envSHs[1:] = torch.from_numpy(np.random.default_rng(91).normal(0, 1.5, (15, 1)).astype(np.float32))
+    assert np.array_equal(net.light_net.brdf_layer.net.weights.detach().numpy(), gl["w_brdf"]) and np.array_equal(net.light_net.envSHs.detach().numpy(), gl["env_shs"])
+    handed, sampled = {}, []
+    net.light_net.register_forward_pre_hook(lambda m, a: handed.update(normal=a[1].detach().float().numpy().copy()))
+    real_grid_sample = torch.nn.functional.grid_sample
+
+    def recording_grid_sample(*a, **k):
+        r = real_grid_sample(*a, **k)
+        sampled.append((k.get("mode", "bilinear"), r))
+        return r
+
+    mff.import_field(features, bounds=[0.5 * grid_gap * H, 0.5 * grid_gap * W], sample_tbn=sample_tbn, sample_tbn_ids=sample_tbn_ids, local_tbn=local_tbn,
+                     phi_embed=phi_embed)
+    # MeshFeatureField.import_shape (:939-949) behind its MeshProjector(...) call
+    assert mff.imported_type == "field" and mff.rescale
+    mff.meshprojector_imported = mp
+    mff.sdf_scale_factor = mp.recommended_sdf_factor / mff.bounds[0]
+    mff.imported, mff.imported_type = True, "shape"
+    assert abs(float(mff.sdf_scale_factor) / float(gs["sdf_scale_factor"]) - 1) < 1e-12
+
+    x, d = torch.from_numpy(gs["xyz"]), torch.from_numpy(gs["dirs"])
+    out = dict(mesh_and_points_of="ref_python_import_shape.npz", maps_and_weights_of="ref_python_import_field_sh.npz", tbn=tbn.astype(np.float32))
+    net.eval()
+    torch.nn.functional.grid_sample = recording_grid_sample
+    try:
+        for k in range(3):
+            key = f"S{k}"
+            K, rate, factor, off = int(gs[key + "_K"]), float(gs[key + "_rate"]), float(gs[key + "_sdf_factor"]), float(gs[key + "_offset"])
+            mff.K_for_uv, mff.uv_utilize_rate, mff.sdf_scale_factor, mff.sdf_offset = K, rate, factor, off
+            with torch.no_grad(), emulated_autocast():
+                uvh, hm_u, normal, new_tbn = mp.uvh(x, K=K, h_threshold=h_threshold, sdf_scale=factor / rate, sdf_offset=off)
+                del sampled[:]
+                embed, nc, nf, hm = mff(x)
+                assert [m for m, _ in sampled] == ["bilinear", "nearest", "nearest", "bilinear"]  # features, ids, local_tbn, phi_embed (:697-706)
+                ids = sampled[1][1].squeeze().long()
+                s_local = sampled[2][1].squeeze().permute(1, 0).reshape(-1, 3, 3)
+                s_phi = sampled[3][1].squeeze().permute(1, 0)
+                _, _, d1, f1 = mp.raytracer.trace(x, normal)
+                _, _, d2, f2 = mp.raytracer.trace(x, -normal)
+            face = torch.where(d1 < d2, f1, f2)  # (-1 kept as the tracer gives it; new_tbn is tbn[max(face, 0)])
+            assert torch.equal(hm, hm_u) and np.array_equal(uvh.numpy(), gs[key + "_uvh"]) and np.array_equal(hm.numpy(), gs[key + "_h_mask"])
+            assert np.array_equal(face.numpy().astype(np.int32), gs[key + "_face"]) and torch.equal(new_tbn, mp.tbn[face.clamp(min=0)])
+            # rows whose ix or iy lies within the nearest read's margin of a half-integer: the u, v bar of 2e-6 times (size - 1) / 2
+            p_sur = uvh[:, :2].double().numpy() * rate
+            near = np.zeros(len(p_sur), bool)
+            for axis, size in ((0, H), (1, W)):
+                i = (p_sur[:, axis] + 1) / 2 * (size - 1)
+                near |= np.abs(i - np.floor(i) - 0.5) <= 2e-6 * (size - 1) / 2
+            assert near.sum() <= 0.01 * len(near), (key, int(near.sum()))
+            out.update({key + "_uvh": uvh.float().numpy(), key + "_h_mask": hm.numpy(), key + "_face": face.numpy().astype(np.int32),
+                        key + "_id": ids.numpy().astype(np.int32), key + "_local_tbn": s_local.numpy(), key + "_sample_tbn_inv": mff.sample_tbn_inv_imported[ids].numpy(),
+                        key + "_new_tbn": new_tbn.numpy(), key + "_phi": s_phi.numpy(), key + "_embed28": embed.float().numpy()[:, :28], key + "_normal": nc.float().numpy(), key + "_normal_fine": nf.float().numpy(),
+                        key + "_near_texel_edge": int(near.sum())})
+            for fc in (1.0, 0.7):
+                net.fc_weight = fc
+                with torch.no_grad(), emulated_autocast():
+                    for visual in ("Full", "Specular", "Diffuse", "Albedo"):
+                        net.light_visual_mode = visual
+                        sigma, color, ret = net(x, d, is_gui_mode=False)
+                        assert ret == {}
+                        out[f"{key}_fc{fc}_color_{visual.lower()}"] = color.half().numpy()
+                out[key + "_sigma"], out[f"{key}_fc{fc}_shading_normal"] = sigma.float().numpy(), handed["normal"]
+            print("ref_python_import_shape_sh.npz:", key, "inside the mask", float(hm.float().mean()), "sigma max", float(sigma.max()), "rows near a texel edge",
+                  int(near.sum()), "fine normal away from the face normal by (median)",
+                  float(np.median(np.abs(nf.numpy() - new_tbn.numpy()[:, 2]).max(-1)[hm.numpy()])))
+    finally:
+        torch.nn.functional.grid_sample = real_grid_sample
+    np.savez_compressed(os.path.join(OUT, "ref_python_import_shape_sh.npz"), **out)
     new = [os.path.join(r, n) for r, _, names in os.walk(REF) for n in names if os.lstat(os.path.join(r, n)).st_mtime >= started]
     assert not new, "files appeared under the reference tree:\n" + "\n".join(new[:20])
 
