@@ -612,6 +612,13 @@ int nerftex_compact_rays_budget_mirror_dev(uint32_t n_alive_bound, const int32_t
  * numbers (noise / rand_coords / rand_pick, each optional: NULL = the library's
  * counter-based generator keyed by `seed`) the grid and bitfield equal what the
  * reference's Python computes.
+ * Accepted shapes, all four entry points: 1 <= cascade <= 8; H a power of two,
+ * 8 ... 1024 (cells are indexed by their 3-D Morton code, which runs past H^3
+ * for any other grid size); cascade * H^3 < 2^32 and cascade * rows per
+ * cascade (2 N, rows_per_cascade) < 2^32 (cell and row indices are 32-bit).
+ * Anything else returns NERFTEX_ERR_INVALID before any allocation or launch
+ * (tests/test_gpu_occupancy_edges.py holds the kernels against a host model
+ * at H = 8 ... 64).
  * ------------------------------------------------------------------------- */
 
 /* Full sweep (renderer.py:579-605): jittered query position of every cell of every cascade, row = cas * H^3 + Morton index,

@@ -209,7 +209,9 @@ __global__ __launch_bounds__(kBlock) void scatter_max_kernel(const float* __rest
     if (idx < 0) return;
     const float s = sigmas[row];
     if (!(s >= 0.0f)) return;  // a negative (or NaN) estimate never passes the reference's `tmp_grid >= 0` either
-    atomicMax(reinterpret_cast<int*>(tmp) + (size_t)(row / rows_per_cascade) * H3 + (uint32_t)idx, __builtin_bit_cast(int, s));
+    // -0.0f passes (`-0 >= 0`, in the reference too: the cell is valid and decays) but its bit pattern is the smallest int, below the fill's -1.0f:
+    // it lands as +0
+    atomicMax(reinterpret_cast<int*>(tmp) + (size_t)(row / rows_per_cascade) * H3 + (uint32_t)idx, __builtin_bit_cast(int, s) & 0x7FFFFFFF);
 }
 
 constexpr uint32_t kEmaPerThread = 4;
@@ -229,15 +231,7 @@ __global__ __launch_bounds__(kBlock) void ema_kernel(float* __restrict__ grid, c
             acc += (double)fmaxf(g[k], 0.0f);
         }
         *reinterpret_cast<float4_t*>(grid + i0) = g;
-    } else {
-        for (size_t i = i0; i < n; i++) {
-            float g = grid[i];
-            const float t = tmp[i];
-            if (force_full_grid || (g >= 0.0f && t >= 0.0f)) g = fmaxf(g * decay, t);
-            grid[i] = g;
-            acc += (double)fmaxf(g, 0.0f);
-        }
-    }
+    }  // no ragged end: check_shape admits powers of two from 8 up, so n is a multiple of 512
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
     if ((threadIdx.x & 63u) == 0) s_sum[threadIdx.x >> 6] = acc;
@@ -283,9 +277,24 @@ __global__ __launch_bounds__(kBlock) void packbits_dev_thresh_kernel(const float
     bitfield[n] = (uint8_t)bits;
 }
 
+// The kernels index cells by their 3-D Morton code, which stays below H^3 only for a power of two (H = 24 decodes coordinates up to 31 and encodes
+// indices up to 32767 against 13824 cells), and they form every row and cell count in 32 bits.
 int check_shape(uint32_t cascade, uint32_t H) {
-    if (cascade == 0 || cascade > kMaxCascade || H == 0 || H > 1024 || (H & 7u)) {
-        set_error("occupancy: need 1 <= cascade <= %u and a grid size that is a multiple of 8 up to 1024", kMaxCascade);
+    if (cascade == 0 || cascade > kMaxCascade || H < 8 || H > 1024 || (H & (H - 1u))) {
+        set_error("occupancy: need 1 <= cascade <= %u and a grid size that is a power of two, 8 ... 1024", kMaxCascade);
+        return NERFTEX_ERR_INVALID;
+    }
+    if ((uint64_t)cascade * H * H * H >= (1ull << 32)) {
+        set_error("occupancy: cascade * H^3 = %llu cells do not fit the kernels' 32-bit cell index", (unsigned long long)cascade * H * H * H);
+        return NERFTEX_ERR_INVALID;
+    }
+    return NERFTEX_OK;
+}
+
+// cascade * rows_per_cascade, the launch size of the partial sampler (2 N rows per cascade) and of the scatter, is a 32-bit row index too
+int check_rows(const char* who, uint32_t cascade, uint64_t rows_per_cascade) {
+    if ((uint64_t)cascade * rows_per_cascade >= (1ull << 32)) {
+        set_error("%s: cascade * rows per cascade = %llu rows do not fit the kernels' 32-bit row index", who, (unsigned long long)cascade * rows_per_cascade);
         return NERFTEX_ERR_INVALID;
     }
     return NERFTEX_OK;
@@ -317,12 +326,13 @@ extern "C" int nerftex_occupancy_sample_partial_ordered(const float* density_gri
                                                         const int32_t* rand_coords, const int32_t* rand_pick, const float* noise, uint64_t seed,
                                                         int32_t* indices, float* xyzs, uint32_t* n_occupied, int stratified, void* stream) {
     clear_error();
+    int rc = check_shape(cascade, H);
+    if (rc != NERFTEX_OK) return rc;
+    if ((rc = check_rows("occupancy_sample_partial", cascade, 2ull * N)) != NERFTEX_OK) return rc;
     if (stratified && N != 0 && (H * H * H) % N != 0) {
         set_error("occupancy_sample_partial_ordered: the stratified draw needs N to divide H^3");
         return NERFTEX_ERR_INVALID;
     }
-    int rc = check_shape(cascade, H);
-    if (rc != NERFTEX_OK) return rc;
     if (N == 0) return NERFTEX_OK;
     hipStream_t st = as_stream(stream);
     const uint32_t H3 = H * H * H, nblk = div_up(H3, kBlock);
@@ -354,8 +364,13 @@ extern "C" int nerftex_occupancy_update(float* density_grid, const float* sigmas
     clear_error();
     int rc = check_shape(cascade, H);
     if (rc != NERFTEX_OK) return rc;
+    if ((rc = check_rows("occupancy_update", cascade, rows_per_cascade)) != NERFTEX_OK) return rc;
     if (!mean_thresh) {
         set_error("occupancy_update: mean_thresh (2 floats on the device: mean density, packing threshold) must not be NULL");
+        return NERFTEX_ERR_INVALID;
+    }
+    if (!indices && rows_per_cascade != H * H * H) {
+        set_error("occupancy_update: a full sweep (indices == NULL) carries H^3 estimates per cascade in Morton order");
         return NERFTEX_ERR_INVALID;
     }
     hipStream_t st = as_stream(stream);
@@ -374,9 +389,6 @@ extern "C" int nerftex_occupancy_update(float* density_grid, const float* sigmas
         hipLaunchKernelGGL(fill_kernel, dim3(2048), dim3(kBlock), 0, st, t, n, -1.0f);
         hipLaunchKernelGGL(scatter_max_kernel, dim3(div_up(cascade * rows_per_cascade, kBlock)), dim3(kBlock), 0, st, sigmas, indices, rows_per_cascade, cascade, H3, t);
         tmp = t;
-    } else if (rows_per_cascade != H3) {
-        set_error("occupancy_update: a full sweep (indices == NULL) carries H^3 estimates per cascade in Morton order");
-        return NERFTEX_ERR_INVALID;
     }
     {
         KernelTimer kt("occupancy_ema_kernel", st);
