@@ -10,6 +10,8 @@ import numpy as np
 import pytest
 import torch
 
+from infer_loop_model import unit_rows as _unit_rows  # unit_rows of csrc/common.hpp, restated once for the tests
+
 pytestmark = pytest.mark.gpu
 
 SENTINEL = -7.5
@@ -32,14 +34,6 @@ def _curved_field(dev):
         field.encoder.embeddings.uniform_(-0.5, 0.5)
         field.sigma_net.weights.mul_(3.0)
     return field.eval(), v
-
-
-def _unit_rows(code, count):
-    """unit_rows of csrc/common.hpp: a plain number, or NERFTEX_ROWS_AUTO(N, F) -> clamp(F N / count, F, 8 F)."""
-    if not code >> 31:
-        return code
-    F, N = (code >> 24) & 127, code & 0xFFFFFF
-    return min(max(F * N // max(count, 1), F), 8 * F)
 
 
 def _batch(dev, n):
