@@ -1195,6 +1195,47 @@ size_t nerftex_curved_light_shape_infer_scratch_bytes(uint32_t B);
 int nerftex_curved_light_shape_infer(const nerftex_curved_light_shape_infer_desc* d, void* stream);
 
 /* -------------------------------------------------------------------------
+ * Extension: the front of the patch export -- the per-candidate part of MeshFeatureField.sample_patches (tools/map.py:1030-1084, the
+ * non-trimesh path) for a CHUNK of B candidate patches of S x S pixels in three launches and no host synchronisation, instead of one
+ * 16 384-ray trace, one CPU KD-tree query and one read-back per candidate.
+ *   cast    grid (ceil(S^2 / 64), B), one pixel per lane.  Pixel p = i S + j has the local coordinates (x, y) = (calibration[i],
+ *           calibration[j]) (meshgrid(indexing='ij')).  With T = frames[b] ([3,4] row-major: columns x axis, y axis, z axis, centre), per axis a
+ *               o[a]      = (T[a][0] x + T[a][1] y) + T[a][3]      the pre-lift origin: every product and sum rounded on its own (fp32,
+ *                                                                  no fused multiply-add); the reference's T[a][2] * 0 term is dropped
+ *               origin[a] = o[a] + (0.1f T[a][2]),  direction[a] = -T[a][2]
+ *           and the ray is traced as nerftex_raytracer_trace traces it (intersection = fma(depth, direction, origin); depth 10 on a miss).
+ *           origins [B,S^2,3] takes the PRE-LIFT origins, intersections [B,S^2,3] the hits, rays [B,S^2,6] (optional) the lifted origin and
+ *           the direction.  Per patch: the maximum depth and "a pre-lift origin is NaN", reduced per wave, one vector atomic per wave.
+ *   scan    only with a scan cloud: the distance of every pre-lift origin to its nearest scan point (nerftex_knn_query's search with K = 1,
+ *           its distance bit for bit) and per patch the maximum.
+ *   select  one workgroup.  verdict[b], in the reference's order of tests -- 2: a NaN origin; 3: maximum scan distance > max_scan_dist;
+ *           4: maximum depth > 9.5 (a ray missed); 0: accepted -- and 5 for EVERY candidate behind the one that made the running count reach
+ *           max_patch_num (the reference's loop has ended there).  count[0] is the device-resident number of patches accepted so far (the caller zeroes
+ *           it once); slot[b] = the global patch index of an accepted candidate (count[0] before the call + its rank among the chunk's accepted,
+ *           in candidate order), -1 otherwise; count[0] grows by the number accepted.  (Code 1, "below y = 0 with no scan cloud", is the host's.)
+ * stats [B,4] uint32 is scratch (zeroed by the call): {bits of the maximum depth, NaN flag, bits of the maximum scan distance, 0}.
+ * NERFTEX_ERR_INVALID before anything touches a device: a NULL descriptor or tracer, frames, calibration, origins, intersections, stats,
+ * verdict, slot or count; B = 0; S = 0; S^2 B beyond uint32; max_patch_num = 0.
+ * ------------------------------------------------------------------------- */
+typedef struct nerftex_patch_front_desc {
+    const nerftex_raytracer* tracer;   /* the mesh the patches are cast on                                                        */
+    const nerftex_knn* scan;           /* the scan cloud's grid, or NULL: no scan test                                            */
+    const float* frames;               /* [B,12] fp32: T[:3,:4] of every candidate, row-major                                     */
+    const float* calibration;          /* [S] fp32                                                                                */
+    uint32_t B, S;
+    float max_scan_dist;               /* min(0.1, 3 h_threshold) of tools/map.py:1078                                            */
+    uint32_t max_patch_num;
+    float* origins;                    /* [B,S^2,3] fp32 out: the pre-lift origins                                                */
+    float* intersections;              /* [B,S^2,3] fp32 out                                                                      */
+    float* rays;                       /* [B,S^2,6] fp32 out, or NULL                                                             */
+    uint32_t* stats;                   /* [B,4] scratch                                                                           */
+    uint8_t* verdict;                  /* [B] out                                                                                 */
+    int32_t* slot;                     /* [B] out                                                                                 */
+    uint32_t* count;                   /* [1] in / out, device-resident                                                           */
+} nerftex_patch_front_desc;
+int nerftex_patch_front(const nerftex_patch_front_desc* d, void* stream);
+
+/* -------------------------------------------------------------------------
  * Extension: the SH light head of the curved field -- SH_EnvmapMaterialNet.forward behind its BRDF MLP (nerf/sh_light_model.py:554-616) -- as one
  * streaming kernel per direction instead of ~40 framework ops per sample batch, the framework's arithmetic at its rounding points:
  *   albedo = half(sigmoid(brdf[:, :3])), spec_w = half(sigmoid(brdf[:, 3]))              (fp32 sigmoid narrowed to half)

@@ -65,6 +65,10 @@ int curved_shape_light_rows(const nerftex_raytracer* rt, const float* xyz, const
                             uint32_t K, const float* mesh_vertices, const float* vertex_normals, uint32_t n_verts, const ShapeLookup& s, const ShapeLight& t,
                             uint8_t* mask, float* normal, const int32_t* units_dev, uint32_t rows_per_unit, hipStream_t st);
 
+// The scan launch of nerftex_patch_front (raytracer.hip / patch_export.inc; the kernel sits beside the neighbour search in knn.hip): for the
+// chunk's pre-lift origins [B, S2, 3], stats[4 b + 2] = max(stats[4 b + 2], bits of the patch's largest nearest-scan-point distance).
+int patch_scan(const nerftex_knn* scan, const float* origins, uint32_t B, uint32_t S2, uint32_t* stats, hipStream_t st);
+
 // nerftex_ffmlp_inference (fp16, ReLU, no output activation) of the curved field's networks -- (IN, H, NL) = (48, 32, 2), (32, 64, 3) or the SH
 // light head's BRDF net (16, 64, 3) -- over the 128-row workgroups that hold a live row; a workgroup wholly past the live rows exits before it
 // stages its weights.

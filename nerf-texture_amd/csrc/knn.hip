@@ -81,18 +81,16 @@ __device__ __forceinline__ void scan_range(const P4* __restrict__ points, uint32
 // The search grows a block of cells around the query's cell: radius 1 (3 x 3 x 3), then 2, ...  The vertex array is sorted by cell with
 // x fastest, so a ROW of the block (cells x0..x1 at one y, z) is ONE contiguous range: nine ranges for the first block instead of 27
 // cells.  A larger block adds whole rows on its new y / z faces and the two end cells of the rows it already covered.
+// -> best[K] (SQUARED distances, ascending) and ids[K] of the query point q
 template <int K>
-__device__ __forceinline__ void knn_query_point(const uint32_t i, const float* __restrict__ xyz, const GridDesc& g, const uint32_t* __restrict__ cell_start,
-                                                const P4* __restrict__ points, uint32_t k_out, int32_t* __restrict__ idx, float* __restrict__ dist) {
-    const float q[3] = {xyz[3 * (size_t)i], xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2]};
+__device__ __forceinline__ void knn_search_point(const float (&q)[3], const GridDesc& g, const uint32_t* __restrict__ cell_start, const P4* __restrict__ points,
+                                                 float (&best)[K], int (&ids)[K]) {
     int c[3];
 #pragma unroll
     for (int d = 0; d < 3; d++) {
         const float f = floorf((q[d] - g.lo[d]) * g.inv_cell);
         c[d] = (int)fminf(fmaxf(f, 0.0f), (float)(g.dims[d] - 1));  // NaN -> 0
     }
-    float best[K];
-    int ids[K];
 #pragma unroll
     for (int k = 0; k < K; k++) { best[k] = INFINITY; ids[k] = -1; }
     const int rmax = max(g.dims[0], max(g.dims[1], g.dims[2]));
@@ -140,6 +138,15 @@ __device__ __forceinline__ void knn_query_point(const uint32_t i, const float* _
         reach = fmaxf(reach - g.eps, 0.0f);
         if (best[K - 1] <= reach * reach) break;
     }
+}
+
+template <int K>
+__device__ __forceinline__ void knn_query_point(const uint32_t i, const float* __restrict__ xyz, const GridDesc& g, const uint32_t* __restrict__ cell_start,
+                                                const P4* __restrict__ points, uint32_t k_out, int32_t* __restrict__ idx, float* __restrict__ dist) {
+    const float q[3] = {xyz[3 * (size_t)i], xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2]};
+    float best[K];
+    int ids[K];
+    knn_search_point<K>(q, g, cell_start, points, best, ids);
 #pragma unroll
     for (int k = 0; k < K; k++)
         if ((uint32_t)k < k_out) {
@@ -167,6 +174,26 @@ __global__ __launch_bounds__(256) void knn_query_rows_kernel(uint32_t N, const f
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= live_rows(N, units_dev, rows_per_unit) || slot_unused(dirs, i)) return;
     knn_query_point<K>(i, xyz, g, cell_start, points, k_out, idx, dist);
+}
+
+// the scan launch of nerftex_patch_front (patch_export.inc): the distance of every pre-lift origin of a chunk to its nearest scan point -- the K = 1
+// search, sqrtf(best[0]) as knn_query_point reports it -- and per patch the maximum: a wave lies inside one patch (grid row b), reduces by shuffle
+// and sends one atomicMax of the bits (a distance is never negative and never NaN: +inf where nothing compares)
+__global__ __launch_bounds__(256) void patch_scan_kernel(const uint32_t S2, const float* __restrict__ origins, const GridDesc g, const uint32_t* __restrict__ cell_start,
+                                                         const P4* __restrict__ points, uint32_t* __restrict__ stats) {
+    const uint32_t b = blockIdx.y, p = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t bits = 0u;  // what a lane past S^2 contributes: nothing
+    if (p < S2) {
+        const size_t row = (size_t)b * S2 + p;
+        const float q[3] = {origins[3 * row], origins[3 * row + 1], origins[3 * row + 2]};
+        float best[1];
+        int ids[1];
+        knn_search_point<1>(q, g, cell_start, points, best, ids);
+        bits = __float_as_uint(sqrtf(best[0]));
+    }
+#pragma unroll
+    for (int m = kWave / 2; m > 0; m >>= 1) bits = max(bits, (uint32_t)__shfl_xor((int)bits, m, kWave));
+    if ((threadIdx.x & (kWave - 1)) == 0) atomicMax(stats + 4 * (size_t)b + 2, bits);
 }
 
 }  // namespace
@@ -294,4 +321,14 @@ extern "C" int nerftex_knn_query(const nerftex_knn* kn, const float* xyz, uint32
         else hipLaunchKernelGGL(knn_query_kernel<16>, grid, block, 0, as_stream(stream), N, xyz, g, cs, pts, K, idx, dist);
     }
     return check_launch("knn_query");
+}
+
+int nerftex::patch_scan(const nerftex_knn* scan, const float* origins, uint32_t B, uint32_t S2, uint32_t* stats, hipStream_t st) {
+    const GridDesc g = grid_desc(scan);
+    {
+        KernelTimer kt("patch_scan_kernel", st);
+        hipLaunchKernelGGL(patch_scan_kernel, dim3(div_up(S2, 256u), B), dim3(256), 0, st, S2, origins, g, static_cast<const uint32_t*>(scan->cell_start),
+                           static_cast<const P4*>(scan->points), stats);
+    }
+    return check_launch("patch_front(scan)");
 }

@@ -841,3 +841,5 @@ extern "C" int nerftex_shape_lookup(const nerftex_raytracer* rt, const float* xy
                                static_cast<half_t*>(xin), nullptr, 0u);
     return check_launch("shape_lookup");
 }
+
+#include "patch_export.inc"

@@ -59,6 +59,7 @@ _SIGNATURES = {
     "nerftex_shape_light_lookup": [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _u32, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _f32, _f32, _f32,
                                    _f32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "nerftex_curved_light_shape_infer": [_vp, _vp],
+    "nerftex_patch_front": [_vp, _vp],
     "nerftex_sh_light_forward": [_vp, _vp],
     "nerftex_sh_light_backward": [_vp, _vp],
     "nerftex_field_mid_backward": [_vp, _vp, _vp, _u32, _vp, _vp],
@@ -286,6 +287,15 @@ class CurvedLightShapeInferDesc(C.Structure):
                 ("env_shs", _vp), ("n_sh", _u32), ("n_color", _u32), ("gamma", _f32), ("flags", _u32), ("visual_mode", _u32), ("fc_weight", _f32), ("eval", _i),
                 ("sigma", _vp), ("rgbs", _vp), ("shading_normal", _vp), ("units_dev", _vp), ("rows_per_unit", _u32), ("scratch", _vp), ("scratch_bytes", _sz)]
 
+
+class PatchFrontDesc(C.Structure):
+    """nerftex_patch_front_desc of include/nerftex_hip.h, field for field: the front of the patch export for a chunk of candidates."""
+    _fields_ = [("tracer", _vp), ("scan", _vp), ("frames", _vp), ("calibration", _vp), ("B", _u32), ("S", _u32), ("max_scan_dist", _f32),
+                ("max_patch_num", _u32), ("origins", _vp), ("intersections", _vp), ("rays", _vp), ("stats", _vp), ("verdict", _vp), ("slot", _vp),
+                ("count", _vp)]
+
+
+PATCH_ACCEPTED, PATCH_BELOW, PATCH_NAN, PATCH_FAR, PATCH_MISSED, PATCH_NOT_NEEDED = 0, 1, 2, 3, 4, 5  # the verdict codes of nerftex_patch_front (1: the host's)
 
 SH_LIGHT_SPECULAR = 1  # nerftex_sh_light_desc.flags
 

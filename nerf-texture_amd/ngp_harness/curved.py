@@ -545,6 +545,7 @@ class CurvedField(torch.nn.Module):
 
         self.bound, self.h_threshold, self.geo_feat_dim, self.multires, self.fc_weight = bound, h_threshold, geo_feat_dim, 12, 1.0
         self.projector = MeshProjector(vertices, faces, h_threshold=h_threshold, K=K, vertex_normals=vertex_normals, tbn=tbn)
+        self.mesh_faces = np.array(torch.as_tensor(faces).cpu() if torch.is_tensor(faces) else faces, dtype=np.int64)  # (export_field: the mesh's unique edges)
         self._init_import_state()
         kw = dict(input_dim=3, num_levels=num_level, level_dim=2, base_resolution=512, log2_hashmap_size=19, desired_resolution=1024, gridtype="hash",
                   align_corners=True)
@@ -854,6 +855,37 @@ class CurvedField(torch.nn.Module):
         if details:
             return embed, normal_coarse, h_mask, fine, p_uv, sdf, face, phi, local_tbn, ids, sample_tbn_inv, new_tbn
         return embed, normal_coarse, h_mask, fine
+
+    # ---- the trained field exported as texture patches (NeRFNetwork.export_field -> MeshFeatureField.sample_patches, tools/map.py:951-1128) ----
+
+    def export_field(self, sample_points, sample_normals, *, scan_points=None, first_component=None, grid_gap=None, pattern_rate=1 / 50, patch_size=128,
+                     max_patch_num=2000, sample_mesh=None, record_rays=False, patches_per_chunk=None, fused=True):
+        """The reference's non-trimesh path (use_trimesh_raycast=False, cast_on_mfs=True): an S x S pixel patch is laid on the tangent plane of every
+        candidate, aligned with the mesh's first principal direction, cast onto the mesh along -normal, and -- unless a pixel's origin is NaN, the
+        patch lies farther than min(0.1, 3 h_threshold) from the scan cloud, or a ray misses -- its hits are projected and looked up in the
+        field's own tables.  What the reference gets from open3d / trimesh / sklearn comes from the caller:
+          sample_points, sample_normals [n,3]  the candidate centres and their normals (Poisson-disk samples with face normals, or template vertices)
+          scan_points [m,3]                    the scan cloud; None: no scan test, and candidates below y = 0 are dropped (:1026)
+          sample_mesh = (vertices, faces)      the picked faces to cast on (and whose edges set grid_gap); default: the field's own mesh and tracer
+          first_component, grid_gap            default: `patches.principal_direction` of the field's mesh, `patches.patch_grid_gap` of sample_mesh
+        patches_per_chunk: candidates per front call (default: about 2^18 rays).  Every chunk is one nerftex_patch_front call and one read-back of
+        its verdicts and slots -- the chunk's only host synchronisation; everything else stays on the device until the loop has ended, at
+        max_patch_num accepted patches or the last candidate.  fused=False: the staged form (`patches._export_field_reference`), the
+        reference's loop patch by patch; the two agree bit for bit.
+        -> dict of float32 numpy arrays (the reference holds the same fp32 values in float64 arrays), P accepted patches, S = patch_size:
+          patches [P,S,S,16], grid_gap (float), patch_coors [P,S,S,3], patch_norms [P,3], patch_sample_tbn [P,9] (the frame's axes x, y, z in
+          fp32), patch_local_tbn [P,S,S,9], picked_vertices [P,3], patch_phi_embed [P,S,S,8] (None without a normal net), patch_rays [P,S,S,6]
+          (None unless record_rays), and two keys the reference does not have: candidate_ids [P] int64 and verdicts [n] uint8
+          (`patches.ACCEPTED` ... `patches.NOT_NEEDED`).
+        Deviations: the reference's 'mesh' entry is dropped (the caller has it), and where it returns an untruncated zero array for the rays
+        without record_rays, this returns None.  An imported field refuses: switch_import() back first."""
+        from . import patches
+
+        kw = dict(scan_points=scan_points, first_component=first_component, grid_gap=grid_gap, pattern_rate=pattern_rate, patch_size=patch_size,
+                  max_patch_num=max_patch_num, sample_mesh=sample_mesh, record_rays=record_rays)
+        if fused:
+            return patches.export_field(self, sample_points, sample_normals, patches_per_chunk=patches_per_chunk, **kw)
+        return patches._export_field_reference(self, sample_points, sample_normals, **kw)
 
     def switch_import(self):
         """network_curvedfield.py:519-521: between the imported map and the field's own mesh and table (the map is kept)."""
