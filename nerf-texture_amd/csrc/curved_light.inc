@@ -1,7 +1,8 @@
 // nerftex_curved_light_infer: the curved field with the SH light model as ONE device-count call (include/nerftex_hip.h), the rows contract of
 // nerftex_curved_field_infer.  Included at the end of fieldglue.hip behind shlight.inc: the closing kernel below shades a row with the head's own
-// row functions (shade_row, row_output) under that file's fp contract(off), restated here; the light mid kernel and the packed normal-net
-// block's constants live in fieldglue.hip in front of both.
+// row functions (shade_row, row_output) under that file's fp contract(off), restated here; the light mid kernel, the packed normal-net
+// block's constants and the back half's buffers (LightBack) live in fieldglue.hip in front of both.  curved_light_back_half below is the closing
+// sequence of all three lit entries (this one, planar_light.inc, shape_light.inc): light mid -> BRDF net -> closing kernel.
 
 #pragma clang fp contract(off)  // every framework op rounds on its own (file scope, as shlight.inc)
 
@@ -42,12 +43,9 @@ struct CurvedLightScratch {
     CurvedFront f;
     float* tbn;
     half_t* n_lbc;
-    float* sigma_raw;
-    half_t *brdf_in, *brdf;
-    float* shading;  // (used when the caller does not ask for the shading normal)
+    LightBack back;
     CurvedLightScratch(void* scratch, size_t B)
-        : carve{reinterpret_cast<uintptr_t>(scratch), B}, f(carve), tbn(carve.take<float>(9)), n_lbc(carve.take<half_t>(8)), sigma_raw(carve.take<float>(1)),
-          brdf_in(carve.take<half_t>(16)), brdf(carve.take<half_t>(16)), shading(carve.take<float>(3)) {}
+        : carve{reinterpret_cast<uintptr_t>(scratch), B}, f(carve), tbn(carve.take<float>(9)), n_lbc(carve.take<half_t>(8)), back(carve) {}
 };
 
 // The refusals over the light head's members (n_sh .. eval), which the two lit chains' descriptors share; `who`: the entry's name in the messages.
@@ -66,7 +64,7 @@ bool light_head_ok(const Desc* d, const char* who) {
     return true;
 }
 
-// the closing launch of the two lit chains
+// the closing launch of the lit chains
 template <typename Desc>
 void launch_light_out(const Desc* d, const half_t* brdf, const float* shading, const uint8_t* mask, const float* sigma_raw, hipStream_t st) {
     const dim3 grid(div_up(d->B, 256u)), block(256);
@@ -79,6 +77,29 @@ void launch_light_out(const Desc* d, const half_t* brdf, const float* shading, c
     else
         hipLaunchKernelGGL(curved_light_out_rows_kernel<1>, grid, block, 0, st, brdf, shading, d->dirs, d->env_shs, mask, sigma_raw, d->B, inv_gamma, spec,
                            (int)d->visual_mode, d->sigma, d->rgbs, d->units_dev, d->rows_per_unit);
+}
+
+// The launches of the lit chains' back half: light mid (the normal nets, FRAMES rotations by tbn, tbn2, tbn3 -- curved_light_mid_row -- into the caller's
+// shading_normal or the scratch's) -> BRDF net 16 -> 64 x 3 -> 5 -> the head + mask as fp32.  h [B,16]: the sigma net's output, xin [B,48] its input,
+// n_lbc [4,B,2]: the normal table's features, normal [B,3]: the raw coarse normal, mask [B]; labels: the entry's check_launch labels of the two kernels.
+template <int FRAMES, typename Desc>
+int curved_light_back_half(const Desc* d, const half_t* h, const half_t* xin, const half_t* n_lbc, const float* normal, const float* tbn, const float* tbn2,
+                           const float* tbn3, const uint8_t* mask, const LightBack& k, const char* const (&labels)[2], void* stream) {
+    hipStream_t st = as_stream(stream);
+    float* shading = d->shading_normal ? d->shading_normal : k.shading;
+    const uint32_t B = d->B, rpu = d->rows_per_unit;
+    const int32_t* units = d->units_dev;
+    {
+        KernelTimer kt("curved_light_mid_rows_kernel", st);
+        hipLaunchKernelGGL(curved_light_mid_rows_kernel<FRAMES>, dim3(div_up(B, 256u)), dim3(256), 0, st, h, xin, n_lbc, normal, tbn, tbn2, tbn3, d->dirs,
+                           static_cast<const half_t*>(d->normal_weights), d->normal_biases, B, d->fc_weight, d->eval, k.sigma_raw, k.brdf_in, shading, units, rpu);
+    }
+    int rc = check_launch(labels[0]);
+    if (rc != NERFTEX_OK) return rc;
+    rc = ffmlp_inference_rows(k.brdf_in, d->brdf_weights, B, 16, 64, 3, k.brdf, units, rpu, st);
+    if (rc != NERFTEX_OK) return rc;
+    launch_light_out(d, k.brdf, shading, mask, k.sigma_raw, st);
+    return check_launch(labels[1]);
 }
 
 }  // namespace
@@ -104,35 +125,21 @@ extern "C" int nerftex_curved_light_infer(const nerftex_curved_light_infer_desc*
                   "and hold %zu bytes", sc.carve.at);
         return NERFTEX_ERR_INVALID;
     }
-    if (!front_scales_ok(d) || (reinterpret_cast<uintptr_t>(d->brdf_weights) & 15) ||
+    if (!front_scales_ok(d) || !aligned16(d->brdf_weights) ||
         ((reinterpret_cast<uintptr_t>(d->normal_weights) | reinterpret_cast<uintptr_t>(d->normal_biases)) & 3) || !(d->normal_in_mul > 0.0f) ||
         !std::isfinite(d->normal_in_mul)) {
         set_error("curved_light_infer: the MLP weight vectors must be 16-byte aligned, the normal net's block 4-byte aligned, and the gathers' input scales "
                   "positive and finite");
         return NERFTEX_ERR_INVALID;
     }
-    hipStream_t st = as_stream(stream);
-    float* shading = d->shading_normal ? d->shading_normal : sc.shading;
-    const uint32_t B = d->B, rpu = d->rows_per_unit;
-    const int32_t* units = d->units_dev;
-    const dim3 grid(div_up(B, 256u)), block(256);
-
     int rc = curved_front_gather(d, sc.f, sc.tbn, stream);
     if (rc != NERFTEX_OK) return rc;
     // (the normal table's gather, in front of the pack kernel: an exported entry, as the texture table's)
-    rc = nerftex_grid_encode_forward_rows(sc.f.p_sur, d->normal_table, d->normal_offsets, sc.n_lbc, B, d->D, d->normal_C, d->normal_L, d->normal_S, d->normal_H,
-                                          d->normal_gridtype, d->normal_align_corners, NERFTEX_F16, NERFTEX_LAYOUT_LBC, d->normal_in_add, d->normal_in_mul, units,
-                                          rpu, stream);
+    rc = nerftex_grid_encode_forward_rows(sc.f.p_sur, d->normal_table, d->normal_offsets, sc.n_lbc, d->B, d->D, d->normal_C, d->normal_L, d->normal_S, d->normal_H,
+                                          d->normal_gridtype, d->normal_align_corners, NERFTEX_F16, NERFTEX_LAYOUT_LBC, d->normal_in_add, d->normal_in_mul,
+                                          d->units_dev, d->rows_per_unit, stream);
     if (rc != NERFTEX_OK) return rc;
     if ((rc = curved_front_sigma(d, sc.f, "curved_light_infer(pack)", stream)) != NERFTEX_OK) return rc;
-    {
-        KernelTimer kt("curved_light_mid_rows_kernel", st);
-        hipLaunchKernelGGL(curved_light_mid_rows_kernel<1>, grid, block, 0, st, sc.f.h, sc.f.xin, sc.n_lbc, sc.f.normal, sc.tbn, nullptr, nullptr, d->dirs,
-                           static_cast<const half_t*>(d->normal_weights), d->normal_biases, B, d->fc_weight, d->eval, sc.sigma_raw, sc.brdf_in, shading, units, rpu);
-    }
-    if ((rc = check_launch("curved_light_infer(mid)")) != NERFTEX_OK) return rc;
-    rc = ffmlp_inference_rows(sc.brdf_in, d->brdf_weights, B, 16, 64, 3, sc.brdf, units, rpu, st);
-    if (rc != NERFTEX_OK) return rc;
-    launch_light_out(d, sc.brdf, shading, sc.f.mask, sc.sigma_raw, st);
-    return check_launch("curved_light_infer(out)");
+    static const char* const labels[2] = {"curved_light_infer(mid)", "curved_light_infer(out)"};
+    return curved_light_back_half<1>(d, sc.f.h, sc.f.xin, sc.n_lbc, sc.f.normal, sc.tbn, nullptr, nullptr, sc.f.mask, sc.back, labels, stream);
 }

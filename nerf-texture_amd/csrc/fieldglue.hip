@@ -432,6 +432,8 @@ struct ScratchCarver {
     }
 };
 
+inline bool aligned16(const void* p) { return !(reinterpret_cast<uintptr_t>(p) & 15); }
+
 // the buffers of the front half; each entry's scratch carves them first and its own behind them
 struct CurvedFront {
     int32_t* idx;
@@ -449,6 +451,26 @@ struct CurvedBack {
     explicit CurvedBack(ScratchCarver& c) : sigma_raw(c.take<half_t>(1)), cin(c.take<half_t>(32)), hc(c.take<half_t>(16)) {}
 };
 
+// the buffers of the back half the three lit entries (curved_light.inc, planar_light.inc, shape_light.inc) share: light mid kernel to the closing kernel
+struct LightBack {
+    float* sigma_raw;
+    half_t *brdf_in, *brdf;
+    float* shading;  // (used when the caller does not ask for the shading normal)
+    explicit LightBack(ScratchCarver& c) : sigma_raw(c.take<float>(1)), brdf_in(c.take<half_t>(16)), brdf(c.take<half_t>(16)), shading(c.take<float>(3)) {}
+};
+
+// the leading buffers of the two shape entries (planar.inc, shape_light.inc): neighbour search, shape lookup, sigma net
+struct ShapeFront {
+    int32_t* idx;
+    float* dist;
+    uint8_t* mask;
+    float* normal;
+    half_t *xin, *h;
+    explicit ShapeFront(ScratchCarver& c)
+        : idx(c.take<int32_t>(16)), dist(c.take<float>(16)),  // (sized for the largest K)
+          mask(c.take<uint8_t>(1)), normal(c.take<float>(3)), xin(c.take<half_t>(48)), h(c.take<half_t>(16)) {}
+};
+
 // the scratch of one nerftex_curved_field_infer call
 struct CurvedScratch {
     ScratchCarver carve;
@@ -459,8 +481,9 @@ struct CurvedScratch {
 
 // The refusals over the descriptors' shared members (knn .. in_mul, the sigma net, scratch), in the order include/nerftex_hip.h documents: each
 // entry calls them one after the other and puts its own conditions beside them.  `who`: the entry's name in the messages.
+// batch_ok: what every device-count entry asks first, the ones without a mesh (the import entries) too.
 template <typename Desc>
-bool front_batch_ok(const Desc* d, const char* who) {
+bool batch_ok(const Desc* d, const char* who) {
     if (!d) {
         set_error("%s: NULL descriptor", who);
         return false;
@@ -469,6 +492,12 @@ bool front_batch_ok(const Desc* d, const char* who) {
         set_error("%s: the batch must be a multiple of 128 rows, but got %u", who, d->B);
         return false;
     }
+    return true;
+}
+
+template <typename Desc>
+bool front_batch_ok(const Desc* d, const char* who) {
+    if (!batch_ok(d, who)) return false;
     if (d->B != 0 && (d->n_verts == 0 || d->n_verts > 0x7fffffffu)) {
         set_error("%s: the mesh needs between 1 and 2^31 - 1 vertices, but got %u", who, d->n_verts);
         return false;
@@ -495,7 +524,7 @@ bool front_pointers_ok(const Desc* d, size_t scratch_bytes) {
 
 template <typename Desc>
 bool front_scales_ok(const Desc* d) {
-    return !(reinterpret_cast<uintptr_t>(d->sigma_weights) & 15) && d->in_mul > 0.0f && std::isfinite(d->in_mul);
+    return aligned16(d->sigma_weights) && d->in_mul > 0.0f && std::isfinite(d->in_mul);
 }
 
 // The launches of the front half, in two parts: the light entry gathers its normal table between them.
@@ -618,7 +647,7 @@ extern "C" int nerftex_curved_field_infer(const nerftex_curved_infer_desc* d, vo
                   sc.carve.at);
         return NERFTEX_ERR_INVALID;
     }
-    if (!front_scales_ok(d) || (reinterpret_cast<uintptr_t>(d->color_weights) & 15)) {
+    if (!front_scales_ok(d) || !aligned16(d->color_weights)) {
         set_error("curved_field_infer: the weight vectors must be 16-byte aligned and the gather's input scale positive and finite");
         return NERFTEX_ERR_INVALID;
     }

@@ -102,6 +102,15 @@ inline bool planar_scales_ok(uint32_t mode, float p0, float p1, float h0, float 
     return mode <= 1u && pos(p0) && pos(p1) && pos(h0) && pos(h1) && pos(h_threshold) && std::isfinite(offset);
 }
 
+// The refusal of a map's extent, for the two planar lookups and the two import entries (planar_light.inc: `maps` = the lit ones, which read several).
+inline bool map_extent_ok(const char* who, bool maps, uint32_t map_h, uint32_t map_w) {
+    if (map_h == 0 || map_h > 16384u || map_w == 0 || map_w > 16384u) {
+        set_error("%s: the %s between 1 and 16384 texels along each axis, but got %u x %u", who, maps ? "maps need" : "map needs", map_h, map_w);
+        return false;
+    }
+    return true;
+}
+
 // the scratch of one nerftex_curved_import_infer call
 struct ImportScratch {
     ScratchCarver carve;
@@ -125,12 +134,9 @@ extern "C" int nerftex_planar_lookup(const float* xyz, const float* map, uint32_
         set_error("planar_lookup: the kernel writes the curved field's 12 height bands, but got n_freqs = %u", n_freqs);
         return NERFTEX_ERR_INVALID;
     }
-    if (map_h == 0 || map_h > 16384u || map_w == 0 || map_w > 16384u) {
-        set_error("planar_lookup: the map needs between 1 and 16384 texels along each axis, but got %u x %u", map_h, map_w);
-        return NERFTEX_ERR_INVALID;
-    }
+    if (!map_extent_ok("planar_lookup", false, map_h, map_w)) return NERFTEX_ERR_INVALID;
     if (B == 0) return NERFTEX_OK;
-    if (!xyz || !map || !p_uv || !sdf || !mask || !xin || (reinterpret_cast<uintptr_t>(map) & 15) || (reinterpret_cast<uintptr_t>(xin) & 15)) {
+    if (!xyz || !map || !p_uv || !sdf || !mask || !xin || !aligned16(map) || !aligned16(xin)) {
         set_error("planar_lookup: inputs, map and outputs must not be NULL, and the map and xin must be 16-byte aligned");
         return NERFTEX_ERR_INVALID;
     }
@@ -148,24 +154,14 @@ extern "C" size_t nerftex_curved_import_infer_scratch_bytes(uint32_t B) { return
 
 extern "C" int nerftex_curved_import_infer(const nerftex_curved_import_infer_desc* d, void* stream) {
     clear_error();
-    if (!d) {
-        set_error("curved_import_infer: NULL descriptor");
-        return NERFTEX_ERR_INVALID;
-    }
-    if (d->B % 128 != 0) {
-        set_error("curved_import_infer: the batch must be a multiple of 128 rows, but got %u", d->B);
-        return NERFTEX_ERR_INVALID;
-    }
+    if (!batch_ok(d, "curved_import_infer")) return NERFTEX_ERR_INVALID;
     if (d->n_features != 16 || d->n_freqs != kInferFreqs || d->sigma_in != 48 || d->sigma_hidden != 32 || d->sigma_layers != 2 || d->sigma_out != 16 ||
         !back_shapes_ok(d)) {
         set_error("curved_import_infer: the kernels serve the default curved field only (a map of 16 features, 12 height bands, "
                   "sigma net 48 -> 32 x 2 -> 16, colour net 32 -> 64 x 3 -> 3)");
         return NERFTEX_ERR_INVALID;
     }
-    if (d->map_h == 0 || d->map_h > 16384u || d->map_w == 0 || d->map_w > 16384u) {
-        set_error("curved_import_infer: the map needs between 1 and 16384 texels along each axis, but got %u x %u", d->map_h, d->map_w);
-        return NERFTEX_ERR_INVALID;
-    }
+    if (!map_extent_ok("curved_import_infer", false, d->map_h, d->map_w)) return NERFTEX_ERR_INVALID;
     if (d->B == 0) return NERFTEX_OK;
     const ImportScratch sc(d->scratch, d->B);
     if (!d->xyz || !d->dirs || !d->map || !d->sigma_weights || !d->color_weights || !d->sigma || !d->rgbs || !d->scratch ||
@@ -173,7 +169,7 @@ extern "C" int nerftex_curved_import_infer(const nerftex_curved_import_infer_des
         set_error("curved_import_infer: inputs, map, weights and outputs must not be NULL, and scratch must be 256-byte aligned and hold %zu bytes", sc.carve.at);
         return NERFTEX_ERR_INVALID;
     }
-    if ((reinterpret_cast<uintptr_t>(d->map) & 15) || (reinterpret_cast<uintptr_t>(d->sigma_weights) & 15) || (reinterpret_cast<uintptr_t>(d->color_weights) & 15)) {
+    if (!aligned16(d->map) || !aligned16(d->sigma_weights) || !aligned16(d->color_weights)) {
         set_error("curved_import_infer: the map and the weight vectors must be 16-byte aligned");
         return NERFTEX_ERR_INVALID;
     }
@@ -199,15 +195,9 @@ namespace {
 // the scratch of one nerftex_curved_shape_infer call
 struct ShapeScratch {
     ScratchCarver carve;
-    int32_t* idx;
-    float* dist;
-    uint8_t* mask;
-    float* normal;
-    half_t *xin, *h;
+    ShapeFront f;
     CurvedBack back;
-    ShapeScratch(void* scratch, size_t B)
-        : carve{reinterpret_cast<uintptr_t>(scratch), B}, idx(carve.take<int32_t>(16)), dist(carve.take<float>(16)),  // (sized for the largest K)
-          mask(carve.take<uint8_t>(1)), normal(carve.take<float>(3)), xin(carve.take<half_t>(48)), h(carve.take<half_t>(16)), back(carve) {}
+    ShapeScratch(void* scratch, size_t B) : carve{reinterpret_cast<uintptr_t>(scratch), B}, f(carve), back(carve) {}
 };
 
 }  // namespace
@@ -228,7 +218,7 @@ extern "C" int nerftex_curved_shape_infer(const nerftex_curved_shape_infer_desc*
         return NERFTEX_ERR_INVALID;
     }
     const ShapeScratch sc(d->scratch, d->B);
-    const ShapeLookup s{d->face_uv, d->map, d->map_h, d->map_w, d->sdf_scale, d->sdf_offset, d->uv_rate, d->h_threshold, d->n_freqs, sc.xin};
+    const ShapeLookup s{d->face_uv, d->map, d->map_h, d->map_w, d->sdf_scale, d->sdf_offset, d->uv_rate, d->h_threshold, d->n_freqs, sc.f.xin};
     if (const char* why = shape_lookup_refusal(s)) {
         set_error("curved_shape_infer: %s", why);
         return NERFTEX_ERR_INVALID;
@@ -240,17 +230,17 @@ extern "C" int nerftex_curved_shape_infer(const nerftex_curved_shape_infer_desc*
                   "hold %zu bytes", sc.carve.at);
         return NERFTEX_ERR_INVALID;
     }
-    if ((reinterpret_cast<uintptr_t>(d->sigma_weights) & 15) || (reinterpret_cast<uintptr_t>(d->color_weights) & 15)) {
+    if (!aligned16(d->sigma_weights) || !aligned16(d->color_weights)) {
         set_error("curved_shape_infer: the weight vectors must be 16-byte aligned");
         return NERFTEX_ERR_INVALID;
     }
     hipStream_t st = as_stream(stream);
-    int rc = knn_query_rows(d->knn, d->xyz, d->dirs, d->B, d->K, sc.idx, sc.dist, d->units_dev, d->rows_per_unit, st);
+    int rc = knn_query_rows(d->knn, d->xyz, d->dirs, d->B, d->K, sc.f.idx, sc.f.dist, d->units_dev, d->rows_per_unit, st);
     if (rc != NERFTEX_OK) return rc;
-    if ((rc = curved_shape_rows(d->tracer, d->xyz, d->dirs, sc.idx, sc.dist, d->B, d->K, d->mesh_vertices, d->vertex_normals, d->n_verts, s, sc.mask, sc.normal,
-                                d->units_dev, d->rows_per_unit, st)) != NERFTEX_OK)
+    if ((rc = curved_shape_rows(d->tracer, d->xyz, d->dirs, sc.f.idx, sc.f.dist, d->B, d->K, d->mesh_vertices, d->vertex_normals, d->n_verts, s, sc.f.mask,
+                                sc.f.normal, d->units_dev, d->rows_per_unit, st)) != NERFTEX_OK)
         return rc;
-    if ((rc = ffmlp_inference_rows(sc.xin, d->sigma_weights, d->B, 48, 32, 2, sc.h, d->units_dev, d->rows_per_unit, st)) != NERFTEX_OK) return rc;
+    if ((rc = ffmlp_inference_rows(sc.f.xin, d->sigma_weights, d->B, 48, 32, 2, sc.f.h, d->units_dev, d->rows_per_unit, st)) != NERFTEX_OK) return rc;
     static const char* const labels[2] = {"curved_shape_infer(mid)", "curved_shape_infer(out)"};
-    return curved_back_half(d, sc.h, sc.normal, sc.mask, sc.back, labels, stream);
+    return curved_back_half(d, sc.f.h, sc.f.normal, sc.f.mask, sc.back, labels, stream);
 }

@@ -2,8 +2,8 @@
 // :722-730) -- beside the feature read of planar.inc, a bilinear read of the [H, W, 8] phi map (the normal net's own table features), a nearest read
 // of the per-texel frame and patch id, and the patch's inverted frame -- as one launch (nerftex_planar_light_lookup), and the lit field's no-grad
 // forward over it as one device-count call (nerftex_curved_light_import_infer).  Included at the end of fieldglue.hip behind curved_light.inc: the
-// row function of the lookup is planar.inc's, the lit reads lit_reads.hpp's, the mid kernel fieldglue.hip's (its second frame), the closing kernel
-// curved_light.inc's.
+// row function of the lookup is planar.inc's, the lit reads lit_reads.hpp's, the closing sequence (the mid kernel with its second frame, the BRDF net, the closing
+// kernel) curved_light.inc's curved_light_back_half.
 //
 // Lane mapping: one thread per row (planar.inc's LANES = 1; DESIGN.md 4.15 measured the four-lane mapping no faster for the feature read, and the
 // 6 + 3 + 3 sixteen-byte words a row reads here beside the features do not split over four lanes evenly).  DESIGN.md 4.17.
@@ -43,16 +43,12 @@ struct LightImportScratch {
     uint8_t* mask;
     float* normal;
     half_t *xin, *h, *n_lbc;
-    float *local_tbn, *sample_tbn, *sigma_raw;
-    half_t *brdf_in, *brdf;
-    float* shading;  // (used when the caller does not ask for the shading normal)
+    float *local_tbn, *sample_tbn;
+    LightBack back;
     LightImportScratch(void* scratch, size_t B)
         : carve{reinterpret_cast<uintptr_t>(scratch), B}, mask(carve.take<uint8_t>(1)), normal(carve.take<float>(3)), xin(carve.take<half_t>(48)),
-          h(carve.take<half_t>(16)), n_lbc(carve.take<half_t>(8)), local_tbn(carve.take<float>(9)), sample_tbn(carve.take<float>(9)),
-          sigma_raw(carve.take<float>(1)), brdf_in(carve.take<half_t>(16)), brdf(carve.take<half_t>(16)), shading(carve.take<float>(3)) {}
+          h(carve.take<half_t>(16)), n_lbc(carve.take<half_t>(8)), local_tbn(carve.take<float>(9)), sample_tbn(carve.take<float>(9)), back(carve) {}
 };
-
-inline bool aligned16(const void* p) { return !(reinterpret_cast<uintptr_t>(p) & 15); }
 
 }  // namespace
 }  // namespace nerftex
@@ -67,10 +63,7 @@ extern "C" int nerftex_planar_light_lookup(const float* xyz, const float* map, c
         set_error("planar_light_lookup: the kernel writes the curved field's 12 height bands, but got n_freqs = %u", n_freqs);
         return NERFTEX_ERR_INVALID;
     }
-    if (map_h == 0 || map_h > 16384u || map_w == 0 || map_w > 16384u) {
-        set_error("planar_light_lookup: the maps need between 1 and 16384 texels along each axis, but got %u x %u", map_h, map_w);
-        return NERFTEX_ERR_INVALID;
-    }
+    if (!map_extent_ok("planar_light_lookup", true, map_h, map_w)) return NERFTEX_ERR_INVALID;
     if (n_patches == 0 || n_patches > (1u << 24)) {
         set_error("planar_light_lookup: between 1 and 2^24 patch frames (an id is read from an fp32 texel), but got %u", n_patches);
         return NERFTEX_ERR_INVALID;
@@ -98,14 +91,7 @@ extern "C" size_t nerftex_curved_light_import_infer_scratch_bytes(uint32_t B) { 
 
 extern "C" int nerftex_curved_light_import_infer(const nerftex_curved_light_import_infer_desc* d, void* stream) {
     clear_error();
-    if (!d) {
-        set_error("curved_light_import_infer: NULL descriptor");
-        return NERFTEX_ERR_INVALID;
-    }
-    if (d->B % 128 != 0) {
-        set_error("curved_light_import_infer: the batch must be a multiple of 128 rows, but got %u", d->B);
-        return NERFTEX_ERR_INVALID;
-    }
+    if (!batch_ok(d, "curved_light_import_infer")) return NERFTEX_ERR_INVALID;
     if (d->n_features != 16 || d->n_phi != 8 || d->n_freqs != kInferFreqs || d->sigma_in != 48 || d->sigma_hidden != 32 || d->sigma_layers != 2 ||
         d->sigma_out != 16 || d->normal_hidden != 16 || d->normal_layers != 2 || d->brdf_in != 16 || d->brdf_hidden != 64 || d->brdf_layers != 3 ||
         d->brdf_out != 5) {
@@ -114,10 +100,7 @@ extern "C" int nerftex_curved_light_import_infer(const nerftex_curved_light_impo
         return NERFTEX_ERR_INVALID;
     }
     if (!light_head_ok(d, "curved_light_import_infer")) return NERFTEX_ERR_INVALID;
-    if (d->map_h == 0 || d->map_h > 16384u || d->map_w == 0 || d->map_w > 16384u) {
-        set_error("curved_light_import_infer: the maps need between 1 and 16384 texels along each axis, but got %u x %u", d->map_h, d->map_w);
-        return NERFTEX_ERR_INVALID;
-    }
+    if (!map_extent_ok("curved_light_import_infer", true, d->map_h, d->map_w)) return NERFTEX_ERR_INVALID;
     if (d->n_patches == 0 || d->n_patches > (1u << 24)) {
         set_error("curved_light_import_infer: between 1 and 2^24 patch frames (an id is read from an fp32 texel), but got %u", d->n_patches);
         return NERFTEX_ERR_INVALID;
@@ -143,7 +126,6 @@ extern "C" int nerftex_curved_light_import_infer(const nerftex_curved_light_impo
         return NERFTEX_ERR_INVALID;
     }
     hipStream_t st = as_stream(stream);
-    float* shading = d->shading_normal ? d->shading_normal : sc.shading;
     const uint32_t B = d->B, rpu = d->rows_per_unit;
     const int32_t* units = d->units_dev;
     const PlanarArgs a{d->map, d->map_h, d->map_w, (int)d->mode, d->plane_scale0, d->plane_scale1, d->height_scale0, d->height_scale1, d->sdf_offset, d->h_threshold};
@@ -153,14 +135,6 @@ extern "C" int nerftex_curved_light_import_infer(const nerftex_curved_light_impo
     int rc = check_launch("curved_light_import_infer(lookup)");
     if (rc != NERFTEX_OK) return rc;
     if ((rc = ffmlp_inference_rows(sc.xin, d->sigma_weights, B, 48, 32, 2, sc.h, units, rpu, st)) != NERFTEX_OK) return rc;
-    {
-        KernelTimer kt("curved_light_mid_rows_kernel", st);
-        hipLaunchKernelGGL(curved_light_mid_rows_kernel<2>, dim3(div_up(B, 256u)), dim3(256), 0, st, sc.h, sc.xin, sc.n_lbc, sc.normal, sc.local_tbn, sc.sample_tbn,
-                           nullptr, d->dirs, static_cast<const half_t*>(d->normal_weights), d->normal_biases, B, d->fc_weight, d->eval, sc.sigma_raw, sc.brdf_in, shading, units,
-                           rpu);
-    }
-    if ((rc = check_launch("curved_light_import_infer(mid)")) != NERFTEX_OK) return rc;
-    if ((rc = ffmlp_inference_rows(sc.brdf_in, d->brdf_weights, B, 16, 64, 3, sc.brdf, units, rpu, st)) != NERFTEX_OK) return rc;
-    launch_light_out(d, sc.brdf, shading, sc.mask, sc.sigma_raw, st);
-    return check_launch("curved_light_import_infer(out)");
+    static const char* const labels[2] = {"curved_light_import_infer(mid)", "curved_light_import_infer(out)"};
+    return curved_light_back_half<2>(d, sc.h, sc.xin, sc.n_lbc, sc.normal, sc.local_tbn, sc.sample_tbn, nullptr, sc.mask, sc.back, labels, stream);
 }

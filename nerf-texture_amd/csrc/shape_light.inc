@@ -1,7 +1,8 @@
 // The imported maps on a NEW UV-mapped mesh under the SH light model: the `pred_normal` part of the 'shape' branch of MeshFeatureField.forward
 // (tools/map.py:693-707, :722-730) as one device-count call (nerftex_curved_light_shape_infer).  Included at the end of fieldglue.hip behind
 // planar_light.inc: the neighbour search is knn.hip's, the lit shape lookup raytracer.hip's (shape_lookup_kernel<ROWS, LIT>, the lit reads of
-// lit_reads.hpp), the mid kernel fieldglue.hip's with all three frames, the head's refusals and the closing launch curved_light.inc's.
+// lit_reads.hpp), the head's refusals and the closing sequence (the mid kernel with all three frames, the BRDF net, the closing kernel:
+// curved_light_back_half) curved_light.inc's.
 // DESIGN.md 4.18.
 
 namespace nerftex {
@@ -10,19 +11,13 @@ namespace {
 // the scratch of one nerftex_curved_light_shape_infer call
 struct LightShapeScratch {
     ScratchCarver carve;
-    int32_t* idx;
-    float* dist;
-    uint8_t* mask;
-    float* normal;
-    half_t *xin, *h, *n_lbc;
-    float *local_tbn, *sample_tbn, *new_tbn, *sigma_raw;
-    half_t *brdf_in, *brdf;
-    float* shading;  // (used when the caller does not ask for the shading normal)
+    ShapeFront f;  // (fieldglue.hip: what nerftex_curved_shape_infer's scratch leads with, too)
+    half_t* n_lbc;
+    float *local_tbn, *sample_tbn, *new_tbn;
+    LightBack back;
     LightShapeScratch(void* scratch, size_t B)
-        : carve{reinterpret_cast<uintptr_t>(scratch), B}, idx(carve.take<int32_t>(16)), dist(carve.take<float>(16)),  // (sized for the largest K)
-          mask(carve.take<uint8_t>(1)), normal(carve.take<float>(3)), xin(carve.take<half_t>(48)), h(carve.take<half_t>(16)), n_lbc(carve.take<half_t>(8)),
-          local_tbn(carve.take<float>(9)), sample_tbn(carve.take<float>(9)), new_tbn(carve.take<float>(9)), sigma_raw(carve.take<float>(1)),
-          brdf_in(carve.take<half_t>(16)), brdf(carve.take<half_t>(16)), shading(carve.take<float>(3)) {}
+        : carve{reinterpret_cast<uintptr_t>(scratch), B}, f(carve), n_lbc(carve.take<half_t>(8)), local_tbn(carve.take<float>(9)),
+          sample_tbn(carve.take<float>(9)), new_tbn(carve.take<float>(9)), back(carve) {}
 };
 
 }  // namespace
@@ -45,7 +40,7 @@ extern "C" int nerftex_curved_light_shape_infer(const nerftex_curved_light_shape
         return NERFTEX_ERR_INVALID;
     }
     const LightShapeScratch sc(d->scratch, d->B);
-    const ShapeLookup s{d->face_uv, d->map, d->map_h, d->map_w, d->sdf_scale, d->sdf_offset, d->uv_rate, d->h_threshold, d->n_freqs, sc.xin};
+    const ShapeLookup s{d->face_uv, d->map, d->map_h, d->map_w, d->sdf_scale, d->sdf_offset, d->uv_rate, d->h_threshold, d->n_freqs, sc.f.xin};
     if (const char* why = shape_lookup_refusal(s)) {
         set_error("curved_light_shape_infer: %s", why);
         return NERFTEX_ERR_INVALID;
@@ -73,24 +68,15 @@ extern "C" int nerftex_curved_light_shape_infer(const nerftex_curved_light_shape
         return NERFTEX_ERR_INVALID;
     }
     hipStream_t st = as_stream(stream);
-    float* shading = d->shading_normal ? d->shading_normal : sc.shading;
     const uint32_t B = d->B, rpu = d->rows_per_unit;
     const int32_t* units = d->units_dev;
     const ShapeLight t{d->phi_map, d->frame_map, d->sample_tbn_inv, d->n_patches, d->face_tbn, d->n_tbn_faces, sc.n_lbc, sc.local_tbn, sc.sample_tbn, sc.new_tbn};
-    int rc = knn_query_rows(d->knn, d->xyz, d->dirs, B, d->K, sc.idx, sc.dist, units, rpu, st);
+    int rc = knn_query_rows(d->knn, d->xyz, d->dirs, B, d->K, sc.f.idx, sc.f.dist, units, rpu, st);
     if (rc != NERFTEX_OK) return rc;
-    if ((rc = curved_shape_light_rows(d->tracer, d->xyz, d->dirs, sc.idx, sc.dist, B, d->K, d->mesh_vertices, d->vertex_normals, d->n_verts, s, t, sc.mask, sc.normal,
-                                      units, rpu, st)) != NERFTEX_OK)
+    if ((rc = curved_shape_light_rows(d->tracer, d->xyz, d->dirs, sc.f.idx, sc.f.dist, B, d->K, d->mesh_vertices, d->vertex_normals, d->n_verts, s, t, sc.f.mask,
+                                      sc.f.normal, units, rpu, st)) != NERFTEX_OK)
         return rc;
-    if ((rc = ffmlp_inference_rows(sc.xin, d->sigma_weights, B, 48, 32, 2, sc.h, units, rpu, st)) != NERFTEX_OK) return rc;
-    {
-        KernelTimer kt("curved_light_mid_rows_kernel", st);
-        hipLaunchKernelGGL(curved_light_mid_rows_kernel<3>, dim3(div_up(B, 256u)), dim3(256), 0, st, sc.h, sc.xin, sc.n_lbc, sc.normal, sc.local_tbn, sc.sample_tbn,
-                           sc.new_tbn, d->dirs, static_cast<const half_t*>(d->normal_weights), d->normal_biases, B, d->fc_weight, d->eval, sc.sigma_raw, sc.brdf_in,
-                           shading, units, rpu);
-    }
-    if ((rc = check_launch("curved_light_shape_infer(mid)")) != NERFTEX_OK) return rc;
-    if ((rc = ffmlp_inference_rows(sc.brdf_in, d->brdf_weights, B, 16, 64, 3, sc.brdf, units, rpu, st)) != NERFTEX_OK) return rc;
-    launch_light_out(d, sc.brdf, shading, sc.mask, sc.sigma_raw, st);
-    return check_launch("curved_light_shape_infer(out)");
+    if ((rc = ffmlp_inference_rows(sc.f.xin, d->sigma_weights, B, 48, 32, 2, sc.f.h, units, rpu, st)) != NERFTEX_OK) return rc;
+    static const char* const labels[2] = {"curved_light_shape_infer(mid)", "curved_light_shape_infer(out)"};
+    return curved_light_back_half<3>(d, sc.f.h, sc.f.xin, sc.n_lbc, sc.f.normal, sc.local_tbn, sc.sample_tbn, sc.new_tbn, sc.f.mask, sc.back, labels, stream);
 }

@@ -22,6 +22,8 @@ import numpy as np
 import torch
 
 from gridencoder import GridEncoder_clustering
+from nerftex_hip import (LIGHT_VISUAL, SH_LIGHT_SPECULAR, CurvedImportInferDesc, CurvedInferDesc, CurvedLightImportInferDesc, CurvedLightInferDesc,
+                         CurvedLightShapeInferDesc, CurvedShapeInferDesc, ptr)
 from RayTracer import RayTracer
 
 
@@ -1237,22 +1239,39 @@ class CurvedField(torch.nn.Module):
         return stamp + (True, nn.encoder.embeddings.data_ptr(), nn.encoder.offsets.data_ptr(),
                         tuple((q.data_ptr(), q._version) for q in list(nn.phi_net.parameters()) + list(nn.theta_net.parameters())))
 
+    # ---- the six fused inference chains: what each asks of a call (the entries refuse everything else) ----
+    _SIGMA_NET, _COLOR_NET, _BRDF_NET = (48, 32, 2, 16), (32, 64, 3, 3), (16, 64, 3, 5)  # (in, hidden, layers, out) the entries' kernels are built for
+
+    @staticmethod
+    def _infer_batch_ok(x, d):
+        """The batch every entry takes: whole 128-row workgroups, contiguous fp32 inputs."""
+        B = x.shape[0]
+        return B > 0 and B % 128 == 0 and x.dtype == torch.float32 and d.dtype == torch.float32 and x.is_contiguous() and d.is_contiguous()
+
+    @staticmethod
+    def _on_device_of(x, *tensors):
+        return all(t.device == x.device for t in tensors)
+
+    def _infer_sigma_ok(self):
+        s = self.sigma_net
+        return (s.input_dim, s.hidden_dim, s.num_layers, s.padded_output_dim) == self._SIGMA_NET
+
+    def _infer_color_ok(self):
+        c = self.color_net
+        return c.dtype == torch.float16 and (c.input_dim, c.hidden_dim, c.num_layers, c.output_dim) == self._COLOR_NET
+
     def _infer_fused(self, x, d):
         """Whether nerftex_curved_field_infer serves this call: _glue_fused(), the shapes the entry's kernels are built for (it refuses every
         other one), an fp16 table, and what the entry asks of its buffers.  Everything else goes through forward()."""
-        c = self.color_net
-        return (self._glue_fused() and c.dtype == torch.float16 and (c.input_dim, c.hidden_dim, c.num_layers, c.output_dim) == (32, 64, 3, 3)
-                and self._infer_front_fused(x, d))
+        return self._glue_fused() and self._infer_color_ok() and self._infer_front_fused(x, d)
 
     def _infer_front_fused(self, x, d):
         """What the two fused chains ask alike (their front half, csrc/fieldglue.hip): fp16 autocast, no probabilistic table, the default texture
         table and sigma net, a batch of whole 128-row workgroups, contiguous fp32 inputs, an fp16 table."""
-        B = x.shape[0]
-        enc, s = self.encoder, self.sigma_net
+        enc = self.encoder
         return (torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.float16 and self.encoder_var is None
-                and self.in_dim == 41 and self.in_pad == 48 and self.geo_feat_dim == 15 and B % 128 == 0 and B > 0
-                and x.dtype == torch.float32 and d.dtype == torch.float32 and x.is_contiguous() and d.is_contiguous() and s.dtype == torch.float16
-                and (s.input_dim, s.hidden_dim, s.num_layers, s.padded_output_dim) == (48, 32, 2, 16)
+                and self.in_dim == 41 and self.in_pad == 48 and self.geo_feat_dim == 15 and self._infer_batch_ok(x, d)
+                and self.sigma_net.dtype == torch.float16 and self._infer_sigma_ok()
                 and (enc.input_dim, enc.level_dim, enc.num_levels, self.multires) == (3, 2, 8, 12) and 1 <= self.projector.K <= 16
                 and enc._table().dtype == torch.float16)
 
@@ -1270,77 +1289,101 @@ class CurvedField(torch.nn.Module):
             setattr(self, attr, cache)
         return cache[1:]
 
-    def _infer_front_desc(self, x, d, live, sigma, rgbs, scratch, ws_h):
-        """What both descriptors are built from -- the shared members knn .. in_mul, the sigma net, fc_weight, the outputs, the device count, the
-        scratch -- as keyword arguments, and the 16-bit texture table they point into."""
-        from nerftex_hip import ptr
+    # ---- the descriptors' member blocks: every member is written once, as a keyword argument of the block that owns it.  A descriptor is a composition
+    # of blocks: a member named twice is a TypeError there, a member not named is ctypes' NULL / 0 (tests/test_curved_infer_members_cpu.py).
 
-        enc, p, s = self.encoder, self.projector, self.sigma_net
-        table = enc._table()
+    def _infer_rows(self, x, d, live, sigma, rgbs, scratch, eval_bits=0):
+        """What every descriptor has: the rows and the device count that bounds them (live = (int32 device tensor, rows per unit or code); None: all
+        rows), outputs, scratch, fc_weight, eval = train / eval | eval_bits (static light: bit 1, tools/map.py:720's normalisation in the mid kernel)."""
         units, rows_per_unit = (ptr(live[0]), int(live[1])) if live is not None else (None, 0)
+        return dict(xyz=ptr(x), dirs=ptr(d), B=x.shape[0], fc_weight=float(self.fc_weight), eval=eval_bits | int(not self.training), sigma=ptr(sigma),
+                    rgbs=ptr(rgbs), units_dev=units, rows_per_unit=rows_per_unit, scratch=ptr(scratch), scratch_bytes=scratch.numel())
+
+    def _infer_sigma_net(self, ws_h):
+        s = self.sigma_net
+        return dict(sigma_weights=ptr(ws_h), sigma_in=s.input_dim, sigma_hidden=s.hidden_dim, sigma_layers=s.num_layers, sigma_out=s.padded_output_dim)
+
+    def _infer_static_back(self, x, d, live, sigma, rgbs, scratch):
+        """Behind the front half or the lookup, the static light model's three descriptors alike -- sigma net, colour net, `_infer_rows` -- and the
+        16-bit weights they point into."""
+        c = self.color_net
+        ws_h, wc_h = self._infer_weights("_infer_cache", c)
+        return dict(color_weights=ptr(wc_h), color_in=c.input_dim, color_hidden=c.hidden_dim, color_layers=c.num_layers, color_out=c.output_dim,
+                    **self._infer_sigma_net(ws_h), **self._infer_rows(x, d, live, sigma, rgbs, scratch, eval_bits=2)), (ws_h, wc_h)
+
+    def _infer_lit_back(self, x, d, live, sigma, rgbs, scratch, shading_normal):
+        """... and the SH light model's three: sigma net, the head -- the normal net's packed block, the BRDF net, the lighting, the flags and the
+        output it shows (in training always "Full"), shading_normal (fp32 [B,3] or None) -- and `_infer_rows`; the weights and the lighting."""
+        net = self.light_net
+        br, env = net.brdf_layer, net.envSHs.detach()
+        ws_h, wb_h, nw, nb = self._infer_light_weights()
+        mode = "Full" if self.training else self.light_visual_mode
+        return dict(normal_weights=ptr(nw), normal_biases=ptr(nb), normal_hidden=16, normal_layers=2, brdf_weights=ptr(wb_h), brdf_in=br.input_dim,
+                    brdf_hidden=br.hidden_dim, brdf_layers=br.num_layers, brdf_out=br.output_dim, env_shs=ptr(env), n_sh=env.shape[0], n_color=env.shape[1],
+                    gamma=float(net.gamma), flags=SH_LIGHT_SPECULAR if net.use_specular else 0, visual_mode=LIGHT_VISUAL[mode],
+                    shading_normal=ptr(shading_normal), **self._infer_sigma_net(ws_h), **self._infer_rows(x, d, live, sigma, rgbs, scratch)), (ws_h, wb_h, nw, nb, env)
+
+    @staticmethod
+    def _infer_mesh(p, K):
+        """The neighbour search and the tracer over the projector p's mesh: the field's own, or the imported shape's."""
+        return dict(knn=p._knn.value, tracer=p.tracer._handle.value, n_verts=p.mesh_vertices.shape[0], mesh_vertices=ptr(p.mesh_vertices),
+                    vertex_normals=ptr(p.vertex_normals), K=K)
+
+    def _infer_ladder(self, h_threshold):
+        return dict(h_threshold=h_threshold, n_freqs=int(self.multires))
+
+    def _infer_map(self, sdf_offset, h_threshold):
+        """The imported feature map and the height it is read at: the planar and the shape chains' alike."""
+        f = self.features_imported
+        return dict(map=ptr(f), map_h=f.shape[0], map_w=f.shape[1], n_features=f.shape[2], sdf_offset=sdf_offset, **self._infer_ladder(h_threshold))
+
+    def _infer_planar(self):
+        mode, p0, p1, h0, h1, off, h = self._import_scalars()
+        return dict(mode=mode, plane_scale0=p0, plane_scale1=p1, height_scale0=h0, height_scale1=h1, **self._infer_map(off, h))
+
+    def _infer_shape(self):
+        """The map on the imported mesh: the mesh, its per-face UVs, `_shape_scalars`."""
+        K, scale, off, rate, h = self._shape_scalars()
+        uv = self.shape_face_uv
+        return dict(face_uv=ptr(uv), n_faces=uv.shape[0], sdf_scale=scale, uv_rate=rate, **self._infer_mesh(self.shape_projector, K), **self._infer_map(off, h))
+
+    def _infer_lit_maps(self):
+        """The three maps the lit import chains read beside the features, and the four maps."""
+        phi, frame, rows = self.phi_embed_imported, self.frame_map_imported, self.sample_inv_rows_imported
+        return (dict(phi_map=ptr(phi), frame_map=ptr(frame), sample_tbn_inv=ptr(rows), n_phi=phi.shape[2], n_patches=rows.shape[0]),
+                (self.features_imported, phi, frame, rows))
+
+    def _infer_front_desc(self):
+        """The front half's members of the two mesh-field descriptors, knn .. in_mul, and the 16-bit texture table they point into."""
+        enc, p = self.encoder, self.projector
+        table = enc._table()
         return dict(
-            knn=p._knn.value, tracer=p.tracer._handle.value, xyz=ptr(x), dirs=ptr(d), B=x.shape[0], n_verts=p.mesh_vertices.shape[0],
-            mesh_vertices=ptr(p.mesh_vertices), vertex_normals=ptr(p.vertex_normals), tbn=ptr(p.tbn), K=int(p.K), n_freqs=int(self.multires),
-            dir_vec_wdist=0.05, h_threshold=p._height_limit(...), table=ptr(table), offsets=ptr(enc.offsets), D=int(enc.input_dim), C=int(enc.level_dim),
+            tbn=ptr(p.tbn), dir_vec_wdist=0.05, table=ptr(table), offsets=ptr(enc.offsets), D=int(enc.input_dim), C=int(enc.level_dim),
             L=int(enc.num_levels), S=float(np.log2(enc.per_level_scale)), H=int(enc.base_resolution), gridtype=int(enc.gridtype_id),
             align_corners=int(bool(enc.align_corners)), in_add=float(self.bound), in_mul=float(np.float32(1.0) / np.float32(2 * self.bound)),
-            sigma_weights=ptr(ws_h), sigma_in=s.input_dim, sigma_hidden=s.hidden_dim, sigma_layers=s.num_layers, sigma_out=s.padded_output_dim,
-            fc_weight=float(self.fc_weight), sigma=ptr(sigma), rgbs=ptr(rgbs), units_dev=units, rows_per_unit=rows_per_unit, scratch=ptr(scratch),
-            scratch_bytes=scratch.numel()), table
+            **self._infer_mesh(p, int(p.K)), **self._infer_ladder(p._height_limit(...))), table
 
     def _infer_desc(self, x, d, live, sigma, rgbs, scratch):
         """The nerftex_curved_infer_desc of one call (and the tensors it points into, to be kept until the call is enqueued)."""
-        from nerftex_hip import CurvedInferDesc, ptr
-
-        c = self.color_net
-        ws_h, wc_h = self._infer_weights("_infer_cache", c)
-        front, table = self._infer_front_desc(x, d, live, sigma, rgbs, scratch, ws_h)
-        desc = CurvedInferDesc(color_weights=ptr(wc_h), color_in=c.input_dim, color_hidden=c.hidden_dim, color_layers=c.num_layers, color_out=c.output_dim,
-                               eval=2 | int(not self.training), **front)
-        return desc, (table, ws_h, wc_h)
+        front, table = self._infer_front_desc()
+        back, weights = self._infer_static_back(x, d, live, sigma, rgbs, scratch)
+        return CurvedInferDesc(**front, **back), (table,) + weights
 
     def _infer_import_fused(self, x, d):
-        """Whether nerftex_curved_import_infer serves this call: _infer_fused()'s conditions without the neighbour search's and the table's."""
-        c, s, B = self.color_net, self.sigma_net, x.shape[0]
-        return (self._import_fused(x) and c.dtype == torch.float16 and (c.input_dim, c.hidden_dim, c.num_layers, c.output_dim) == (32, 64, 3, 3)
-                and (s.input_dim, s.hidden_dim, s.num_layers, s.padded_output_dim) == (48, 32, 2, 16) and B % 128 == 0 and B > 0
-                and x.dtype == torch.float32 and d.dtype == torch.float32 and x.is_contiguous() and d.is_contiguous()
-                and self.features_imported.device == x.device)
+        """Whether nerftex_curved_import_infer (or, on an imported mesh, nerftex_curved_shape_infer) serves this call: _infer_fused()'s conditions
+        without the neighbour search's and the table's."""
+        return (self._import_fused(x) and self._infer_color_ok() and self._infer_sigma_ok() and self._infer_batch_ok(x, d)
+                and self._on_device_of(x, self.features_imported))
 
     def _infer_import_desc(self, x, d, live, sigma, rgbs, scratch):
         """The nerftex_curved_import_infer_desc of one call (and the tensors it points into, to be kept until the call is enqueued)."""
-        from nerftex_hip import CurvedImportInferDesc, ptr
-
-        c, s, f = self.color_net, self.sigma_net, self.features_imported
-        ws_h, wc_h = self._infer_weights("_infer_cache", c)
-        mode, p0, p1, h0, h1, off, h = self._import_scalars()
-        units, rows_per_unit = (ptr(live[0]), int(live[1])) if live is not None else (None, 0)
-        desc = CurvedImportInferDesc(
-            xyz=ptr(x), dirs=ptr(d), B=x.shape[0], map=ptr(f), map_h=f.shape[0], map_w=f.shape[1], n_features=f.shape[2], mode=mode, plane_scale0=p0,
-            plane_scale1=p1, height_scale0=h0, height_scale1=h1, sdf_offset=off, h_threshold=h, n_freqs=int(self.multires), sigma_weights=ptr(ws_h),
-            sigma_in=s.input_dim, sigma_hidden=s.hidden_dim, sigma_layers=s.num_layers, sigma_out=s.padded_output_dim, color_weights=ptr(wc_h),
-            color_in=c.input_dim, color_hidden=c.hidden_dim, color_layers=c.num_layers, color_out=c.output_dim, fc_weight=float(self.fc_weight),
-            eval=2 | int(not self.training), sigma=ptr(sigma), rgbs=ptr(rgbs), units_dev=units, rows_per_unit=rows_per_unit, scratch=ptr(scratch),
-            scratch_bytes=scratch.numel())
-        return desc, (f, ws_h, wc_h)
+        back, weights = self._infer_static_back(x, d, live, sigma, rgbs, scratch)
+        return CurvedImportInferDesc(**self._infer_planar(), **back), (self.features_imported,) + weights
 
     def _infer_shape_desc(self, x, d, live, sigma, rgbs, scratch):
         """The nerftex_curved_shape_infer_desc of one call (and the tensors it points into, to be kept until the call is enqueued)."""
-        from nerftex_hip import CurvedShapeInferDesc, ptr
-
-        c, s, f, p = self.color_net, self.sigma_net, self.features_imported, self.shape_projector
-        ws_h, wc_h = self._infer_weights("_infer_cache", c)
-        K, scale, off, rate, h = self._shape_scalars()
-        units, rows_per_unit = (ptr(live[0]), int(live[1])) if live is not None else (None, 0)
-        desc = CurvedShapeInferDesc(
-            knn=p._knn.value, tracer=p.tracer._handle.value, xyz=ptr(x), dirs=ptr(d), B=x.shape[0], n_verts=p.mesh_vertices.shape[0],
-            mesh_vertices=ptr(p.mesh_vertices), vertex_normals=ptr(p.vertex_normals), face_uv=ptr(self.shape_face_uv), n_faces=self.shape_face_uv.shape[0], K=K,
-            map=ptr(f), map_h=f.shape[0], map_w=f.shape[1], n_features=f.shape[2], sdf_scale=scale, sdf_offset=off, uv_rate=rate, h_threshold=h,
-            n_freqs=int(self.multires), sigma_weights=ptr(ws_h), sigma_in=s.input_dim, sigma_hidden=s.hidden_dim, sigma_layers=s.num_layers,
-            sigma_out=s.padded_output_dim, color_weights=ptr(wc_h), color_in=c.input_dim, color_hidden=c.hidden_dim, color_layers=c.num_layers,
-            color_out=c.output_dim, fc_weight=float(self.fc_weight), eval=2 | int(not self.training), sigma=ptr(sigma), rgbs=ptr(rgbs), units_dev=units,
-            rows_per_unit=rows_per_unit, scratch=ptr(scratch), scratch_bytes=scratch.numel())
-        return desc, (f, ws_h, wc_h)
+        back, weights = self._infer_static_back(x, d, live, sigma, rgbs, scratch)
+        return CurvedShapeInferDesc(**self._infer_shape(), **back), (self.features_imported,) + weights
 
     def _infer_light_fused(self, x, d):
         """Whether nerftex_curved_light_infer serves this call: the SH light model with the switch `fused_light_infer` set (default: not), fp16
@@ -1355,12 +1398,10 @@ class CurvedField(torch.nn.Module):
         net's default shapes, no bounded angles, a visual mode the head has, fp32 lighting of 1 or 3 colours."""
         if not (getattr(self, "light_model", None) == "SH" and getattr(self, "fused_light_infer", False)):
             return False
-        from nerftex_hip import LIGHT_VISUAL
-
         nn, net = self.normal_net, self.light_net
         br = net.brdf_layer
         return (bool(net.fused) and nn is not None and not nn.bound_output and (self.training or self.light_visual_mode in LIGHT_VISUAL)
-                and x.is_cuda and br.dtype == torch.float16 and (br.input_dim, br.hidden_dim, br.num_layers, br.output_dim) == (16, 64, 3, 5)
+                and x.is_cuda and br.dtype == torch.float16 and (br.input_dim, br.hidden_dim, br.num_layers, br.output_dim) == self._BRDF_NET
                 and (nn.low_freq_band_len_x, nn.low_freq_band_len_z) == (16, 12)
                 and [tuple(l.W.shape) for l in nn.phi_net.layers] == [(16, 20), (16, 16), (1, 16)]
                 and [tuple(l.W.shape) for l in nn.theta_net.layers] == [(16, 28), (16, 16), (1, 16)]
@@ -1369,44 +1410,32 @@ class CurvedField(torch.nn.Module):
     def _infer_light_import_fused(self, x, d):
         """Whether nerftex_curved_light_import_infer serves this call: _infer_light_fused()'s conditions without the neighbour search's and the
         two tables', with the imported maps on x's device instead."""
-        s, B = self.sigma_net, x.shape[0]
-        return (getattr(self, "imported", False) and self._infer_light_back_fused(x) and self._import_light_fused(x)
-                and (s.input_dim, s.hidden_dim, s.num_layers, s.padded_output_dim) == (48, 32, 2, 16) and B % 128 == 0 and B > 0
-                and x.dtype == torch.float32 and d.dtype == torch.float32 and x.is_contiguous() and d.is_contiguous()
-                and all(m.device == x.device for m in (self.features_imported, self.phi_embed_imported, self.frame_map_imported, self.sample_inv_rows_imported)))
+        return (getattr(self, "imported", False) and self._infer_light_back_fused(x) and self._import_light_fused(x) and self._infer_sigma_ok()
+                and self._infer_batch_ok(x, d)
+                and self._on_device_of(x, self.features_imported, self.phi_embed_imported, self.frame_map_imported, self.sample_inv_rows_imported))
 
     def _infer_light_shape_fused(self, x, d):
         """Whether nerftex_curved_light_shape_infer serves this call: _infer_light_import_fused()'s conditions over the maps on the imported mesh,
         with its frames and a K the neighbour search serves."""
-        s, B = self.sigma_net, x.shape[0]
-        return (getattr(self, "imported", False) and self._infer_light_back_fused(x) and self._shape_light_fused(x)
-                and (s.input_dim, s.hidden_dim, s.num_layers, s.padded_output_dim) == (48, 32, 2, 16) and B % 128 == 0 and B > 0
-                and x.dtype == torch.float32 and d.dtype == torch.float32 and x.is_contiguous() and d.is_contiguous() and 1 <= self._shape_scalars()[0] <= 16
-                and all(m.device == x.device for m in (self.features_imported, self.phi_embed_imported, self.frame_map_imported, self.sample_inv_rows_imported,
-                                                       self.shape_face_uv, self.shape_face_tbn)))
+        return (getattr(self, "imported", False) and self._infer_light_back_fused(x) and self._shape_light_fused(x) and self._infer_sigma_ok()
+                and self._infer_batch_ok(x, d) and 1 <= self._shape_scalars()[0] <= 16
+                and self._on_device_of(x, self.features_imported, self.phi_embed_imported, self.frame_map_imported, self.sample_inv_rows_imported,
+                                       self.shape_face_uv, self.shape_face_tbn))
 
     def _infer_light_desc(self, x, d, live, sigma, rgbs, scratch, shading_normal=None):
         """The nerftex_curved_light_infer_desc of one call (and the tensors it points into).  Kept between calls and re-made when a parameter
         changes: the 16-bit MLP weights, and the normal net's packed block -- every LipLayer's normalization().half(), which is what the
         framework's half GEMM multiplies with under autocast, and its fp32 biases, in the order include/nerftex_hip.h gives."""
-        from nerftex_hip import LIGHT_VISUAL, SH_LIGHT_SPECULAR, CurvedLightInferDesc, ptr
-
-        nn, net = self.normal_net, self.light_net
-        nenc, br = nn.encoder, net.brdf_layer
+        nenc = self.normal_net.encoder
         ntable = nenc._table()
-        ws_h, wb_h, nw, nb = self._infer_light_weights()
-        front, table = self._infer_front_desc(x, d, live, sigma, rgbs, scratch, ws_h)
-        env = net.envSHs.detach()
-        mode = "Full" if self.training else self.light_visual_mode
+        front, table = self._infer_front_desc()
+        back, kept = self._infer_lit_back(x, d, live, sigma, rgbs, scratch, shading_normal)
         desc = CurvedLightInferDesc(
             normal_table=ptr(ntable), normal_offsets=ptr(nenc.offsets), normal_C=int(nenc.level_dim), normal_L=int(nenc.num_levels),
             normal_S=float(np.log2(nenc.per_level_scale)), normal_H=int(nenc.base_resolution), normal_gridtype=int(nenc.gridtype_id),
             normal_align_corners=int(bool(nenc.align_corners)), normal_in_add=1.0, normal_in_mul=float(np.float32(1.0) / np.float32(2)),  # (encoder(p_sur): bound 1)
-            normal_weights=ptr(nw), normal_biases=ptr(nb), normal_hidden=16, normal_layers=2,
-            brdf_weights=ptr(wb_h), brdf_in=br.input_dim, brdf_hidden=br.hidden_dim, brdf_layers=br.num_layers, brdf_out=br.output_dim,
-            env_shs=ptr(env), n_sh=env.shape[0], n_color=env.shape[1], gamma=float(net.gamma), flags=SH_LIGHT_SPECULAR if net.use_specular else 0,
-            visual_mode=LIGHT_VISUAL[mode], eval=int(not self.training), shading_normal=ptr(shading_normal), **front)
-        return desc, (table, ntable, ws_h, wb_h, nw, nb, env)
+            **front, **back)
+        return desc, (table, ntable) + kept
 
     def _infer_light_weights(self):
         """-> (sigma net, BRDF net: 16-bit weights; the normal net's packed block: half weights, fp32 biases) of the two lit chains, kept between
@@ -1429,52 +1458,16 @@ class CurvedField(torch.nn.Module):
 
     def _infer_light_import_desc(self, x, d, live, sigma, rgbs, scratch, shading_normal=None):
         """The nerftex_curved_light_import_infer_desc of one call (and the tensors it points into, to be kept until the call is enqueued)."""
-        from nerftex_hip import LIGHT_VISUAL, SH_LIGHT_SPECULAR, CurvedLightImportInferDesc, ptr
-
-        net, s, f = self.light_net, self.sigma_net, self.features_imported
-        br = net.brdf_layer
-        phi, frame, rows = self.phi_embed_imported, self.frame_map_imported, self.sample_inv_rows_imported
-        ws_h, wb_h, nw, nb = self._infer_light_weights()
-        mode, p0, p1, h0, h1, off, h = self._import_scalars()
-        units, rows_per_unit = (ptr(live[0]), int(live[1])) if live is not None else (None, 0)
-        env = net.envSHs.detach()
-        visual = "Full" if self.training else self.light_visual_mode
-        desc = CurvedLightImportInferDesc(
-            xyz=ptr(x), dirs=ptr(d), B=x.shape[0], map=ptr(f), phi_map=ptr(phi), frame_map=ptr(frame), sample_tbn_inv=ptr(rows), map_h=f.shape[0],
-            map_w=f.shape[1], n_features=f.shape[2], n_phi=phi.shape[2], n_patches=rows.shape[0], mode=mode, plane_scale0=p0, plane_scale1=p1,
-            height_scale0=h0, height_scale1=h1, sdf_offset=off, h_threshold=h, n_freqs=int(self.multires), sigma_weights=ptr(ws_h), sigma_in=s.input_dim,
-            sigma_hidden=s.hidden_dim, sigma_layers=s.num_layers, sigma_out=s.padded_output_dim, normal_weights=ptr(nw), normal_biases=ptr(nb),
-            normal_hidden=16, normal_layers=2, brdf_weights=ptr(wb_h), brdf_in=br.input_dim, brdf_hidden=br.hidden_dim, brdf_layers=br.num_layers,
-            brdf_out=br.output_dim, env_shs=ptr(env), n_sh=env.shape[0], n_color=env.shape[1], gamma=float(net.gamma),
-            flags=SH_LIGHT_SPECULAR if net.use_specular else 0, visual_mode=LIGHT_VISUAL[visual], fc_weight=float(self.fc_weight), eval=int(not self.training),
-            sigma=ptr(sigma), rgbs=ptr(rgbs), shading_normal=ptr(shading_normal), units_dev=units, rows_per_unit=rows_per_unit, scratch=ptr(scratch),
-            scratch_bytes=scratch.numel())
-        return desc, (f, phi, frame, rows, ws_h, wb_h, nw, nb, env)
+        lit, maps = self._infer_lit_maps()
+        back, kept = self._infer_lit_back(x, d, live, sigma, rgbs, scratch, shading_normal)
+        return CurvedLightImportInferDesc(**self._infer_planar(), **lit, **back), maps + kept
 
     def _infer_light_shape_desc(self, x, d, live, sigma, rgbs, scratch, shading_normal=None):
         """The nerftex_curved_light_shape_infer_desc of one call (and the tensors it points into, to be kept until the call is enqueued)."""
-        from nerftex_hip import LIGHT_VISUAL, SH_LIGHT_SPECULAR, CurvedLightShapeInferDesc, ptr
-
-        net, s, f, p = self.light_net, self.sigma_net, self.features_imported, self.shape_projector
-        br = net.brdf_layer
-        phi, frame, rows = self.phi_embed_imported, self.frame_map_imported, self.sample_inv_rows_imported
-        ws_h, wb_h, nw, nb = self._infer_light_weights()
-        K, scale, off, rate, h = self._shape_scalars()
-        units, rows_per_unit = (ptr(live[0]), int(live[1])) if live is not None else (None, 0)
-        env = net.envSHs.detach()
-        visual = "Full" if self.training else self.light_visual_mode
-        desc = CurvedLightShapeInferDesc(
-            knn=p._knn.value, tracer=p.tracer._handle.value, xyz=ptr(x), dirs=ptr(d), B=x.shape[0], n_verts=p.mesh_vertices.shape[0],
-            mesh_vertices=ptr(p.mesh_vertices), vertex_normals=ptr(p.vertex_normals), face_uv=ptr(self.shape_face_uv), face_tbn=ptr(self.shape_face_tbn),
-            n_faces=self.shape_face_uv.shape[0], n_tbn_faces=self.shape_face_tbn.shape[0], K=K, map=ptr(f), phi_map=ptr(phi), frame_map=ptr(frame),
-            sample_tbn_inv=ptr(rows), map_h=f.shape[0], map_w=f.shape[1], n_features=f.shape[2], n_phi=phi.shape[2], n_patches=rows.shape[0], sdf_scale=scale,
-            sdf_offset=off, uv_rate=rate, h_threshold=h, n_freqs=int(self.multires), sigma_weights=ptr(ws_h), sigma_in=s.input_dim, sigma_hidden=s.hidden_dim,
-            sigma_layers=s.num_layers, sigma_out=s.padded_output_dim, normal_weights=ptr(nw), normal_biases=ptr(nb), normal_hidden=16, normal_layers=2,
-            brdf_weights=ptr(wb_h), brdf_in=br.input_dim, brdf_hidden=br.hidden_dim, brdf_layers=br.num_layers, brdf_out=br.output_dim, env_shs=ptr(env),
-            n_sh=env.shape[0], n_color=env.shape[1], gamma=float(net.gamma), flags=SH_LIGHT_SPECULAR if net.use_specular else 0,
-            visual_mode=LIGHT_VISUAL[visual], fc_weight=float(self.fc_weight), eval=int(not self.training), sigma=ptr(sigma), rgbs=ptr(rgbs),
-            shading_normal=ptr(shading_normal), units_dev=units, rows_per_unit=rows_per_unit, scratch=ptr(scratch), scratch_bytes=scratch.numel())
-        return desc, (f, phi, frame, rows, ws_h, wb_h, nw, nb, env)
+        lit, maps = self._infer_lit_maps()
+        back, kept = self._infer_lit_back(x, d, live, sigma, rgbs, scratch, shading_normal)
+        frames = self.shape_face_tbn  # (the new mesh's)
+        return CurvedLightShapeInferDesc(face_tbn=ptr(frames), n_tbn_faces=frames.shape[0], **self._infer_shape(), **lit, **back), maps + kept
 
     def _infer_call(self, entry, make_desc, x, d, live, *more):
         """One call of the library entry `entry` (its scratch query is `entry`_scratch_bytes) over the descriptor make_desc builds: -> (sigma [B],
@@ -1521,6 +1514,24 @@ class CurvedField(torch.nn.Module):
         `_infer_light_shape_fused`, which the caller has checked)."""
         return self._infer_call("nerftex_curved_light_shape_infer", self._infer_light_shape_desc, x, d, live, shading_normal)
 
+    def _infer_route(self, x, d):
+        """The chain that serves infer(x, d): (the library entry's name, the builder of its descriptor), or None: forward().  The one priority
+        ladder -- an imported map: lit on the imported mesh, lit (4.17), on the imported mesh, planar, and never the mesh field's
+        chains; the mesh field: lit (opt-in, `fused_light_infer`; 4.14), static."""
+        if getattr(self, "imported", False):
+            if self._infer_light_shape_fused(x, d):
+                return "nerftex_curved_light_shape_infer", self._infer_light_shape_desc
+            if self._infer_light_import_fused(x, d):
+                return "nerftex_curved_light_import_infer", self._infer_light_import_desc
+            if self._infer_import_fused(x, d):
+                return ("nerftex_curved_shape_infer", self._infer_shape_desc) if self._shape_active() else ("nerftex_curved_import_infer", self._infer_import_desc)
+            return None
+        if self._infer_light_fused(x, d):
+            return "nerftex_curved_light_infer", self._infer_light_desc
+        if self._infer_fused(x, d):
+            return "nerftex_curved_field_infer", self._infer_desc
+        return None
+
     @torch.no_grad()
     def infer_padded(self, x, d):
         """infer(x, d) for a batch of ANY size (the reference loop's iterations, Renderer.render_infer): where the light model's fused chain
@@ -1532,15 +1543,9 @@ class CurvedField(torch.nn.Module):
             xp = torch.full((B + pad, 3), 1e30, dtype=x.dtype, device=x.device)
             dp = torch.full((B + pad, 3), 1e30, dtype=d.dtype, device=d.device)
             xp[:B], dp[:B] = x, d
-            if getattr(self, "imported", False):
-                if self._infer_light_shape_fused(xp, dp):
-                    sigma, rgbs = self.infer_light_shape(xp, dp)
-                    return sigma[:B], rgbs[:B]
-                if self._infer_light_import_fused(xp, dp):
-                    sigma, rgbs = self.infer_light_import(xp, dp)
-                    return sigma[:B], rgbs[:B]
-            elif self._infer_light_fused(xp, dp):
-                sigma, rgbs = self.infer_light(xp, dp)
+            route = self._infer_route(xp, dp)
+            if route is not None and "_light_" in route[0]:  # (the lit chains only)
+                sigma, rgbs = self._infer_call(*route, xp, dp, None)
                 return sigma[:B], rgbs[:B]
         return self.infer(x, d)
 
@@ -1557,23 +1562,11 @@ class CurvedField(torch.nn.Module):
         nerftex_curved_light_infer, under the same rows contract: sigma and the mask are forward()'s bit for bit, the shading normal and the
         colour follow forward()'s arithmetic at its rounding points; over imported maps, nerftex_curved_light_import_infer
         (DESIGN.md 4.17), and over the maps on an imported mesh nerftex_curved_light_shape_infer."""
-        if getattr(self, "imported", False):  # an imported map: its own chain under the same rows contract, or forward() on all rows
-            if self._infer_light_shape_fused(x, d):  # (opt-in, as the mesh field's lit chain: `fused_light_infer`; DESIGN.md 4.18)
-                return self.infer_light_shape(x, d, live)
-            if self._infer_light_import_fused(x, d):
-                return self.infer_light_import(x, d, live)
-            if self._shape_active() and self._infer_import_fused(x, d):
-                return self._infer_call("nerftex_curved_shape_infer", self._infer_shape_desc, x, d, live)
-            if not self._shape_active() and self._infer_import_fused(x, d):
-                return self._infer_call("nerftex_curved_import_infer", self._infer_import_desc, x, d, live)
+        route = self._infer_route(x, d)
+        if route is None:
             sigma, rgbs, _ = self.forward(x, d)
             return sigma.float(), rgbs.float()
-        if self._infer_light_fused(x, d):  # (opt-in: `fused_light_infer`; the SH light model's own chain, the same rows contract)
-            return self.infer_light(x, d, live)
-        if self._infer_fused(x, d):
-            return self._infer_call("nerftex_curved_field_infer", self._infer_desc, x, d, live)
-        sigma, rgbs, _ = self.forward(x, d)
-        return sigma.float(), rgbs.float()
+        return self._infer_call(*route, x, d, live)
 
     @torch.no_grad()
     def forward_graphed(self, x, d):
