@@ -1236,6 +1236,121 @@ typedef struct nerftex_patch_front_desc {
 int nerftex_patch_front(const nerftex_patch_front_desc* d, void* stream);
 
 /* -------------------------------------------------------------------------
+ * Extension: an IMPORTED FEATURE PATCH under the curved field -- the `imported_type == 'patch'` branch of MeshFeatureField.forward
+ * (tools/map.py:676-692) over MeshProjector.weighted_project(weighting='DualD') (:435-452) and knn(use_dir_vec=False, direct_above_check=True,
+ * direct_above_threshold=1., weighting='Shepard') (:454-501): what NeRFNetwork.import_patch shows of one patch nerftex_patch_front's export
+ * produced.  The patch is an oriented point cloud of V = n_points points; `knn` is a nerftex_knn_create grid over their positions.  Per-point
+ * records, fp32, each array 16-byte aligned, row i = the point nerftex_knn_query calls i:
+ *   geom     [V, NERFTEX_PATCH_GEOM_STRIDE = 8]   {px, py, pz, 0, nx, ny, nz, 0}
+ *   features [V, 16]
+ *   lit      [V, NERFTEX_PATCH_LIT_STRIDE = 20]   {phi_embed 0..7, local_tbn 0..8 (row-major 3 x 3), 0, 0, 0}      (the lit forms only)
+ * Per sample x, all fp32, every operation rounded on its own (no fused multiply-add), sums in ascending k:
+ *   idx_k, dis_k       nerftex_knn_query's K = 8 nearest points and Euclidean distances, bit for bit
+ *   dv_k = x - p[idx_k],  dir_k = dv_k / (|dv_k| + 1e-5),  above = 2 min_k |n[idx_k] x dir_k| < 1
+ *   not above:         every dis_k and every component of every dv_k becomes 1e5 (a select: the row goes on with these values)
+ *   a_k = 1 / (dis_k + 1e-7),  a_k /= sum a;  normal = sum_k a_k n_k / (|n_k| + 1e-5),  normal /= |normal| + 1e-5
+ *   s_k = dv_k . normal,  t_k = |(dv_k - s_k normal)^2|_2  (the 2-norm of the component-wise squares),  dk = max t, d1 = min t
+ *   w_k = (((dk - t_k) / ((dk - d1) + 1e-5)) (dk + d1)) / (dk + t_k),  w_k /= sum w + 1e-5;  sdf = sum_k s_k w_k
+ *   mask = |sdf| < h_threshold and dis_0 < h_threshold (both strict; dis_0, the smallest, AFTER the select)
+ *   features = sum_k w_k features[idx_k];  lit: phi = sum_k w_k phi[idx_k], local_tbn = sum_k w_k tbn[idx_k]
+ *   xin [B,48] fp16 = [half(features) | half(FreqEncoder(sdf)), 25 values | 1 x 7];  normal is the RAW coarse normal (normalised once)
+ * A sample that is not finite gets NaNs and mask 0 (idx -1, nothing is read out of bounds).
+ * nerftex_patch_lookup / nerftex_patch_light_lookup are the plain forms (any B, every row): sdf [B], mask [B] bytes, normal [B,3], xin, idx [B,8]
+ * int32, dis [B,8] (before the select), weights [B,8] = w, and lit phi [B,8] fp32 and local_tbn [B,9].  NERFTEX_ERR_INVALID before anything is
+ * launched, in this order: a NULL grid, an n_points that is not the grid's, below 8 or above 2^31 - 1; n_freqs other than 12; (B == 0 returns
+ * NERFTEX_OK here;) a NULL input or output pointer, a phi that is not 16-byte aligned; a NULL record array; a record array or xin that is not
+ * 16-byte aligned; an h_threshold that is not positive and finite.
+ *
+ * nerftex_curved_patch_infer / nerftex_curved_light_patch_infer: the whole no-grad forward over such a patch as ONE call under the rows contract
+ * of nerftex_curved_field_infer --
+ *   lookup (search + resampling, one kernel) -> sigma net -> [static] mid / colour net / sigmoid + mask   (nerftex_curved_import_infer's four)
+ *                                                         -> [lit] light mid / BRDF net / head + mask      (nerftex_curved_light_infer's four:
+ *                                                            ONE rotation, by the lookup's weighted local_tbn, a half product as there)
+ * five launches, nothing allocated, capturable.
+ *   rows >= live                      no work; sigma / rgbs keep what they held.
+ *   live rows the march marked unused no search, no gather; sigma = 0, rgbs = 0.
+ *   every other live row              bit for bit what the plain lookup and the pieces of nerftex_curved_import_infer /
+ *                                     nerftex_curved_light_infer give one after the other.
+ * NERFTEX_ERR_INVALID with a message, before anything is launched, in this order: a NULL descriptor; B % 128 != 0; a NULL grid, an n_points that
+ * is not the grid's, below 8 or above 2^31 - 1; other shapes than 16 features (lit: 8 phi features), 12 height bands and the default networks;
+ * (lit: the light head's refusals, as nerftex_curved_light_infer;) (B == 0 returns NERFTEX_OK here;) a NULL pointer, a scratch that is not
+ * 256-byte aligned or smaller than the entry's _scratch_bytes(B); a weight vector that is not 16-byte aligned (lit: the normal net's block
+ * 4-byte); a record array that is not 16-byte aligned; an h_threshold that is not positive and finite.
+ * The lane mapping of the lookup kernel is the knob `patch_lanes` (nerftex_tune_set): 4 = four lanes per row, anything else one thread per row;
+ * both write the same bits.
+ * ------------------------------------------------------------------------- */
+#define NERFTEX_PATCH_GEOM_STRIDE 8
+#define NERFTEX_PATCH_LIT_STRIDE 20
+int nerftex_patch_lookup(const nerftex_knn* knn, const float* xyz, const float* geom, const float* features, uint32_t n_points, float h_threshold,
+                         uint32_t n_freqs, uint32_t B, float* sdf, uint8_t* mask, float* normal, void* xin, int32_t* idx, float* dis, float* weights,
+                         void* stream);
+int nerftex_patch_light_lookup(const nerftex_knn* knn, const float* xyz, const float* geom, const float* features, const float* lit, uint32_t n_points,
+                               float h_threshold, uint32_t n_freqs, uint32_t B, float* sdf, uint8_t* mask, float* normal, void* xin, int32_t* idx,
+                               float* dis, float* weights, float* phi, float* local_tbn, void* stream);
+typedef struct nerftex_curved_patch_infer_desc {
+    const nerftex_knn* knn;            /* the neighbour grid over the patch's points                                              */
+    const float* xyz;                  /* [B,3] sample positions                                                                  */
+    const float* dirs;                 /* [B,3] view directions; dirs[row][0] > 1e29 marks an unused slot                         */
+    uint32_t B;
+    uint32_t n_points;                 /* V: the grid's point count                                                               */
+    const float* geom;                 /* [V, NERFTEX_PATCH_GEOM_STRIDE] fp32, 16-byte aligned                                    */
+    const float* features;             /* [V, n_features] fp32, 16-byte aligned                                                   */
+    uint32_t n_features;
+    float h_threshold;
+    uint32_t n_freqs;                  /* FreqEncoder(height) bands (multires)                                                    */
+    const void* sigma_weights;         /* fp16, 16-byte aligned                                                                   */
+    uint32_t sigma_in, sigma_hidden, sigma_layers, sigma_out;
+    const void* color_weights;         /* fp16, 16-byte aligned                                                                   */
+    uint32_t color_in, color_hidden, color_layers, color_out;
+    float fc_weight;
+    int eval;                          /* the eval bits of nerftex_curved_mid_forward                                             */
+    float* sigma;                      /* [B] fp32                                                                                */
+    float* rgbs;                       /* [B,3] fp32                                                                              */
+    const int32_t* units_dev;
+    uint32_t rows_per_unit;
+    void* scratch;                     /* caller-owned, 256-byte aligned, >= nerftex_curved_patch_infer_scratch_bytes(B) bytes    */
+    size_t scratch_bytes;
+} nerftex_curved_patch_infer_desc;
+size_t nerftex_curved_patch_infer_scratch_bytes(uint32_t B);
+int nerftex_curved_patch_infer(const nerftex_curved_patch_infer_desc* d, void* stream);
+typedef struct nerftex_curved_light_patch_infer_desc {
+    const nerftex_knn* knn;            /* the neighbour grid over the patch's points                                              */
+    const float* xyz;                  /* [B,3] sample positions                                                                  */
+    const float* dirs;                 /* [B,3] view directions; dirs[row][0] > 1e29 marks an unused slot                         */
+    uint32_t B;
+    uint32_t n_points;                 /* V: the grid's point count                                                               */
+    const float* geom;                 /* [V, NERFTEX_PATCH_GEOM_STRIDE] fp32, 16-byte aligned                                    */
+    const float* features;             /* [V, n_features] fp32, 16-byte aligned                                                   */
+    const float* lit;                  /* [V, NERFTEX_PATCH_LIT_STRIDE] fp32, 16-byte aligned                                     */
+    uint32_t n_features, n_phi;
+    float h_threshold;
+    uint32_t n_freqs;                  /* FreqEncoder(height) bands (multires)                                                    */
+    const void* sigma_weights;         /* fp16, 16-byte aligned                                                                   */
+    uint32_t sigma_in, sigma_hidden, sigma_layers, sigma_out;
+    const void* normal_weights;        /* fp16 [NERFTEX_NORMAL_NET_WEIGHTS], 4-byte aligned: as nerftex_curved_light_infer_desc   */
+    const float* normal_biases;        /* fp32 [NERFTEX_NORMAL_NET_BIASES]                                                        */
+    uint32_t normal_hidden, normal_layers; /* 16, 2                                                                               */
+    const void* brdf_weights;          /* fp16, 16-byte aligned                                                                   */
+    uint32_t brdf_in, brdf_hidden, brdf_layers, brdf_out;
+    const float* env_shs;              /* [n_sh, n_color] fp32, as nerftex_sh_light_desc                                          */
+    uint32_t n_sh, n_color;
+    float gamma;
+    uint32_t flags;                    /* NERFTEX_SH_LIGHT_SPECULAR                                                               */
+    uint32_t visual_mode;              /* NERFTEX_LIGHT_VISUAL_*                                                                  */
+    float fc_weight;
+    int eval;                          /* as nerftex_curved_light_infer_desc                                                      */
+    float* sigma;                      /* [B] fp32                                                                                */
+    float* rgbs;                       /* [B,3] fp32                                                                              */
+    float* shading_normal;             /* [B,3] fp32 or NULL (not written)                                                        */
+    const int32_t* units_dev;
+    uint32_t rows_per_unit;
+    void* scratch;                     /* caller-owned, 256-byte aligned, >= nerftex_curved_light_patch_infer_scratch_bytes(B)    */
+    size_t scratch_bytes;
+} nerftex_curved_light_patch_infer_desc;
+size_t nerftex_curved_light_patch_infer_scratch_bytes(uint32_t B);
+int nerftex_curved_light_patch_infer(const nerftex_curved_light_patch_infer_desc* d, void* stream);
+
+/* -------------------------------------------------------------------------
  * Extension: the SH light head of the curved field -- SH_EnvmapMaterialNet.forward behind its BRDF MLP (nerf/sh_light_model.py:554-616) -- as one
  * streaming kernel per direction instead of ~40 framework ops per sample batch, the framework's arithmetic at its rounding points:
  *   albedo = half(sigmoid(brdf[:, :3])), spec_w = half(sigmoid(brdf[:, 3]))              (fp32 sigmoid narrowed to half)

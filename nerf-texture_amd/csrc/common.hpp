@@ -72,6 +72,7 @@ enum Knob {
     kKnobCompositeKeep,  // composite_step_kernel: 64-sample chunks a wave keeps in registers between its forward and backward walk (1..4; 0 = default 2)
     kKnobMarchCountProbe,  // phase ablation of march_count_parallel_kernel for profiling: 1..3 = every segment stops after that phase (0 = off; results are garbage when set)
     kKnobPlanarLanes,    // planar_lookup_rows_kernel: 4 = four lanes per row (A/B: measured no faster); anything else: one thread per row
+    kKnobPatchLanes,     // patch_lookup_kernel: 4 = four lanes per row (A/B); anything else: one thread per row
     kKnobCount
 };
 extern long g_knobs[kKnobCount];

@@ -65,6 +65,28 @@ int curved_shape_light_rows(const nerftex_raytracer* rt, const float* xyz, const
                             uint32_t K, const float* mesh_vertices, const float* vertex_normals, uint32_t n_verts, const ShapeLookup& s, const ShapeLight& t,
                             uint8_t* mask, float* normal, const int32_t* units_dev, uint32_t rows_per_unit, hipStream_t st);
 
+// The patch lookup (knn.hip / patch_import.inc: an imported feature patch resampled from its 8 nearest points) -- what the two plain entries and
+// nerftex_curved_patch_infer / nerftex_curved_light_patch_infer (patch_chain.inc) hand it alike.
+struct PatchLookup {
+    const nerftex_knn* knn;  // the neighbour grid over the patch's points
+    const float* geom;       // [n_points, 8] fp32
+    const float* features;   // [n_points, 16] fp32
+    const float* lit;        // [n_points, 20] fp32 (the lit forms)
+    uint32_t n_points;
+    float h_threshold;
+    uint32_t n_freqs;
+    void* xin;               // [N,48] half
+};
+uint32_t knn_points(const nerftex_knn* kn);
+// NULL, or why the entries refuse these values -- in the order include/nerftex_hip.h documents: the grid and the point count, n_freqs, a NULL record
+// array, alignment of the records and of xin, h_threshold
+const char* patch_lookup_refusal(const PatchLookup& s, bool lit);
+// the lookup's rows for unmarked live rows: mask [N], the raw coarse normal [N,3], the whole sigma-net input row xin [N,48] and -- n_lbc not NULL: the
+// lit form -- phi as half, level-major [4,N,2], and the weighted frame tbn [N,9].  A marked live row: mask = 0, normal = 0, features 0, z = 0 | ones;
+// nothing is searched or gathered, phi and tbn are not written.  The caller has validated (patch_lookup_refusal).
+int patch_lookup_rows(const PatchLookup& s, const float* xyz, const float* dirs, uint32_t N, uint8_t* mask, float* normal, void* n_lbc, float* tbn,
+                      const int32_t* units_dev, uint32_t rows_per_unit, hipStream_t st);
+
 // The scan launch of nerftex_patch_front (raytracer.hip / patch_export.inc; the kernel sits beside the neighbour search in knn.hip): for the
 // chunk's pre-lift origins [B, S2, 3], stats[4 b + 2] = max(stats[4 b + 2], bits of the patch's largest nearest-scan-point distance).
 int patch_scan(const nerftex_knn* scan, const float* origins, uint32_t B, uint32_t S2, uint32_t* stats, hipStream_t st);

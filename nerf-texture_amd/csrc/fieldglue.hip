@@ -718,3 +718,6 @@ extern "C" int nerftex_field_out_backward(const float* grad_rgbs, const float* r
 
 // ---- the imported map on a new mesh under the SH light model (nerftex_curved_light_shape_infer): the lit shape lookup (raytracer.hip) in front ----------
 #include "shape_light.inc"
+
+// ---- an imported feature patch (nerftex_curved_patch_infer, nerftex_curved_light_patch_infer): the patch lookup (knn.hip) in front of either back half ----
+#include "patch_chain.inc"

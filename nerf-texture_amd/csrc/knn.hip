@@ -17,6 +17,7 @@
 //     Sample points sit within a few cell sizes of the surface, so the first block (nine contiguous row ranges) decides nearly all.
 #include "common.hpp"
 #include "curved_infer.hpp"
+#include "height_ladder.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -332,3 +333,6 @@ int nerftex::patch_scan(const nerftex_knn* scan, const float* origins, uint32_t 
     }
     return check_launch("patch_front(scan)");
 }
+
+// ---- an imported feature patch: the K = 8 search above, the reference's dual-distance resampling behind it (nerftex_patch_lookup, nerftex_patch_light_lookup) ----
+#include "patch_import.inc"

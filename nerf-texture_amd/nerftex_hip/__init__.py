@@ -60,6 +60,10 @@ _SIGNATURES = {
                                    _f32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "nerftex_curved_light_shape_infer": [_vp, _vp],
     "nerftex_patch_front": [_vp, _vp],
+    "nerftex_patch_lookup": [_vp, _vp, _vp, _vp, _u32, _f32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "nerftex_patch_light_lookup": [_vp, _vp, _vp, _vp, _vp, _u32, _f32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "nerftex_curved_patch_infer": [_vp, _vp],
+    "nerftex_curved_light_patch_infer": [_vp, _vp],
     "nerftex_sh_light_forward": [_vp, _vp],
     "nerftex_sh_light_backward": [_vp, _vp],
     "nerftex_field_mid_backward": [_vp, _vp, _vp, _u32, _vp, _vp],
@@ -295,6 +299,29 @@ class PatchFrontDesc(C.Structure):
                 ("count", _vp)]
 
 
+PATCH_GEOM_STRIDE, PATCH_LIT_STRIDE = 8, 20  # NERFTEX_PATCH_*_STRIDE: floats per point of an imported patch's geom and lit records
+
+
+class CurvedPatchInferDesc(C.Structure):
+    """nerftex_curved_patch_infer_desc of include/nerftex_hip.h, field for field: the curved field's no-grad forward over an imported feature patch."""
+    _fields_ = [("knn", _vp), ("xyz", _vp), ("dirs", _vp), ("B", _u32), ("n_points", _u32), ("geom", _vp), ("features", _vp), ("n_features", _u32),
+                ("h_threshold", _f32), ("n_freqs", _u32), ("sigma_weights", _vp), ("sigma_in", _u32), ("sigma_hidden", _u32), ("sigma_layers", _u32),
+                ("sigma_out", _u32), ("color_weights", _vp), ("color_in", _u32), ("color_hidden", _u32), ("color_layers", _u32), ("color_out", _u32),
+                ("fc_weight", _f32), ("eval", _i), ("sigma", _vp), ("rgbs", _vp), ("units_dev", _vp), ("rows_per_unit", _u32), ("scratch", _vp),
+                ("scratch_bytes", _sz)]
+
+
+class CurvedLightPatchInferDesc(C.Structure):
+    """nerftex_curved_light_patch_infer_desc of include/nerftex_hip.h, field for field: the SH-lit curved field's no-grad forward over an imported
+    feature patch."""
+    _fields_ = [("knn", _vp), ("xyz", _vp), ("dirs", _vp), ("B", _u32), ("n_points", _u32), ("geom", _vp), ("features", _vp), ("lit", _vp),
+                ("n_features", _u32), ("n_phi", _u32), ("h_threshold", _f32), ("n_freqs", _u32), ("sigma_weights", _vp), ("sigma_in", _u32),
+                ("sigma_hidden", _u32), ("sigma_layers", _u32), ("sigma_out", _u32), ("normal_weights", _vp), ("normal_biases", _vp), ("normal_hidden", _u32),
+                ("normal_layers", _u32), ("brdf_weights", _vp), ("brdf_in", _u32), ("brdf_hidden", _u32), ("brdf_layers", _u32), ("brdf_out", _u32),
+                ("env_shs", _vp), ("n_sh", _u32), ("n_color", _u32), ("gamma", _f32), ("flags", _u32), ("visual_mode", _u32), ("fc_weight", _f32), ("eval", _i),
+                ("sigma", _vp), ("rgbs", _vp), ("shading_normal", _vp), ("units_dev", _vp), ("rows_per_unit", _u32), ("scratch", _vp), ("scratch_bytes", _sz)]
+
+
 PATCH_ACCEPTED, PATCH_BELOW, PATCH_NAN, PATCH_FAR, PATCH_MISSED, PATCH_NOT_NEEDED = 0, 1, 2, 3, 4, 5  # the verdict codes of nerftex_patch_front (1: the host's)
 
 SH_LIGHT_SPECULAR = 1  # nerftex_sh_light_desc.flags
@@ -309,7 +336,8 @@ class SHLightDesc(C.Structure):
 
 EXPORTS = ["nerftex_last_error", "nerftex_version", "nerftex_tune_get", "nerftex_workspace_slots_touched", "nerftex_curved_field_infer_scratch_bytes",
            "nerftex_curved_light_infer_scratch_bytes", "nerftex_curved_import_infer_scratch_bytes", "nerftex_curved_shape_infer_scratch_bytes",
-           "nerftex_curved_light_import_infer_scratch_bytes", "nerftex_curved_light_shape_infer_scratch_bytes", "nerftex_sh_light_scratch_bytes"] + list(_SIGNATURES)
+           "nerftex_curved_light_import_infer_scratch_bytes", "nerftex_curved_light_shape_infer_scratch_bytes", "nerftex_curved_patch_infer_scratch_bytes",
+           "nerftex_curved_light_patch_infer_scratch_bytes", "nerftex_sh_light_scratch_bytes"] + list(_SIGNATURES)
 
 
 def _load():
@@ -337,6 +365,10 @@ def _load():
     lib.nerftex_curved_light_import_infer_scratch_bytes.restype = _sz
     lib.nerftex_curved_light_shape_infer_scratch_bytes.argtypes = [_u32]
     lib.nerftex_curved_light_shape_infer_scratch_bytes.restype = _sz
+    lib.nerftex_curved_patch_infer_scratch_bytes.argtypes = [_u32]
+    lib.nerftex_curved_patch_infer_scratch_bytes.restype = _sz
+    lib.nerftex_curved_light_patch_infer_scratch_bytes.argtypes = [_u32]
+    lib.nerftex_curved_light_patch_infer_scratch_bytes.restype = _sz
     lib.nerftex_sh_light_scratch_bytes.argtypes = [_u32]
     lib.nerftex_sh_light_scratch_bytes.restype = _sz
     for name, args in _SIGNATURES.items():

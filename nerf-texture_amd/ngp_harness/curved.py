@@ -23,7 +23,7 @@ import torch
 
 from gridencoder import GridEncoder_clustering
 from nerftex_hip import (LIGHT_VISUAL, SH_LIGHT_SPECULAR, CurvedImportInferDesc, CurvedInferDesc, CurvedLightImportInferDesc, CurvedLightInferDesc,
-                         CurvedLightShapeInferDesc, CurvedShapeInferDesc, ptr)
+                         CurvedLightPatchInferDesc, CurvedLightShapeInferDesc, CurvedPatchInferDesc, CurvedShapeInferDesc, ptr)
 from RayTracer import RayTracer
 
 
@@ -524,6 +524,34 @@ class _CurvedOut(torch.autograd.Function):
         return g_hc, g_raw, None
 
 
+class PointGrid:
+    """The neighbour grid (nerftex_knn) over a point cloud without a mesh -- an imported patch's points --, destroyed with the object."""
+
+    def __init__(self, points, device):
+        import ctypes
+
+        from nerftex_hip import check, lib
+
+        host = np.ascontiguousarray(points, dtype=np.float32)
+        self._handle, self.n_points = ctypes.c_void_p(), int(host.shape[0])
+        with torch.cuda.device(device):
+            check(lib.nerftex_knn_create(host.ctypes.data, host.shape[0], ctypes.byref(self._handle)))
+
+    @property
+    def value(self):
+        return self._handle.value
+
+    def __del__(self):
+        h = getattr(self, "_handle", None)
+        if h is not None and h.value:
+            try:
+                from nerftex_hip import lib
+            except ImportError:  # (the interpreter is shutting down: the process's memory goes with it)
+                return
+            lib.nerftex_knn_destroy(h)
+            self._handle = None
+
+
 class CurvedField(torch.nn.Module):
     """The curved-field network with the static light model (see the module docstring), over a MeshProjector.
 
@@ -591,6 +619,10 @@ class CurvedField(torch.nn.Module):
         self.frame_map_imported = self.sample_inv_rows_imported = None
         # ... and the new mesh's per-face frames (`new_tbn`, :542): none
         self.shape_face_tbn = None
+        # ... and of the 'patch' branch (:929-937; the counter: network_curvedfield.py's patch_id): no patch, the counter at 0
+        self.patch_id = 0
+        self.patch_points = self.patch_normals = self.patch_phi_embed = self.patch_local_tbn = None
+        self.patch_geom = self.patch_lit = self._patch_knn = None
 
     def _lit(self):
         """A field whose forward reads a fine normal: the normal net, or a light model (which shades with it)."""
@@ -858,6 +890,204 @@ class CurvedField(torch.nn.Module):
             return embed, normal_coarse, h_mask, fine, p_uv, sdf, face, phi, local_tbn, ids, sample_tbn_inv, new_tbn
         return embed, normal_coarse, h_mask, fine
 
+    # ---- an exported feature patch (NeRFNetwork.import_patch, network_curvedfield.py:477-492; the 'patch' branch, tools/map.py:676-692) ----
+
+    def import_patch(self, field_dict=None, patch_id=None, *, features=..., points=..., normals=..., local_tbn=None, phi_embed=None):
+        """NeRFNetwork.import_patch -> MeshFeatureField.import_patch (tools/map.py:929-937): ONE patch of an export as an oriented point cloud the
+        samples are resampled from (8 nearest points, the reference's dual-distance weights) -- what shows an exported patch before any synthesis.
+        field_dict: what `export_field` returns (`patches`, `patch_coors`, `patch_norms`, `patch_local_tbn`, `patch_phi_embed`); patch_id picks
+        the patch, None follows the reference's counter `self.patch_id` (taken modulo the patch count, advanced after the import; an explicit
+        patch_id leaves the counter alone).  Or explicit arrays (keywords): features [V,16], points [V,3], normals [3] (the patch's one normal,
+        as the reference stores it at every point) or [V,3]; a field with the fine-normal net or a light model needs local_tbn [V,9] or
+        [V,3,3] and phi_embed [V,8] as well, a field without takes neither (a field_dict's are not read there).  V >= 8.
+        From here on embed() / density() / forward() / infer() read the patch and touch neither the projector nor the hash table, until
+        switch_import() or the next import_field() / import_patch().  The caller re-estimates the occupancy grid
+        (Renderer.initialize_states), as the reference does.  A refused call changes nothing of the field's state."""
+        explicit = (features, points, normals)
+        if field_dict is not None:
+            if any(a is not ... for a in explicit) or local_tbn is not None or phi_embed is not None:
+                raise ValueError("CurvedField.import_patch: a field_dict or explicit arrays, not both")
+            missing = [k for k in ("patches", "patch_coors", "patch_norms", "patch_local_tbn", "patch_phi_embed") if k not in field_dict]
+            if missing:
+                raise ValueError(f"CurvedField.import_patch: the field_dict lacks {missing} (it is what export_field returns)")
+            count = int(np.asarray(field_dict["patch_coors"]).shape[0])
+            if count < 1:
+                raise ValueError("CurvedField.import_patch: the field_dict holds no patch")
+            pid = self.patch_id % count if patch_id is None else int(patch_id)
+            if not 0 <= pid < count:
+                raise ValueError(f"CurvedField.import_patch: patch_id lies in [0, {count}), but got {patch_id}")
+            features = np.asarray(field_dict["patches"][pid])
+            features = features.reshape(-1, features.shape[-1])
+            points, normals = np.asarray(field_dict["patch_coors"][pid]).reshape(-1, 3), np.asarray(field_dict["patch_norms"][pid])
+            if self._lit():  # (a field without a normal net does not read them: the reference hands them over and ignores them)
+                local_tbn = np.asarray(field_dict["patch_local_tbn"][pid]).reshape(-1, 9)
+                phi = field_dict["patch_phi_embed"]
+                phi_embed = None if phi is None else np.asarray(phi[pid]).reshape(-1, np.asarray(phi[pid]).shape[-1])
+                local_tbn = None if phi is None else local_tbn  # (an export of a field without a normal net: refused below, as a patch without either)
+        elif any(a is ... for a in explicit):
+            raise ValueError("CurvedField.import_patch: a field_dict (what export_field returns), or features=, points= and normals=")
+        elif patch_id is not None:
+            raise ValueError("CurvedField.import_patch: patch_id picks a patch of a field_dict; explicit arrays are one patch")
+        if not self._lit() and (local_tbn is not None or phi_embed is not None):
+            raise ValueError("CurvedField.import_patch: local_tbn and phi_embed are read by the fine-normal net only; this field has none and would ignore them")
+        if self._lit() and (local_tbn is None) != (phi_embed is None):
+            raise ValueError("CurvedField.import_patch: local_tbn and phi_embed come together, both or none")
+        if self._lit() and phi_embed is None:
+            raise NotImplementedError("CurvedField.import_patch: a field with the fine-normal net or a light model would also need the patch's local_tbn and "
+                                      "phi_embed (tools/map.py:687-692); only the static light model without a normal net imports without them")
+
+        def arr(a):
+            return torch.as_tensor(np.asarray(a) if not torch.is_tensor(a) else a).detach().cpu().to(torch.float32)
+
+        f, p, n = arr(features), arr(points), arr(normals)
+        if f.dim() != 2 or f.shape[1] != self.encoder.output_dim or f.shape[0] < 8:
+            raise ValueError(f"CurvedField.import_patch: features are [V, {self.encoder.output_dim}] with V >= 8 (a sample reads its 8 nearest points), "
+                             f"but got {tuple(f.shape)}")
+        V = int(f.shape[0])
+        if tuple(p.shape) != (V, 3) or not bool(torch.isfinite(p).all()):
+            raise ValueError(f"CurvedField.import_patch: points are [V, 3] = {(V, 3)} and finite, but got {tuple(p.shape)}")
+        if tuple(n.shape) not in ((3,), (V, 3)) or not bool(torch.isfinite(n).all()):
+            raise ValueError(f"CurvedField.import_patch: normals are [3] or [V, 3] = {(V, 3)} and finite, but got {tuple(n.shape)}")
+        n = n.expand(V, 3).contiguous()  # (:485-486: the one normal at every point)
+        geom = torch.zeros(V, 8, dtype=torch.float32)
+        geom[:, :3], geom[:, 4:7] = p, n
+        lit = phi = loc = None
+        if self._lit():
+            phi, loc = arr(phi_embed), arr(local_tbn)
+            if tuple(phi.shape) != (V, 8):
+                raise ValueError(f"CurvedField.import_patch: phi_embed is [V, 8] = {(V, 8)}, but got {tuple(phi.shape)}")
+            if tuple(loc.shape) not in ((V, 9), (V, 3, 3)):
+                raise ValueError(f"CurvedField.import_patch: local_tbn is [V, 9] or [V, 3, 3] with V = {V}, but got {tuple(loc.shape)}")
+            loc = loc.reshape(V, 9)
+            lit = torch.zeros(V, 20, dtype=torch.float32)
+            lit[:, :8], lit[:, 8:17] = phi, loc
+        dev = self.sigma_net.weights.device
+        grid = PointGrid(p.numpy(), dev) if dev.type == "cuda" else None  # (the last thing that can fail; without a device the op-by-op route searches by brute force)
+        self.features_imported = f.to(dev).contiguous()
+        self.patch_points, self.patch_normals, self.patch_geom = p.to(dev).contiguous(), n.to(dev), geom.to(dev).contiguous()
+        self.patch_phi_embed, self.patch_local_tbn = (None, None) if lit is None else (phi.to(dev).contiguous(), loc.to(dev).contiguous())
+        self.patch_lit = None if lit is None else lit.to(dev).contiguous()
+        self._patch_knn = grid
+        self.imported, self.imported_type = True, "patch"
+        if field_dict is not None and patch_id is None:
+            self.patch_id = pid + 1
+        self._import_version += 1
+
+    def _patch_active(self):
+        return bool(getattr(self, "imported", False)) and getattr(self, "imported_type", None) == "patch"
+
+    def _patch_fused(self, x):
+        """Whether the patch lookup kernel serves this call: a neighbour grid on the device, the default shapes under fp16 autocast without the
+        probabilistic table (the static light model: unless `fused_glue` is off)."""
+        return (x.is_cuda and self._patch_active() and self._patch_knn is not None and self.encoder_var is None and self.in_dim == 41 and self.in_pad == 48
+                and self.geo_feat_dim == 15 and self.multires == 12 and self.sigma_net.dtype == torch.float16 and torch.is_autocast_enabled()
+                and torch.get_autocast_dtype("cuda") == torch.float16 and (self._lit() or getattr(self, "fused_glue", True))
+                and self._on_device_of(x, self.features_imported, self.patch_geom))
+
+    @torch.no_grad()
+    def _patch_lookup(self, x, lit=False):
+        """nerftex_patch_lookup (lit: nerftex_patch_light_lookup): -> sdf [N], h_mask [N] bool, normal [N,3] (raw), xin [N,48] half, idx [N,8],
+        dis [N,8] (the search's), weights [N,8] (+ lit: phi [N,8] fp32, local_tbn [N,3,3])."""
+        from nerftex_hip import check, lib, ptr, stream
+
+        x = x.detach().float().contiguous()
+        N, dev, f = x.shape[0], x.device, self.features_imported
+        sdf = torch.empty(N, device=dev)
+        mask = torch.empty(N, dtype=torch.uint8, device=dev)
+        normal = torch.empty(N, 3, device=dev)
+        xin = torch.empty(N, 48, dtype=torch.float16, device=dev)
+        idx = torch.empty(N, 8, dtype=torch.int32, device=dev)
+        dis, weights = torch.empty(N, 8, device=dev), torch.empty(N, 8, device=dev)
+        head = (self._patch_knn.value, ptr(x), ptr(self.patch_geom), ptr(f))
+        tail = (f.shape[0], float(self.h_threshold), int(self.multires), N, ptr(sdf), ptr(mask), ptr(normal), ptr(xin), ptr(idx), ptr(dis), ptr(weights))
+        if not lit:
+            check(lib.nerftex_patch_lookup(*head, *tail, stream()))
+            return sdf, mask.bool(), normal, xin, idx, dis, weights
+        phi, tbn = torch.empty(N, 8, device=dev), torch.empty(N, 9, device=dev)
+        check(lib.nerftex_patch_light_lookup(*head, ptr(self.patch_lit), *tail, ptr(phi), ptr(tbn), stream()))
+        return sdf, mask.bool(), normal, xin, idx, dis, weights, phi, tbn.view(N, 3, 3)
+
+    def _patch_neighbours(self, x):
+        """The 8 nearest patch points of every sample (idx, Euclidean distances, ascending): the library's exact search where the grid is, brute
+        force elsewhere."""
+        from nerftex_hip import check, lib, ptr, stream
+
+        if x.is_cuda and self._patch_knn is not None:
+            x = x.contiguous()
+            idx = torch.empty(x.shape[0], 8, dtype=torch.int32, device=x.device)
+            dis = torch.empty(x.shape[0], 8, dtype=torch.float32, device=x.device)
+            check(lib.nerftex_knn_query(self._patch_knn.value, ptr(x), x.shape[0], 8, ptr(idx), ptr(dis), stream()))
+            return idx, dis
+        points, idx, dis = self.patch_points.to(x.device), [], []
+        for a in range(0, x.shape[0], 8192):  # (differences, not the matrix-product form of cdist: that one loses half the digits of a distance)
+            d = torch.cdist(x[a:a + 8192], points, compute_mode="donot_use_mm_for_euclid_dist")
+            dd, ii = torch.topk(d, 8, dim=-1, largest=False, sorted=True)
+            idx.append(ii.int())
+            dis.append(dd)
+        return torch.cat(idx).contiguous(), torch.cat(dis).contiguous()
+
+    def _patch_embed_reference(self, x, neighbours=None, with_fine_normal=False, details=False):
+        """The 'patch' branch op by op, the reference's expressions line by line (tools/map.py:678-692 over weighted_project(weighting='DualD'),
+        :435-452, and knn(use_dir_vec=False, direct_above_check=True, direct_above_threshold=1., weighting='Shepard'), :454-501):
+        -> embed [N,41] fp32, normal_coarse, h_mask (+ normal_fine with with_fine_normal; details: + sdf, the raw normal, idx, dis after the
+        direct-above select, weights, and with the fine normal the weighted phi_embed and local_tbn).  neighbours: a neighbour list from
+        elsewhere (default: `_patch_neighbours`)."""
+        x = x.float()
+        points, vertex_normals = self.patch_points.to(x.device), self.patch_normals.to(x.device)
+        idx, dis = self._patch_neighbours(x) if neighbours is None else neighbours
+        idx = idx.long()
+        # knn(), :459-471
+        normals = vertex_normals[idx]
+        dir_vec_ori = x.unsqueeze(-2) - points[idx]
+        dir_vec = dir_vec_ori / (dir_vec_ori.norm(dim=-1, keepdim=True) + 1e-5)
+        p2n_dis_min = 2 * torch.cross(normals, dir_vec, dim=-1).norm(dim=-1).min(dim=-1)[0]
+        direct_above_mask = (p2n_dis_min < 1.0).reshape([-1, 1])
+        dis = torch.where(direct_above_mask, dis, 1e5 * torch.ones_like(dis))
+        dir_vec_ori = torch.where(direct_above_mask.unsqueeze(-1), dir_vec_ori, 1e5 * torch.ones_like(dir_vec_ori))
+        # :486-499
+        weights = 1 / (dis + 1e-7)
+        weights = weights / torch.sum(weights, dim=-1, keepdim=True)
+        normals = normals / (normals.norm(dim=-1, keepdim=True) + 1e-5)
+        normal = (normals * weights.unsqueeze(-1)).sum(-2)
+        normal = normal / (normal.norm(dim=-1, keepdim=True) + 1e-5)
+        # weighted_project(), :437-448 (sdf_scale 1, sdf_offset 0: neither setter reaches this branch)
+        sdfs = (dir_vec_ori * normal.unsqueeze(1)).sum(-1)
+        dist2D_sq = ((dir_vec_ori - sdfs.unsqueeze(-1) * normal.unsqueeze(1)) ** 2).norm(dim=-1)
+        dk = dist2D_sq.max(dim=-1, keepdim=True)[0]
+        d1 = dist2D_sq.min(dim=-1, keepdim=True)[0]
+        weights = (dk - dist2D_sq) / (dk - d1 + 1e-5) * (dk + d1) / (dk + dist2D_sq)
+        weights = weights / (weights.sum(-1, keepdim=True) + 1e-5)
+        sdf = (sdfs * weights).sum(-1, keepdim=True) / max(1e-5, 1.0) - 0.0
+        # forward(), :679-685
+        x_embed = (weights.unsqueeze(-1) * self.features_imported.to(x.device)[idx]).sum(-2)
+        z_embed = freq_encode(sdf, self.multires)
+        h_mask = sdf[..., 0].abs() < self.h_threshold
+        h_mask = torch.logical_and(h_mask, dis.min(dim=-1)[0] < self.h_threshold)
+        embed = torch.cat([x_embed, z_embed], dim=-1)
+        normal_coarse = normal / (normal.norm(dim=-1, keepdim=True) + 1e-5)  # :720
+        out = (embed, normal_coarse, h_mask)
+        more = (sdf[..., 0], normal, idx, dis, weights)
+        if with_fine_normal:  # :687-692, :722-730: ONE rotation, by the weighted local_tbn
+            phi = (weights.unsqueeze(-1) * self.patch_phi_embed.to(x.device)[idx]).sum(-2)
+            local_tbn = (weights.unsqueeze(-1).unsqueeze(-1) * self.patch_local_tbn.to(x.device)[idx].reshape(*idx.shape, 3, 3)).sum(-3)
+            local = self.normal_net(phi_embed=phi, z_embed=z_embed, x_embed=x_embed)
+            fine = torch.einsum("nba,nb->na", local_tbn, local)
+            out += (fine / (fine.norm(dim=-1, keepdim=True) + 1e-5),)
+            more += (phi, local_tbn)
+        return out + more if details else out
+
+    def _patch_embed(self, x, with_fine_normal=False):
+        """embed() over the imported patch: the lookup kernel where it applies (`_patch_fused`), the op-by-op route elsewhere."""
+        if not self._patch_fused(x):
+            return self._patch_embed_reference(x, with_fine_normal=with_fine_normal)
+        if not with_fine_normal:
+            _, h_mask, normal, xin = self._patch_lookup(x)[:4]
+            return xin[:, :self.in_dim], normal / (normal.norm(dim=-1, keepdim=True) + 1e-5), h_mask
+        _, h_mask, normal, xin, _, _, _, phi, local_tbn = self._patch_lookup(x, lit=True)
+        local = self.normal_net(phi_embed=phi, z_embed=xin[:, 16:self.in_dim], x_embed=xin[:, :16])
+        fine = torch.einsum("nba,nb->na", local_tbn, local)
+        return xin[:, :self.in_dim], normal / (normal.norm(dim=-1, keepdim=True) + 1e-5), h_mask, fine / (fine.norm(dim=-1, keepdim=True) + 1e-5)
+
     # ---- the trained field exported as texture patches (NeRFNetwork.export_field -> MeshFeatureField.sample_patches, tools/map.py:951-1128) ----
 
     def export_field(self, sample_points, sample_normals, *, scan_points=None, first_component=None, grid_gap=None, pattern_rate=1 / 50, patch_size=128,
@@ -924,6 +1154,10 @@ class CurvedField(torch.nn.Module):
         if not getattr(self, "imported", False):
             return ()
         f = self.features_imported
+        if self._patch_active():  # the patch's records, its neighbour grid, the threshold
+            kn = self._patch_knn
+            return (("import-patch", f.data_ptr(), tuple(f.shape), None if kn is None else kn.value, self.patch_geom.data_ptr(),
+                     None if self.patch_lit is None else self.patch_lit.data_ptr(), float(self.h_threshold), self._import_version))
         if self._shape_active():
             p = self.shape_projector
             stamp = (("import-shape", f.data_ptr(), tuple(f.shape), p._knn.value, p.tracer._handle.value, p.mesh_vertices.data_ptr(), p.vertex_normals.data_ptr(),
@@ -1062,6 +1296,11 @@ class CurvedField(torch.nn.Module):
         requires_grad_xyz (network_curvedfield.py:236-259, the branch that differentiates sigma with respect to the sample position): the
         projection carries `diff_project_layer`'s gradient, the hash table is looked up with input gradients (dy_dx) and the height ladder
         is evaluated by framework ops on the differentiable height -- dL/dembed reaches x."""
+        if self._patch_active():  # the 'patch' branch (:676-692): the patch's 8 nearest points instead of the mesh and the table
+            if requires_grad_xyz or (with_fine_normal and self.patch_lit is None):
+                raise NotImplementedError("CurvedField.embed: an imported patch is rendered without gradients to the sample position, and without a fine "
+                                          "normal unless it came with local_tbn and phi_embed")
+            return self._patch_embed(x, with_fine_normal=with_fine_normal)
         if getattr(self, "imported", False):  # the import branch (:646-668): the map instead of the mesh and the table
             lit_maps = self._lit() and self.phi_embed_imported is not None and (not self._shape_active() or self.shape_face_tbn is not None)
             if requires_grad_xyz or (with_fine_normal and not lit_maps):
@@ -1113,7 +1352,12 @@ class CurvedField(torch.nn.Module):
         return _TruncExp.apply(h[..., 0]), h[..., 1:]
 
     def density(self, x, requires_grad_xyz=False):
-        if getattr(self, "imported", False) and not requires_grad_xyz and (self._import_fused(x) or self._import_light_fused(x) or self._shape_light_fused(x)):
+        if self._patch_active() and not requires_grad_xyz and self._patch_fused(x):
+            h_mask, xin = (self._patch_lookup(x)[i] for i in (1, 3))
+            h = self.sigma_net(xin)
+            sigma = _TruncExp.apply(h[..., 0])
+            return {"sigma": torch.where(h_mask, sigma, torch.zeros_like(sigma)), "geo_feat": h[..., 1:]}
+        if getattr(self, "imported", False) and not self._patch_active() and not requires_grad_xyz and (self._import_fused(x) or self._import_light_fused(x) or self._shape_light_fused(x)):
             h_mask, xin = (self._shape_lookup(x)[i] for i in (2, 5)) if self._shape_active() else self._import_lookup(x)[2:]
             h = self.sigma_net(xin)
             sigma = _TruncExp.apply(h[..., 0])
@@ -1185,7 +1429,13 @@ class CurvedField(torch.nn.Module):
     def forward(self, x, d, **kwargs):
         if getattr(self, "light_model", None) == "SH":
             return self._forward_light(x, d, normal_supervision=bool(kwargs.get("normal_supervision", False)))
-        if getattr(self, "imported", False) and self._import_fused(x):
+        if self._patch_active() and self._patch_fused(x) and self._glue_fused():
+            _, h_mask, normal, xin = self._patch_lookup(x)[:4]
+            h = self.sigma_net(xin)
+            sigma_raw, cin = _CurvedMid.apply(h, normal, d, self.fc_weight, 2 | int(not self.training))  # (bit 1: tools/map.py:720 in the kernel)
+            sigma, color = _CurvedOut.apply(self.color_net(cin), sigma_raw, h_mask)
+            return sigma, color, {}
+        if getattr(self, "imported", False) and not self._patch_active() and self._import_fused(x):
             if self._shape_active():
                 _, _, h_mask, normal, _, xin = self._shape_lookup(x)
             else:
@@ -1422,6 +1672,38 @@ class CurvedField(torch.nn.Module):
                 and self._on_device_of(x, self.features_imported, self.phi_embed_imported, self.frame_map_imported, self.sample_inv_rows_imported,
                                        self.shape_face_uv, self.shape_face_tbn))
 
+    def _infer_patch_fused(self, x, d):
+        """Whether nerftex_curved_patch_infer serves this call: an imported patch, and _infer_import_fused()'s conditions over it."""
+        if getattr(self, "imported_type", None) != "patch":
+            return False
+        return (self._patch_fused(x) and self._glue_fused() and self._infer_color_ok() and self._infer_sigma_ok() and self._infer_batch_ok(x, d))
+
+    def _infer_light_patch_fused(self, x, d):
+        """Whether nerftex_curved_light_patch_infer serves this call: an imported patch with its lit records, and
+        _infer_light_import_fused()'s conditions over it."""
+        if getattr(self, "imported_type", None) != "patch":
+            return False
+        return (self._infer_light_back_fused(x) and self._patch_fused(x) and self.patch_lit is not None and self._infer_sigma_ok()
+                and self._infer_batch_ok(x, d) and self._on_device_of(x, self.patch_lit))
+
+    def _infer_patch(self):
+        """The imported patch: its neighbour grid and records, the threshold and the ladder."""
+        f = self.features_imported
+        return dict(knn=self._patch_knn.value, n_points=f.shape[0], geom=ptr(self.patch_geom), features=ptr(f), n_features=f.shape[1],
+                    **self._infer_ladder(float(self.h_threshold)))
+
+    def _infer_patch_desc(self, x, d, live, sigma, rgbs, scratch):
+        """The nerftex_curved_patch_infer_desc of one call (and the tensors it points into, to be kept until the call is enqueued)."""
+        back, weights = self._infer_static_back(x, d, live, sigma, rgbs, scratch)
+        return CurvedPatchInferDesc(**self._infer_patch(), **back), (self.features_imported, self.patch_geom, self._patch_knn) + weights
+
+    def _infer_light_patch_desc(self, x, d, live, sigma, rgbs, scratch, shading_normal=None):
+        """The nerftex_curved_light_patch_infer_desc of one call (and the tensors it points into, to be kept until the call is enqueued)."""
+        back, kept = self._infer_lit_back(x, d, live, sigma, rgbs, scratch, shading_normal)
+        lit = self.patch_lit
+        return (CurvedLightPatchInferDesc(lit=ptr(lit), n_phi=self.patch_phi_embed.shape[1], **self._infer_patch(), **back),
+                (self.features_imported, self.patch_geom, lit, self._patch_knn) + kept)
+
     def _infer_light_desc(self, x, d, live, sigma, rgbs, scratch, shading_normal=None):
         """The nerftex_curved_light_infer_desc of one call (and the tensors it points into).  Kept between calls and re-made when a parameter
         changes: the 16-bit MLP weights, and the normal net's packed block -- every LipLayer's normalization().half(), which is what the
@@ -1516,9 +1798,15 @@ class CurvedField(torch.nn.Module):
 
     def _infer_route(self, x, d):
         """The chain that serves infer(x, d): (the library entry's name, the builder of its descriptor), or None: forward().  The one priority
-        ladder -- an imported map: lit on the imported mesh, lit (4.17), on the imported mesh, planar, and never the mesh field's
+        ladder -- an imported patch: lit, static, and nothing else; an imported map: lit on the imported mesh, lit (4.17), on the imported mesh, planar, and never the mesh field's
         chains; the mesh field: lit (opt-in, `fused_light_infer`; 4.14), static."""
         if getattr(self, "imported", False):
+            if self._infer_light_patch_fused(x, d):
+                return "nerftex_curved_light_patch_infer", self._infer_light_patch_desc
+            if self._infer_patch_fused(x, d):
+                return "nerftex_curved_patch_infer", self._infer_patch_desc
+            if getattr(self, "imported_type", None) == "patch":  # (the maps of an earlier import_field are not this import's)
+                return None
             if self._infer_light_shape_fused(x, d):
                 return "nerftex_curved_light_shape_infer", self._infer_light_shape_desc
             if self._infer_light_import_fused(x, d):
@@ -1561,7 +1849,9 @@ class CurvedField(torch.nn.Module):
         light_model="SH": forward(x, d) on all rows unless `fused_light_infer` is set (default False) -- then the light model's own chain,
         nerftex_curved_light_infer, under the same rows contract: sigma and the mask are forward()'s bit for bit, the shading normal and the
         colour follow forward()'s arithmetic at its rounding points; over imported maps, nerftex_curved_light_import_infer
-        (DESIGN.md 4.17), and over the maps on an imported mesh nerftex_curved_light_shape_infer."""
+        (DESIGN.md 4.17), and over the maps on an imported mesh nerftex_curved_light_shape_infer.
+        An imported patch (import_patch): nerftex_curved_patch_infer, and for the SH-lit field with the switch set
+        nerftex_curved_light_patch_infer, under the same contract."""
         route = self._infer_route(x, d)
         if route is None:
             sigma, rgbs, _ = self.forward(x, d)

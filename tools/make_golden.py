@@ -511,6 +511,12 @@ def main():
     if "--import-shape-sh-only" in sys.argv:
         import_shape_sh_goldens()
         return
+    if "--import-patch-only" in sys.argv:
+        import_patch_goldens()
+        return
+    if "--import-patch-sh-only" in sys.argv:
+        import_patch_sh_goldens()
+        return
     if "--sh-light-only" in sys.argv:
         sh_light_goldens()
         sh_field_goldens()
@@ -1484,6 +1490,177 @@ def import_shape_goldens():
     np.savez_compressed(os.path.join(OUT, "ref_python_import_shape.npz"), **out)
     new = [os.path.join(r, n) for r, _, names in os.walk(REF) for n in names if os.lstat(os.path.join(r, n)).st_mtime >= started]
     assert not new, "files appeared under the reference tree:\n" + "\n".join(new[:20])
+
+
+def _import_patch_goldens(lit):
+    """The two import_patch fixtures: MeshFeatureField.import_patch (tools/map.py:929-937) and the `imported_type == 'patch'` branch of its
+    forward (:676-692, :719-730) over MeshProjector.weighted_project / knn (:435-501) executed on the CPU under emulated_autocast, with
+    NeRFNetwork.forward (and, static, density) behind it.  The patch: 12 x 12 points, grid gap 1/32, on z = 0.2 (x^2 - y^2), the one patch normal
+    (0, 0, 1) at every point as NeRFNetwork.import_patch stores it (:485-486), seeded features (lit: phi_embed and frames that are not
+    orthonormal).  import_patch's MeshProjector(...) call is answered by a projector made past its trimesh / open3d constructor from the
+    arrays (mesh_vertices, vertex_normals, the search's members); frnn -> exact brute force.  512 points, h_threshold 0.0625: right above and
+    below points, between four points, outside the rim, beyond the threshold, and seeded ones in the patch's box.  Values only."""
+    import time
+
+    import torch
+
+    started = time.time()
+    _install_map_imports()
+    if lit:
+        _stub("imageio")
+        for name in ("nerf.sh_light_model", "nerf.network_curvedfield", "tools.shape_tools"):
+            sys.modules.pop(name, None)
+        for name, cls in (("sg_light_model", "SG_EnvmapMaterialNet"), ("envmap_light_model", "Envmap_EnvmapMaterialNet")):
+            _stub("nerf." + name, **{cls: None})
+        import nerf.sh_light_model as ref_sh
+    else:
+        for name, cls in (("sg_light_model", "SG_EnvmapMaterialNet"), ("sh_light_model", "SH_EnvmapMaterialNet"), ("envmap_light_model", "Envmap_EnvmapMaterialNet")):
+            if "nerf." + name not in sys.modules:
+                _stub("nerf." + name, **{cls: None})
+    import nerf.network_curvedfield as ref_cf
+    import tools.map as ref_map
+    from tools.encoding import get_encoder
+
+    c = np.load(os.path.join(OUT, "ref_python_curvedfield.npz"))
+    S, gap, h_threshold, curve = 12, 1.0 / 32, 0.0625, 0.2
+    rng = np.random.default_rng(171 if lit else 151)
+    axis = (np.arange(S) - (S - 1) / 2) * gap
+    gx, gy = np.meshgrid(axis, axis, indexing="ij")
+    points = np.stack([gx, gy, curve * (gx * gx - gy * gy)], -1).reshape(-1, 3).astype(np.float32)
+    V, half = S * S, (S - 1) / 2 * gap
+    normal = np.array([0.0, 0.0, 1.0], np.float32)
+    features = rng.uniform(-0.5, 0.5, (V, 16)).astype(np.float32)
+    phi_embed = rng.uniform(-0.5, 0.5, (V, 8)).astype(np.float32)
+    local_tbn = (np.eye(3, dtype=np.float32).reshape(9) + rng.normal(0, 0.35, (V, 9))).astype(np.float32)
+    rows = []
+    for b in range(512):
+        i, t = int(rng.integers(0, V)), rng.uniform(-1.3, 1.3) * h_threshold
+        kind = b % 5
+        if kind == 0:
+            q = points[i].astype(np.float64) + t * normal + rng.normal(0, 1e-3, 3) * gap
+        elif kind == 1:
+            xy = points[i, :2] + 0.5 * gap * np.where(points[i, :2] > 0, -1.0, 1.0)
+            q = np.array([xy[0], xy[1], curve * (xy[0] ** 2 - xy[1] ** 2) + t])
+        elif kind == 2:
+            out_, along = half + rng.uniform(0.2, 3.0) * gap, rng.uniform(-half, half)
+            xy = [(out_, along), (-out_, along), (along, out_), (along, -out_)][int(rng.integers(0, 4))]
+            q = np.array([xy[0], xy[1], curve * (xy[0] ** 2 - xy[1] ** 2) + t])
+        elif kind == 3:
+            q = points[i].astype(np.float64) + np.sign(t) * rng.uniform(1.05, 1.6) * h_threshold * normal + rng.normal(0, 0.1, 3) * gap * np.array([1, 1, 0])
+        else:
+            xy = rng.uniform(-(half + 2 * gap), half + 2 * gap, 2)
+            q = np.array([xy[0], xy[1], curve * (xy[0] ** 2 - xy[1] ** 2) + rng.uniform(-1.4, 1.4) * h_threshold])
+        rows.append(q)
+    pts = np.asarray(rows, np.float64).astype(np.float32)
+    dirs = rng.normal(size=(512, 3))
+    dirs = (dirs / np.linalg.norm(dirs, axis=-1, keepdims=True)).astype(np.float32)
+
+    mff = object.__new__(ref_map.MeshFeatureField)
+    torch.nn.Module.__init__(mff)
+    mff.device, mff.h_threshold, mff.K, mff.bound, mff.hash, mff.prob_model, mff.pred_normal, mff.clustering = "cpu", h_threshold, 8, 1, True, False, lit, True
+    mff.imported, mff.imported_type, mff.rescale = False, None, False  # (the constructor's values, :604-618)
+    mff.sdf_scale_factor, mff.sdf_offset, mff.uv_utilize_rate, mff.K_for_uv = 1.0, 0.0, 1.0, 5
+    mff.encoder_f_out_dim = 16
+    mff.encoder_z, mff.encoder_z_outdim = get_encoder("frequency", input_dim=1, multires=12)
+    mff.meshprojector = types.SimpleNamespace(mean_edge_length=gap)  # (import_patch hands it on; the 'patch' branch does not read it)
+    mff.normal_net = None
+    if lit:
+        torch.manual_seed(11)
+        mff.normal_net = ref_map.Factorized_Normal_Net(x_dim=mff.encoder_f_out_dim, z_dim=mff.encoder_z_outdim, lip=True, direct_pred_coor=False, bound_output=False)
+        gen = torch.Generator().manual_seed(13)
+        with torch.no_grad():
+            for mlp in (mff.normal_net.phi_net, mff.normal_net.theta_net):
+                for layer in mlp.layers:
+                    layer.W.mul_(6.0)
+                    layer.b.copy_(torch.randn(layer.b.shape, generator=gen) * 0.3)
+                    layer.c.fill_(2.0)
+    net = object.__new__(ref_cf.NeRFNetwork)
+    torch.nn.Module.__init__(net)
+    net.visual_mode, net.render_light_model, net.use_grad_normal, net.fc_weight, net.dir_degree = "RGB", lit, False, 1.0, 4
+    net.optimize_gamma, net.meshfea_field = False, mff
+    tcnn = sys.modules["tinycudann"]
+    torch.manual_seed(42)
+    net.sigma_net = tcnn.Network(n_input_dims=mff.encoder_z_outdim + mff.encoder_f_out_dim, n_output_dims=16,
+                                 network_config={"otype": "FullyFusedMLP", "activation": "ReLU", "output_activation": "None", "n_neurons": 32, "n_hidden_layers": 1})
+    if lit:
+        net.light_model, net.smooth_grad_weight = "SH", 1e-1
+        net.use_coarse_normal, net.coarse_as_primary, net.no_visibility, net.shade_visibility, net.light_visual_mode = False, False, False, True, "Full"
+        net.color_net = None
+        net.light_net = ref_sh.SH_EnvmapMaterialNet(input_dim=15, sh_order=3, white_light=True, use_specular=True)
+        with torch.no_grad():
+            net.light_net.envSHs[1:] = torch.from_numpy(np.random.default_rng(91).normal(0, 1.5, (15, 1)).astype(np.float32))
+    else:
+        net.encoder_dir = tcnn.Encoding(n_input_dims=3, encoding_config={"otype": "SphericalHarmonics", "degree": 4})
+        net.color_net = tcnn.Network(n_input_dims=net.encoder_dir.n_output_dims + 15, n_output_dims=3,
+                                     network_config={"otype": "FullyFusedMLP", "activation": "ReLU", "output_activation": "None", "n_neurons": 64, "n_hidden_layers": 2})
+        assert np.array_equal(net.color_net.net.weights.detach().numpy(), c["w_color"])
+    assert np.array_equal(net.sigma_net.net.weights.detach().numpy(), c["w_sigma"]), "the sigma net of ref_python_curvedfield.npz"
+    net.eval()
+
+    real_projector = ref_map.MeshProjector
+
+    def projector_past_its_constructor(device, mesh, **kw):  # (the members knn() and weighted_project() read, :396-400)
+        mp = object.__new__(real_projector)
+        mp.mesh_vertices, mp.vertex_normals = torch.FloatTensor(mesh.vertices), torch.FloatTensor(mesh.normals)
+        mp.grid, mp.radius, mp.max_K, mp.depth_threshold, mp.mean_edge_length = None, 100.0, len(mesh.vertices), 9.5, kw["mean_edge_length"]
+        return mp
+
+    # NeRFNetwork.import_patch (:484-487) on the arrays: the patch's points, its one normal at every point
+    normals = np.zeros_like(points)
+    normals[:] = normal
+    mesh = types.SimpleNamespace(vertices=points, normals=normals)
+    ref_map.MeshProjector = projector_past_its_constructor
+    try:
+        mff.import_patch(features=features, mesh=mesh, local_tbn=local_tbn, phi_embed=phi_embed if lit else None)
+    finally:
+        ref_map.MeshProjector = real_projector
+    assert mff.imported and mff.imported_type == "patch"
+
+    x, d = torch.from_numpy(pts), torch.from_numpy(dirs)
+    name = "ref_python_import_patch_sh.npz" if lit else "ref_python_import_patch.npz"
+    out = dict(features=features, points=points, normals=normal, grid_gap=gap, h_threshold=h_threshold, xyz=pts, dirs=dirs)
+    with torch.no_grad(), emulated_autocast():
+        embed, nc, nf, hm = mff(x)
+        out.update(h_mask=hm.numpy(), embed=embed.float().numpy(), normal=nc.float().numpy())
+        if not lit:
+            sigma, color, _ = net(x, d)
+            dens = net.density(x)
+            assert torch.equal(dens["sigma"], sigma) and torch.equal(color.half().float(), color.float())
+            out.update(sigma=sigma.float().numpy(), color=color.half().numpy(), weights_of="ref_python_curvedfield.npz")
+        else:
+            handed = {}
+            net.light_net.register_forward_pre_hook(lambda m, a: handed.update(normal=a[1].detach().float().numpy().copy()))
+            out.update(phi_embed=phi_embed, local_tbn=local_tbn, normal_fine=nf.float().numpy(), w_sigma=c["w_sigma"],
+                       w_brdf=net.light_net.brdf_layer.net.weights.detach().numpy().copy(), env_shs=net.light_net.envSHs.detach().numpy().copy())
+            for nm, mlp in (("phi", mff.normal_net.phi_net), ("theta", mff.normal_net.theta_net)):
+                for i, layer in enumerate(mlp.layers):
+                    out[f"{nm}_W{i}"], out[f"{nm}_b{i}"], out[f"{nm}_c{i}"] = layer.W.detach().numpy().copy(), layer.b.detach().numpy().copy(), float(layer.c)
+            for fc in (1.0, 0.7):
+                net.fc_weight = fc
+                for visual in ("Full", "Specular", "Diffuse", "Albedo"):
+                    net.light_visual_mode = visual
+                    sigma, color, ret = net(x, d, is_gui_mode=False)
+                    assert ret == {}
+                    out[f"fc{fc}_color_{visual.lower()}"] = color.float().numpy()
+                out["sigma"], out[f"fc{fc}_shading_normal"] = sigma.float().numpy(), handed["normal"]
+    print(name + ":", "inside the mask", float(hm.float().mean()), "sigma max", float(sigma.max()), "rows that fail the direct-above test (sdf exactly 0)",
+          int((embed[:, 16] == 0).sum()))
+    np.savez_compressed(os.path.join(OUT, name), **out)
+    new = [os.path.join(r, n) for r, _, names in os.walk(REF) for n in names if os.lstat(os.path.join(r, n)).st_mtime >= started]
+    assert not new, "files appeared under the reference tree:\n" + "\n".join(new[:20])
+
+
+def import_patch_goldens():
+    """ref_python_import_patch.npz: the static light model (the sigma and colour nets of ref_python_curvedfield.npz); see _import_patch_goldens.
+    Reads one fixture; writes this one file."""
+    _import_patch_goldens(False)
+
+
+def import_patch_sh_goldens():
+    """ref_python_import_patch_sh.npz: the `pred_normal` part too (:687-692: the weighted phi_embed and local_tbn, ONE rotation), NeRFNetwork.forward
+    in eval with the real SH_EnvmapMaterialNet, fc_weight 1.0 and 0.7, the four light_visual_modes; the normal net and the lighting of
+    ref_python_import_field_sh.npz's recipe.  See _import_patch_goldens.  Reads one fixture (the sigma net's weights, as a check); writes this one."""
+    _import_patch_goldens(True)
 
 
 def import_shape_sh_goldens():
