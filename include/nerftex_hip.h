@@ -1630,6 +1630,80 @@ typedef struct nerftex_ema_desc {
 int nerftex_ema_update(const nerftex_ema_desc* desc, int count, float* const* shadow, const float* const* param0,
                        const float* const* param1 /* NULL without live */, const uint64_t* n, void* stream);
 
+/* The planar texture synthesized from exported patches (csrc/synthesis.inc): the path the reference's patch_matching_and_quilting.py runs --
+ * patchBasedTextureSynthesis with mode 'Cut', quilt off, coarse_KDtree, rotate off, picked_vertices given (close_patch_check), PARM_truncation 0 --
+ * and the closing lines of its __main__ (:485-511).  The canvas is filled cell by cell in raster order: the k = 16 examples whose coarse overlap
+ * strips are nearest the canvas's (Euclidean, float64 sums over fp32 block sums), the close-patch filter, k doubled while nothing survives, a
+ * weighted draw from one uniform number per cell, a minimum-error boundary cut against the left and then the top neighbour, a masked copy.
+ * Examples: the P patches, then their row-flipped copies (mirror_hor), then the column-flipped copies of all of those (mirror_vert); they are read
+ * through the flips, never stored.  Canvas, databases and outputs are fp32; a copied pixel is the example's pixel bit for bit, a seam's mean is
+ * the correctly rounded float64 mean (its fp32 residual is kept beside the canvas for the cuts and for a second mean in a corner); distances, seam
+ * energies and the selection are float64 in a fixed order: the same bits from run to run.
+ *   create   validates (NERFTEX_ERR_INVALID with a message, before any device call: a NULL descriptor, out or array; P, S, C of 0; match_dim outside
+ *            1..C; overlap_size of 0 or above 256; overlap_size * 2 + patch_size != S; a non-square or too small output (output_h != output_w,
+ *            output_h <= overlap_size, a canvas side above 16384); attenuation other than 1 or 3; max_patch_res of 0; mode other than
+ *            NERFTEX_SYNTH_CUT; quilt set; more than 2^31 - 1 examples or database entries), then builds the two coarse databases
+ *            [examples, overlap * ceil(S / block) * match_dim] fp32, block = max(S / max_patch_res, 1), and allocates canvas, ids, id map, log and
+ *            workspaces.  The descriptor's three arrays are device memory and must outlive the handle.
+ *   resolve  cells [cell_begin, cell_end) in raster order, at most four launches a cell and no host synchronisation: the coarse query, the distances
+ *            (examples x slices of the strip, float64 partial sums), the selection and the cuts (one workgroup), the masked copy.  Cell 0 takes
+ *            first_patch uncut.  draws [cells] and forced [cells] (or NULL) are DEVICE arrays indexed by the cell (entry 0 unused); with forced the
+ *            placed example is forced[cell] while the one the draw picks is still logged.  NERFTEX_ERR_INVALID: first_patch >= examples, a cell
+ *            range outside the canvas or not starting where the last call ended, NULL draws.
+ *            A cell whose k would exceed the example set (sklearn raises there) sets a device status; the cells behind it do nothing.
+ *   finish   the closing remap -- total_id = the sorted distinct ids of canvas_id, sample_tbn = example_tbn[total_id], sample_tbn_ids = canvas_id
+ *            as positions in total_id -- then waits for the stream and reports the status: NERFTEX_ERR_EXHAUSTED (with the cell in the message)
+ *            if a cell ran out of examples, NERFTEX_ERR_INVALID for a forced id outside the example set or non-finite distances.
+ *   result   pointers and sizes (device memory owned by the handle; n_total is valid after finish);  read: an asynchronous device-to-device copy
+ *            of one of the arrays, `bytes` being its exact size.
+ * The log, per cell: log_ids [cells, NERFTEX_SYNTH_LOG_STRIDE] int32 = k used, survivor count, the id the draw picked, the placed id, the first 16
+ * ranked ids, the first 16 survivors (-1 padded); log_dist [cells, 16] float64 = the first 16 ranked distances.                                      */
+#define NERFTEX_ERR_EXHAUSTED 3
+#define NERFTEX_SYNTH_CUT 0
+#define NERFTEX_SYNTH_BLEND 1
+#define NERFTEX_SYNTH_LOG_STRIDE 36
+#define NERFTEX_SYNTH_CANVAS 0
+#define NERFTEX_SYNTH_CANVAS_ID 1
+#define NERFTEX_SYNTH_ID_MAP 2
+#define NERFTEX_SYNTH_LOG_IDS 3
+#define NERFTEX_SYNTH_LOG_DIST 4
+#define NERFTEX_SYNTH_TBN_IDS 5
+#define NERFTEX_SYNTH_TBN 6
+#define NERFTEX_SYNTH_TOTAL_ID 7
+typedef struct nerftex_synth nerftex_synth;
+typedef struct nerftex_synth_desc {
+    const float* patches;         /* device [P, S, S, C] fp32: features, then phi_embed, then local_tbn                    */
+    const float* sample_tbn;      /* device [P, 9]                                                                         */
+    const float* picked_vertices; /* device [P, 3]                                                                         */
+    uint32_t P, S, C, match_dim;
+    uint32_t patch_size, overlap_size;
+    uint32_t output_h, output_w;  /* the requested output; the canvas is the next size that holds whole cells              */
+    uint32_t mirror_hor, mirror_vert;
+    uint32_t attenuation;         /* 3: strict_match, 1: not                                                               */
+    uint32_t max_patch_res;       /* 32 in the reference                                                                   */
+    uint32_t mode, quilt;         /* NERFTEX_SYNTH_CUT, 0                                                                  */
+    double close_threshold;       /* 0.2 in the reference                                                                  */
+    double patch_length;          /* S * grid_gap                                                                          */
+} nerftex_synth_desc;
+typedef struct nerftex_synth_view {
+    const float* canvas;          /* [side, side, C]                                                                       */
+    const int32_t* canvas_id;     /* [side, side]                                                                          */
+    const int32_t* id_map;        /* [cells_per_side^2]                                                                    */
+    const int32_t* log_ids;       /* [cells, NERFTEX_SYNTH_LOG_STRIDE]                                                     */
+    const double* log_dist;       /* [cells, 16]                                                                           */
+    const int32_t* sample_tbn_ids; /* [side, side]                                                                         */
+    const float* sample_tbn;      /* [n_total, 9]                                                                          */
+    const int32_t* total_id;      /* [n_total]                                                                             */
+    uint32_t side, cells_per_side, examples, channels, block, strip_floats, slices, n_total;
+} nerftex_synth_view;
+int nerftex_synth_create(const nerftex_synth_desc* desc, nerftex_synth** out);
+int nerftex_synth_resolve(nerftex_synth* synth, uint32_t first_patch, const double* draws, const int32_t* forced, uint32_t cell_begin, uint32_t cell_end,
+                          void* stream);
+int nerftex_synth_finish(nerftex_synth* synth, void* stream);
+int nerftex_synth_result(const nerftex_synth* synth, nerftex_synth_view* out);
+int nerftex_synth_read(const nerftex_synth* synth, uint32_t what, void* dst, size_t bytes, void* stream);
+int nerftex_synth_destroy(nerftex_synth* synth);
+
 #ifdef __cplusplus
 }
 #endif

@@ -336,3 +336,6 @@ int nerftex::patch_scan(const nerftex_knn* scan, const float* origins, uint32_t 
 
 // ---- an imported feature patch: the K = 8 search above, the reference's dual-distance resampling behind it (nerftex_patch_lookup, nerftex_patch_light_lookup) ----
 #include "patch_import.inc"
+
+// ---- the planar texture synthesized from exported patches: quilting with minimum-error boundary cuts, cell by cell (nerftex_synth_*) ----
+#include "synthesis.inc"

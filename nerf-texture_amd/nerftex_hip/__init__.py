@@ -165,6 +165,12 @@ _SIGNATURES = {
     "nerftex_knn_create": [_vp, _u32, C.POINTER(_vp)],
     "nerftex_knn_destroy": [_vp],
     "nerftex_knn_query": [_vp, _vp, _u32, _u32, _vp, _vp, _vp],
+    "nerftex_synth_create": [_vp, C.POINTER(_vp)],
+    "nerftex_synth_resolve": [_vp, _u32, _vp, _vp, _u32, _u32, _vp],
+    "nerftex_synth_finish": [_vp, _vp],
+    "nerftex_synth_result": [_vp, _vp],
+    "nerftex_synth_read": [_vp, _u32, _vp, _sz, _vp],
+    "nerftex_synth_destroy": [_vp],
     "nerftex_debug_workspace": [C.c_int, _vp, C.POINTER(_vp), C.POINTER(C.c_size_t)],
     "nerftex_raytracer_trace": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp],
 }
@@ -332,6 +338,26 @@ class SHLightDesc(C.Structure):
     _fields_ = [("brdf", _vp), ("brdf_stride", _u32), ("normals", _vp), ("dirs", _vp), ("env_shs", _vp), ("n_sh", _u32), ("n_color", _u32), ("mask", _vp),
                 ("B", _u32), ("gamma", _f32), ("flags", _u32), ("color", _vp), ("specular", _vp), ("diffuse", _vp), ("albedo", _vp), ("grad_color", _vp),
                 ("grad_brdf", _vp), ("grad_env_shs", _vp), ("scratch", _vp), ("scratch_bytes", _sz)]
+
+
+# texture synthesis (nerftex_synth_*): status codes, modes, log layout and the arrays nerftex_synth_read copies
+ERR_INVALID, ERR_HIP, ERR_EXHAUSTED = 1, 2, 3
+SYNTH_CUT, SYNTH_BLEND, SYNTH_LOG_STRIDE = 0, 1, 36
+SYNTH_CANVAS, SYNTH_CANVAS_ID, SYNTH_ID_MAP, SYNTH_LOG_IDS, SYNTH_LOG_DIST, SYNTH_TBN_IDS, SYNTH_TBN, SYNTH_TOTAL_ID = range(8)
+
+
+class SynthDesc(C.Structure):
+    """nerftex_synth_desc of include/nerftex_hip.h, field for field: what a texture synthesis is made of."""
+    _fields_ = [("patches", _vp), ("sample_tbn", _vp), ("picked_vertices", _vp), ("P", _u32), ("S", _u32), ("C", _u32), ("match_dim", _u32),
+                ("patch_size", _u32), ("overlap_size", _u32), ("output_h", _u32), ("output_w", _u32), ("mirror_hor", _u32), ("mirror_vert", _u32),
+                ("attenuation", _u32), ("max_patch_res", _u32), ("mode", _u32), ("quilt", _u32), ("close_threshold", _f64), ("patch_length", _f64)]
+
+
+class SynthView(C.Structure):
+    """nerftex_synth_view of include/nerftex_hip.h, field for field: the device arrays of a synthesis and their sizes."""
+    _fields_ = [("canvas", _vp), ("canvas_id", _vp), ("id_map", _vp), ("log_ids", _vp), ("log_dist", _vp), ("sample_tbn_ids", _vp), ("sample_tbn", _vp),
+                ("total_id", _vp), ("side", _u32), ("cells_per_side", _u32), ("examples", _u32), ("channels", _u32), ("block", _u32), ("strip_floats", _u32),
+                ("slices", _u32), ("n_total", _u32)]
 
 
 EXPORTS = ["nerftex_last_error", "nerftex_version", "nerftex_tune_get", "nerftex_workspace_slots_touched", "nerftex_curved_field_infer_scratch_bytes",

@@ -1119,6 +1119,17 @@ class CurvedField(torch.nn.Module):
             return patches.export_field(self, sample_points, sample_normals, patches_per_chunk=patches_per_chunk, **kw)
         return patches._export_field_reference(self, sample_points, sample_normals, **kw)
 
+    def synthesize_field(self, result, output_size, *, rescale=None, **kw):
+        """The step between export and import (the reference's offline patch_matching_and_quilting.py): `synthesis.synthesize_texture` over what
+        `export_field` returned, on this field's device, and `import_field` of the map it makes -- with the four light maps if this field reads a
+        fine normal, without them otherwise.  -> (texture, log) as synthesize_texture returns them.  kw: its keywords."""
+        from . import synthesis
+
+        kw.setdefault("light_maps", self._lit())
+        texture, log = synthesis.synthesize_texture(result, output_size, device=self.sigma_net.weights.device, **kw)
+        self.import_field(rescale=rescale, **texture)
+        return texture, log
+
     def switch_import(self):
         """network_curvedfield.py:519-521: between the imported map and the field's own mesh and table (the map is kept)."""
         if self.features_imported is None:

@@ -517,6 +517,9 @@ def main():
     if "--import-patch-sh-only" in sys.argv:
         import_patch_sh_goldens()
         return
+    if "--synthesis-only" in sys.argv:
+        synthesis_goldens()
+        return
     if "--sh-light-only" in sys.argv:
         sh_light_goldens()
         sh_field_goldens()
@@ -1843,6 +1846,157 @@ def import_shape_sh_goldens():
     finally:
         torch.nn.functional.grid_sample = real_grid_sample
     np.savez_compressed(os.path.join(OUT, "ref_python_import_shape_sh.npz"), **out)
+    new = [os.path.join(r, n) for r, _, names in os.walk(REF) for n in names if os.lstat(os.path.join(r, n)).st_mtime >= started]
+    assert not new, "files appeared under the reference tree:\n" + "\n".join(new[:20])
+
+
+# the two cases of ref_python_synthesis.npz: patch count, patch side, channels (features + phi_embed + local_tbn), max_patch_res, mirrors, output side,
+# patch_length, and the seed of both the inputs and the reference's random streams
+SYNTHESIS_CASES = {
+    "A": dict(P=40, S=12, match_dim=16, phi_dim=8, max_patch_res=4, mirrors=False, output=30, patch_length=1.0, seed=2),
+    "B": dict(P=24, S=13, match_dim=16, phi_dim=8, max_patch_res=4, mirrors=True, output=30, patch_length=7.5, seed=10),
+}
+
+
+def synthesis_inputs(case):
+    """The random inputs of one synthesis case: fp32 values, as an export holds them.  The patch values are multiples of 1 / 256 in [-0.5, 0.5): eight
+    random bits a value keep the compressed fixture small."""
+    rng = np.random.default_rng(1000 + case["seed"])
+    P, S, C = case["P"], case["S"], case["match_dim"] + case["phi_dim"] + 9
+    patches = (rng.integers(-128, 128, (P, S, S, C)) / 256).astype(np.float32)
+    sample_tbn = (np.eye(3, dtype=np.float32).reshape(9) + rng.normal(0, 0.3, (P, 9))).astype(np.float32)
+    picked_vertices = rng.uniform(-1, 1, (P, 3)).astype(np.float32)
+    return patches, sample_tbn, picked_vertices
+
+
+def run_reference_synthesis(case, patches=None, sample_tbn=None, picked_vertices=None):
+    """One run of the reference's patchBasedTextureSynthesis (patch_matching_and_quilting.py) with the options of its __main__ -- mode 'Cut',
+    coarse_KDtree, rotate=False, strict_match, picked_vertices given -- on the CPU, and the closing lines of __main__ (:485-511) behind it.
+    skimage is absent: block_reduce is stubbed as what its defaults compute, the zero-padded block sum.  visualize, saveParams, the directory check
+    and the PCA of the snapshots do nothing.  `random` and `np.random` are seeded; np.random.choice is wrapped by a recorder that calls through."""
+    import random
+
+    os.environ.setdefault("MPLBACKEND", "Agg")
+
+    def block_reduce(a, block_size):
+        a = np.asarray(a)
+        pad = [(0, (-s) % b) for s, b in zip(a.shape, block_size)]
+        a = np.pad(a, pad)
+        shape = []
+        for s, b in zip(a.shape, block_size):
+            shape += [s // b, b]
+        return a.reshape(shape).sum(axis=tuple(range(1, 2 * a.ndim, 2)))
+
+    _stub("skimage")
+    _stub("skimage.measure", block_reduce=block_reduce)
+    if REF not in sys.path:
+        sys.path.insert(0, REF)
+    import patch_matching_and_quilting as ref
+
+    ref.get_transform = lambda data, dim: None
+    if patches is None:
+        patches, sample_tbn, picked_vertices = synthesis_inputs(case)
+    S, match_dim = case["S"], case["match_dim"]
+    patch_size = int(S / 4)
+    if (S - patch_size) % 2 == 1:
+        patch_size -= 1
+    overlap = int((S - patch_size) / 2)
+    record = dict(k=[], survivors=[], distances=[], probabilities=[], chosen=[], draws=[])
+
+    class Recorded(ref.patchBasedTextureSynthesis):
+        def checkIfDirectoryExists(self):
+            pass
+
+        def saveParams(self):
+            pass
+
+        def visualize(self):
+            pass
+
+        def initKDtrees(self):
+            self.max_patch_res = case["max_patch_res"]
+            return super().initKDtrees()
+
+        def resolveNext(self):
+            self.ks = []
+            super().resolveNext()
+            record["k"].append(self.ks[-1])
+
+        def findMostSimilarPatches(self, top, left, coord, in_k=16):
+            self.ks.append(in_k)
+            return super().findMostSimilarPatches(top, left, coord, in_k=in_k)
+
+        def distances2probability(self, distances, truncation, attenuation):
+            record["distances"].append(np.array(distances, dtype=np.float64))
+            p = super().distances2probability(distances, truncation, attenuation)
+            record["probabilities"].append(np.array(p, dtype=np.float64))
+            return p
+
+    real_choice = np.random.choice
+
+    def recording_choice(a, size=None, replace=True, p=None):
+        peek = np.random.RandomState()
+        peek.set_state(np.random.get_state())
+        record["draws"].append(float(peek.random_sample()))
+        out = real_choice(a, size, replace, p)
+        record["survivors"].append(np.array(a, dtype=np.int64))
+        record["chosen"].append(int(out[0]))
+        return out
+
+    random.seed(case["seed"])
+    np.random.seed(case["seed"])
+    np.random.choice = recording_choice
+    try:
+        mirrors = case["mirrors"]
+        pbts = Recorded(patches.astype(np.float64), "unused/", [case["output"], case["output"]], patch_size, overlap, in_windowStep=5, in_mirror_hor=mirrors,
+                        in_mirror_vert=mirrors, rotate=False, in_shapshots=True, picked_vertices=picked_vertices.astype(np.float64), patch_length=case["patch_length"],
+                        coarse_KDtree=True, sample_tbn=sample_tbn.astype(np.float64), match_dim=match_dim, strict_match=True, mode="Cut")
+        canvas, canvas_id = pbts.resolveAll()
+    finally:
+        np.random.choice = real_choice
+    # __main__ :485-511
+    canvas_id = np.array(canvas_id, dtype=np.int32)
+    raw_id = canvas_id.copy()
+    total_id = np.sort(np.unique(canvas_id.reshape([-1])))
+    index = {total_id[i]: i for i in range(total_id.shape[0])}
+    for i in range(canvas_id.shape[0]):
+        for j in range(canvas_id.shape[1]):
+            canvas_id[i, j] = index[canvas_id[i, j]]
+    return dict(record=record, canvas=pbts.canvas, canvas_id=raw_id, id_map=pbts.idMap.astype(np.int32), total_id=total_id.astype(np.int32),
+                sample_tbn=pbts.example_tbn[total_id], sample_tbn_ids=canvas_id, examples=pbts.examplePatches.shape[0], block=pbts.block_size,
+                patch_size=patch_size, overlap_size=overlap, inputs=(patches, sample_tbn, picked_vertices))
+
+
+def synthesis_goldens():
+    """ref_python_synthesis.npz: the reference's own texture synthesis class run on the two cases of SYNTHESIS_CASES (see run_reference_synthesis).
+    Stored per case: the inputs, the first patch, the draws the seeded stream gave, per cell k, the survivors, their distances, the probabilities
+    and the chosen id (ragged lists, flattened with the survivor counts beside them), the final canvas (float64), canvas_id and idMap, and the
+    closing arrays.  Reads nothing; writes this one file."""
+    import time
+
+    started = time.time()
+    out = {}
+    for name, case in SYNTHESIS_CASES.items():
+        r = run_reference_synthesis(case)
+        rec = r["record"]
+        patches, sample_tbn, picked_vertices = r["inputs"]
+        counts = np.array([len(s) for s in rec["survivors"]], dtype=np.int32)
+        cells = r["id_map"].size
+        assert len(rec["chosen"]) == cells - 1 == len(rec["draws"]) == len(rec["k"]) and r["canvas_id"].min() >= 0
+        assert np.array_equal(np.array(rec["chosen"]), r["id_map"].reshape(-1)[1:])
+        pre = name + "_"
+        out.update({pre + "patches": patches, pre + "sample_tbn_in": sample_tbn, pre + "picked_vertices": picked_vertices,
+                    pre + "options": np.array([case["match_dim"], case["phi_dim"], case["max_patch_res"], int(case["mirrors"]), case["output"], case["seed"],
+                                               r["patch_size"], r["overlap_size"], r["block"], r["examples"]], dtype=np.int64),
+                    pre + "patch_length": np.float64(case["patch_length"]), pre + "first_patch": np.int32(r["id_map"][0, 0]),
+                    pre + "draws": np.array(rec["draws"]), pre + "k": np.array(rec["k"], dtype=np.int32), pre + "survivor_counts": counts,
+                    pre + "survivors": np.concatenate(rec["survivors"]).astype(np.int32), pre + "distances": np.concatenate(rec["distances"]),
+                    pre + "probabilities": np.concatenate(rec["probabilities"]), pre + "chosen": np.array(rec["chosen"], dtype=np.int32),
+                    pre + "canvas": r["canvas"], pre + "canvas_id": r["canvas_id"], pre + "id_map": r["id_map"], pre + "total_id": r["total_id"],
+                    pre + "sample_tbn": r["sample_tbn"], pre + "sample_tbn_ids": r["sample_tbn_ids"].astype(np.int32)})
+        print("ref_python_synthesis.npz: case", name, "canvas", r["canvas"].shape, "examples", r["examples"], "k per cell", rec["k"], "survivors per cell",
+              counts.tolist())
+    np.savez_compressed(os.path.join(OUT, "ref_python_synthesis.npz"), **out)
     new = [os.path.join(r, n) for r, _, names in os.walk(REF) for n in names if os.lstat(os.path.join(r, n)).st_mtime >= started]
     assert not new, "files appeared under the reference tree:\n" + "\n".join(new[:20])
 
