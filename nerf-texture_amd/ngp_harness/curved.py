@@ -18,6 +18,8 @@ xatlas, open3d, trimesh).
                      normal net or the light model, the planar map comes with its phi_embed, local_tbn and sample_tbn maps (:670-675);
   CurvedFieldLookup  round 1's minimal chain (analytic normals -> traces -> hash lookup), kept for its test.
 """
+from typing import NamedTuple, Optional
+
 import numpy as np
 import torch
 
@@ -452,6 +454,15 @@ class _TruncExp(torch.autograd.Function):  # tools/activation.py:5-17
         return g * torch.exp(x.clamp(-15, 15))
 
 
+class _SourceLookup(NamedTuple):
+    """What CurvedField._source_lookup hands embed(), density() and forward(), whichever source is imported."""
+    h_mask: torch.Tensor
+    normal: Optional[torch.Tensor]  # raw; None: the planar map's (0, 0, 1)
+    xin: torch.Tensor
+    phi: Optional[torch.Tensor] = None  # lit only
+    frames: tuple = ()  # lit only, in `_rotate_fine`'s order
+
+
 class _CurvedPack(torch.autograd.Function):
     """[x_embed | half(z_embed) | ones] -- the sigma net's padded input (tools/map.py:641 `torch.cat` + tcnn's padding with ones) as one launch."""
 
@@ -777,25 +788,34 @@ class CurvedField(torch.nn.Module):
         K = max(1, min(int(self.K_for_uv), int(self.shape_projector.mesh_vertices.shape[0])))
         return K, scale, float(self.sdf_offset), float(self.uv_utilize_rate), float(self.h_threshold)
 
+    # what the lookup kernels write per sample, by name: (trailing shape, dtype)
+    _LOOKUP_BUFFERS = {"p_uv": ((2,), torch.float32), "sdf": ((), torch.float32), "mask": ((), torch.uint8), "normal": ((3,), torch.float32),
+                       "face": ((), torch.int64), "xin": ((48,), torch.float16), "phi": ((8,), torch.float32), "ids": ((), torch.int32),
+                       "frame": ((9,), torch.float32), "idx": ((8,), torch.int32), "dis": ((8,), torch.float32), "weights": ((8,), torch.float32)}
+
+    @classmethod
+    def _lookup_buffers(cls, x, *names):
+        """The lookup wrappers' one allocator: an uninitialised [N, ...] output on x's device per name of `_LOOKUP_BUFFERS`."""
+        return [torch.empty(x.shape[0], *cls._LOOKUP_BUFFERS[n][0], dtype=cls._LOOKUP_BUFFERS[n][1], device=x.device) for n in names]
+
+    def _shape_query(self, x, neighbours):
+        """What the two shape lookups start from: the samples as the kernels read them, their neighbours on the imported mesh (default: the
+        library's search) and the arguments the two entries share, the tracer .. the UV table's face count."""
+        x, p, uv = x.detach().float().contiguous(), self.shape_projector, self.shape_face_uv
+        idx, dis = p.knn(x, self._shape_scalars()[0]) if neighbours is None else neighbours
+        idx, dis = idx.int().contiguous(), dis.float().contiguous()
+        return x, (p.tracer._handle, ptr(x), ptr(idx), ptr(dis), x.shape[0], idx.shape[1], ptr(p.mesh_vertices), ptr(p.vertex_normals),
+                   p.mesh_vertices.shape[0], ptr(uv), uv.shape[0]), (idx, dis)
+
     @torch.no_grad()
     def _shape_lookup(self, x, neighbours=None):
         """nerftex_knn_query + nerftex_shape_lookup: -> p_uv [N,2], sdf [N], h_mask [N] bool, normal [N,3] (raw), face [N], xin [N,48] half."""
-        from nerftex_hip import check, lib, ptr, stream
+        from nerftex_hip import check, lib, stream
 
-        x = x.detach().float().contiguous()
-        N, dev, f, p = x.shape[0], x.device, self.features_imported, self.shape_projector
-        K, scale, off, rate, h = self._shape_scalars()
-        idx, dis = p.knn(x, K) if neighbours is None else neighbours
-        idx, dis = idx.int().contiguous(), dis.float().contiguous()
-        p_uv = torch.empty(N, 2, device=dev)
-        sdf = torch.empty(N, device=dev)
-        mask = torch.empty(N, dtype=torch.uint8, device=dev)
-        normal = torch.empty(N, 3, device=dev)
-        face = torch.empty(N, dtype=torch.int64, device=dev)
-        xin = torch.empty(N, 48, dtype=torch.float16, device=dev)
-        check(lib.nerftex_shape_lookup(p.tracer._handle, ptr(x), ptr(idx), ptr(dis), N, idx.shape[1], ptr(p.mesh_vertices), ptr(p.vertex_normals),
-                                       p.mesh_vertices.shape[0], ptr(self.shape_face_uv), self.shape_face_uv.shape[0], ptr(f), f.shape[0], f.shape[1], scale, off,
-                                       rate, h, int(self.multires), ptr(p_uv), ptr(sdf), ptr(mask), ptr(normal), ptr(face), ptr(xin), stream()))
+        x, head, _keep = self._shape_query(x, neighbours)
+        f, (_, scale, off, rate, h) = self.features_imported, self._shape_scalars()
+        p_uv, sdf, mask, normal, face, xin = out = self._lookup_buffers(x, "p_uv", "sdf", "mask", "normal", "face", "xin")
+        check(lib.nerftex_shape_lookup(*head, ptr(f), f.shape[0], f.shape[1], scale, off, rate, h, int(self.multires), *map(ptr, out), stream()))
         return p_uv, sdf, mask.bool(), normal, face, xin
 
     def _shape_embed_reference(self, x, neighbours=None, details=False):
@@ -821,9 +841,7 @@ class CurvedField(torch.nn.Module):
         bary = points_to_barycentric(p.mesh_vertices[vertex_idx], p_sur)
         uv = (self.shape_uvs[vertex_idx] * bary.unsqueeze(-1)).sum(-2)
         p_uv = uv * rate
-        image = self.features_imported.to(x.device).permute(2, 1, 0).unsqueeze(0)
-        x_embed = torch.nn.functional.grid_sample(image, p_uv[None, None], align_corners=True, padding_mode="zeros")[0, :, 0].permute(1, 0)
-        embed = torch.cat([x_embed, freq_encode(sdf, self.multires)], dim=-1)
+        embed = torch.cat([self._sample_map(self.features_imported, p_uv).permute(1, 0), freq_encode(sdf, self.multires)], dim=-1)
         normal_coarse = normal / (normal.norm(dim=-1, keepdim=True) + 1e-5)
         if details:
             return embed, normal_coarse, h_mask, p_uv, sdf[..., 0], normal, face
@@ -832,37 +850,22 @@ class CurvedField(torch.nn.Module):
     def _shape_light_fused(self, x):
         """_import_light_fused() for the maps on the imported mesh: the lit shape lookup serves the default shapes under fp16 autocast, once the
         four lit maps and the new mesh's frames are there."""
-        return (x.is_cuda and self._lit() and self._shape_active() and self.phi_embed_imported is not None and self.shape_face_tbn is not None
-                and self.encoder_var is None and self.in_dim == 41 and self.in_pad == 48 and self.geo_feat_dim == 15 and self.multires == 12
-                and self.sigma_net.dtype == torch.float16 and torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.float16)
+        return (self._lit() and self._shape_active() and self.phi_embed_imported is not None and self.shape_face_tbn is not None
+                and self._sigma_fused(x))
 
     @torch.no_grad()
     def _shape_light_lookup(self, x, neighbours=None):
         """nerftex_knn_query + nerftex_shape_light_lookup: -> p_uv [N,2], sdf [N], h_mask [N] bool, normal [N,3] (raw), face [N], xin [N,48] half,
         phi [N,8] fp32, id [N] int32, local_tbn, sample_tbn_inv, new_tbn [N,3,3]."""
-        from nerftex_hip import check, lib, ptr, stream
+        from nerftex_hip import check, lib, stream
 
-        x = x.detach().float().contiguous()
-        N, dev, f, p = x.shape[0], x.device, self.features_imported, self.shape_projector
-        K, scale, off, rate, h = self._shape_scalars()
-        idx, dis = p.knn(x, K) if neighbours is None else neighbours
-        idx, dis = idx.int().contiguous(), dis.float().contiguous()
-        p_uv = torch.empty(N, 2, device=dev)
-        sdf = torch.empty(N, device=dev)
-        mask = torch.empty(N, dtype=torch.uint8, device=dev)
-        normal = torch.empty(N, 3, device=dev)
-        face = torch.empty(N, dtype=torch.int64, device=dev)
-        xin = torch.empty(N, 48, dtype=torch.float16, device=dev)
-        phi = torch.empty(N, 8, device=dev)
-        ids = torch.empty(N, dtype=torch.int32, device=dev)
-        local, sample, new = (torch.empty(N, 9, device=dev) for _ in range(3))
-        rows = self.sample_inv_rows_imported
-        check(lib.nerftex_shape_light_lookup(p.tracer._handle, ptr(x), ptr(idx), ptr(dis), N, idx.shape[1], ptr(p.mesh_vertices), ptr(p.vertex_normals),
-                                             p.mesh_vertices.shape[0], ptr(self.shape_face_uv), self.shape_face_uv.shape[0], ptr(self.shape_face_tbn),
-                                             self.shape_face_tbn.shape[0], ptr(f), ptr(self.phi_embed_imported), ptr(self.frame_map_imported), ptr(rows),
-                                             f.shape[0], f.shape[1], rows.shape[0], scale, off, rate, h, int(self.multires), ptr(p_uv), ptr(sdf), ptr(mask),
-                                             ptr(normal), ptr(face), ptr(xin), ptr(phi), ptr(ids), ptr(local), ptr(sample), ptr(new), stream()))
-        return p_uv, sdf, mask.bool(), normal, face, xin, phi, ids, local.view(N, 3, 3), sample.view(N, 3, 3), new.view(N, 3, 3)
+        x, head, _keep = self._shape_query(x, neighbours)
+        f, rows, frames, (_, scale, off, rate, h) = self.features_imported, self.sample_inv_rows_imported, self.shape_face_tbn, self._shape_scalars()
+        out = self._lookup_buffers(x, "p_uv", "sdf", "mask", "normal", "face", "xin", "phi", "ids", "frame", "frame", "frame")
+        check(lib.nerftex_shape_light_lookup(*head, ptr(frames), frames.shape[0], ptr(f), ptr(self.phi_embed_imported), ptr(self.frame_map_imported), ptr(rows),
+                                             f.shape[0], f.shape[1], rows.shape[0], scale, off, rate, h, int(self.multires), *map(ptr, out), stream()))
+        p_uv, sdf, mask, normal, face, xin, phi, ids, *tbn = out
+        return (p_uv, sdf, mask.bool(), normal, face, xin, phi, ids) + tuple(t.view(x.shape[0], 3, 3) for t in tbn)
 
     def _shape_light_embed_reference(self, x, neighbours=None, details=False):
         """The 'shape' branch with `pred_normal` op by op (tools/map.py:693-707, :722-730): `_shape_embed_reference`'s expressions, the four
@@ -870,19 +873,9 @@ class CurvedField(torch.nn.Module):
         three rotations.  -> embed [N,41] fp32, normal_coarse, h_mask, normal_fine (details: + p_uv, sdf, face, the sampled phi_embed,
         local_tbn, id, sample_tbn_inv rows and new_tbn)."""
         embed, normal_coarse, h_mask, p_uv, sdf, _, face = self._shape_embed_reference(x, neighbours=neighbours, details=True)
-        x = x.float()
-        grid = p_uv[None, None]
-
-        def image(m):  # [H, W, C] -> [1, C, W, H], as `_import_embed_reference`
-            return m.to(x.device).permute(2, 1, 0).unsqueeze(0)
-
-        gs = torch.nn.functional.grid_sample
-        ids = gs(image(self.sample_tbn_ids_imported[..., None]), grid, mode="nearest", align_corners=True, padding_mode="zeros")[0, 0, 0].long()
-        sample_tbn_inv = self.sample_tbn_inv_imported.to(x.device)[ids]
-        local_tbn = gs(image(self.local_tbn_imported), grid, mode="nearest", align_corners=True, padding_mode="zeros")[0, :, 0].permute(1, 0).reshape(-1, 3, 3)
-        phi = gs(image(self.phi_embed_imported), grid, align_corners=True, padding_mode="zeros")[0, :, 0].permute(1, 0)
+        phi, local_tbn, ids, sample_tbn_inv = self._lit_maps_reference(p_uv)
         face0 = torch.where(face == -1, torch.zeros_like(face), face)
-        new_tbn = self.shape_face_tbn.to(x.device)[face0, :9].reshape(-1, 3, 3)
+        new_tbn = self.shape_face_tbn.to(p_uv.device)[face0, :9].reshape(-1, 3, 3)
         x_embed, z_embed = embed[:, :self.encoder.output_dim], embed[:, self.encoder.output_dim:]
         local = self.normal_net(phi_embed=phi, z_embed=z_embed, x_embed=x_embed)
         fine = self._rotate_fine(local, local_tbn, sample_tbn_inv, new_tbn)
@@ -979,31 +972,24 @@ class CurvedField(torch.nn.Module):
     def _patch_fused(self, x):
         """Whether the patch lookup kernel serves this call: a neighbour grid on the device, the default shapes under fp16 autocast without the
         probabilistic table (the static light model: unless `fused_glue` is off)."""
-        return (x.is_cuda and self._patch_active() and self._patch_knn is not None and self.encoder_var is None and self.in_dim == 41 and self.in_pad == 48
-                and self.geo_feat_dim == 15 and self.multires == 12 and self.sigma_net.dtype == torch.float16 and torch.is_autocast_enabled()
-                and torch.get_autocast_dtype("cuda") == torch.float16 and (self._lit() or getattr(self, "fused_glue", True))
+        return (self._patch_active() and self._patch_knn is not None and self._sigma_fused(x) and (self._lit() or getattr(self, "fused_glue", True))
                 and self._on_device_of(x, self.features_imported, self.patch_geom))
 
     @torch.no_grad()
     def _patch_lookup(self, x, lit=False):
         """nerftex_patch_lookup (lit: nerftex_patch_light_lookup): -> sdf [N], h_mask [N] bool, normal [N,3] (raw), xin [N,48] half, idx [N,8],
         dis [N,8] (the search's), weights [N,8] (+ lit: phi [N,8] fp32, local_tbn [N,3,3])."""
-        from nerftex_hip import check, lib, ptr, stream
+        from nerftex_hip import check, lib, stream
 
         x = x.detach().float().contiguous()
-        N, dev, f = x.shape[0], x.device, self.features_imported
-        sdf = torch.empty(N, device=dev)
-        mask = torch.empty(N, dtype=torch.uint8, device=dev)
-        normal = torch.empty(N, 3, device=dev)
-        xin = torch.empty(N, 48, dtype=torch.float16, device=dev)
-        idx = torch.empty(N, 8, dtype=torch.int32, device=dev)
-        dis, weights = torch.empty(N, 8, device=dev), torch.empty(N, 8, device=dev)
+        N, f = x.shape[0], self.features_imported
+        sdf, mask, normal, xin, idx, dis, weights = out = self._lookup_buffers(x, "sdf", "mask", "normal", "xin", "idx", "dis", "weights")
         head = (self._patch_knn.value, ptr(x), ptr(self.patch_geom), ptr(f))
-        tail = (f.shape[0], float(self.h_threshold), int(self.multires), N, ptr(sdf), ptr(mask), ptr(normal), ptr(xin), ptr(idx), ptr(dis), ptr(weights))
+        tail = (f.shape[0], float(self.h_threshold), int(self.multires), N, *map(ptr, out))
         if not lit:
             check(lib.nerftex_patch_lookup(*head, *tail, stream()))
             return sdf, mask.bool(), normal, xin, idx, dis, weights
-        phi, tbn = torch.empty(N, 8, device=dev), torch.empty(N, 9, device=dev)
+        phi, tbn = self._lookup_buffers(x, "phi", "frame")
         check(lib.nerftex_patch_light_lookup(*head, ptr(self.patch_lit), *tail, ptr(phi), ptr(tbn), stream()))
         return sdf, mask.bool(), normal, xin, idx, dis, weights, phi, tbn.view(N, 3, 3)
 
@@ -1071,22 +1057,9 @@ class CurvedField(torch.nn.Module):
             phi = (weights.unsqueeze(-1) * self.patch_phi_embed.to(x.device)[idx]).sum(-2)
             local_tbn = (weights.unsqueeze(-1).unsqueeze(-1) * self.patch_local_tbn.to(x.device)[idx].reshape(*idx.shape, 3, 3)).sum(-3)
             local = self.normal_net(phi_embed=phi, z_embed=z_embed, x_embed=x_embed)
-            fine = torch.einsum("nba,nb->na", local_tbn, local)
-            out += (fine / (fine.norm(dim=-1, keepdim=True) + 1e-5),)
+            out += (self._rotate_fine(local, local_tbn),)
             more += (phi, local_tbn)
         return out + more if details else out
-
-    def _patch_embed(self, x, with_fine_normal=False):
-        """embed() over the imported patch: the lookup kernel where it applies (`_patch_fused`), the op-by-op route elsewhere."""
-        if not self._patch_fused(x):
-            return self._patch_embed_reference(x, with_fine_normal=with_fine_normal)
-        if not with_fine_normal:
-            _, h_mask, normal, xin = self._patch_lookup(x)[:4]
-            return xin[:, :self.in_dim], normal / (normal.norm(dim=-1, keepdim=True) + 1e-5), h_mask
-        _, h_mask, normal, xin, _, _, _, phi, local_tbn = self._patch_lookup(x, lit=True)
-        local = self.normal_net(phi_embed=phi, z_embed=xin[:, 16:self.in_dim], x_embed=xin[:, :16])
-        fine = torch.einsum("nba,nb->na", local_tbn, local)
-        return xin[:, :self.in_dim], normal / (normal.norm(dim=-1, keepdim=True) + 1e-5), h_mask, fine / (fine.norm(dim=-1, keepdim=True) + 1e-5)
 
     # ---- the trained field exported as texture patches (NeRFNetwork.export_field -> MeshFeatureField.sample_patches, tools/map.py:951-1128) ----
 
@@ -1173,31 +1146,26 @@ class CurvedField(torch.nn.Module):
             p = self.shape_projector
             stamp = (("import-shape", f.data_ptr(), tuple(f.shape), p._knn.value, p.tracer._handle.value, p.mesh_vertices.data_ptr(), p.vertex_normals.data_ptr(),
                       self.shape_face_uv.data_ptr()) + self._shape_scalars() + (self._import_version,))
-            if self._lit() and self.phi_embed_imported is not None and getattr(self, "shape_face_tbn", None) is not None:  # the lit field's maps and frames
-                stamp += tuple((m.data_ptr(), tuple(m.shape)) for m in (self.phi_embed_imported, self.local_tbn_imported, self.sample_tbn_inv_imported,
-                                                                        self.sample_tbn_ids_imported, self.frame_map_imported, self.sample_inv_rows_imported,
-                                                                        self.shape_face_tbn))
+            if getattr(self, "shape_face_tbn", None) is not None:  # the lit field's maps and frames
+                stamp += self._lit_maps_stamp(self.shape_face_tbn)
             return stamp
-        stamp = ("import", f.data_ptr(), tuple(f.shape)) + self._import_scalars() + (self._import_version,)
-        if self._lit() and self.phi_embed_imported is not None:  # the lit field's maps: their storage and shapes
-            stamp += tuple((m.data_ptr(), tuple(m.shape)) for m in (self.phi_embed_imported, self.local_tbn_imported, self.sample_tbn_inv_imported,
-                                                                    self.sample_tbn_ids_imported, self.frame_map_imported, self.sample_inv_rows_imported))
-        return stamp
+        return ("import", f.data_ptr(), tuple(f.shape)) + self._import_scalars() + (self._import_version,) + self._lit_maps_stamp()
+
+    def _lit_maps_stamp(self, *more):
+        """_import_stamp()'s share of the lit field's maps (and `more`): their storage and shapes; nothing for a field that reads no fine normal."""
+        if not (self._lit() and self.phi_embed_imported is not None):
+            return ()
+        return tuple((m.data_ptr(), tuple(m.shape)) for m in (self.phi_embed_imported, self.local_tbn_imported, self.sample_tbn_inv_imported,
+                                                              self.sample_tbn_ids_imported, self.frame_map_imported, self.sample_inv_rows_imported) + more)
 
     @torch.no_grad()
     def _import_lookup(self, x):
         """nerftex_planar_lookup: -> p_uv [N,2], sdf [N], h_mask [N] bool, xin [N,48] half (the sigma net's padded input)."""
-        from nerftex_hip import check, lib, ptr, stream
+        from nerftex_hip import check, lib, stream
 
-        x = x.detach().float().contiguous()
-        N, dev, f = x.shape[0], x.device, self.features_imported
-        p_uv = torch.empty(N, 2, device=dev)
-        sdf = torch.empty(N, device=dev)
-        mask = torch.empty(N, dtype=torch.uint8, device=dev)
-        xin = torch.empty(N, 48, dtype=torch.float16, device=dev)
-        mode, p0, p1, h0, h1, off, h = self._import_scalars()
-        check(lib.nerftex_planar_lookup(ptr(x), ptr(f), f.shape[0], f.shape[1], mode, p0, p1, h0, h1, off, h, int(self.multires), N, ptr(p_uv), ptr(sdf),
-                                        ptr(mask), ptr(xin), stream()))
+        x, f = x.detach().float().contiguous(), self.features_imported
+        p_uv, sdf, mask, xin = out = self._lookup_buffers(x, "p_uv", "sdf", "mask", "xin")
+        check(lib.nerftex_planar_lookup(ptr(x), ptr(f), f.shape[0], f.shape[1], *self._import_scalars(), int(self.multires), x.shape[0], *map(ptr, out), stream()))
         return p_uv, sdf, mask.bool(), xin
 
     def _import_normal(self, x, normalised):
@@ -1206,10 +1174,24 @@ class CurvedField(torch.nn.Module):
         n[:, 2] = 1.0
         return n / (n.norm(dim=-1, keepdim=True) + 1e-5) if normalised else n
 
-    def _import_embed_reference(self, x):
-        """The import branch op by op, the reference's expressions (tools/map.py:649-668): -> embed [N,41] fp32, normal_coarse, h_mask.
-        The divisors are tensors: a device division by a Python scalar is a multiplication by its reciprocal, the reference's (as executed) is
-        a true division."""
+    def _sample_map(self, m, p_uv, mode="bilinear"):
+        """grid_sample of the map m [H, W, C] at p_uv [N, 2] -> [C, N].  [H, W, C] -> [1, C, W, H]: the grid's first coordinate indexes the last
+        axis, so u runs along the map's first axis (tools/map.py:915-919)."""
+        image = m.to(p_uv.device).permute(2, 1, 0).unsqueeze(0)
+        return torch.nn.functional.grid_sample(image, p_uv[None, None], mode=mode, align_corners=True, padding_mode="zeros")[0, :, 0]
+
+    def _lit_maps_reference(self, p_uv):
+        """The four reads of the `pred_normal` part at p_uv (tools/map.py:670-675), the planar map's and the imported mesh's alike: -> the
+        sampled phi_embed [N,8], local_tbn [N,3,3] and id [N] (nearest texel), and the inverted patch frames' rows `id` [N,3,3]."""
+        ids = self._sample_map(self.sample_tbn_ids_imported[..., None], p_uv, mode="nearest")[0].long()
+        sample_tbn_inv = self.sample_tbn_inv_imported.to(p_uv.device)[ids]
+        local_tbn = self._sample_map(self.local_tbn_imported, p_uv, mode="nearest").permute(1, 0).reshape(-1, 3, 3)
+        return self._sample_map(self.phi_embed_imported, p_uv).permute(1, 0), local_tbn, ids, sample_tbn_inv
+
+    def _import_embed_reference(self, x, details=False):
+        """The import branch op by op, the reference's expressions (tools/map.py:649-668): -> embed [N,41] fp32, normal_coarse, h_mask (details:
+        + p_uv).  The divisors are tensors: a device division by a Python scalar is a multiplication by its reciprocal, the reference's (as
+        executed) is a true division."""
         x = x.float()
         b0, b1 = (torch.tensor(b, dtype=torch.float32, device=x.device) for b in self.bounds)
         if self.rescale:
@@ -1222,70 +1204,71 @@ class CurvedField(torch.nn.Module):
         h_mask = sdf[..., 0].abs() < self.h_threshold
         h_mask = torch.logical_and(h_mask, (p_sur >= -1.0).all(dim=-1))
         h_mask = torch.logical_and(h_mask, (p_sur <= 1.0).all(dim=-1))
-        # [H, W, C] -> [1, C, W, H]: the grid's first coordinate indexes the last axis, so u runs along the map's first axis (:915-919)
-        image = self.features_imported.to(x.device).permute(2, 1, 0).unsqueeze(0)
-        x_embed = torch.nn.functional.grid_sample(image, p_sur[None, None], align_corners=True, padding_mode="zeros")[0, :, 0].permute(1, 0)
-        embed = torch.cat([x_embed, freq_encode(sdf, self.multires)], dim=-1)
-        return embed, self._import_normal(x, True), h_mask
+        embed = torch.cat([self._sample_map(self.features_imported, p_sur).permute(1, 0), freq_encode(sdf, self.multires)], dim=-1)
+        return (embed, self._import_normal(x, True), h_mask) + ((p_sur,) if details else ())
+
+    def _sigma_fused(self, x=None):
+        """The one shape predicate every lookup and chain below asks: the sigma side has the default shapes under fp16 autocast without the
+        probabilistic table, and the samples x are on a device (None: a question about the field alone, `_glue_fused()`)."""
+        return ((x is None or x.is_cuda) and self.encoder_var is None and self.in_dim == 41 and self.in_pad == 48 and self.geo_feat_dim == 15
+                and self.multires == 12 and self.sigma_net.dtype == torch.float16 and torch.is_autocast_enabled()
+                and torch.get_autocast_dtype("cuda") == torch.float16)
 
     def _import_fused(self, x):
-        return x.is_cuda and self._glue_fused() and self.multires == 12 and self.sigma_net.dtype == torch.float16
+        """Whether the lookup kernels serve the static field's imported map: what the glue launches behind them ask."""
+        return self._glue_fused(x)
 
     def _import_light_fused(self, x):
-        """_import_fused() for the lit field (which has no colour net for _glue_fused() to ask about): the planar lookups serve the default
-        shapes under fp16 autocast without the probabilistic table, once the four maps are there."""
-        return (x.is_cuda and self._lit() and self.phi_embed_imported is not None and not self._shape_active() and self.encoder_var is None
-                and self.in_dim == 41 and self.in_pad == 48 and self.geo_feat_dim == 15 and self.multires == 12 and self.sigma_net.dtype == torch.float16
-                and torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.float16)
+        """_import_fused() for the lit field (which has no colour net for _glue_fused() to ask about): the planar lookups serve it once the four
+        maps are there."""
+        return self._lit() and self.phi_embed_imported is not None and not self._shape_active() and self._sigma_fused(x)
+
+    def _source_fused(self, x, lit=False):
+        """Whether the lookup kernels serve the ACTIVE imported source for this call (lit: with the reads the fine normal needs)."""
+        if self._patch_active():
+            return self._patch_fused(x)
+        lit_reads = self._shape_light_fused(x) if self._shape_active() else self._import_light_fused(x)
+        return lit_reads or (not lit and self._import_fused(x))  # (the lit field without a fine normal: none of the lit reads is needed)
+
+    def _source_lookup(self, x, lit=False):
+        """The one lookup of the active imported source -- patch, map on the imported mesh, planar map -- through its kernel (`_source_fused`
+        holds): h_mask [N], the raw normal [N,3] (None: the planar map's, `_import_normal`), xin [N,48] half, and with `lit` the phi_embed
+        [N,8] and the frames [N,3,3] in the order `_rotate_fine` takes them."""
+        if self._patch_active():
+            out = self._patch_lookup(x, lit=lit)
+            return _SourceLookup(out[1], out[2], out[3], *((out[7], out[8:]) if lit else ()))
+        if self._shape_active():
+            out = self._shape_light_lookup(x) if lit else self._shape_lookup(x)
+            return _SourceLookup(out[2], out[3], out[5], *((out[6], out[8:]) if lit else ()))
+        out = self._import_light_lookup(x) if lit else self._import_lookup(x)
+        return _SourceLookup(out[2], None, out[3], *((out[4], out[6:]) if lit else ()))
 
     @torch.no_grad()
     def _import_light_lookup(self, x):
         """nerftex_planar_light_lookup: -> p_uv [N,2], sdf [N], h_mask [N] bool, xin [N,48] half, phi [N,8] fp32, id [N] int32, local_tbn [N,3,3],
         sample_tbn_inv [N,3,3] (row `id` of the inverted patch frames)."""
-        from nerftex_hip import check, lib, ptr, stream
+        from nerftex_hip import check, lib, stream
 
-        x = x.detach().float().contiguous()
-        N, dev, f = x.shape[0], x.device, self.features_imported
-        p_uv = torch.empty(N, 2, device=dev)
-        sdf = torch.empty(N, device=dev)
-        mask = torch.empty(N, dtype=torch.uint8, device=dev)
-        xin = torch.empty(N, 48, dtype=torch.float16, device=dev)
-        phi = torch.empty(N, 8, device=dev)
-        ids = torch.empty(N, dtype=torch.int32, device=dev)
-        local, sample = torch.empty(N, 9, device=dev), torch.empty(N, 9, device=dev)
-        mode, p0, p1, h0, h1, off, h = self._import_scalars()
-        check(lib.nerftex_planar_light_lookup(ptr(x), ptr(f), ptr(self.phi_embed_imported), ptr(self.frame_map_imported), ptr(self.sample_inv_rows_imported),
-                                              f.shape[0], f.shape[1], self.sample_inv_rows_imported.shape[0], mode, p0, p1, h0, h1, off, h, int(self.multires), N,
-                                              ptr(p_uv), ptr(sdf), ptr(mask), ptr(xin), ptr(phi), ptr(ids), ptr(local), ptr(sample), stream()))
-        return p_uv, sdf, mask.bool(), xin, phi, ids, local.view(N, 3, 3), sample.view(N, 3, 3)
+        x, f, rows = x.detach().float().contiguous(), self.features_imported, self.sample_inv_rows_imported
+        p_uv, sdf, mask, xin, phi, ids, local, sample = out = self._lookup_buffers(x, "p_uv", "sdf", "mask", "xin", "phi", "ids", "frame", "frame")
+        check(lib.nerftex_planar_light_lookup(ptr(x), ptr(f), ptr(self.phi_embed_imported), ptr(self.frame_map_imported), ptr(rows), f.shape[0], f.shape[1],
+                                              rows.shape[0], *self._import_scalars(), int(self.multires), x.shape[0], *map(ptr, out), stream()))
+        return p_uv, sdf, mask.bool(), xin, phi, ids, local.view(x.shape[0], 3, 3), sample.view(x.shape[0], 3, 3)
 
     @staticmethod
-    def _rotate_fine(local, local_tbn, sample_tbn_inv, new_tbn=None):
-        """tools/map.py:724-730: the local normal rotated by the texel's frame, then by the patch's inverted frame, then (the 'shape' branch) by
-        the new mesh's face frame, normalised."""
-        fine = torch.einsum("nba,nb->na", local_tbn, local)
-        fine = torch.einsum("nba,nb->na", sample_tbn_inv, fine)
-        if new_tbn is not None:
-            fine = torch.einsum("nba,nb->na", new_tbn, fine)
+    def _rotate_fine(local, *frames):
+        """tools/map.py:724-730: the local normal rotated by the texel's frame, then (a map) by the patch's inverted frame, then (the 'shape'
+        branch) by the new mesh's face frame, normalised."""
+        fine = local
+        for tbn in frames:
+            fine = torch.einsum("nba,nb->na", tbn, fine)
         return fine / (fine.norm(dim=-1, keepdim=True) + 1e-5)
 
     def _import_light_embed_reference(self, x, details=False):
         """The import branch with `pred_normal` op by op, the reference's expressions (tools/map.py:649-675, :722-730) over grid_sample:
         -> embed [N,41] fp32, normal_coarse, h_mask, normal_fine (details: + the sampled phi_embed, local_tbn, id and sample_tbn_inv rows)."""
-        embed, normal_coarse, h_mask = self._import_embed_reference(x)
-        x = x.float()
-        b0, b1 = (torch.tensor(b, dtype=torch.float32, device=x.device) for b in self.bounds)
-        p_sur = x[..., :2] * self.uv_utilize_rate if self.rescale else torch.stack([x[..., 0] / b0, x[..., 1] / b1], dim=-1)
-        grid = p_sur[None, None]
-
-        def image(m):  # [H, W, C] -> [1, C, W, H], as `_import_embed_reference`
-            return m.to(x.device).permute(2, 1, 0).unsqueeze(0)
-
-        gs = torch.nn.functional.grid_sample
-        ids = gs(image(self.sample_tbn_ids_imported[..., None]), grid, mode="nearest", align_corners=True, padding_mode="zeros")[0, 0, 0].long()
-        sample_tbn_inv = self.sample_tbn_inv_imported.to(x.device)[ids]
-        local_tbn = gs(image(self.local_tbn_imported), grid, mode="nearest", align_corners=True, padding_mode="zeros")[0, :, 0].permute(1, 0).reshape(-1, 3, 3)
-        phi = gs(image(self.phi_embed_imported), grid, align_corners=True, padding_mode="zeros")[0, :, 0].permute(1, 0)
+        embed, normal_coarse, h_mask, p_sur = self._import_embed_reference(x, details=True)
+        phi, local_tbn, ids, sample_tbn_inv = self._lit_maps_reference(p_sur)
         x_embed, z_embed = embed[:, :self.encoder.output_dim], embed[:, self.encoder.output_dim:]
         local = self.normal_net(phi_embed=phi, z_embed=z_embed, x_embed=x_embed)
         fine = self._rotate_fine(local, local_tbn, sample_tbn_inv)
@@ -1307,37 +1290,28 @@ class CurvedField(torch.nn.Module):
         requires_grad_xyz (network_curvedfield.py:236-259, the branch that differentiates sigma with respect to the sample position): the
         projection carries `diff_project_layer`'s gradient, the hash table is looked up with input gradients (dy_dx) and the height ladder
         is evaluated by framework ops on the differentiable height -- dL/dembed reaches x."""
-        if self._patch_active():  # the 'patch' branch (:676-692): the patch's 8 nearest points instead of the mesh and the table
-            if requires_grad_xyz or (with_fine_normal and self.patch_lit is None):
-                raise NotImplementedError("CurvedField.embed: an imported patch is rendered without gradients to the sample position, and without a fine "
-                                          "normal unless it came with local_tbn and phi_embed")
-            return self._patch_embed(x, with_fine_normal=with_fine_normal)
-        if getattr(self, "imported", False):  # the import branch (:646-668): the map instead of the mesh and the table
-            lit_maps = self._lit() and self.phi_embed_imported is not None and (not self._shape_active() or self.shape_face_tbn is not None)
-            if requires_grad_xyz or (with_fine_normal and not lit_maps):
-                raise NotImplementedError("CurvedField.embed: an imported map is rendered without gradients to the sample position and without a fine normal")
-            if with_fine_normal and self._shape_active():  # the same on the imported mesh (:702-707): a third rotation, by the hit face's frame
-                if self._shape_light_fused(x):
-                    _, _, h_mask, normal, _, xin, phi, _, local_tbn, sample_tbn_inv, new_tbn = self._shape_light_lookup(x)
-                    local = self.normal_net(phi_embed=phi, z_embed=xin[:, 16:self.in_dim], x_embed=xin[:, :16])
-                    return (xin[:, :self.in_dim], normal / (normal.norm(dim=-1, keepdim=True) + 1e-5), h_mask,
-                            self._rotate_fine(local, local_tbn, sample_tbn_inv, new_tbn))
-                return self._shape_light_embed_reference(x)
-            if with_fine_normal:  # the `pred_normal` part (:670-675, :722-730): the normal net fed from the phi map, two rotations
-                if self._import_light_fused(x):
-                    _, _, h_mask, xin, phi, _, local_tbn, sample_tbn_inv = self._import_light_lookup(x)
-                    local = self.normal_net(phi_embed=phi, z_embed=xin[:, 16:self.in_dim], x_embed=xin[:, :16])
-                    return xin[:, :self.in_dim], self._import_normal(x, True), h_mask, self._rotate_fine(local, local_tbn, sample_tbn_inv)
-                return self._import_light_embed_reference(x)
-            if self._shape_active():  # the 'shape' branch (:693-700): the map at the UV of the hit on the imported mesh
-                if self._import_fused(x) or self._shape_light_fused(x):  # (the lit field: none of the lit reads is needed here)
-                    _, _, h_mask, normal, _, xin = self._shape_lookup(x)
-                    return xin[:, :self.in_dim], normal / (normal.norm(dim=-1, keepdim=True) + 1e-5), h_mask
-                return self._shape_embed_reference(x)
-            if self._import_fused(x) or self._import_light_fused(x):
-                _, _, h_mask, xin = self._import_lookup(x)
-                return xin[:, :self.in_dim], self._import_normal(x, True), h_mask
-            return self._import_embed_reference(x)
+        if getattr(self, "imported", False):  # the import branches (:646-707): a patch, the planar map or the map on the imported mesh instead of the mesh and the table
+            if self._patch_active():
+                if requires_grad_xyz or (with_fine_normal and self.patch_lit is None):
+                    raise NotImplementedError("CurvedField.embed: an imported patch is rendered without gradients to the sample position, and without a fine "
+                                              "normal unless it came with local_tbn and phi_embed")
+            else:
+                lit_maps = self._lit() and self.phi_embed_imported is not None and (not self._shape_active() or self.shape_face_tbn is not None)
+                if requires_grad_xyz or (with_fine_normal and not lit_maps):
+                    raise NotImplementedError("CurvedField.embed: an imported map is rendered without gradients to the sample position and without a fine normal")
+            if self._source_fused(x, with_fine_normal):
+                s = self._source_lookup(x, with_fine_normal)
+                coarse = self._import_normal(x, True) if s.normal is None else s.normal / (s.normal.norm(dim=-1, keepdim=True) + 1e-5)
+                if not with_fine_normal:
+                    return s.xin[:, :self.in_dim], coarse, s.h_mask
+                # the `pred_normal` part (:670-675, :687-692, :702-707, :722-730): the normal net fed from the source's phi_embed, one rotation per frame
+                local = self.normal_net(phi_embed=s.phi, z_embed=s.xin[:, 16:self.in_dim], x_embed=s.xin[:, :16])
+                return s.xin[:, :self.in_dim], coarse, s.h_mask, self._rotate_fine(local, *s.frames)
+            if self._patch_active():  # ... and op by op where the kernels do not serve the call
+                return self._patch_embed_reference(x, with_fine_normal=with_fine_normal)
+            if self._shape_active():
+                return self._shape_light_embed_reference(x) if with_fine_normal else self._shape_embed_reference(x)
+            return self._import_light_embed_reference(x) if with_fine_normal else self._import_embed_reference(x)
         if requires_grad_xyz:
             p_sur, sdf, h_mask, normal, local_tbn = self.projector.project(x, K=self.projector.K, h_threshold=self.h_threshold, requires_grad_xyz=True)
             z_embed = freq_encode(sdf, self.multires)
@@ -1363,16 +1337,11 @@ class CurvedField(torch.nn.Module):
         return _TruncExp.apply(h[..., 0]), h[..., 1:]
 
     def density(self, x, requires_grad_xyz=False):
-        if self._patch_active() and not requires_grad_xyz and self._patch_fused(x):
-            h_mask, xin = (self._patch_lookup(x)[i] for i in (1, 3))
-            h = self.sigma_net(xin)
+        if getattr(self, "imported", False) and not requires_grad_xyz and self._source_fused(x):
+            s = self._source_lookup(x)
+            h = self.sigma_net(s.xin)
             sigma = _TruncExp.apply(h[..., 0])
-            return {"sigma": torch.where(h_mask, sigma, torch.zeros_like(sigma)), "geo_feat": h[..., 1:]}
-        if getattr(self, "imported", False) and not self._patch_active() and not requires_grad_xyz and (self._import_fused(x) or self._import_light_fused(x) or self._shape_light_fused(x)):
-            h_mask, xin = (self._shape_lookup(x)[i] for i in (2, 5)) if self._shape_active() else self._import_lookup(x)[2:]
-            h = self.sigma_net(xin)
-            sigma = _TruncExp.apply(h[..., 0])
-            return {"sigma": torch.where(h_mask, sigma, torch.zeros_like(sigma)), "geo_feat": h[..., 1:]}
+            return {"sigma": torch.where(s.h_mask, sigma, torch.zeros_like(sigma)), "geo_feat": h[..., 1:]}
         embed, _, h_mask = self.embed(x, requires_grad_xyz=requires_grad_xyz)
         sigma, geo = self._sigma(embed)
         return {"sigma": torch.where(h_mask, sigma, torch.zeros_like(sigma)), "geo_feat": geo}
@@ -1402,10 +1371,11 @@ class CurvedField(torch.nn.Module):
         h_mask = torch.logical_and(h_mask, torch.logical_not(normal_grad.isnan()).all(dim=-1))
         return sigma, normal_grad, h_mask
 
-    def _glue_fused(self, x_dtype_ok=True):
-        """The three glue launches (csrc/fieldglue.hip, round 6) serve the default shapes under fp16 autocast without the probabilistic table."""
-        return (getattr(self, "light_model", None) is None and getattr(self, "fused_glue", True) and self.encoder_var is None and self.in_dim == 41 and self.in_pad == 48 and self.color_pad == 32
-                and self.geo_feat_dim == 15 and self.encoder_dir.output_dim == 16 and torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.float16)
+    def _glue_fused(self, x=None):
+        """The three glue launches (csrc/fieldglue.hip, round 6) serve the static light model's default shapes (`_sigma_fused`, and the colour
+        side's), unless `fused_glue` is off."""
+        return (getattr(self, "light_model", None) is None and getattr(self, "fused_glue", True) and self._sigma_fused(x) and self.color_pad == 32
+                and self.encoder_dir.output_dim == 16)
 
     def _forward_light(self, x, d, normal_supervision=False):
         """network_curvedfield.py:272-301, 327-349, 396-409 with the SH light model: the head shades with the fine normal -- detached in training
@@ -1440,23 +1410,14 @@ class CurvedField(torch.nn.Module):
     def forward(self, x, d, **kwargs):
         if getattr(self, "light_model", None) == "SH":
             return self._forward_light(x, d, normal_supervision=bool(kwargs.get("normal_supervision", False)))
-        if self._patch_active() and self._patch_fused(x) and self._glue_fused():
-            _, h_mask, normal, xin = self._patch_lookup(x)[:4]
-            h = self.sigma_net(xin)
+        if getattr(self, "imported", False) and self._glue_fused(x) and self._source_fused(x):
+            s = self._source_lookup(x)
+            normal = self._import_normal(x, False) if s.normal is None else s.normal
+            h = self.sigma_net(s.xin)
             sigma_raw, cin = _CurvedMid.apply(h, normal, d, self.fc_weight, 2 | int(not self.training))  # (bit 1: tools/map.py:720 in the kernel)
-            sigma, color = _CurvedOut.apply(self.color_net(cin), sigma_raw, h_mask)
+            sigma, color = _CurvedOut.apply(self.color_net(cin), sigma_raw, s.h_mask)
             return sigma, color, {}
-        if getattr(self, "imported", False) and not self._patch_active() and self._import_fused(x):
-            if self._shape_active():
-                _, _, h_mask, normal, _, xin = self._shape_lookup(x)
-            else:
-                _, _, h_mask, xin = self._import_lookup(x)
-                normal = self._import_normal(x, False)
-            h = self.sigma_net(xin)
-            sigma_raw, cin = _CurvedMid.apply(h, normal, d, self.fc_weight, 2 | int(not self.training))  # (bit 1: tools/map.py:720 in the kernel)
-            sigma, color = _CurvedOut.apply(self.color_net(cin), sigma_raw, h_mask)
-            return sigma, color, {}
-        if self._glue_fused() and not getattr(self, "imported", False):
+        if self._glue_fused(x) and not getattr(self, "imported", False):
             p_sur, sdf, h_mask, normal, local_tbn, _, z_embed = self.projector.project_fused(x, multires=self.multires)
             x_embed = self.encoder(p_sur, bound=self.bound)
             if x_embed.dtype == torch.float16 and z_embed.dtype == torch.float32:
@@ -1500,40 +1461,41 @@ class CurvedField(torch.nn.Module):
         return stamp + (True, nn.encoder.embeddings.data_ptr(), nn.encoder.offsets.data_ptr(),
                         tuple((q.data_ptr(), q._version) for q in list(nn.phi_net.parameters()) + list(nn.theta_net.parameters())))
 
-    # ---- the six fused inference chains: what each asks of a call (the entries refuse everything else) ----
+    # ---- the eight fused inference chains: what each asks of a call (the entries refuse everything else) ----
     _SIGMA_NET, _COLOR_NET, _BRDF_NET = (48, 32, 2, 16), (32, 64, 3, 3), (16, 64, 3, 5)  # (in, hidden, layers, out) the entries' kernels are built for
-
-    @staticmethod
-    def _infer_batch_ok(x, d):
-        """The batch every entry takes: whole 128-row workgroups, contiguous fp32 inputs."""
-        B = x.shape[0]
-        return B > 0 and B % 128 == 0 and x.dtype == torch.float32 and d.dtype == torch.float32 and x.is_contiguous() and d.is_contiguous()
 
     @staticmethod
     def _on_device_of(x, *tensors):
         return all(t.device == x.device for t in tensors)
 
-    def _infer_sigma_ok(self):
-        s = self.sigma_net
-        return (s.input_dim, s.hidden_dim, s.num_layers, s.padded_output_dim) == self._SIGMA_NET
+    # ---- the predicates of `_INFER_ROUTES`, composed of four conjuncts: the batch and the sigma net (`_infer_rows_ok`), the static back half
+    # (`_infer_static_back_ok`), the lit one (`_infer_light_back_fused`), the source's tensors on the device of x (`_on_device_of`) -- and of what
+    # serves the source's lookup (`_infer_front_fused`, `_import_fused`, `_import_light_fused`, `_shape_light_fused`, `_patch_fused`).
 
-    def _infer_color_ok(self):
+    def _infer_rows_ok(self, x, d):
+        """The batch every entry takes -- whole 128-row workgroups, contiguous fp32 inputs -- and the sigma net its kernels are built for."""
+        B, s = x.shape[0], self.sigma_net
+        return (B > 0 and B % 128 == 0 and x.dtype == torch.float32 and d.dtype == torch.float32 and x.is_contiguous() and d.is_contiguous()
+                and (s.input_dim, s.hidden_dim, s.num_layers, s.padded_output_dim) == self._SIGMA_NET)
+
+    def _infer_static_back_ok(self, x):
+        """What the static light model's three chains ask alike behind the lookup: _glue_fused() and the colour net the entries are built for."""
         c = self.color_net
-        return c.dtype == torch.float16 and (c.input_dim, c.hidden_dim, c.num_layers, c.output_dim) == self._COLOR_NET
+        return self._glue_fused(x) and c.dtype == torch.float16 and (c.input_dim, c.hidden_dim, c.num_layers, c.output_dim) == self._COLOR_NET
 
     def _infer_fused(self, x, d):
         """Whether nerftex_curved_field_infer serves this call: _glue_fused(), the shapes the entry's kernels are built for (it refuses every
         other one), an fp16 table, and what the entry asks of its buffers.  Everything else goes through forward()."""
-        return self._glue_fused() and self._infer_color_ok() and self._infer_front_fused(x, d)
+        return self._infer_static_back_ok(x) and self._infer_front_ok(x, d)  # (`_sigma_fused`: _glue_fused() has asked)
 
     def _infer_front_fused(self, x, d):
         """What the two fused chains ask alike (their front half, csrc/fieldglue.hip): fp16 autocast, no probabilistic table, the default texture
         table and sigma net, a batch of whole 128-row workgroups, contiguous fp32 inputs, an fp16 table."""
+        return self._sigma_fused(x) and self._infer_front_ok(x, d)
+
+    def _infer_front_ok(self, x, d):
         enc = self.encoder
-        return (torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.float16 and self.encoder_var is None
-                and self.in_dim == 41 and self.in_pad == 48 and self.geo_feat_dim == 15 and self._infer_batch_ok(x, d)
-                and self.sigma_net.dtype == torch.float16 and self._infer_sigma_ok()
-                and (enc.input_dim, enc.level_dim, enc.num_levels, self.multires) == (3, 2, 8, 12) and 1 <= self.projector.K <= 16
+        return (self._infer_rows_ok(x, d) and (enc.input_dim, enc.level_dim, enc.num_levels) == (3, 2, 8) and 1 <= self.projector.K <= 16
                 and enc._table().dtype == torch.float16)
 
     def _infer_weights(self, attr, net2, more_stamp=(), more=None):
@@ -1608,11 +1570,25 @@ class CurvedField(torch.nn.Module):
         uv = self.shape_face_uv
         return dict(face_uv=ptr(uv), n_faces=uv.shape[0], sdf_scale=scale, uv_rate=rate, **self._infer_mesh(self.shape_projector, K), **self._infer_map(off, h))
 
+    def _infer_patch(self):
+        """The imported patch: its neighbour grid and records, the threshold and the ladder."""
+        f = self.features_imported
+        return dict(knn=self._patch_knn.value, n_points=f.shape[0], geom=ptr(self.patch_geom), features=ptr(f), n_features=f.shape[1],
+                    **self._infer_ladder(float(self.h_threshold)))
+
+    def _lit_maps(self):
+        """The four maps the lit import chains read: the features and the three beside them."""
+        return self.features_imported, self.phi_embed_imported, self.frame_map_imported, self.sample_inv_rows_imported
+
     def _infer_lit_maps(self):
         """The three maps the lit import chains read beside the features, and the four maps."""
-        phi, frame, rows = self.phi_embed_imported, self.frame_map_imported, self.sample_inv_rows_imported
-        return (dict(phi_map=ptr(phi), frame_map=ptr(frame), sample_tbn_inv=ptr(rows), n_phi=phi.shape[2], n_patches=rows.shape[0]),
-                (self.features_imported, phi, frame, rows))
+        _, phi, frame, rows = maps = self._lit_maps()
+        return dict(phi_map=ptr(phi), frame_map=ptr(frame), sample_tbn_inv=ptr(rows), n_phi=phi.shape[2], n_patches=rows.shape[0]), maps
+
+    def _infer_lit_patch(self):
+        """The lit records the lit patch chain reads beside the patch's own, and everything of the patch the call points into."""
+        lit = self.patch_lit
+        return dict(lit=ptr(lit), n_phi=self.patch_phi_embed.shape[1]), (self.features_imported, self.patch_geom, lit, self._patch_knn)
 
     def _infer_front_desc(self):
         """The front half's members of the two mesh-field descriptors, knn .. in_mul, and the 16-bit texture table they point into."""
@@ -1633,8 +1609,7 @@ class CurvedField(torch.nn.Module):
     def _infer_import_fused(self, x, d):
         """Whether nerftex_curved_import_infer (or, on an imported mesh, nerftex_curved_shape_infer) serves this call: _infer_fused()'s conditions
         without the neighbour search's and the table's."""
-        return (self._import_fused(x) and self._infer_color_ok() and self._infer_sigma_ok() and self._infer_batch_ok(x, d)
-                and self._on_device_of(x, self.features_imported))
+        return self._infer_static_back_ok(x) and self._infer_rows_ok(x, d) and self._on_device_of(x, self.features_imported)
 
     def _infer_import_desc(self, x, d, live, sigma, rgbs, scratch):
         """The nerftex_curved_import_infer_desc of one call (and the tensors it points into, to be kept until the call is enqueued)."""
@@ -1671,37 +1646,24 @@ class CurvedField(torch.nn.Module):
     def _infer_light_import_fused(self, x, d):
         """Whether nerftex_curved_light_import_infer serves this call: _infer_light_fused()'s conditions without the neighbour search's and the
         two tables', with the imported maps on x's device instead."""
-        return (getattr(self, "imported", False) and self._infer_light_back_fused(x) and self._import_light_fused(x) and self._infer_sigma_ok()
-                and self._infer_batch_ok(x, d)
-                and self._on_device_of(x, self.features_imported, self.phi_embed_imported, self.frame_map_imported, self.sample_inv_rows_imported))
+        return (getattr(self, "imported", False) and self._infer_light_back_fused(x) and self._import_light_fused(x) and self._infer_rows_ok(x, d)
+                and self._on_device_of(x, *self._lit_maps()))
 
     def _infer_light_shape_fused(self, x, d):
         """Whether nerftex_curved_light_shape_infer serves this call: _infer_light_import_fused()'s conditions over the maps on the imported mesh,
         with its frames and a K the neighbour search serves."""
-        return (getattr(self, "imported", False) and self._infer_light_back_fused(x) and self._shape_light_fused(x) and self._infer_sigma_ok()
-                and self._infer_batch_ok(x, d) and 1 <= self._shape_scalars()[0] <= 16
-                and self._on_device_of(x, self.features_imported, self.phi_embed_imported, self.frame_map_imported, self.sample_inv_rows_imported,
-                                       self.shape_face_uv, self.shape_face_tbn))
+        return (self._infer_light_back_fused(x) and self._shape_light_fused(x) and self._infer_rows_ok(x, d) and 1 <= self._shape_scalars()[0] <= 16
+                and self._on_device_of(x, *self._lit_maps(), self.shape_face_uv, self.shape_face_tbn))
 
     def _infer_patch_fused(self, x, d):
         """Whether nerftex_curved_patch_infer serves this call: an imported patch, and _infer_import_fused()'s conditions over it."""
-        if getattr(self, "imported_type", None) != "patch":
-            return False
-        return (self._patch_fused(x) and self._glue_fused() and self._infer_color_ok() and self._infer_sigma_ok() and self._infer_batch_ok(x, d))
+        return self._patch_fused(x) and self._infer_static_back_ok(x) and self._infer_rows_ok(x, d)
 
     def _infer_light_patch_fused(self, x, d):
         """Whether nerftex_curved_light_patch_infer serves this call: an imported patch with its lit records, and
         _infer_light_import_fused()'s conditions over it."""
-        if getattr(self, "imported_type", None) != "patch":
-            return False
-        return (self._infer_light_back_fused(x) and self._patch_fused(x) and self.patch_lit is not None and self._infer_sigma_ok()
-                and self._infer_batch_ok(x, d) and self._on_device_of(x, self.patch_lit))
-
-    def _infer_patch(self):
-        """The imported patch: its neighbour grid and records, the threshold and the ladder."""
-        f = self.features_imported
-        return dict(knn=self._patch_knn.value, n_points=f.shape[0], geom=ptr(self.patch_geom), features=ptr(f), n_features=f.shape[1],
-                    **self._infer_ladder(float(self.h_threshold)))
+        return (self._infer_light_back_fused(x) and self._patch_fused(x) and self.patch_lit is not None and self._infer_rows_ok(x, d)
+                and self._on_device_of(x, self.patch_lit))
 
     def _infer_patch_desc(self, x, d, live, sigma, rgbs, scratch):
         """The nerftex_curved_patch_infer_desc of one call (and the tensors it points into, to be kept until the call is enqueued)."""
@@ -1710,10 +1672,9 @@ class CurvedField(torch.nn.Module):
 
     def _infer_light_patch_desc(self, x, d, live, sigma, rgbs, scratch, shading_normal=None):
         """The nerftex_curved_light_patch_infer_desc of one call (and the tensors it points into, to be kept until the call is enqueued)."""
+        lit, records = self._infer_lit_patch()
         back, kept = self._infer_lit_back(x, d, live, sigma, rgbs, scratch, shading_normal)
-        lit = self.patch_lit
-        return (CurvedLightPatchInferDesc(lit=ptr(lit), n_phi=self.patch_phi_embed.shape[1], **self._infer_patch(), **back),
-                (self.features_imported, self.patch_geom, lit, self._patch_knn) + kept)
+        return CurvedLightPatchInferDesc(**self._infer_patch(), **lit, **back), records + kept
 
     def _infer_light_desc(self, x, d, live, sigma, rgbs, scratch, shading_normal=None):
         """The nerftex_curved_light_infer_desc of one call (and the tensors it points into).  Kept between calls and re-made when a parameter
@@ -1807,29 +1768,34 @@ class CurvedField(torch.nn.Module):
         `_infer_light_shape_fused`, which the caller has checked)."""
         return self._infer_call("nerftex_curved_light_shape_infer", self._infer_light_shape_desc, x, d, live, shading_normal)
 
-    def _infer_route(self, x, d):
-        """The chain that serves infer(x, d): (the library entry's name, the builder of its descriptor), or None: forward().  The one priority
-        ladder -- an imported patch: lit, static, and nothing else; an imported map: lit on the imported mesh, lit (4.17), on the imported mesh, planar, and never the mesh field's
-        chains; the mesh field: lit (opt-in, `fused_light_infer`; 4.14), static."""
-        if getattr(self, "imported", False):
-            if self._infer_light_patch_fused(x, d):
-                return "nerftex_curved_light_patch_infer", self._infer_light_patch_desc
-            if self._infer_patch_fused(x, d):
-                return "nerftex_curved_patch_infer", self._infer_patch_desc
-            if getattr(self, "imported_type", None) == "patch":  # (the maps of an earlier import_field are not this import's)
-                return None
-            if self._infer_light_shape_fused(x, d):
-                return "nerftex_curved_light_shape_infer", self._infer_light_shape_desc
-            if self._infer_light_import_fused(x, d):
-                return "nerftex_curved_light_import_infer", self._infer_light_import_desc
-            if self._infer_import_fused(x, d):
-                return ("nerftex_curved_shape_infer", self._infer_shape_desc) if self._shape_active() else ("nerftex_curved_import_infer", self._infer_import_desc)
-            return None
-        if self._infer_light_fused(x, d):
-            return "nerftex_curved_light_infer", self._infer_light_desc
-        if self._infer_fused(x, d):
-            return "nerftex_curved_field_infer", self._infer_desc
+    # The one priority table of the eight chains: (the sources a row serves, its predicate, the library entry, the builder of its descriptor, lit).
+    # The first row of the ACTIVE source whose predicate holds serves the call.  A source sees its own rows only: an imported patch never takes a
+    # map's chain (the maps of an earlier import_field are not this import's), an import never the mesh field's.  Patch: DESIGN.md 4.20; the maps:
+    # 4.18, 4.17, 4.16, 4.15 (the lit planar row serves either map source: its predicate refuses the imported mesh); the mesh field: lit (4.14, opt-in:
+    # `fused_light_infer`), static.  The predicates are looked up by name: the tests substitute them.
+    _INFER_ROUTES = (
+        (("mesh",), "_infer_light_fused", "nerftex_curved_light_infer", "_infer_light_desc", True),
+        (("mesh",), "_infer_fused", "nerftex_curved_field_infer", "_infer_desc", False),
+        (("patch",), "_infer_light_patch_fused", "nerftex_curved_light_patch_infer", "_infer_light_patch_desc", True),
+        (("patch",), "_infer_patch_fused", "nerftex_curved_patch_infer", "_infer_patch_desc", False),
+        (("shape",), "_infer_light_shape_fused", "nerftex_curved_light_shape_infer", "_infer_light_shape_desc", True),
+        (("field", "shape"), "_infer_light_import_fused", "nerftex_curved_light_import_infer", "_infer_light_import_desc", True),
+        (("shape",), "_infer_import_fused", "nerftex_curved_shape_infer", "_infer_shape_desc", False),
+        (("field",), "_infer_import_fused", "nerftex_curved_import_infer", "_infer_import_desc", False),
+    )
+
+    def _infer_row(self, x, d):
+        """The row of `_INFER_ROUTES` that serves infer(x, d), or None: forward()."""
+        source = getattr(self, "imported_type", None) if getattr(self, "imported", False) else "mesh"
+        for row in self._INFER_ROUTES:
+            if source in row[0] and getattr(self, row[1])(x, d):
+                return row
         return None
+
+    def _infer_route(self, x, d):
+        """The chain that serves infer(x, d): (the library entry's name, the builder of its descriptor), or None: forward()."""
+        row = self._infer_row(x, d)
+        return None if row is None else (row[2], getattr(self, row[3]))
 
     @torch.no_grad()
     def infer_padded(self, x, d):
@@ -1842,9 +1808,9 @@ class CurvedField(torch.nn.Module):
             xp = torch.full((B + pad, 3), 1e30, dtype=x.dtype, device=x.device)
             dp = torch.full((B + pad, 3), 1e30, dtype=d.dtype, device=d.device)
             xp[:B], dp[:B] = x, d
-            route = self._infer_route(xp, dp)
-            if route is not None and "_light_" in route[0]:  # (the lit chains only)
-                sigma, rgbs = self._infer_call(*route, xp, dp, None)
+            row = self._infer_row(xp, dp)
+            if row is not None and row[4]:  # (the lit chains only)
+                sigma, rgbs = self._infer_call(row[2], getattr(self, row[3]), xp, dp, None)
                 return sigma[:B], rgbs[:B]
         return self.infer(x, d)
 
@@ -1863,11 +1829,11 @@ class CurvedField(torch.nn.Module):
         (DESIGN.md 4.17), and over the maps on an imported mesh nerftex_curved_light_shape_infer.
         An imported patch (import_patch): nerftex_curved_patch_infer, and for the SH-lit field with the switch set
         nerftex_curved_light_patch_infer, under the same contract."""
-        route = self._infer_route(x, d)
-        if route is None:
+        row = self._infer_row(x, d)
+        if row is None:
             sigma, rgbs, _ = self.forward(x, d)
             return sigma.float(), rgbs.float()
-        return self._infer_call(*route, x, d, live)
+        return self._infer_call(row[2], getattr(self, row[3]), x, d, live)
 
     @torch.no_grad()
     def forward_graphed(self, x, d):

@@ -1,4 +1,4 @@
-"""The six curved-field inference descriptors as compositions of member blocks (ngp_harness/curved.py), the CPU side (no GPU): every builder
+"""The eight curved-field inference descriptors as compositions of member blocks (ngp_harness/curved.py), the CPU side (no GPU): every builder
 passes exactly the members its ctypes structure declares -- a member no block names would be the NULL / 0 ctypes fills in, which only a GPU run
 finds; a member two blocks name is a TypeError where they are composed -- and the one route picks the chain both infer() and infer_padded() take."""
 import types
@@ -6,13 +6,15 @@ import types
 import pytest
 import torch
 
-DESCS = {  # the descriptor's class -> its builder, whether the field is lit, whether a map is imported onto a new mesh ("shape"), planar ("field") or not
+DESCS = {  # the descriptor's class -> its builder, whether the field is lit, what is imported: a map onto a new mesh ("shape"), planar ("field"), a "patch", nothing
     "CurvedInferDesc": ("_infer_desc", False, None),
     "CurvedImportInferDesc": ("_infer_import_desc", False, "field"),
     "CurvedShapeInferDesc": ("_infer_shape_desc", False, "shape"),
     "CurvedLightInferDesc": ("_infer_light_desc", True, None),
     "CurvedLightImportInferDesc": ("_infer_light_import_desc", True, "field"),
     "CurvedLightShapeInferDesc": ("_infer_light_shape_desc", True, "shape"),
+    "CurvedPatchInferDesc": ("_infer_patch_desc", False, "patch"),
+    "CurvedLightPatchInferDesc": ("_infer_light_patch_desc", True, "patch"),
 }
 
 
@@ -42,16 +44,22 @@ def _field(lit, imported):
     f.light_model, f.multires, f.h_threshold, f.fc_weight, f.bound, f.encoder_var = ("SH" if lit else None), 12, 0.0625, 0.7, 1.0, None
     f.encoder, f.projector, f.sigma_net, f.color_net = _encoder(8), _projector(), _net(48, 32, 2, 16), _net(32, 64, 3, 3)
     f.normal_net = types.SimpleNamespace(encoder=_encoder(4)) if lit else None
-    f.light_net = types.SimpleNamespace(brdf_layer=_net(16, 64, 3, 5), envSHs=torch.zeros(9, 3), gamma=2.4, use_specular=True) if lit else None
+    f.light_net = types.SimpleNamespace(brdf_layer=_net(16, 64, 3, 5), envSHs=torch.zeros(9, 3), gamma=2.4, use_specular=True, fused=True) if lit else None
     f.light_visual_mode = "Diffuse"
     half, single = torch.zeros(8, dtype=torch.float16), torch.zeros(8)
     f._infer_weights = lambda *a, **k: (half, half)  # (the cached 16-bit copies: `_infer_weights` asks the library to register the offsets)
     f._infer_light_weights = lambda: (half, half, half, single)
     f._init_import_state()
-    if imported:
+    if imported == "patch":
+        f.imported, f.imported_type = True, imported
+        f.features_imported, f.patch_geom, f._patch_knn = torch.zeros(8, 16), torch.zeros(8, 8), types.SimpleNamespace(value=13)
+        if lit:
+            f.patch_lit, f.patch_phi_embed = torch.zeros(8, 20), torch.zeros(8, 8)
+    elif imported:
         f.imported, f.imported_type, f.bounds = True, imported, (0.5, 0.5)
         f.features_imported = torch.zeros(2, 3, 16)
         f.phi_embed_imported, f.frame_map_imported, f.sample_inv_rows_imported = torch.zeros(2, 3, 8), torch.zeros(2, 3, 12), torch.zeros(5, 12)
+        f.local_tbn_imported, f.sample_tbn_ids_imported, f.sample_tbn_inv_imported = torch.zeros(2, 3, 9), torch.zeros(2, 3), torch.zeros(5, 3, 3)
         f.shape_projector, f.shape_face_uv, f.shape_face_tbn = _projector(9), torch.zeros(10, 8), torch.zeros(10, 12)
     return f.eval()
 
@@ -83,10 +91,12 @@ def test_a_builder_passes_every_member_of_its_descriptor_and_nothing_else(monkey
     import nerftex_hip
 
     desc = getattr(nerftex_hip, name)(**passed)
-    held = {t.data_ptr() for t in keep}
+    held = {t.data_ptr() for t in keep if torch.is_tensor(t)}
     pointers = [n for n in ("table", "normal_table", "map", "phi_map", "frame_map", "sample_tbn_inv", "sigma_weights", "color_weights", "brdf_weights",
-                            "normal_weights", "normal_biases", "env_shs") if n in passed]
+                            "normal_weights", "normal_biases", "env_shs", "geom", "features", "lit") if n in passed]
     assert pointers and all(getattr(desc, n) in held for n in pointers), [n for n in pointers if getattr(desc, n) not in held]
+    if DESCS[name][2] == "patch":  # the neighbour grid is the patch's own, kept alive with the records
+        assert passed["knn"] == 13 and f._patch_knn in keep and {"geom", "features"} <= set(pointers) and ("lit" in pointers) == DESCS[name][1]
     assert desc.B == 128 and desc.eval == (1 if DESCS[name][1] else 3) and desc.fc_weight == pytest.approx(0.7)
 
 
@@ -110,7 +120,9 @@ def test_composing_two_blocks_that_name_the_same_member_raises():
     f = _field(True, "shape")
     rows = (torch.zeros(128, 3), torch.zeros(128, 3), None, torch.zeros(128), torch.zeros(128, 3), torch.zeros(256, dtype=torch.uint8))
     front, _ = f._infer_front_desc()
+    patch = _field(True, "patch")._infer_patch()
     for a, b, twice in [(front, f._infer_shape(), "knn"),  # two meshes
+                        (patch, f._infer_shape(), "knn"),  # a patch and a mesh
                         (f._infer_planar(), f._infer_shape(), "map"),  # two lookups of the one map
                         (f._infer_static_back(*rows)[0], f._infer_lit_back(*rows, None)[0], "sigma_weights")]:  # two light models
         assert twice in a and twice in b
@@ -119,25 +131,29 @@ def test_composing_two_blocks_that_name_the_same_member_raises():
 
 
 def test_one_route_serves_infer_and_infer_padded(monkeypatch):
-    """The ladder, once: lit shape, lit import, shape, import; lit mesh, mesh; forward().  infer() takes whatever the route names; infer_padded()
-    pads for the lit chains alone and leaves every other batch to infer()."""
+    """The table, once: lit patch, patch; lit shape, lit import, shape, import; lit mesh, mesh; forward().  infer() takes whatever the route names;
+    infer_padded() pads for the lit chains alone and leaves every other batch to infer()."""
     from ngp_harness.curved import CurvedField
 
-    rungs = ["_infer_light_shape_fused", "_infer_light_import_fused", "_infer_import_fused", "_infer_light_fused", "_infer_fused"]
+    rungs = ["_infer_light_patch_fused", "_infer_patch_fused", "_infer_light_shape_fused", "_infer_light_import_fused", "_infer_import_fused",
+             "_infer_light_fused", "_infer_fused"]
 
     def field(imported, shape, *true):
-        f = _field(True, ("shape" if shape else "field") if imported else None)
+        f = _field(True, (shape if isinstance(shape, str) else "shape" if shape else "field") if imported else None)
         for r in rungs:
             setattr(f, r, lambda x, d, on=r in true: on)
         return f
 
     x = d = torch.zeros(128, 3)
     entry = lambda f: (lambda r: None if r is None else (r[0], r[1].__name__))(f._infer_route(x, d))  # noqa: E731
+    assert entry(field(True, "patch", *rungs)) == ("nerftex_curved_light_patch_infer", "_infer_light_patch_desc")
+    assert entry(field(True, "patch", *rungs[1:])) == ("nerftex_curved_patch_infer", "_infer_patch_desc")
+    assert entry(field(True, "patch", *rungs[2:])) is None, "an imported patch never takes a map's chains, nor the mesh field's"
     assert entry(field(True, True, *rungs)) == ("nerftex_curved_light_shape_infer", "_infer_light_shape_desc")
-    assert entry(field(True, True, *rungs[1:])) == ("nerftex_curved_light_import_infer", "_infer_light_import_desc")
-    assert entry(field(True, True, *rungs[2:])) == ("nerftex_curved_shape_infer", "_infer_shape_desc")
-    assert entry(field(True, False, *rungs[2:])) == ("nerftex_curved_import_infer", "_infer_import_desc")
-    assert entry(field(True, False, *rungs[3:])) is None, "an imported map never takes the mesh field's chains"
+    assert entry(field(True, True, *rungs[3:])) == ("nerftex_curved_light_import_infer", "_infer_light_import_desc")
+    assert entry(field(True, True, *rungs[4:])) == ("nerftex_curved_shape_infer", "_infer_shape_desc")
+    assert entry(field(True, False, *rungs[4:])) == ("nerftex_curved_import_infer", "_infer_import_desc")
+    assert entry(field(True, False, *rungs[5:])) is None, "an imported map never takes the mesh field's chains"
     assert entry(field(False, False, *rungs)) == ("nerftex_curved_light_infer", "_infer_light_desc")
     assert entry(field(False, False, "_infer_fused")) == ("nerftex_curved_field_infer", "_infer_desc")
     assert entry(field(False, False)) is None
