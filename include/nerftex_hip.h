@@ -1393,6 +1393,73 @@ int nerftex_sh_light_forward(const nerftex_sh_light_desc* d, void* stream);
 int nerftex_sh_light_backward(const nerftex_sh_light_desc* d, void* stream);
 size_t nerftex_sh_light_scratch_bytes(uint32_t B);
 
+/* -------------------------------------------------------------------------
+ * Extension: the head under imported lighting with visibility (sh_light_model.py:561-571, eval with import_envmap and shade_visibility): every
+ * row is lit by one of K coefficient sets, the one whose probe direction is closest to the row's secondary (coarse) normal n2:
+ *   k* = argmax_k (n2 . probes[k]),  the dot product (x px + y py) + z pz in fp32, every operation rounded on its own; the LOWEST index among
+ *        equal maxima
+ *   the row is then shaded exactly as nerftex_sh_light_forward shades it with n_color = 3 and env_shs = probe_shs[k*]  ([9,3])
+ * A workgroup stages probes and probe_shs (x lobe) in LDS once, K * 120 bytes.  Rows with mask[b] == 0 give 0 in every output.  Forward only: the
+ * reference uses imported lighting only when not training.  B == 0: NERFTEX_OK.  NERFTEX_ERR_INVALID with a message, before anything is
+ * launched: a NULL descriptor or a NULL buffer that the call needs, K == 0 or K > 256, brdf_stride < 5, gamma not positive and finite, an unknown
+ * flag.  Nothing is allocated and the host never waits: the call can be captured.
+ * ------------------------------------------------------------------------- */
+typedef struct nerftex_sh_light_probe_desc { /* device pointers unless noted */
+    const void* brdf;                  /* [B, brdf_stride] fp16, columns 0..4 used, as nerftex_sh_light_desc                      */
+    uint32_t brdf_stride;
+    const float* normals;              /* [B,3] fp32 shading normals, already normalised                                          */
+    const float* dirs;                 /* [B,3] fp32 view directions                                                              */
+    const float* normals_secondary;    /* [B,3] fp32: what the probe is chosen by                                                 */
+    const float* probes;               /* [K,3] fp32 probe directions                                                             */
+    const float* probe_shs;            /* [K,9,3] fp32: one lighting per probe                                                    */
+    uint32_t K;                        /* 1 .. 256                                                                                */
+    const uint8_t* mask;               /* [B] bytes or NULL: rows with 0 give 0                                                   */
+    uint32_t B;
+    float gamma;                       /* host value                                                                              */
+    uint32_t flags;                    /* NERFTEX_SH_LIGHT_SPECULAR                                                               */
+    float* color;                      /* [B,3] fp32                                                                              */
+    float* specular;                   /* [B,3] fp32 or NULL                                                                      */
+    float* diffuse;                    /* [B,3] fp32 or NULL                                                                      */
+    float* albedo;                     /* [B,3] fp32 or NULL                                                                      */
+} nerftex_sh_light_probe_desc;
+int nerftex_sh_light_probe_forward(const nerftex_sh_light_probe_desc* d, void* stream);
+
+/* -------------------------------------------------------------------------
+ * Extension: SH lighting fitted to an equirectangular environment map -- EnvMap2SH (nerf/sh_light_model.py:730-766): up to max_steps iterations
+ * of torch.optim.Adam(lr) on  loss(c) = mean((SH2Envmap(c) - envmap)^2)  from c = 0.  The objective is linear least squares in the 27 numbers
+ * c[0..8][0..2], so the map is read once:
+ *   moments    one thread per pixel (grid-stride above 262 144 pixels): direction (cos theta sin phi, cos phi, sin theta sin phi) in fp32, the
+ *              nine svox2 bases Y in fp32, then in fp64  G = sum Y Y^T (45 entries), b = sum Y y^T (27), s = sum y^2 (3): wave butterfly, the four
+ *              waves in order through LDS, one partial per workgroup in `scratch`; the grid is a function of H W alone
+ *   iteration  ONE wave: sums the partials in workgroup order, then runs the loop, lane k * 3 + c owning c[k][c]:
+ *              loss_t = (c^T G c - 2 c^T b + s) / (3 H W) in fp64 of the parameters BEFORE the update; g = fp32(2 / (3 H W) (G c - b));
+ *              torch's single-tensor Adam on fp32 state (betas 0.9 / 0.999, eps 1e-8, step size lr / (1 - 0.9^t) and sqrt(1 - 0.999^t)
+ *              from double, rounded to fp32):  m += 0.1 (g - m);  v = 0.999 v + (0.001 g) g;  c += (-step_size m) / (sqrt(v) / bc2 + eps)
+ *              and stops AFTER the update of the first step t (counted from 1) with loss_t < min_loss and t - 1 > min_steps, or after max_steps.
+ * env_shs rows 9.. are written as 0 (they receive no gradient in the reference).  steps_run = the number of updates made; final_loss = the last
+ * loss_t.  Two launches, nothing allocated, the host never waits: the call can be captured; the same bits on every run.
+ * NERFTEX_ERR_INVALID with a message, before anything is launched: a NULL descriptor or buffer, H W == 0, n_sh < 9, lr not positive and finite,
+ * max_steps == 0, scratch or final_loss not 8-byte aligned, scratch smaller than nerftex_envmap_fit_scratch_bytes(H, W).
+ * ------------------------------------------------------------------------- */
+typedef struct nerftex_envmap_fit_desc { /* device pointers unless noted */
+    const float* envmap;               /* [H,W,3] fp32                                                                            */
+    const float* phi;                  /* [H] fp32 polar angles: torch.linspace(0, pi, H)                                         */
+    const float* theta;                /* [W] fp32 azimuths: torch.linspace(-pi / 2, 3 pi / 2, W)                                 */
+    uint32_t H, W;
+    uint32_t n_sh;                     /* rows of env_shs, >= 9                                                                   */
+    uint32_t max_steps;                /* the reference: 5000                                                                     */
+    uint32_t min_steps;                /* the reference: 2000                                                                     */
+    double lr;                         /* host value; the reference: 1e-2                                                         */
+    double min_loss;                   /* host value; the reference: 1e-5                                                         */
+    float* env_shs;                    /* [n_sh,3] fp32 out                                                                       */
+    int32_t* steps_run;                /* [1] out                                                                                 */
+    double* final_loss;                /* [1] out                                                                                 */
+    void* scratch;                     /* caller-owned, 8-byte aligned, >= nerftex_envmap_fit_scratch_bytes(H, W) bytes           */
+    size_t scratch_bytes;
+} nerftex_envmap_fit_desc;
+int nerftex_envmap_fit(const nerftex_envmap_fit_desc* d, void* stream);
+size_t nerftex_envmap_fit_scratch_bytes(uint32_t H, uint32_t W);
+
 /* grad_hc [B,16] fp16 = sigmoid backward of the fp16-narrowed grad_rgbs, columns 3..15 zero                      */
 int nerftex_field_out_backward(const float* grad_rgbs, const float* rgbs, uint32_t B, void* grad_hc, void* stream);
 

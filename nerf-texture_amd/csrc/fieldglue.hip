@@ -721,3 +721,6 @@ extern "C" int nerftex_field_out_backward(const float* grad_rgbs, const float* r
 
 // ---- an imported feature patch (nerftex_curved_patch_infer, nerftex_curved_light_patch_infer): the patch lookup (knn.hip) in front of either back half ----
 #include "patch_chain.inc"
+
+// ---- fitting SH lighting to an imported environment map (nerftex_envmap_fit): svox2_basis9 comes from shlight.inc -----------------------------------------
+#include "envmap.inc"

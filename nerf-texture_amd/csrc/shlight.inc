@@ -374,3 +374,108 @@ extern "C" int nerftex_sh_light_backward(const nerftex_sh_light_desc* d, void* s
     }
     return check_launch("sh_light_backward(sum)");
 }
+
+// ---- per-sample probe lighting (sh_light_model.py:561-571 with shade_visibility): imported lighting in eval, one of K coefficient sets per row ----
+// The reference picks, per sample, the probe whose direction is closest to the sample's coarse normal -- argmax over a [B, K] product -- and
+// gathers a [B, 9, 3] table for the head.  Here a workgroup stages the K directions and the K tables (x lobe) in LDS once; a row walks the
+// directions (every lane reads the same word), keeps the first best and shades itself with shade_row<3> / row_output<3> from its table.
+
+namespace nerftex {
+namespace {
+
+constexpr uint32_t kMaxProbes = 256;
+
+__global__ __launch_bounds__(kThreads) void sh_light_probe_forward_kernel(const half_t* __restrict__ brdf, const uint32_t stride, const bool wide,
+                                                                          const float* __restrict__ normals, const float* __restrict__ dirs,
+                                                                          const float* __restrict__ normals2, const float* __restrict__ probes,
+                                                                          const float* __restrict__ probe_shs, const uint32_t K,
+                                                                          const uint8_t* __restrict__ mask, const uint32_t B, const float inv_gamma,
+                                                                          const bool use_specular, float* __restrict__ color, float* __restrict__ specular,
+                                                                          float* __restrict__ diffuse, float* __restrict__ albedo) {
+    extern __shared__ float probe_lds[];  // [K][3] directions, then [K][9][3] tables x lobe
+    float* dir_lds = probe_lds;
+    float* el_lds = probe_lds + (size_t)K * 3;
+    for (uint32_t i = threadIdx.x; i < K * 3; i += kThreads) dir_lds[i] = probes[i];
+    for (uint32_t i = threadIdx.x; i < K * 27; i += kThreads) el_lds[i] = probe_shs[i] * lobe((int)((i % 27) / 3));
+    __syncthreads();
+    const uint32_t b = blockIdx.x * kThreads + threadIdx.x;
+    if (b >= B) return;
+    if (mask && !mask[b]) {
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            color[(size_t)b * 3 + c] = 0.0f;
+            if (specular) specular[(size_t)b * 3 + c] = 0.0f;
+            if (diffuse) diffuse[(size_t)b * 3 + c] = 0.0f;
+            if (albedo) albedo[(size_t)b * 3 + c] = 0.0f;
+        }
+        return;
+    }
+    const float n2[3] = {normals2[(size_t)b * 3], normals2[(size_t)b * 3 + 1], normals2[(size_t)b * 3 + 2]};
+    uint32_t best = 0;
+    float best_dot = (n2[0] * dir_lds[0] + n2[1] * dir_lds[1]) + n2[2] * dir_lds[2];
+    for (uint32_t k = 1; k < K; k++) {
+        const float dot = (n2[0] * dir_lds[k * 3] + n2[1] * dir_lds[k * 3 + 1]) + n2[2] * dir_lds[k * 3 + 2];
+        if (dot > best_dot) best_dot = dot, best = k;  // (strictly: the lowest index among equal maxima)
+    }
+    float el[9][3];
+#pragma unroll
+    for (int k = 0; k < 9; k++)
+#pragma unroll
+        for (int c = 0; c < 3; c++) el[k][c] = el_lds[best * 27 + k * 3 + c];
+    half_t x[4];
+    load_brdf(brdf, stride, wide, b, x);
+    Row<3> r;
+    shade_row<3>(x, normals, dirs, b, el, use_specular, r);
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        color[(size_t)b * 3 + c] = row_output<3>(r, c, 0, inv_gamma);
+        if (specular) specular[(size_t)b * 3 + c] = row_output<3>(r, c, 1, inv_gamma);
+        if (diffuse) diffuse[(size_t)b * 3 + c] = row_output<3>(r, c, 2, inv_gamma);
+        if (albedo) albedo[(size_t)b * 3 + c] = row_output<3>(r, c, 3, inv_gamma);
+    }
+}
+
+int check_probe_desc(const nerftex_sh_light_probe_desc* d) {
+    const char* what = "sh_light_probe_forward";
+    if (!d) {
+        set_error("%s: NULL descriptor", what);
+        return NERFTEX_ERR_INVALID;
+    }
+    if (d->K == 0 || d->K > kMaxProbes) {
+        set_error("%s: between 1 and %u probes, but got %u", what, kMaxProbes, d->K);
+        return NERFTEX_ERR_INVALID;
+    }
+    if (d->brdf_stride < 5 || !(d->gamma > 0.0f) || !std::isfinite(d->gamma)) {
+        set_error("%s: the BRDF rows hold at least 5 values (got %u) and gamma is positive and finite", what, d->brdf_stride);
+        return NERFTEX_ERR_INVALID;
+    }
+    if (d->flags & ~(uint32_t)NERFTEX_SH_LIGHT_SPECULAR) {
+        set_error("%s: unknown flags 0x%x", what, d->flags);
+        return NERFTEX_ERR_INVALID;
+    }
+    if (d->B == 0) return NERFTEX_OK;
+    if (!d->brdf || !d->normals || !d->dirs || !d->normals_secondary || !d->probes || !d->probe_shs || !d->color) {
+        set_error("%s: brdf, normals, dirs, normals_secondary, probes, probe_shs and color must not be NULL", what);
+        return NERFTEX_ERR_INVALID;
+    }
+    return NERFTEX_OK;
+}
+
+}  // namespace
+}  // namespace nerftex
+
+extern "C" int nerftex_sh_light_probe_forward(const nerftex_sh_light_probe_desc* d, void* stream) {
+    clear_error();
+    const int rc = check_probe_desc(d);
+    if (rc != NERFTEX_OK || d->B == 0) return rc;
+    hipStream_t st = as_stream(stream);
+    const bool wide = wide_rows(d->brdf, nullptr, d->brdf_stride), spec = (d->flags & NERFTEX_SH_LIGHT_SPECULAR) != 0;
+    const float inv_gamma = (float)(1.0 / (double)d->gamma);
+    {
+        KernelTimer kt("sh_light_probe_forward_kernel", st);
+        hipLaunchKernelGGL(sh_light_probe_forward_kernel, dim3(div_up(d->B, (uint32_t)kThreads)), dim3(kThreads), (size_t)d->K * 30 * sizeof(float), st,
+                           static_cast<const half_t*>(d->brdf), d->brdf_stride, wide, d->normals, d->dirs, d->normals_secondary, d->probes, d->probe_shs, d->K,
+                           d->mask, d->B, inv_gamma, spec, d->color, d->specular, d->diffuse, d->albedo);
+    }
+    return check_launch("sh_light_probe_forward");
+}

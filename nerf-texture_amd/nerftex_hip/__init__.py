@@ -66,6 +66,8 @@ _SIGNATURES = {
     "nerftex_curved_light_patch_infer": [_vp, _vp],
     "nerftex_sh_light_forward": [_vp, _vp],
     "nerftex_sh_light_backward": [_vp, _vp],
+    "nerftex_sh_light_probe_forward": [_vp, _vp],
+    "nerftex_envmap_fit": [_vp, _vp],
     "nerftex_field_mid_backward": [_vp, _vp, _vp, _u32, _vp, _vp],
     "nerftex_field_out_forward": [_vp, _u32, _vp, _vp],
     "nerftex_field_out_backward": [_vp, _vp, _u32, _vp, _vp],
@@ -340,6 +342,21 @@ class SHLightDesc(C.Structure):
                 ("grad_brdf", _vp), ("grad_env_shs", _vp), ("scratch", _vp), ("scratch_bytes", _sz)]
 
 
+SH_LIGHT_MAX_PROBES = 256  # nerftex_sh_light_probe_desc.K
+
+
+class SHLightProbeDesc(C.Structure):
+    """nerftex_sh_light_probe_desc of include/nerftex_hip.h, field for field: the head under per-probe imported lighting (forward only)."""
+    _fields_ = [("brdf", _vp), ("brdf_stride", _u32), ("normals", _vp), ("dirs", _vp), ("normals_secondary", _vp), ("probes", _vp), ("probe_shs", _vp),
+                ("K", _u32), ("mask", _vp), ("B", _u32), ("gamma", _f32), ("flags", _u32), ("color", _vp), ("specular", _vp), ("diffuse", _vp), ("albedo", _vp)]
+
+
+class EnvmapFitDesc(C.Structure):
+    """nerftex_envmap_fit_desc of include/nerftex_hip.h, field for field: SH lighting fitted to an environment map."""
+    _fields_ = [("envmap", _vp), ("phi", _vp), ("theta", _vp), ("H", _u32), ("W", _u32), ("n_sh", _u32), ("max_steps", _u32), ("min_steps", _u32),
+                ("lr", _f64), ("min_loss", _f64), ("env_shs", _vp), ("steps_run", _vp), ("final_loss", _vp), ("scratch", _vp), ("scratch_bytes", _sz)]
+
+
 # texture synthesis (nerftex_synth_*): status codes, modes, log layout and the arrays nerftex_synth_read copies
 ERR_INVALID, ERR_HIP, ERR_EXHAUSTED = 1, 2, 3
 SYNTH_CUT, SYNTH_BLEND, SYNTH_LOG_STRIDE = 0, 1, 36
@@ -363,7 +380,7 @@ class SynthView(C.Structure):
 EXPORTS = ["nerftex_last_error", "nerftex_version", "nerftex_tune_get", "nerftex_workspace_slots_touched", "nerftex_curved_field_infer_scratch_bytes",
            "nerftex_curved_light_infer_scratch_bytes", "nerftex_curved_import_infer_scratch_bytes", "nerftex_curved_shape_infer_scratch_bytes",
            "nerftex_curved_light_import_infer_scratch_bytes", "nerftex_curved_light_shape_infer_scratch_bytes", "nerftex_curved_patch_infer_scratch_bytes",
-           "nerftex_curved_light_patch_infer_scratch_bytes", "nerftex_sh_light_scratch_bytes"] + list(_SIGNATURES)
+           "nerftex_curved_light_patch_infer_scratch_bytes", "nerftex_sh_light_scratch_bytes", "nerftex_envmap_fit_scratch_bytes"] + list(_SIGNATURES)
 
 
 def _load():
@@ -397,6 +414,8 @@ def _load():
     lib.nerftex_curved_light_patch_infer_scratch_bytes.restype = _sz
     lib.nerftex_sh_light_scratch_bytes.argtypes = [_u32]
     lib.nerftex_sh_light_scratch_bytes.restype = _sz
+    lib.nerftex_envmap_fit_scratch_bytes.argtypes = [_u32, _u32]
+    lib.nerftex_envmap_fit_scratch_bytes.restype = _sz
     for name, args in _SIGNATURES.items():
         fn = getattr(lib, name)  # AttributeError here == a symbol the header declares is not exported
         fn.argtypes = args

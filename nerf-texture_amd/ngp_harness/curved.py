@@ -609,6 +609,7 @@ class CurvedField(torch.nn.Module):
 
             self.light_net = SHLightNet(input_dim=geo_feat_dim, white_light=white_light, use_specular=use_specular)  # (NeRFNetwork's keywords and defaults, :61)
             self.light_visual_mode, self.smooth_grad_weight = "Full", 1e-1
+            self.shade_visibility = True  # network_curvedfield.py:86: under imported lighting in eval, one lighting per visibility probe (read by _forward_light only)
             self.encoder_dir = self.color_net = None
             return
         self.encoder_dir = SHEncoder(input_dim=3, degree=dir_degree)
@@ -1400,7 +1401,13 @@ class CurvedField(torch.nn.Module):
             coarse = normal_coarse / (normal_coarse.norm(dim=-1, keepdim=True) + 1e-5)
             normal = self.fc_weight * normal + (1 - self.fc_weight) * coarse
             normal = normal / (normal.norm(dim=-1, keepdim=True) + 1e-5)
-        full, specular, diffuse, albedo = self.light_net(geo, normal, d, mask=h_mask)
+        relight = {}
+        if not self.training and getattr(self.light_net, "import_envmap", False):
+            # the probe of an imported lighting is chosen by the coarse normal (:296, :339, :341: shade_visibility = self.shade_visibility or
+            # self.training); the head reads neither outside eval with an import, so only then are they handed over
+            relight = dict(normal_secondary=normal_coarse / (normal_coarse.norm(dim=-1, keepdim=True) + 1e-5),
+                           shade_visibility=bool(getattr(self, "shade_visibility", True)))
+        full, specular, diffuse, albedo = self.light_net(geo, normal, d, mask=h_mask, **relight)
         modes = {"Full": full, "Specular": specular, "Diffuse": diffuse, "Albedo": albedo}
         if not self.training and self.light_visual_mode not in modes:
             raise ValueError(f"CurvedField.light_visual_mode is one of {sorted(modes)}, but got {self.light_visual_mode!r}")
@@ -1455,11 +1462,27 @@ class CurvedField(torch.nn.Module):
         net = self.light_net
         stamp = (self.light_model, self.light_visual_mode, float(net.gamma), bool(net.use_specular), bool(net.fused), net.envSHs.data_ptr(), tuple(net.envSHs.shape))
         if not getattr(self, "fused_light_infer", False):
-            return stamp + (False,)
+            return stamp + (False,) + self._relight_stamp()
         # the fused chain bakes in the normal net's table and the packed copy of its weights: the table's storage and every parameter's version
         nn = self.normal_net
         return stamp + (True, nn.encoder.embeddings.data_ptr(), nn.encoder.offsets.data_ptr(),
-                        tuple((q.data_ptr(), q._version) for q in list(nn.phi_net.parameters()) + list(nn.theta_net.parameters())))
+                        tuple((q.data_ptr(), q._version) for q in list(nn.phi_net.parameters()) + list(nn.theta_net.parameters()))) + self._relight_stamp()
+
+    def _lighting(self):
+        """The lighting the head shades with: light_net.lighting() -- the imported coefficients in eval once switched on, envSHs otherwise (and
+        of a head that knows no imported lighting)."""
+        net = self.light_net
+        return net.lighting() if hasattr(net, "lighting") else net.envSHs
+
+    def _relight_stamp(self):
+        """_light_stamp()'s share of an imported lighting, appended only once one has been loaded (the stamp without one is unchanged): the
+        storage and shape of the lighting in effect, the import switch, shade_visibility and the probe tables' storage."""
+        net = self.light_net
+        if getattr(net, "envSHs_import", None) is None:
+            return ()
+        env = self._lighting()
+        return (env.data_ptr(), tuple(env.shape), bool(net.import_envmap), bool(getattr(self, "shade_visibility", True)),
+                0 if net.envSHs_import_vis is None else net.envSHs_import_vis.data_ptr(), 0 if net.probes is None else net.probes.data_ptr())
 
     # ---- the eight fused inference chains: what each asks of a call (the entries refuse everything else) ----
     _SIGMA_NET, _COLOR_NET, _BRDF_NET = (48, 32, 2, 16), (32, 64, 3, 3), (16, 64, 3, 5)  # (in, hidden, layers, out) the entries' kernels are built for
@@ -1538,7 +1561,7 @@ class CurvedField(torch.nn.Module):
         """... and the SH light model's three: sigma net, the head -- the normal net's packed block, the BRDF net, the lighting, the flags and the
         output it shows (in training always "Full"), shading_normal (fp32 [B,3] or None) -- and `_infer_rows`; the weights and the lighting."""
         net = self.light_net
-        br, env = net.brdf_layer, net.envSHs.detach()
+        br, env = net.brdf_layer, self._lighting().detach()
         ws_h, wb_h, nw, nb = self._infer_light_weights()
         mode = "Full" if self.training else self.light_visual_mode
         return dict(normal_weights=ptr(nw), normal_biases=ptr(nb), normal_hidden=16, normal_layers=2, brdf_weights=ptr(wb_h), brdf_in=br.input_dim,
@@ -1635,13 +1658,15 @@ class CurvedField(torch.nn.Module):
         if not (getattr(self, "light_model", None) == "SH" and getattr(self, "fused_light_infer", False)):
             return False
         nn, net = self.normal_net, self.light_net
-        br = net.brdf_layer
+        if not self.training and getattr(net, "import_envmap", False) and net.envSHs_import is not None and getattr(self, "shade_visibility", True):
+            return False  # per-probe lighting (or its refusal without tables) is forward()'s: the chains' descriptors hold one lighting
+        br, env = net.brdf_layer, self._lighting()
         return (bool(net.fused) and nn is not None and not nn.bound_output and (self.training or self.light_visual_mode in LIGHT_VISUAL)
                 and x.is_cuda and br.dtype == torch.float16 and (br.input_dim, br.hidden_dim, br.num_layers, br.output_dim) == self._BRDF_NET
                 and (nn.low_freq_band_len_x, nn.low_freq_band_len_z) == (16, 12)
                 and [tuple(l.W.shape) for l in nn.phi_net.layers] == [(16, 20), (16, 16), (1, 16)]
                 and [tuple(l.W.shape) for l in nn.theta_net.layers] == [(16, 28), (16, 16), (1, 16)]
-                and net.envSHs.shape[0] >= 9 and net.envSHs.shape[1] in (1, 3) and net.envSHs.dtype == torch.float32)
+                and env.shape[0] >= 9 and env.shape[1] in (1, 3) and env.dtype == torch.float32)
 
     def _infer_light_import_fused(self, x, d):
         """Whether nerftex_curved_light_import_infer serves this call: _infer_light_fused()'s conditions without the neighbour search's and the
@@ -1826,7 +1851,9 @@ class CurvedField(torch.nn.Module):
         light_model="SH": forward(x, d) on all rows unless `fused_light_infer` is set (default False) -- then the light model's own chain,
         nerftex_curved_light_infer, under the same rows contract: sigma and the mask are forward()'s bit for bit, the shading normal and the
         colour follow forward()'s arithmetic at its rounding points; over imported maps, nerftex_curved_light_import_infer
-        (DESIGN.md 4.17), and over the maps on an imported mesh nerftex_curved_light_shape_infer.
+        (DESIGN.md 4.17), and over the maps on an imported mesh nerftex_curved_light_shape_infer.  The lit chains shade with
+        light_net.lighting(), so a uniform imported lighting goes through them; per-probe lighting (`shade_visibility` with an imported
+        lighting in eval) is forward()'s.
         An imported patch (import_patch): nerftex_curved_patch_infer, and for the SH-lit field with the switch set
         nerftex_curved_light_patch_infer, under the same contract."""
         row = self._infer_row(x, d)

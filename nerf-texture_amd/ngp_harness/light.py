@@ -15,7 +15,17 @@ Two paths with the same arithmetic:
 
 As the reference EXECUTES it (sh_light_model.py:594-597): `order_coeff` is built from the first dimension of the [1, N, C] view of
 envSHs, i.e. arange(0, 1), so every band's glossiness attenuation is exp(0) = 1: the glossiness does not change the value and the
-gradient into brdf[:, 4] is exactly zero.  Out of scope: imported environment maps, visibility probes, the SG and Envmap models.
+gradient into brdf[:, 4] is exactly zero.
+
+Relighting (the reference's load_envmap :625, switch_envmap_import :675, the eval branch of forward :561-571):
+  envmap_to_sh      EnvMap2SH (:730): SH coefficients fitted to an equirectangular [H, W, 3] map.  On the GPU one call of nerftex_envmap_fit
+                    (csrc/envmap.inc: the map's moments in one launch, the whole Adam loop in one wave); `fused = False` or a CPU tensor runs the
+                    reference's loop op by op with torch.optim.Adam.
+  load_envmap       takes such a map, or fitted coefficients (the reference's .npy), and optionally the reference's _vis.npz tables: one
+                    lighting per probe direction, chosen per sample by its coarse normal (`shade_visibility`); fused: nerftex_sh_light_probe_forward.
+  lighting()        the coefficients in effect: the imported ones in eval once switched on, envSHs otherwise.  Training never sees the import.
+Out of scope: COMPUTING the probe tables (load_envmap_with_visibility's branch without a file: a stochastic Adam fit over
+rotate_coeff_by_normal's band rotations), the reference's `euler` lighting rotation, reading image files, the SG and Envmap models.
 """
 import math
 
@@ -58,7 +68,11 @@ def sh_light_shade(brdf, normals, view_dirs, env_shs, use_specular=True, gamma=G
     """SH_EnvmapMaterialNet.forward behind the BRDF MLP (:579-616), op by op.  brdf [B, >= 5] (half under autocast: the sigmoids then are
     half tensors), normals / view_dirs [B, 3], env_shs [(order + 1)^2, C] -> (color, specular, diffuse, albedo), each [B, 3]; rows with
     mask == False are 0 in all four."""
-    envs = env_shs[None]
+    return _shade(brdf, normals, view_dirs, env_shs[None], use_specular, gamma, mask)
+
+
+def _shade(brdf, normals, view_dirs, envs, use_specular, gamma, mask):
+    """sh_light_shade behind its [1, N, C] view of the lighting; sh_light_shade_probes hands it one lighting per row, [B, N, C]."""
     albedo = torch.sigmoid(brdf[..., :3])
     specular = torch.sigmoid(brdf[..., 3:4])
     glossiness = torch.nn.functional.softplus(brdf[..., 4:5]) + 1.0
@@ -68,7 +82,10 @@ def sh_light_shade(brdf, normals, view_dirs, env_shs, use_specular=True, gamma=G
         rays_d = _normalize(view_dirs)
         cos_theta = -(rays_d * normals).sum(dim=-1, keepdim=True)
         reflect_d = _normalize(2 * cos_theta * normals + rays_d)
-        order_coeff = torch.arange(0, envs.shape[0], device=envs.device)[:, None]  # (the [1, N, C] view's first dimension: arange(0, 1))
+        # (the [1, N, C] view's first dimension: arange(0, 1).  Under per-probe lighting the reference's view is [B, 9, 3] and its arange(0, B)
+        # attenuates the specular lighting of row b by exp(-floor(sqrt(b))^2 / 2 / glossiness): the sample's position in its batch.  Not followed:
+        # a row is lit as the first row of a batch is.)
+        order_coeff = torch.arange(0, 1, device=envs.device)[:, None]
         order_coeff = torch.pow(order_coeff, 0.5).floor()
         sh_coeff = torch.exp(-order_coeff * order_coeff / 2 / glossiness.float())[..., None] * envs[:, :9, :3]
         specular = specular * irradiance(sh_coeff, reflect_d)
@@ -84,6 +101,87 @@ def sh_light_shade(brdf, normals, view_dirs, env_shs, use_specular=True, gamma=G
     if mask is not None:
         out = tuple(torch.where(mask.unsqueeze(-1), o, torch.zeros_like(o)) for o in out)
     return out
+
+
+def sh_light_shade_probes(brdf, normals, view_dirs, normals_secondary, probes, probe_shs, use_specular=True, gamma=GAMMA, mask=None):
+    """The head under per-probe imported lighting, op by op: the probe choice of sh_light_model.py:566-567 -- argmax over the [B, K] products of
+    the secondary normal with the probe directions, the [B, 9, 3] gather -- and then sh_light_shade's arithmetic with one lighting per row."""
+    prob_idx = (normals_secondary[:, None] * probes[None]).sum(dim=-1).argmax(dim=-1)
+    return _shade(brdf, normals, view_dirs, probe_shs[prob_idx], use_specular, gamma, mask)
+
+
+def sh_to_envmap(env_shs, H, W):
+    """SH2Envmap (:712-727) op by op: [>= 9, C] coefficients -> the [H, W, C] equirectangular map (Mitsuba's convention) and its directions."""
+    phi, theta = torch.meshgrid([torch.linspace(0.0, math.pi, H), torch.linspace(-0.5 * math.pi, 1.5 * math.pi, W)], indexing="ij")
+    viewdirs = torch.stack([torch.cos(theta) * torch.sin(phi), torch.cos(phi), torch.sin(theta) * torch.sin(phi)], dim=-1)
+    viewdirs = viewdirs.to(device=env_shs.device, dtype=env_shs.dtype).reshape(-1, 3)
+    rgb = (env_shs[None, :9, :3] * svox2_basis9(viewdirs)[..., None]).sum(dim=1)
+    return rgb.reshape(H, W, rgb.shape[-1]), viewdirs.reshape(H, W, 3)
+
+
+def image_to_envmap(array, force_white=True):
+    """image2envmap's arithmetic (:769-791) on an array ALREADY in [0, 1] (the reference divides the 8-bit image by 255): ** (1 / 1.24), then the
+    channel mean in every channel under force_white.  It does not read files and does not do the reference's cv2 resize of images taller than
+    200 rows: hand it the array at the size it is to be fitted at."""
+    import numpy as np
+
+    envmap = np.asarray(array)[..., :3] ** (1 / 1.24)
+    if force_white:
+        envmap[..., :] = envmap.mean(axis=-1, keepdims=True)
+    return envmap
+
+
+def _envmap_fit_reference(envmap, n_sh, min_loss, max_steps, min_steps, lr):
+    """EnvMap2SH's loop (:738-760) op by op, without its logging."""
+    H, W = envmap.shape[:2]
+    env_shs = nn.Parameter(torch.zeros(n_sh, 3, dtype=envmap.dtype, device=envmap.device))
+    optimizer = torch.optim.Adam([env_shs], lr=lr)
+    steps, value = 0, float("nan")
+    for step in range(max_steps):
+        optimizer.zero_grad()
+        env_map, _ = sh_to_envmap(env_shs, H, W)
+        loss = torch.mean((env_map - envmap) * (env_map - envmap))
+        loss.backward()
+        optimizer.step()
+        steps, value = step + 1, loss.item()
+        if value < min_loss and step > min_steps:
+            break
+    return env_shs.detach(), {"steps": steps, "loss": value}
+
+
+def envmap_to_sh(envmap, sh_order=3, *, min_loss=1e-5, max_steps=5000, min_steps=2000, lr=1e-2, fused=None):
+    """EnvMap2SH (:730-766): envmap [H, W, 3] (array or tensor) -> (envSHs [(sh_order + 1)^2, 3] on the map's device, info) with info["steps"]
+    the optimizer updates made and info["loss"] the loss of the last step (of the parameters before its update, as the reference prints it).
+    A GPU tensor goes through nerftex_envmap_fit -- two launches, and one wait here for the two numbers of info; fused = False or a CPU tensor
+    runs the reference's loop op by op."""
+    envmap = torch.as_tensor(envmap)
+    if envmap.dim() != 3 or envmap.shape[2] != 3 or envmap.shape[0] * envmap.shape[1] == 0:
+        raise ValueError(f"envmap_to_sh: an [H, W, 3] map, but got {tuple(envmap.shape)}")
+    if sh_order < 2:
+        raise ValueError(f"envmap_to_sh: the map is fitted with the SH bands 0..2, sh_order must be at least 2 (got {sh_order})")
+    n_sh = (sh_order + 1) ** 2
+    if fused is None:
+        fused = envmap.is_cuda
+    if not fused:
+        return _envmap_fit_reference(envmap if envmap.dtype == torch.float64 else envmap.float(), n_sh, min_loss, max_steps, min_steps, lr)
+    if not envmap.is_cuda:
+        raise RuntimeError("envmap_to_sh(fused=True) needs the map on the GPU: there is no fused CPU path")
+    import ctypes
+
+    from nerftex_hip import EnvmapFitDesc, check, lib, ptr, stream
+
+    envmap = envmap.contiguous().float()
+    H, W = envmap.shape[:2]
+    dev = envmap.device
+    phi, theta = torch.linspace(0.0, math.pi, H).to(dev), torch.linspace(-0.5 * math.pi, 1.5 * math.pi, W).to(dev)  # (as sh_to_envmap: made on the host)
+    env_shs = torch.empty(n_sh, 3, dtype=torch.float32, device=dev)
+    steps, loss = torch.zeros(1, dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.float64, device=dev)
+    scratch = torch.empty(lib.nerftex_envmap_fit_scratch_bytes(H, W) // 8, dtype=torch.float64, device=dev)
+    desc = EnvmapFitDesc(envmap=ptr(envmap), phi=ptr(phi), theta=ptr(theta), H=H, W=W, n_sh=n_sh, max_steps=int(max_steps), min_steps=int(min_steps),
+                         lr=float(lr), min_loss=float(min_loss), env_shs=ptr(env_shs), steps_run=ptr(steps), final_loss=ptr(loss), scratch=ptr(scratch),
+                         scratch_bytes=scratch.numel() * 8)
+    check(lib.nerftex_envmap_fit(ctypes.byref(desc), stream()))
+    return env_shs, {"steps": int(steps.item()), "loss": float(loss.item())}
 
 
 class _SHLight(torch.autograd.Function):
@@ -136,6 +234,27 @@ class _SHLight(torch.autograd.Function):
         return g_brdf[:, :brdf.shape[1]], None, None, g_env, None, None, None
 
 
+def _shade_probes_fused(brdf, normals, dirs, normals_secondary, probes, probe_shs, mask, gamma, use_specular):
+    """nerftex_sh_light_probe_forward: one launch, no gradient (imported lighting is eval only)."""
+    import ctypes
+
+    from nerftex_hip import SH_LIGHT_SPECULAR, SHLightProbeDesc, check, lib, ptr, stream
+
+    brdf = brdf.detach()
+    if brdf.stride(1) != 1 or brdf.stride(0) < 5:
+        brdf = brdf.contiguous()
+    normals, dirs, n2 = normals.detach().contiguous().float(), dirs.detach().contiguous().float(), normals_secondary.detach().contiguous().float()
+    probes, tables = probes.contiguous().float(), probe_shs.contiguous().float()
+    mask_b = None if mask is None else mask.contiguous().view(torch.uint8)
+    B = brdf.shape[0]
+    out = torch.empty(4, B, 3, dtype=torch.float32, device=brdf.device)
+    desc = SHLightProbeDesc(brdf=ptr(brdf), brdf_stride=int(brdf.stride(0)) if B else 16, normals=ptr(normals), dirs=ptr(dirs), normals_secondary=ptr(n2),
+                            probes=ptr(probes), probe_shs=ptr(tables), K=probes.shape[0], mask=ptr(mask_b), B=B, gamma=float(gamma),
+                            flags=SH_LIGHT_SPECULAR if use_specular else 0, color=ptr(out[0]), specular=ptr(out[1]), diffuse=ptr(out[2]), albedo=ptr(out[3]))
+    check(lib.nerftex_sh_light_probe_forward(ctypes.byref(desc), stream()))
+    return out.unbind(0)
+
+
 class SHLightNet(nn.Module):
     """SH_EnvmapMaterialNet (sh_light_model.py:509-552): envSHs zeros with row 0 = 3; sh_pow_num / sh_s under the reference's names, shapes
     and dtypes so that its state_dict loads -- the reference never reads them (its fast_sh_sum is commented out as buggy, :506) and neither
@@ -157,20 +276,85 @@ class SHLightNet(nn.Module):
         self.in_pad = (input_dim + 15) // 16 * 16
         self.brdf_layer = FFMLP(input_dim=self.in_pad, output_dim=5, hidden_dim=64, num_layers=3)  # albedo[3], specular[1], glossiness[1]
         self.fused = True
+        # imported lighting under the reference's names (:546-548, :652): not part of the checkpoint, as there
+        self.import_envmap = False
+        for name in ("envSHs_import", "envSHs_import_vis", "probes"):
+            self.register_buffer(name, None, persistent=False)
+
+    def load_envmap(self, envmap=None, *, env_shs=None, env_shs_vis=None, probes=None, force_white=True):
+        """load_envmap (:625-645) without the files: an [H, W, 3] array in [0, 1] that is tone-mapped (image_to_envmap) and fitted (envmap_to_sh),
+        or fitted coefficients env_shs [N >= 9, 3] (the reference's .npy); optionally the contents of its _vis.npz, env_shs_vis [K, 9, 3] and
+        probes [K, 3], 1 <= K <= 256.  Switches the imported lighting on and returns True; ValueError for shapes that do not match."""
+        dev = self.envSHs.device
+        if (envmap is None) == (env_shs is None):
+            raise ValueError("SHLightNet.load_envmap: give either an [H, W, 3] map or fitted coefficients env_shs [N, 3]")
+        if (env_shs_vis is None) != (probes is None):
+            raise ValueError("SHLightNet.load_envmap: env_shs_vis [K, 9, 3] and probes [K, 3] come together")
+        if env_shs_vis is not None:
+            env_shs_vis = torch.as_tensor(env_shs_vis).detach().to(device=dev, dtype=torch.float32)
+            probes = torch.as_tensor(probes).detach().to(device=dev, dtype=torch.float32)
+            K = probes.shape[0] if probes.dim() == 2 else 0
+            if tuple(probes.shape) != (K, 3) or tuple(env_shs_vis.shape) != (K, 9, 3) or not 1 <= K <= 256:
+                raise ValueError(f"SHLightNet.load_envmap: probes [K, 3] and env_shs_vis [K, 9, 3] with 1 <= K <= 256, but got {tuple(probes.shape)} "
+                                 f"and {tuple(env_shs_vis.shape)}")
+        if envmap is not None:
+            envmap = torch.as_tensor(envmap)
+            if envmap.dim() != 3 or envmap.shape[2] != 3 or envmap.shape[0] * envmap.shape[1] == 0:
+                raise ValueError(f"SHLightNet.load_envmap: an [H, W, 3] map, but got {tuple(envmap.shape)}")
+            tone = torch.from_numpy(image_to_envmap(envmap.detach().cpu().numpy().copy(), force_white=force_white))
+            env_shs, _ = envmap_to_sh(tone.to(device=dev, dtype=torch.float32), sh_order=self.sh_order)
+        else:
+            env_shs = torch.as_tensor(env_shs).detach().to(device=dev, dtype=torch.float32)
+            if env_shs.dim() != 2 or env_shs.shape[0] < 9 or env_shs.shape[1] != 3:
+                raise ValueError(f"SHLightNet.load_envmap: env_shs is [N >= 9, 3], but got {tuple(env_shs.shape)}")
+        self.envSHs_import = env_shs.contiguous().clone()
+        self.envSHs_import_vis = None if env_shs_vis is None else env_shs_vis.contiguous().clone()
+        self.probes = None if probes is None else probes.contiguous().clone()
+        self.import_envmap = True
+        return True
+
+    def switch_envmap_import(self):
+        """switch_envmap_import (:675-681): toggles the imported lighting and returns the new state; False while nothing is loaded."""
+        self.import_envmap = False if self.envSHs_import is None else not self.import_envmap
+        return self.import_envmap
+
+    def _imported(self):
+        return bool(self.import_envmap) and not self.training and self.envSHs_import is not None
+
+    def lighting(self):
+        """The coefficients in effect (:561-571): envSHs_import in eval with the import switched on, envSHs otherwise."""
+        return self.envSHs_import if self._imported() else self.envSHs
+
+    def probe_lighting(self, shade_visibility=True):
+        """Whether a forward with this shade_visibility lights every sample by its probe: eval, imported lighting, the tables loaded."""
+        return bool(shade_visibility) and self._imported() and self.envSHs_import_vis is not None
 
     def _fused(self, brdf, normals):
         return (self.fused and brdf.is_cuda and brdf.dtype == torch.float16 and normals.dtype == torch.float32 and torch.is_autocast_enabled()
                 and torch.get_autocast_dtype("cuda") == torch.float16)
 
-    def forward(self, geo_feat, normals, view_dirs, mask=None, gamma=None):
+    def forward(self, geo_feat, normals, view_dirs, mask=None, gamma=None, normal_secondary=None, shade_visibility=False):
+        probe = self.probe_lighting(shade_visibility)
+        if shade_visibility and self._imported() and not probe:
+            raise RuntimeError("SHLightNet: shade_visibility asks for one imported lighting per visibility probe, but no probe tables are loaded: "
+                               "give them to load_envmap(env_shs_vis=, probes=), or set field.shade_visibility = False to light every sample "
+                               "with envSHs_import")
+        if probe and normal_secondary is None:
+            raise ValueError("SHLightNet: shade_visibility needs normal_secondary, the normal the probe is chosen by")
         prefix = geo_feat.shape[:-1]
         geo_feat, normals, view_dirs = geo_feat.reshape(-1, geo_feat.shape[-1]), normals.reshape(-1, 3), view_dirs.reshape(-1, 3)
         mask = None if mask is None else mask.reshape(-1)
         ones = torch.ones(geo_feat.shape[0], self.in_pad - self.input_dim, dtype=geo_feat.dtype, device=geo_feat.device)
         brdf = self.brdf_layer(torch.cat([geo_feat, ones], dim=-1))
         gamma = self.gamma if gamma is None else gamma
-        if self._fused(brdf, normals):
-            out = _SHLight.apply(brdf, normals, view_dirs, self.envSHs, mask, gamma, self.use_specular)
+        if probe:
+            n2 = normal_secondary.reshape(-1, 3)
+            if self._fused(brdf, normals):
+                out = _shade_probes_fused(brdf, normals, view_dirs, n2, self.probes, self.envSHs_import_vis, mask, gamma, self.use_specular)
+            else:
+                out = sh_light_shade_probes(brdf, normals, view_dirs, n2, self.probes, self.envSHs_import_vis, self.use_specular, gamma, mask)
+        elif self._fused(brdf, normals):
+            out = _SHLight.apply(brdf, normals, view_dirs, self.lighting(), mask, gamma, self.use_specular)
         else:
-            out = sh_light_shade(brdf, normals, view_dirs, self.envSHs, self.use_specular, gamma, mask)
+            out = sh_light_shade(brdf, normals, view_dirs, self.lighting(), self.use_specular, gamma, mask)
         return tuple(o.reshape(*prefix, 3) for o in out)
