@@ -1351,6 +1351,35 @@ size_t nerftex_curved_light_patch_infer_scratch_bytes(uint32_t B);
 int nerftex_curved_light_patch_infer(const nerftex_curved_light_patch_infer_desc* d, void* stream);
 
 /* -------------------------------------------------------------------------
+ * Extension: relighting through the four lit chains above -- one imported lighting per visibility probe (the reference's shade_visibility, its
+ * default under an imported environment map) and its `euler` lighting rotation (network_curvedfield.py:303-308).  Each _relit entry is its
+ * chain's entry with a second, optional descriptor; the chain's own descriptor, scratch query, launches in front of the closing kernel and rows
+ * contract are unchanged.  r == NULL, or K == 0 with a NULL rotation: the chain's entry itself, the same launches, the same bits (the plain
+ * entries are this case).  Otherwise the closing launch is a second kernel that, per unmarked live row inside the mask,
+ *   normalises the raw coarse normal the back half holds twice as n / (|n| + 1e-5) in fp32 (tools/map.py:720, network_curvedfield.py:295),
+ *   rotation: rotates the view direction, the shading normal the light mid wrote and that coarse normal by the 3 x 3 matrix -- einsum('ab,nb->na')
+ *             under fp16 autocast: matrix and vector rounded to half, the three products added in fp32 in ascending b, the sum rounded to half,
+ *   K > 0:    picks the probe as nerftex_sh_light_probe_forward does ((x px + y py) + z pz in fp32 on the (rotated) coarse normal, the lowest
+ *             index among equal maxima) and shades with that probe's table; d->env_shs is then not read for shading,
+ *   shades with the row function of nerftex_sh_light_forward.
+ * shading_normal, where asked for, stays what the light mid wrote: the UNROTATED shading normal.  rotation is read on the device when the kernel
+ * runs: new values in the same buffer need no new call sequence (a captured call replays with them).  Nothing is allocated; capturable.
+ * NERFTEX_ERR_INVALID with a message, before anything is launched, behind the chain's own shape refusals and in front of its B == 0 return:
+ * K > 256 (the probe kernel's limit); K > 0 with a NULL probes or probe_shs; K > 0 with n_color != 3; a non-NULL r with eval == 0 (imported
+ * lighting and the rotation are eval-only, as in the reference); a rotation that is not 4-byte aligned.
+ * ------------------------------------------------------------------------- */
+typedef struct nerftex_relight_desc { /* device pointers */
+    const float* probes;               /* [K,3] fp32 probe directions, or NULL with K == 0                                        */
+    const float* probe_shs;            /* [K,9,3] fp32: one lighting per probe                                                    */
+    uint32_t K;                        /* 0: no probes (the chain descriptor's env_shs lights every row)                          */
+    const float* rotation;             /* [9] fp32 row-major, 4-byte aligned, or NULL: no rotation                                */
+} nerftex_relight_desc;
+int nerftex_curved_light_infer_relit(const nerftex_curved_light_infer_desc* d, const nerftex_relight_desc* r, void* stream);
+int nerftex_curved_light_import_infer_relit(const nerftex_curved_light_import_infer_desc* d, const nerftex_relight_desc* r, void* stream);
+int nerftex_curved_light_shape_infer_relit(const nerftex_curved_light_shape_infer_desc* d, const nerftex_relight_desc* r, void* stream);
+int nerftex_curved_light_patch_infer_relit(const nerftex_curved_light_patch_infer_desc* d, const nerftex_relight_desc* r, void* stream);
+
+/* -------------------------------------------------------------------------
  * Extension: the SH light head of the curved field -- SH_EnvmapMaterialNet.forward behind its BRDF MLP (nerf/sh_light_model.py:554-616) -- as one
  * streaming kernel per direction instead of ~40 framework ops per sample batch, the framework's arithmetic at its rounding points:
  *   albedo = half(sigmoid(brdf[:, :3])), spec_w = half(sigmoid(brdf[:, 3]))              (fp32 sigmoid narrowed to half)

@@ -75,7 +75,9 @@ extern "C" int nerftex_curved_patch_infer(const nerftex_curved_patch_infer_desc*
 
 extern "C" size_t nerftex_curved_light_patch_infer_scratch_bytes(uint32_t B) { return LightPatchScratch(nullptr, B).carve.at; }
 
-extern "C" int nerftex_curved_light_patch_infer(const nerftex_curved_light_patch_infer_desc* d, void* stream) {
+extern "C" int nerftex_curved_light_patch_infer(const nerftex_curved_light_patch_infer_desc* d, void* stream) { return nerftex_curved_light_patch_infer_relit(d, nullptr, stream); }
+
+extern "C" int nerftex_curved_light_patch_infer_relit(const nerftex_curved_light_patch_infer_desc* d, const nerftex_relight_desc* r, void* stream) {
     clear_error();
     if (!batch_ok(d, "curved_light_patch_infer")) return NERFTEX_ERR_INVALID;
     if (!patch_points_ok(d, "curved_light_patch_infer")) return NERFTEX_ERR_INVALID;
@@ -86,7 +88,7 @@ extern "C" int nerftex_curved_light_patch_infer(const nerftex_curved_light_patch
                   "bands, sigma net 48 -> 32 x 2 -> 16, normal nets 16 wide with 2 hidden layers, BRDF net 16 -> 64 x 3 -> 5)");
         return NERFTEX_ERR_INVALID;
     }
-    if (!light_head_ok(d, "curved_light_patch_infer")) return NERFTEX_ERR_INVALID;
+    if (!light_head_ok(d, "curved_light_patch_infer") || !relight_ok(d, r, "curved_light_patch_infer")) return NERFTEX_ERR_INVALID;
     if (d->B == 0) return NERFTEX_OK;
     const LightPatchScratch sc(d->scratch, d->B);
     if (!d->xyz || !d->dirs || !d->geom || !d->features || !d->lit || !d->sigma_weights || !d->normal_weights || !d->normal_biases || !d->brdf_weights ||
@@ -112,5 +114,5 @@ extern "C" int nerftex_curved_light_patch_infer(const nerftex_curved_light_patch
     if (rc != NERFTEX_OK) return rc;
     if ((rc = ffmlp_inference_rows(sc.xin, d->sigma_weights, B, 48, 32, 2, sc.h, units, rpu, st)) != NERFTEX_OK) return rc;
     static const char* const labels[2] = {"curved_light_patch_infer(mid)", "curved_light_patch_infer(out)"};
-    return curved_light_back_half<1>(d, sc.h, sc.xin, sc.n_lbc, sc.normal, sc.tbn, nullptr, nullptr, sc.mask, sc.back, labels, stream);
+    return curved_light_back_half<1>(d, r, sc.h, sc.xin, sc.n_lbc, sc.normal, sc.tbn, nullptr, nullptr, sc.mask, sc.back, labels, stream);
 }

@@ -89,7 +89,9 @@ extern "C" int nerftex_planar_light_lookup(const float* xyz, const float* map, c
 
 extern "C" size_t nerftex_curved_light_import_infer_scratch_bytes(uint32_t B) { return LightImportScratch(nullptr, B).carve.at; }
 
-extern "C" int nerftex_curved_light_import_infer(const nerftex_curved_light_import_infer_desc* d, void* stream) {
+extern "C" int nerftex_curved_light_import_infer(const nerftex_curved_light_import_infer_desc* d, void* stream) { return nerftex_curved_light_import_infer_relit(d, nullptr, stream); }
+
+extern "C" int nerftex_curved_light_import_infer_relit(const nerftex_curved_light_import_infer_desc* d, const nerftex_relight_desc* r, void* stream) {
     clear_error();
     if (!batch_ok(d, "curved_light_import_infer")) return NERFTEX_ERR_INVALID;
     if (d->n_features != 16 || d->n_phi != 8 || d->n_freqs != kInferFreqs || d->sigma_in != 48 || d->sigma_hidden != 32 || d->sigma_layers != 2 ||
@@ -99,7 +101,7 @@ extern "C" int nerftex_curved_light_import_infer(const nerftex_curved_light_impo
                   "sigma net 48 -> 32 x 2 -> 16, normal nets 16 wide with 2 hidden layers, BRDF net 16 -> 64 x 3 -> 5)");
         return NERFTEX_ERR_INVALID;
     }
-    if (!light_head_ok(d, "curved_light_import_infer")) return NERFTEX_ERR_INVALID;
+    if (!light_head_ok(d, "curved_light_import_infer") || !relight_ok(d, r, "curved_light_import_infer")) return NERFTEX_ERR_INVALID;
     if (!map_extent_ok("curved_light_import_infer", true, d->map_h, d->map_w)) return NERFTEX_ERR_INVALID;
     if (d->n_patches == 0 || d->n_patches > (1u << 24)) {
         set_error("curved_light_import_infer: between 1 and 2^24 patch frames (an id is read from an fp32 texel), but got %u", d->n_patches);
@@ -136,5 +138,5 @@ extern "C" int nerftex_curved_light_import_infer(const nerftex_curved_light_impo
     if (rc != NERFTEX_OK) return rc;
     if ((rc = ffmlp_inference_rows(sc.xin, d->sigma_weights, B, 48, 32, 2, sc.h, units, rpu, st)) != NERFTEX_OK) return rc;
     static const char* const labels[2] = {"curved_light_import_infer(mid)", "curved_light_import_infer(out)"};
-    return curved_light_back_half<2>(d, sc.h, sc.xin, sc.n_lbc, sc.normal, sc.local_tbn, sc.sample_tbn, nullptr, sc.mask, sc.back, labels, stream);
+    return curved_light_back_half<2>(d, r, sc.h, sc.xin, sc.n_lbc, sc.normal, sc.local_tbn, sc.sample_tbn, nullptr, sc.mask, sc.back, labels, stream);
 }

@@ -25,7 +25,9 @@ struct LightShapeScratch {
 
 extern "C" size_t nerftex_curved_light_shape_infer_scratch_bytes(uint32_t B) { return LightShapeScratch(nullptr, B).carve.at; }
 
-extern "C" int nerftex_curved_light_shape_infer(const nerftex_curved_light_shape_infer_desc* d, void* stream) {
+extern "C" int nerftex_curved_light_shape_infer(const nerftex_curved_light_shape_infer_desc* d, void* stream) { return nerftex_curved_light_shape_infer_relit(d, nullptr, stream); }
+
+extern "C" int nerftex_curved_light_shape_infer_relit(const nerftex_curved_light_shape_infer_desc* d, const nerftex_relight_desc* r, void* stream) {
     clear_error();
     if (!front_batch_ok(d, "curved_light_shape_infer")) return NERFTEX_ERR_INVALID;  // NULL descriptor, B % 128, n_verts, K
     if (d->n_features != 16 || d->n_phi != 8 || d->sigma_in != 48 || d->sigma_hidden != 32 || d->sigma_layers != 2 || d->sigma_out != 16 ||
@@ -34,7 +36,7 @@ extern "C" int nerftex_curved_light_shape_infer(const nerftex_curved_light_shape
                   "48 -> 32 x 2 -> 16, normal nets 16 wide with 2 hidden layers, BRDF net 16 -> 64 x 3 -> 5)");
         return NERFTEX_ERR_INVALID;
     }
-    if (!light_head_ok(d, "curved_light_shape_infer")) return NERFTEX_ERR_INVALID;
+    if (!light_head_ok(d, "curved_light_shape_infer") || !relight_ok(d, r, "curved_light_shape_infer")) return NERFTEX_ERR_INVALID;
     if (!d->tracer || d->n_faces != raytracer_triangles(d->tracer)) {
         set_error("curved_light_shape_infer: a raytracer is required and face_uv must hold its %u faces, but got %u", raytracer_triangles(d->tracer), d->n_faces);
         return NERFTEX_ERR_INVALID;
@@ -78,5 +80,5 @@ extern "C" int nerftex_curved_light_shape_infer(const nerftex_curved_light_shape
         return rc;
     if ((rc = ffmlp_inference_rows(sc.f.xin, d->sigma_weights, B, 48, 32, 2, sc.f.h, units, rpu, st)) != NERFTEX_OK) return rc;
     static const char* const labels[2] = {"curved_light_shape_infer(mid)", "curved_light_shape_infer(out)"};
-    return curved_light_back_half<3>(d, sc.f.h, sc.f.xin, sc.n_lbc, sc.f.normal, sc.local_tbn, sc.sample_tbn, sc.new_tbn, sc.f.mask, sc.back, labels, stream);
+    return curved_light_back_half<3>(d, r, sc.f.h, sc.f.xin, sc.n_lbc, sc.f.normal, sc.local_tbn, sc.sample_tbn, sc.new_tbn, sc.f.mask, sc.back, labels, stream);
 }

@@ -78,13 +78,13 @@ __device__ __forceinline__ void load_brdf(const half_t* __restrict__ brdf, uint3
     }
 }
 
+// the head's arithmetic of one row: n the shading normal, view the view direction (not normalised), both in registers
 template <int C>
-__device__ __forceinline__ void shade_row(const half_t (&x)[4], const float* __restrict__ normals, const float* __restrict__ dirs, const size_t b,
-                                          const float (&el)[9][C], const bool use_specular, Row<C>& r) {
+__device__ __forceinline__ void shade_vectors(const half_t (&x)[4], const float (&n)[3], const float (&view)[3], const float (&el)[9][C],
+                                              const bool use_specular, Row<C>& r) {
 #pragma unroll
     for (int c = 0; c < 3; c++) r.a[c] = narrow(1.0f / (1.0f + expf(-(float)x[c])));
     r.sw = narrow(1.0f / (1.0f + expf(-(float)x[3])));
-    const float n[3] = {normals[b * 3], normals[b * 3 + 1], normals[b * 3 + 2]};
     svox2_basis9(n[0], n[1], n[2], r.yn);
     float drgb[C];
 #pragma unroll
@@ -98,7 +98,7 @@ __device__ __forceinline__ void shade_row(const half_t (&x)[4], const float* __r
 #pragma unroll
     for (int c = 0; c < 3; c++) r.diffuse[c] = (float)r.a[c] * drgb[C == 3 ? c : 0];
     if (use_specular) {
-        float d[3] = {dirs[b * 3], dirs[b * 3 + 1], dirs[b * 3 + 2]};
+        float d[3] = {view[0], view[1], view[2]};
         auto unit = [](float (&v)[3]) {  // v / (|v| + 1e-9)
             const float len = sqrtf((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]) + 1e-9f;
 #pragma unroll
@@ -127,6 +127,16 @@ __device__ __forceinline__ void shade_row(const half_t (&x)[4], const float* __r
     }
 #pragma unroll
     for (int c = 0; c < 3; c++) r.sum[c] = r.diffuse[c] + r.spec[C == 3 ? c : 0];
+}
+
+// shade_vectors with row b's normal and direction loaded from global memory (the direction only where the specular term reads it)
+template <int C>
+__device__ __forceinline__ void shade_row(const half_t (&x)[4], const float* __restrict__ normals, const float* __restrict__ dirs, const size_t b,
+                                          const float (&el)[9][C], const bool use_specular, Row<C>& r) {
+    const float n[3] = {normals[b * 3], normals[b * 3 + 1], normals[b * 3 + 2]};
+    float view[3] = {0.0f, 0.0f, 0.0f};
+    if (use_specular) view[0] = dirs[b * 3], view[1] = dirs[b * 3 + 1], view[2] = dirs[b * 3 + 2];
+    shade_vectors<C>(x, n, view, el, use_specular, r);
 }
 
 // the head's four outputs of a shaded row, component c: 0 colour, 1 specular, 2 diffuse, 3 albedo (NERFTEX_LIGHT_VISUAL_*)

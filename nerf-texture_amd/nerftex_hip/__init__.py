@@ -64,6 +64,10 @@ _SIGNATURES = {
     "nerftex_patch_light_lookup": [_vp, _vp, _vp, _vp, _vp, _u32, _f32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "nerftex_curved_patch_infer": [_vp, _vp],
     "nerftex_curved_light_patch_infer": [_vp, _vp],
+    "nerftex_curved_light_infer_relit": [_vp, _vp, _vp],
+    "nerftex_curved_light_import_infer_relit": [_vp, _vp, _vp],
+    "nerftex_curved_light_shape_infer_relit": [_vp, _vp, _vp],
+    "nerftex_curved_light_patch_infer_relit": [_vp, _vp, _vp],
     "nerftex_sh_light_forward": [_vp, _vp],
     "nerftex_sh_light_backward": [_vp, _vp],
     "nerftex_sh_light_probe_forward": [_vp, _vp],
@@ -349,6 +353,11 @@ class SHLightProbeDesc(C.Structure):
     """nerftex_sh_light_probe_desc of include/nerftex_hip.h, field for field: the head under per-probe imported lighting (forward only)."""
     _fields_ = [("brdf", _vp), ("brdf_stride", _u32), ("normals", _vp), ("dirs", _vp), ("normals_secondary", _vp), ("probes", _vp), ("probe_shs", _vp),
                 ("K", _u32), ("mask", _vp), ("B", _u32), ("gamma", _f32), ("flags", _u32), ("color", _vp), ("specular", _vp), ("diffuse", _vp), ("albedo", _vp)]
+
+
+class RelightDesc(C.Structure):
+    """nerftex_relight_desc of include/nerftex_hip.h, field for field: per-probe lighting and the lighting rotation of the four _relit entries."""
+    _fields_ = [("probes", _vp), ("probe_shs", _vp), ("K", _u32), ("rotation", _vp)]
 
 
 class EnvmapFitDesc(C.Structure):

@@ -25,7 +25,7 @@ import torch
 
 from gridencoder import GridEncoder_clustering
 from nerftex_hip import (LIGHT_VISUAL, SH_LIGHT_SPECULAR, CurvedImportInferDesc, CurvedInferDesc, CurvedLightImportInferDesc, CurvedLightInferDesc,
-                         CurvedLightPatchInferDesc, CurvedLightShapeInferDesc, CurvedPatchInferDesc, CurvedShapeInferDesc, ptr)
+                         CurvedLightPatchInferDesc, CurvedLightShapeInferDesc, CurvedPatchInferDesc, CurvedShapeInferDesc, RelightDesc, ptr)
 from RayTracer import RayTracer
 
 
@@ -1378,7 +1378,75 @@ class CurvedField(torch.nn.Module):
         return (getattr(self, "light_model", None) is None and getattr(self, "fused_glue", True) and self._sigma_fused(x) and self.color_pad == 32
                 and self.encoder_dir.output_dim == 16)
 
-    def _forward_light(self, x, d, normal_supervision=False):
+    # ---- the lighting rotation (network_curvedfield.py:303-308, the reference's `euler`; its light turntable: nerf/utils.py:871-902) ----
+
+    @staticmethod
+    def light_rotation_matrix(euler):
+        """R.from_rotvec(euler).as_matrix() without scipy: Rodrigues' formula in float64, I + sin(t) K + (1 - cos(t)) K^2 with K the unit axis'
+        cross-product matrix.  -> float64 [3, 3]; a zero vector gives the identity exactly."""
+        v = np.asarray(euler, dtype=np.float64).reshape(-1)
+        if v.shape != (3,) or not np.isfinite(v).all():
+            raise ValueError(f"CurvedField: a lighting rotation is a finite rotation vector of 3 values, but got {euler!r}")
+        t = float(np.sqrt(v @ v))
+        if t == 0.0:
+            return np.eye(3)
+        k = v / t
+        K = np.array([[0.0, -k[2], k[1]], [k[2], 0.0, -k[0]], [-k[1], k[0], 0.0]])
+        return np.eye(3) + np.sin(t) * K + (1.0 - np.cos(t)) * (K @ K)
+
+    def set_light_rotation(self, euler):
+        """The reference's `euler`, kept on the field: in eval the light head sees the view direction, the shading normal and the coarse normal
+        rotated by R.from_rotvec(euler) (forward(), and the lit chains with `fused_relight_infer`).  None switches the rotation off; a zero vector
+        does not -- as in the reference it is a product with the identity, which rounds to half under autocast.  The fp32 matrix is written IN PLACE
+        into one persistent [9] device buffer: a new vector changes values a recorded graph reads, not what it bakes in (`_light_stamp`)."""
+        if euler is None:
+            self._light_rotation_on, self._light_euler = False, None
+            return
+        if getattr(self, "light_model", None) is None:
+            raise ValueError("CurvedField.set_light_rotation: the static field has no light model to rotate (light_model='SH' has)")
+        m = torch.from_numpy(self.light_rotation_matrix(euler).astype(np.float32).reshape(9))
+        buf = getattr(self, "_light_rotation", None)
+        dev = self.light_net.envSHs.device
+        if buf is None or buf.device != dev:
+            buf = self._light_rotation = torch.empty(9, dtype=torch.float32, device=dev)
+        buf.copy_(m)
+        self._light_rotation_on, self._light_euler = True, tuple(float(e) for e in np.asarray(euler, dtype=np.float64).reshape(3))
+
+    def light_rotation(self):
+        """The rotation vector set_light_rotation keeps, or None."""
+        return getattr(self, "_light_euler", None) if getattr(self, "_light_rotation_on", False) else None
+
+    def _light_rotation_active(self):
+        """Whether the stored rotation turns the lighting of this call: it is set, and the field is in eval (the reference's `not self.training`)."""
+        return bool(getattr(self, "_light_rotation_on", False)) and not self.training
+
+    def _per_probe_lighting(self):
+        """Whether forward() asks the head for one lighting per visibility probe (or its refusal without tables): eval, an imported lighting
+        switched on, `shade_visibility`."""
+        net = self.light_net
+        return (not self.training and bool(getattr(net, "import_envmap", False)) and getattr(net, "envSHs_import", None) is not None
+                and bool(getattr(self, "shade_visibility", True)))
+
+    def _relight_desc(self):
+        """The nerftex_relight_desc of a lit chain's call (and the tensors it points into), or None where neither per-probe lighting nor a rotation
+        is in effect: then the plain entry is called, as before."""
+        probe, rot = self._per_probe_lighting(), self._light_rotation_active()
+        if not (probe or rot):
+            return None
+        net = self.light_net
+        probes, tables = (net.probes, net.envSHs_import_vis) if probe else (None, None)
+        buf = self._light_rotation if rot else None
+        return RelightDesc(probes=ptr(probes), probe_shs=ptr(tables), K=0 if probes is None else probes.shape[0], rotation=ptr(buf)), (probes, tables, buf)
+
+    @staticmethod
+    def _rotate_lighting(rotation, *vectors):
+        """network_curvedfield.py:305-308: einsum('ab,nb->na', rot, v) for each [N,3] vector (None stays None), rot in the vectors' dtype and on
+        their device as there; the results as fp32."""
+        ref = next(v for v in vectors if v is not None)
+        rot = rotation.to(device=ref.device, dtype=ref.dtype)
+        return tuple(None if v is None else torch.einsum("ab,nb->na", rot, v).float() for v in vectors)
+
+    def _forward_light(self, x, d, normal_supervision=False, rotation=None):
         """network_curvedfield.py:272-301, 327-349, 396-409 with the SH light model: the head shades with the fine normal -- detached in training
         (:331), blended with the coarse normal by fc_weight and renormalised in eval (:293-301) -- and the view direction as it is.  In eval
         `light_visual_mode` picks the head's output.  normal_supervision (training): the reference's ret_dict, 'normal' = the fine normal on the
@@ -1407,6 +1475,12 @@ class CurvedField(torch.nn.Module):
             # self.training); the head reads neither outside eval with an import, so only then are they handed over
             relight = dict(normal_secondary=normal_coarse / (normal_coarse.norm(dim=-1, keepdim=True) + 1e-5),
                            shade_visibility=bool(getattr(self, "shade_visibility", True)))
+        if rotation is not None and not self.training:
+            # :304-308 op by op.  Under fp16 autocast each einsum is a half product (both operands cast to half, fp32 accumulation, a half result);
+            # the head's kernels take fp32 vectors, so the half values are widened again
+            d, normal, secondary = self._rotate_lighting(rotation, d, normal, relight.get("normal_secondary"))
+            if relight:
+                relight["normal_secondary"] = secondary
         full, specular, diffuse, albedo = self.light_net(geo, normal, d, mask=h_mask, **relight)
         modes = {"Full": full, "Specular": specular, "Diffuse": diffuse, "Albedo": albedo}
         if not self.training and self.light_visual_mode not in modes:
@@ -1415,8 +1489,16 @@ class CurvedField(torch.nn.Module):
         return torch.where(h_mask, sigma, torch.zeros_like(sigma)), color, ret
 
     def forward(self, x, d, **kwargs):
+        """euler (keyword, as NeRFNetwork.forward's): a lighting rotation vector for this call, overriding set_light_rotation's -- None: no
+        rotation.  The static field has no lighting to rotate and raises ValueError rather than ignore one."""
         if getattr(self, "light_model", None) == "SH":
-            return self._forward_light(x, d, normal_supervision=bool(kwargs.get("normal_supervision", False)))
+            if "euler" in kwargs:
+                rotation = None if kwargs["euler"] is None else torch.from_numpy(self.light_rotation_matrix(kwargs["euler"]).astype(np.float32))
+            else:
+                rotation = self._light_rotation.view(3, 3) if self._light_rotation_active() else None
+            return self._forward_light(x, d, normal_supervision=bool(kwargs.get("normal_supervision", False)), rotation=rotation)
+        if kwargs.get("euler") is not None or getattr(self, "_light_rotation_on", False):
+            raise ValueError("CurvedField.forward: a lighting rotation is set, but the static field has no light model to rotate")
         if getattr(self, "imported", False) and self._glue_fused(x) and self._source_fused(x):
             s = self._source_lookup(x)
             normal = self._import_normal(x, False) if s.normal is None else s.normal
@@ -1462,11 +1544,21 @@ class CurvedField(torch.nn.Module):
         net = self.light_net
         stamp = (self.light_model, self.light_visual_mode, float(net.gamma), bool(net.use_specular), bool(net.fused), net.envSHs.data_ptr(), tuple(net.envSHs.shape))
         if not getattr(self, "fused_light_infer", False):
-            return stamp + (False,) + self._relight_stamp()
+            return stamp + (False,) + self._relight_stamp() + self._rotation_stamp()
         # the fused chain bakes in the normal net's table and the packed copy of its weights: the table's storage and every parameter's version
         nn = self.normal_net
         return stamp + (True, nn.encoder.embeddings.data_ptr(), nn.encoder.offsets.data_ptr(),
-                        tuple((q.data_ptr(), q._version) for q in list(nn.phi_net.parameters()) + list(nn.theta_net.parameters()))) + self._relight_stamp()
+                        tuple((q.data_ptr(), q._version) for q in list(nn.phi_net.parameters()) + list(nn.theta_net.parameters()))) + self._relight_stamp() + self._rotation_stamp()
+
+    def _rotation_stamp(self):
+        """_light_stamp()'s share of `fused_relight_infer` and the lighting rotation, appended only once the switch is on or a rotation is set (the
+        stamp without either is unchanged): the switch, whether a rotation is on, the rotation buffer's storage.  Never the rotation's VALUES: the
+        kernels read them from that buffer when they run, so a new rotation vector replays the recorded graphs."""
+        switch, on = bool(getattr(self, "fused_relight_infer", False)), bool(getattr(self, "_light_rotation_on", False))
+        if not (switch or on):
+            return ()
+        buf = getattr(self, "_light_rotation", None)
+        return (switch, on, buf.data_ptr() if on and buf is not None else 0)
 
     def _lighting(self):
         """The lighting the head shades with: light_net.lighting() -- the imported coefficients in eval once switched on, envSHs otherwise (and
@@ -1658,8 +1750,16 @@ class CurvedField(torch.nn.Module):
         if not (getattr(self, "light_model", None) == "SH" and getattr(self, "fused_light_infer", False)):
             return False
         nn, net = self.normal_net, self.light_net
-        if not self.training and getattr(net, "import_envmap", False) and net.envSHs_import is not None and getattr(self, "shade_visibility", True):
-            return False  # per-probe lighting (or its refusal without tables) is forward()'s: the chains' descriptors hold one lighting
+        probe, rot = self._per_probe_lighting(), self._light_rotation_active()
+        if probe or rot:
+            # per-probe lighting and the rotation are the _relit entries' (DESIGN.md 4.23), opt-in: without `fused_relight_infer` they are forward()'s,
+            # as is per-probe lighting without its tables (forward() raises there: the chain must not render it)
+            if not getattr(self, "fused_relight_infer", False):
+                return False
+            if probe and (net.envSHs_import_vis is None or net.probes is None or not self._on_device_of(x, net.envSHs_import_vis, net.probes)):
+                return False
+            if rot and not self._on_device_of(x, self._light_rotation):
+                return False
         br, env = net.brdf_layer, self._lighting()
         return (bool(net.fused) and nn is not None and not nn.bound_output and (self.training or self.light_visual_mode in LIGHT_VISUAL)
                 and x.is_cuda and br.dtype == torch.float16 and (br.input_dim, br.hidden_dim, br.num_layers, br.output_dim) == self._BRDF_NET
@@ -1772,7 +1872,11 @@ class CurvedField(torch.nn.Module):
         out = torch.empty(4 * B, dtype=torch.float32, device=x.device)  # [sigma | rgb] in one allocation
         sigma, rgbs = out[:B], out[B:].view(B, 3)
         desc, _keep = make_desc(x, d, live, sigma, rgbs, scratch, *more)
-        check(getattr(lib, entry)(ctypes.byref(desc), st))
+        relight = self._relight_desc() if getattr(self, "light_model", None) == "SH" and hasattr(desc, "env_shs") else None
+        if relight is None:
+            check(getattr(lib, entry)(ctypes.byref(desc), st))
+        else:  # (per-probe lighting or a rotation in effect: the lit chain's _relit entry, the same scratch)
+            check(getattr(lib, entry + "_relit")(ctypes.byref(desc), ctypes.byref(relight[0]), st))
         return sigma, rgbs
 
     @torch.no_grad()
@@ -1853,7 +1957,8 @@ class CurvedField(torch.nn.Module):
         colour follow forward()'s arithmetic at its rounding points; over imported maps, nerftex_curved_light_import_infer
         (DESIGN.md 4.17), and over the maps on an imported mesh nerftex_curved_light_shape_infer.  The lit chains shade with
         light_net.lighting(), so a uniform imported lighting goes through them; per-probe lighting (`shade_visibility` with an imported
-        lighting in eval) is forward()'s.
+        lighting in eval) is forward()'s, and so is a lighting rotation (set_light_rotation) -- unless `fused_relight_infer` is
+        set (default False): then the chain's _relit entry shades with the probe tables and the rotation.
         An imported patch (import_patch): nerftex_curved_patch_infer, and for the SH-lit field with the switch set
         nerftex_curved_light_patch_infer, under the same contract."""
         row = self._infer_row(x, d)

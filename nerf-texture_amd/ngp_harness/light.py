@@ -25,7 +25,8 @@ Relighting (the reference's load_envmap :625, switch_envmap_import :675, the eva
                     lighting per probe direction, chosen per sample by its coarse normal (`shade_visibility`); fused: nerftex_sh_light_probe_forward.
   lighting()        the coefficients in effect: the imported ones in eval once switched on, envSHs otherwise.  Training never sees the import.
 Out of scope: COMPUTING the probe tables (load_envmap_with_visibility's branch without a file: a stochastic Adam fit over
-rotate_coeff_by_normal's band rotations), the reference's `euler` lighting rotation, reading image files, the SG and Envmap models.
+rotate_coeff_by_normal's band rotations), reading image files, the SG and Envmap models.  The reference's `euler` lighting rotation lives in front
+of the head, on the field: CurvedField.set_light_rotation / forward(euler=) hand this module rotated vectors.
 """
 import math
 

@@ -698,6 +698,27 @@ class Renderer(nn.Module):
         self.last_iters = rounds * int(block)
         return image + (1 - weights_sum).unsqueeze(-1) * bg_color, depth, rounds * int(block) * sum(j.M for j in jobs)  # (slots of full-size launches: an upper bound)
 
+    def render_light_turntable(self, rays_o, rays_d, n_frames, axis=0, **kw):
+        """The reference's light turntable (nerf/utils.py:871-902) over one view: a generator of n_frames render_infer_graphed results, frame i under
+        the lighting rotation euler[axis] = np.linspace(0, 2 pi, n_frames)[i], the other two components 0 (axis 1: the reference's shape
+        rendering).  Each frame sets the field's rotation (CurvedField.set_light_rotation: new values in the same device buffer) and replays the
+        recorded graphs -- with `fused_relight_infer` they are recorded once, since their stamp holds the buffer, not its values.  The rotation set
+        before is restored at the end (also when the generator is closed early).  kw: render_infer_graphed's keywords."""
+        import numpy as np
+
+        field = self.field
+        if not hasattr(field, "set_light_rotation"):
+            raise ValueError("Renderer.render_light_turntable: the field has no lighting rotation (CurvedField(light_model='SH') has)")
+        before = field.light_rotation()
+        try:
+            for angle in np.linspace(0.0, 2.0 * np.pi, int(n_frames)):
+                euler = [0.0, 0.0, 0.0]
+                euler[int(axis)] = float(angle)
+                field.set_light_rotation(euler)
+                yield self.render_infer_graphed(rays_o, rays_d, **kw)
+        finally:
+            field.set_light_rotation(before)
+
 
 class _InferGraphPart:
     """One range of rays of Renderer.render_infer_graphed: persistent buffers + two HIP graphs -- `init` (near / far, cleared accumulators, every

@@ -1068,6 +1068,40 @@ def sh_field_goldens():
     fixtures; writes this one file."""
     import torch
 
+    net, mff, x, d, out = sh_field_network()
+    handed = {}  # what NeRFNetwork.forward hands to the light head (:341): the shading normal and the view direction
+    net.light_net.register_forward_pre_hook(lambda m, a: handed.update(normal=a[1].detach().float().numpy().copy(), view_dirs=a[2].detach().float().numpy().copy(),
+                                                                       normal_attached=bool(a[1].requires_grad)))
+    net.eval()
+    with torch.no_grad(), emulated_autocast():
+        _, nc, nf, hm = mff(x)
+        out.update(eval_normal_coarse=nc.float().numpy(), eval_normal_fine=nf.float().numpy(), eval_h_mask=hm.numpy())
+        for mode in ("Full", "Specular", "Diffuse", "Albedo"):
+            net.light_visual_mode = mode
+            sigma, color, ret = net(x, d, is_gui_mode=False)
+            assert ret == {}
+            out["eval_sigma"], out["eval_color_" + mode.lower()] = sigma.float().numpy(), color.float().numpy()
+        net.light_visual_mode = "Full"
+        out.update(eval_shading_normal=handed["normal"], eval_view_dirs=handed["view_dirs"])
+    net.train()
+    with emulated_autocast():
+        sigma, color, ret = net(x.clone(), d)
+    assert sorted(ret) == ["normal", "normal_grad"] and ret["normal"].requires_grad
+    assert not handed["normal_attached"], "the training head shades with the detached normal (:331)"
+    out.update(train_shading_normal=handed["normal"], train_view_dirs=handed["view_dirs"])
+    out.update(train_sigma=sigma.detach().float().numpy(), train_color=color.detach().float().numpy(), train_normal=ret["normal"].detach().float().numpy(),
+               train_normal_grad=ret["normal_grad"].detach().float().numpy(), train_h_mask=(sigma.detach() != 0).numpy() | (color.detach() != 0).any(-1).numpy())
+    np.savez_compressed(os.path.join(OUT, "ref_python_curvedfield_sh.npz"), **out)
+    print("ref_python_curvedfield_sh.npz: eval colour", float(out["eval_color_full"].min()), float(out["eval_color_full"].max()), "inside", float(out["eval_h_mask"].mean()),
+          "train rows shaded", float(out["train_h_mask"].mean()), "normal_grad not a number on", int(np.isnan(out["train_normal_grad"]).any(-1).sum()), "rows")
+
+
+def sh_field_network():
+    """The construction of ref_python_curvedfield_sh.npz (sh_field_goldens; tools/make_relight_golden.py builds on it too): -> the reference's
+    NeRFNetwork with the SH light head over its MeshFeatureField, that field, the 768 points and directions as tensors, and the dictionary of
+    the seeds and weights the fixture records."""
+    import torch
+
     _install_map_imports()
     _stub("imageio")
     for name in ("nerf.sh_light_model", "nerf.network_curvedfield", "tools.shape_tools"):  # (stubs of earlier functions: tools/map.py needs the real shape_tools)
@@ -1125,31 +1159,7 @@ def sh_field_goldens():
     for name, mlp in (("phi", mff.normal_net.phi_net), ("theta", mff.normal_net.theta_net)):
         for i, layer in enumerate(mlp.layers):
             out[f"{name}_W{i}"], out[f"{name}_b{i}"], out[f"{name}_c{i}"] = layer.W.detach().numpy().copy(), layer.b.detach().numpy().copy(), float(layer.c)
-    handed = {}  # what NeRFNetwork.forward hands to the light head (:341): the shading normal and the view direction
-    net.light_net.register_forward_pre_hook(lambda m, a: handed.update(normal=a[1].detach().float().numpy().copy(), view_dirs=a[2].detach().float().numpy().copy(),
-                                                                       normal_attached=bool(a[1].requires_grad)))
-    net.eval()
-    with torch.no_grad(), emulated_autocast():
-        _, nc, nf, hm = mff(x)
-        out.update(eval_normal_coarse=nc.float().numpy(), eval_normal_fine=nf.float().numpy(), eval_h_mask=hm.numpy())
-        for mode in ("Full", "Specular", "Diffuse", "Albedo"):
-            net.light_visual_mode = mode
-            sigma, color, ret = net(x, d, is_gui_mode=False)
-            assert ret == {}
-            out["eval_sigma"], out["eval_color_" + mode.lower()] = sigma.float().numpy(), color.float().numpy()
-        net.light_visual_mode = "Full"
-        out.update(eval_shading_normal=handed["normal"], eval_view_dirs=handed["view_dirs"])
-    net.train()
-    with emulated_autocast():
-        sigma, color, ret = net(x.clone(), d)
-    assert sorted(ret) == ["normal", "normal_grad"] and ret["normal"].requires_grad
-    assert not handed["normal_attached"], "the training head shades with the detached normal (:331)"
-    out.update(train_shading_normal=handed["normal"], train_view_dirs=handed["view_dirs"])
-    out.update(train_sigma=sigma.detach().float().numpy(), train_color=color.detach().float().numpy(), train_normal=ret["normal"].detach().float().numpy(),
-               train_normal_grad=ret["normal_grad"].detach().float().numpy(), train_h_mask=(sigma.detach() != 0).numpy() | (color.detach() != 0).any(-1).numpy())
-    np.savez_compressed(os.path.join(OUT, "ref_python_curvedfield_sh.npz"), **out)
-    print("ref_python_curvedfield_sh.npz: eval colour", float(out["eval_color_full"].min()), float(out["eval_color_full"].max()), "inside", float(out["eval_h_mask"].mean()),
-          "train rows shaded", float(out["train_h_mask"].mean()), "normal_grad not a number on", int(np.isnan(out["train_normal_grad"]).any(-1).sum()), "rows")
+    return net, mff, x, d, out
 
 
 def import_field_goldens():
