@@ -79,7 +79,8 @@ const char* nerftex_version(void);
 /* Tuning knobs / A-B switches of the kernels (profiling aid; the defaults are what is measured and shipped).  The library
  * reads its environment ONCE when it is loaded (NERFTEX_TUNE="name=value,..."), a launch never calls getenv().  Names:
  * grid_fwd, grid_bwd, grid_bwd_sweep, grid_bwd_items, grid_bwd_slice, grid_bwd_nomerge, grid_bwd_probe,
- * march, march_serial, ffmlp_wg_per_cu, ffmlp_bwd_split (csrc/common.hpp documents the values).
+ * march, march_serial, ffmlp_wg_per_cu, ffmlp_bwd_split, march_lean, grid_bwd_stage, composite_keep,
+ * march_count_probe (the one list in csrc/common.hpp documents the values).
  * tune_set: NERFTEX_ERR_INVALID for an unknown name; tune_get: -1 for an unknown name.                                    */
 int nerftex_tune_set(const char* name, long value);
 long nerftex_tune_get(const char* name);
@@ -1276,8 +1277,6 @@ int nerftex_patch_front(const nerftex_patch_front_desc* d, void* stream);
  * (lit: the light head's refusals, as nerftex_curved_light_infer;) (B == 0 returns NERFTEX_OK here;) a NULL pointer, a scratch that is not
  * 256-byte aligned or smaller than the entry's _scratch_bytes(B); a weight vector that is not 16-byte aligned (lit: the normal net's block
  * 4-byte); a record array that is not 16-byte aligned; an h_threshold that is not positive and finite.
- * The lane mapping of the lookup kernel is the knob `patch_lanes` (nerftex_tune_set): 4 = four lanes per row, anything else one thread per row;
- * both write the same bits.
  * ------------------------------------------------------------------------- */
 #define NERFTEX_PATCH_GEOM_STRIDE 8
 #define NERFTEX_PATCH_LIT_STRIDE 20

@@ -7,16 +7,14 @@
 
 namespace nerftex {
 
-// LANES = 1: the calling thread reads the four corners' 4 C bytes each as C / 4 16-byte loads (all of them independent, in flight together) and gets
-// all C features, o[0 .. C / 4 - 1]; LANES = 4 (C = 16): lane q of four reads quarter q of each corner and gets its four features, o[0].
+// The calling thread reads the four corners' 4 C bytes each as C / 4 16-byte loads (all of them independent, in flight together) and gets all C
+// features, o[0 .. C / 4 - 1].
 // V = half4_t: the values narrowed to half; V = float4_t: the fp32 values those are the narrowing of.
 // Every framework op rounds on its own (no contraction); a corner outside [0,H) x [0,W) contributes nothing and is not read; the comparisons are on
 // the floats (a NaN or a huge coordinate fails them all) and the index is converted only inside the range, then widened to size_t.
-template <int LANES, int C = 16, typename V = half4_t>
-__device__ __forceinline__ void bilinear_read(const float* __restrict__ map, const uint32_t H, const uint32_t W, const float u, const float v, const uint32_t q,
-                                              V (&o)[C / 4 / LANES]) {
+template <int C = 16, typename V = half4_t>
+__device__ __forceinline__ void bilinear_read(const float* __restrict__ map, const uint32_t H, const uint32_t W, const float u, const float v, V (&o)[C / 4]) {
 #pragma clang fp contract(off)
-    static_assert(LANES == 1 || (LANES == 4 && C == 16), "one thread per row, or four lanes per row of 16 features");
     static_assert(C % 4 == 0 && C >= 4, "whole 16-byte words per texel");
     auto narrow = [](float x) {  // (fieldglue.hip's narrow: the value rounded to fp32 first, then to half; fp32 out: the value as it is)
         asm volatile("" : "+v"(x));
@@ -32,7 +30,7 @@ __device__ __forceinline__ void bilinear_read(const float* __restrict__ map, con
     const float hi_i = (float)(H - 1), hi_j = (float)(W - 1);
     const bool in_i[2] = {i0 >= 0.0f && i0 <= hi_i, i0 + 1.0f >= 0.0f && i0 + 1.0f <= hi_i};
     const bool in_j[2] = {j0 >= 0.0f && j0 <= hi_j, j0 + 1.0f >= 0.0f && j0 + 1.0f <= hi_j};
-    constexpr int Q = C / 4 / LANES;  // 16-byte words of a texel this lane reads: all of them, or quarter q
+    constexpr int Q = C / 4;  // 16-byte words of a texel
     float4_t t[4][Q];
 #pragma unroll
     for (int k = 0; k < 4; k++) {
@@ -41,7 +39,7 @@ __device__ __forceinline__ void bilinear_read(const float* __restrict__ map, con
             const size_t i = (size_t)(int)(i0 + (float)di), j = (size_t)(int)(j0 + (float)dj);
             const float4_t* src = reinterpret_cast<const float4_t*>(map + (i * (size_t)W + j) * C);
 #pragma unroll
-            for (int qq = 0; qq < Q; qq++) t[k][qq] = src[LANES == 1 ? (uint32_t)qq : q];
+            for (int qq = 0; qq < Q; qq++) t[k][qq] = src[qq];
         } else {
 #pragma unroll
             for (int qq = 0; qq < Q; qq++) t[k][qq] = float4_t{0.0f, 0.0f, 0.0f, 0.0f};
@@ -57,7 +55,7 @@ __device__ __forceinline__ void bilinear_read(const float* __restrict__ map, con
     }
 }
 
-// the 16 features of a LANES = 1 read as the two 16-byte stores of columns 0..15 of the sigma net's input row
+// the 16 features of a read as the two 16-byte stores of columns 0..15 of the sigma net's input row
 __device__ __forceinline__ void store_features(const half4_t (&o)[4], half_t* __restrict__ row48) {
     half8_t o8[2];
 #pragma unroll

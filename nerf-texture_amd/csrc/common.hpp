@@ -54,25 +54,27 @@ inline int device_cus() {
 // ---- tuning knobs (runtime.hip) ----------------------------------------------------------------------------------------
 // A/B switches and tuning parameters of the kernels.  Read ONCE when the library is loaded (NERFTEX_TUNE="name=value,..." plus
 // the older one-variable-per-switch names), changed afterwards only through nerftex_tune_set(); a launch reads a plain array.
+// ONE list: X(enumerator, "name of nerftex_tune_set / NERFTEX_TUNE") -- the enum below and the name table of runtime.hip are both generated from it.
+#define NERFTEX_KNOBS(X)                                                                                                                           \
+    X(kKnobGridFwd, "grid_fwd")                   /* 0 auto, 1 thread-per-sample kernel, 2 level-per-XCD kernel */                                 \
+    X(kKnobGridBwd, "grid_bwd")                   /* 0 auto, 1 per-sample atomics, 2 tile owners (binned / sweep) */                               \
+    X(kKnobGridBwdSweep, "grid_bwd_sweep")        /* 1: the tile-owner sweep instead of binning */                                                 \
+    X(kKnobGridBwdItems, "grid_bwd_items")        /* sweep: work items per level (0 = auto) */                                                     \
+    X(kKnobGridBwdSlice, "grid_bwd_slice")        /* binning: records per K4 work item (0 = default) */                                            \
+    X(kKnobGridBwdNoMerge, "grid_bwd_nomerge")    /* binning: 1 = do not merge runs of samples that share a cell */                                \
+    X(kKnobGridBwdProbe, "grid_bwd_probe")        /* phase ablation of K3 / K4 for profiling (0 = off; results are garbage when set) */            \
+    X(kKnobMarch, "march")                        /* 0 auto, 1 replay, 2 log */                                                                    \
+    X(kKnobMarchSerial, "march_serial")           /* 1: one-ray-per-lane DDA for the counting pass */                                              \
+    X(kKnobFfmlpWgPerCu, "ffmlp_wg_per_cu")       /* forward: workgroups per CU (0 = default) */                                                   \
+    X(kKnobFfmlpBwdSplit, "ffmlp_bwd_split")      /* 1: dgrad kernel + wgrad kernel through backward_buffer instead of the fused backward */       \
+    X(kKnobMarchLean, "march_lean")               /* 1: the training march's count pass compiled for 64 registers (spills; slower alone, a better neighbour on a shared CU) */ \
+    X(kKnobGridBwdStage, "grid_bwd_stage")        /* binning: LDS record slots per fill workgroup (0 = default; the rest of a workgroup's block goes straight to memory) */ \
+    X(kKnobCompositeKeep, "composite_keep")       /* composite_step_kernel: 64-sample chunks a wave keeps in registers between its forward and backward walk (1..4; 0 = default 2) */ \
+    X(kKnobMarchCountProbe, "march_count_probe")  /* phase ablation of march_count_parallel_kernel for profiling: 1..3 = every segment stops after that phase (0 = off; results are garbage when set) */
 enum Knob {
-    kKnobGridFwd,        // 0 auto, 1 thread-per-sample kernel, 2 level-per-XCD kernel
-    kKnobGridBwd,        // 0 auto, 1 per-sample atomics, 2 tile owners (binned / sweep)
-    kKnobGridBwdSweep,   // 1: the tile-owner sweep instead of binning
-    kKnobGridBwdItems,   // sweep: work items per level (0 = auto)
-    kKnobGridBwdSlice,   // binning: records per K4 work item (0 = default)
-    kKnobGridBwdNoMerge, // binning: 1 = do not merge runs of samples that share a cell
-    kKnobGridBwdProbe,   // phase ablation of K3 / K4 for profiling (0 = off; results are garbage when set)
-    kKnobMarch,          // 0 auto, 1 replay, 2 log
-    kKnobMarchSerial,    // 1: one-ray-per-lane DDA for the counting pass
-    kKnobFfmlpWgPerCu,   // forward: workgroups per CU (0 = default)
-    kKnobFfmlpBwdSplit,  // 1: dgrad kernel + wgrad kernel through backward_buffer instead of the fused backward
-    kKnobMarchLean,      // 1: the training march's count pass compiled for 64 registers (spills; slower alone, a better neighbour on a shared CU)
-    kKnobFfmlpBwdTr,     // 1: fused MLP backward builds its weight-gradient operands with ds_read_b64_tr_b16 instead of selection-matrix MFMAs (slower: A/B)
-    kKnobGridBwdStage,   // binning: LDS record slots per fill workgroup (0 = default; the rest of a workgroup's block goes straight to memory)
-    kKnobCompositeKeep,  // composite_step_kernel: 64-sample chunks a wave keeps in registers between its forward and backward walk (1..4; 0 = default 2)
-    kKnobMarchCountProbe,  // phase ablation of march_count_parallel_kernel for profiling: 1..3 = every segment stops after that phase (0 = off; results are garbage when set)
-    kKnobPlanarLanes,    // planar_lookup_rows_kernel: 4 = four lanes per row (A/B: measured no faster); anything else: one thread per row
-    kKnobPatchLanes,     // patch_lookup_kernel: 4 = four lanes per row (A/B); anything else: one thread per row
+#define NERFTEX_KNOB_ENUM(id, name) id,
+    NERFTEX_KNOBS(NERFTEX_KNOB_ENUM)
+#undef NERFTEX_KNOB_ENUM
     kKnobCount
 };
 extern long g_knobs[kKnobCount];

@@ -774,15 +774,8 @@ __device__ __forceinline__ void flush_tiles(const float4_t (&tiles)[NA][NB], flo
 //      (field_out_backward_kernel), the other 13 columns zero;
 //   2  sigma net: grad = grad_cin [B,32] (the colour net's dL/dinput), aux0 = grad_sigma [B] fp32, aux1 = h [B,16]:
 //      dL/dh = [grad_sigma exp(clamp(h0, -15, 15)) | grad_cin[:, 16:31]]  (field_mid_backward_kernel).
-// TR (round 4): the operands of the weight-gradient MFMAs -- dPre^T and Y^T, i.e. (lane = feature, slots = the 32 batch rows) where the
-// chain holds (lane = batch row, slots = features) -- are produced by gfx950's transposing LDS read instead of by matrix-core work: the
-// wave writes the tensor it holds anyway (packed operand registers) into a private [32 rows][HIDDEN + 8] patch of LDS (ds_write_b64 /
-// b128) and reads each 16-feature tile back with two ds_read_b64_tr_b16 (4 batch rows x 16 features per 16-lane group, delivered
-// column-major: lane = feature).  Replaces, per 16 features x 32 rows, two 0/1 selection-matrix MFMAs + 8 conversions + the packing
-// (38 of the sigma net's 122 MFMAs per 32-row step, 54 of the colour net's 172) and the four selection operands' registers.  The batch
-// index lands in the slots in the order {4G .. 4G+3, 16+4G .. 16+4G+3} (G = lane >> 4) for BOTH operands of a weight-gradient MFMA: a
-// permutation of the contraction index, same products.  TR = false (the default: it is the faster one, see launch_fused) is the
-// selection-matrix form; knob ffmlp_bwd_tr = 1 selects TR for the ngp field's shapes.
+// The weight-gradient operands dPre^T and Y^T are built by 0/1 selection-matrix MFMAs.  Round 4 also built them with gfx950's transposing LDS read
+// (ds_read_b64_tr_b16 over a per-wave LDS patch): slower, 64.8 / 49.7 us against 59.6 / 47.0 (profiles/r04_ffmlp_tr_ab.json, DESIGN.md 4.3); removed.
 // LIVE (round 6, the two field forms): `step_live` holds one word per 32 consecutive batch rows -- 0: the compositing backward handed exactly zero
 // gradients to all 32 samples (raymarching.cu:843-870 past the point where a ray's transmittance has underflowed: 42 % of the samples after 100
 // steps of the bench's scene, 99.6 % after 1000).  Such a step adds exact zeros to every weight gradient and has a zero input gradient: a wave
@@ -792,7 +785,7 @@ __device__ __forceinline__ void flush_tiles(const float4_t (&tiles)[NA][NB], flo
 // is the sum of the same terms in the same order minus exact zeros: the gradients are those of the kernel without flags, bit for bit.
 // (Round 5's form tested the gradient's CONTENT after loading it -- a skipped step had paid for its loads and the test cost a young field
 // 9 %: removed.)
-template <int HIDDEN, int NL, int IT, bool RECOMPUTE, int ACT, int FIELD = 0, bool TR = false, bool LIVE = false>  // IT = input_dim / 16; ACT: see act_fwd
+template <int HIDDEN, int NL, int IT, bool RECOMPUTE, int ACT, int FIELD = 0, bool LIVE = false>  // IT = input_dim / 16; ACT: see act_fwd
 __global__ __launch_bounds__(kBlockThreads, 1) void ffmlp_backward_fused_kernel(const elem_t* __restrict__ grad, const elem_t* __restrict__ X,
                                                                                const elem_t* __restrict__ W, const elem_t* __restrict__ fwd,
                                                                                elem_t* __restrict__ grad_inputs, uint32_t B, uint32_t act,
@@ -840,14 +833,12 @@ __global__ __launch_bounds__(kBlockThreads, 1) void ffmlp_backward_fused_kernel(
     //   permuted order (operand packed from two result tiles / two half4 activation loads): j < 4 <-> tile 2s feature 4g + j,
     //                                                                                       j >= 4 <-> tile 2s+1 feature 4g + j - 4
     elem8_t sel0, sel1, selP0, selP1;
-    if constexpr (!TR) {
 #pragma unroll
-        for (int j = 0; j < 8; j++) {
-            sel0[j] = (8 * g + j == r) ? (elem_t)1.0f : (elem_t)0.0f;
-            sel1[j] = (8 * g + j == 16 + r) ? (elem_t)1.0f : (elem_t)0.0f;
-            selP0[j] = (j < 4 && 4 * g + j == r) ? (elem_t)1.0f : (elem_t)0.0f;
-            selP1[j] = (j >= 4 && 4 * g + j - 4 == r) ? (elem_t)1.0f : (elem_t)0.0f;
-        }
+    for (int j = 0; j < 8; j++) {
+        sel0[j] = (8 * g + j == r) ? (elem_t)1.0f : (elem_t)0.0f;
+        sel1[j] = (8 * g + j == 16 + r) ? (elem_t)1.0f : (elem_t)0.0f;
+        selP0[j] = (j < 4 && 4 * g + j == r) ? (elem_t)1.0f : (elem_t)0.0f;
+        selP1[j] = (j >= 4 && 4 * g + j - 4 == r) ? (elem_t)1.0f : (elem_t)0.0f;
     }
 
     float4_t gw_out[1][OT];                         // dW_out [16 x HIDDEN]
@@ -877,38 +868,6 @@ __global__ __launch_bounds__(kBlockThreads, 1) void ffmlp_backward_fused_kernel(
     constexpr int kLoads = (FIELD == 0 ? NT : 4) + NT * KS0;
     constexpr size_t kRingOffset = ((size_t)(base_fh + (NL - 1) * per_hidden) * 1024 > 64 * 1024) ? (size_t)(base_fh + (NL - 1) * per_hidden) * 1024 : 64 * 1024;
     elem8_t* ring = reinterpret_cast<elem8_t*>(smem + kRingOffset) + (size_t)wave * 2 * kPieces * 64;
-    // ---- the wave's transposition patch (TR): [32 batch rows][kTrStride halfs], behind the ring.  Row stride 144 B for 64 features: 16-byte
-    // aligned rows (ds_write_b128 of the natural-order tensors), the 8-byte chunks of the transposing read 8-byte aligned (a misaligned
-    // ds_read_b64_tr_b16 silently returns the aligned address's data), and rows 4G .. 4G+3 of a 16-lane group in distinct banks.
-    constexpr int kTrCols = HIDDEN > 32 * KS0 ? HIDDEN : 32 * KS0;
-    constexpr int kTrStride = kTrCols + 8;
-    constexpr size_t kTrBytes = (size_t)32 * kTrStride * sizeof(elem_t);
-    constexpr size_t kTrOffset = RECOMPUTE ? kRingOffset + (size_t)4 * 2 * kPieces * 1024
-                                           : ((size_t)base_f0 * 1024 > 64 * 1024 ? (size_t)base_f0 * 1024 : 64 * 1024);
-    static_assert(kTrStride % 8 == 0 && kTrOffset % 16 == 0 && kTrBytes % 16 == 0, "alignment of the transposition patch");
-    typedef __attribute__((address_space(3))) elem_t lds_elem_t;
-    typedef __attribute__((address_space(3))) elem4_t lds_elem4_t;
-    typedef __attribute__((address_space(3))) elem8_t lds_elem8_t;
-    typedef short short4_t __attribute__((ext_vector_type(4)));
-    typedef __attribute__((address_space(3))) short4_t lds_short4_t;
-    lds_elem_t* const tr_buf = (lds_elem_t*)(smem + kTrOffset + (size_t)wave * kTrBytes);
-    lds_elem_t* const tr_wr_packed = tr_buf + r * kTrStride + 4 * g;    // + 16 t rows, + 32 s (+ 16) features
-    lds_elem_t* const tr_wr_natural = tr_buf + r * kTrStride + 8 * g;   // + 16 t rows, + 32 ks features
-    lds_elem_t* const tr_rd = tr_buf + (4 * g + (r >> 2)) * kTrStride + 4 * (r & 3);  // + 16 f features, + 16 rows for the second half
-    // packed operand (slots q < 4: feature 16 (2s) + 4g + q, slots 4 + q: feature 16 (2s + 1) + 4g + q of row 16t + r) -> the patch
-    auto tr_store_packed = [&](int t, int sidx, const elem8_t& v) {
-        lds_elem_t* p = tr_wr_packed + 16 * t * kTrStride + 32 * sidx;
-        *(lds_elem4_t*)p = __builtin_shufflevector(v, v, 0, 1, 2, 3);
-        *(lds_elem4_t*)(p + 16) = __builtin_shufflevector(v, v, 4, 5, 6, 7);
-    };
-    // natural-order operand (slots j: feature 32 ks + 8g + j of row 16t + r) -> the patch
-    auto tr_store_natural = [&](int t, int ks, const elem8_t& v) { *(lds_elem8_t*)(tr_wr_natural + 16 * t * kTrStride + 32 * ks) = v; };
-    // features 16 f .. 16 f + 15 of the patch as an MFMA operand: lane (n, G) <- feature 16 f + n, batch rows {4G .. 4G+3, 16 + 4G .. 16 + 4G + 3}
-    auto tr_load = [&](int f) {
-        const short4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_short4_t*)(tr_rd + 16 * f));
-        const short4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_short4_t*)(tr_rd + 16 * f + 16 * kTrStride));
-        return __builtin_bit_cast(elem8_t, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-    };
     const uint32_t row_step = gridDim.x * kRowsPerBlock;
     typedef const __attribute__((address_space(1))) void* gptr_t;
     typedef __attribute__((address_space(3))) void* lptr_t;
@@ -1130,13 +1089,7 @@ __global__ __launch_bounds__(kBlockThreads, 1) void ffmlp_backward_fused_kernel(
         }
         // A operands (lane = output neuron, slots = the 32 batch rows) of the gradient whose matrix comes next: first dL/dOut
         elem8_t Aprev[OT];
-        if constexpr (TR) {
-#pragma unroll
-            for (int t = 0; t < NT; t++) tr_store_natural(t, 0, bg[t]);  // (lane groups 2, 3 hold zeros: features 16 .. 31, never read back)
-            Aprev[0] = tr_load(0);
-        } else {
-            Aprev[0] = pack_operand(mfma16(bg[0], sel0, zero), mfma16(bg[1], sel0, zero));
-        }
+        Aprev[0] = pack_operand(mfma16(bg[0], sel0, zero), mfma16(bg[1], sel0, zero));
 
         elem8_t bop[NT][KSH];
 #pragma unroll
@@ -1144,19 +1097,10 @@ __global__ __launch_bounds__(kBlockThreads, 1) void ffmlp_backward_fused_kernel(
             // B operands (lane = input neuron, slots = batch rows) from the activations of layer NL-1-j = the inputs of the matrix
             // whose gradient Aprev holds
             elem8_t Bm[OT];
-            if constexpr (TR) {
 #pragma unroll
-                for (int t = 0; t < NT; t++)
-#pragma unroll
-                    for (int s = 0; s < KSH; s++) tr_store_packed(t, s, yop[j][t][s]);
-#pragma unroll
-                for (int b = 0; b < OT; b++) Bm[b] = tr_load(b);
-            } else {
-#pragma unroll
-                for (int s = 0; s < KSH; s++) {
-                    Bm[2 * s] = pack_operand(mfma16(yop[j][0][s], selP0, zero), mfma16(yop[j][1][s], selP0, zero));
-                    Bm[2 * s + 1] = pack_operand(mfma16(yop[j][0][s], selP1, zero), mfma16(yop[j][1][s], selP1, zero));
-                }
+            for (int s = 0; s < KSH; s++) {
+                Bm[2 * s] = pack_operand(mfma16(yop[j][0][s], selP0, zero), mfma16(yop[j][1][s], selP0, zero));
+                Bm[2 * s + 1] = pack_operand(mfma16(yop[j][0][s], selP1, zero), mfma16(yop[j][1][s], selP1, zero));
             }
             if (j == 0) {
 #pragma unroll
@@ -1185,19 +1129,10 @@ __global__ __launch_bounds__(kBlockThreads, 1) void ffmlp_backward_fused_kernel(
 #pragma unroll
                 for (int s = 0; s < KSH; s++) bop[t][s] = pack_operand(acc[t][2 * s], acc[t][2 * s + 1]);
             }
-            if constexpr (TR) {
 #pragma unroll
-                for (int t = 0; t < NT; t++)
-#pragma unroll
-                    for (int s = 0; s < KSH; s++) tr_store_packed(t, s, bop[t][s]);
-#pragma unroll
-                for (int a = 0; a < OT; a++) Aprev[a] = tr_load(a);
-            } else {
-#pragma unroll
-                for (int s = 0; s < KSH; s++) {
-                    Aprev[2 * s] = pack_operand(mfma16(bop[0][s], selP0, zero), mfma16(bop[1][s], selP0, zero));
-                    Aprev[2 * s + 1] = pack_operand(mfma16(bop[0][s], selP1, zero), mfma16(bop[1][s], selP1, zero));
-                }
+            for (int s = 0; s < KSH; s++) {
+                Aprev[2 * s] = pack_operand(mfma16(bop[0][s], selP0, zero), mfma16(bop[1][s], selP0, zero));
+                Aprev[2 * s + 1] = pack_operand(mfma16(bop[0][s], selP1, zero), mfma16(bop[1][s], selP1, zero));
             }
             if (j + 1 < NL) layer_products<OT, KSH, NT>(frags + (size_t)(base_hidden + j * per_hidden) * 64 + lane, bop, acc);  // W_{NL-1-j}^T
         }
@@ -1205,19 +1140,10 @@ __global__ __launch_bounds__(kBlockThreads, 1) void ffmlp_backward_fused_kernel(
         // ---- first matrix: dW_0 += dPre_0^T . X
         {
             elem8_t Bx[2 * KS0];
-            if constexpr (TR) {
 #pragma unroll
-                for (int ks = 0; ks < KS0; ks++)
-#pragma unroll
-                    for (int t = 0; t < NT; t++) tr_store_natural(t, ks, xin[t][ks]);
-#pragma unroll
-                for (int b = 0; b < IT; b++) Bx[b] = tr_load(b);
-            } else {
-#pragma unroll
-                for (int ks = 0; ks < KS0; ks++) {
-                    Bx[2 * ks] = pack_operand(mfma16(xin[0][ks], sel0, zero), mfma16(xin[1][ks], sel0, zero));
-                    Bx[2 * ks + 1] = pack_operand(mfma16(xin[0][ks], sel1, zero), mfma16(xin[1][ks], sel1, zero));
-                }
+            for (int ks = 0; ks < KS0; ks++) {
+                Bx[2 * ks] = pack_operand(mfma16(xin[0][ks], sel0, zero), mfma16(xin[1][ks], sel0, zero));
+                Bx[2 * ks + 1] = pack_operand(mfma16(xin[0][ks], sel1, zero), mfma16(xin[1][ks], sel1, zero));
             }
 #pragma unroll
             for (int a = 0; a < OT; a++)
@@ -1462,14 +1388,8 @@ int launch_fused(const void* grad, const void* inputs, const void* weights, cons
     size_t lds = lds_bytes_dgrad(H, 16 * IT, NL, true) + (recompute ? (size_t)(frag_count(H, 16 * IT) + (NL - 1) * frag_count(H, H)) * 1024 : 0);
     if (lds < 64 * 1024) lds = 64 * 1024;  // the end-of-kernel combine reuses the fragment area
     if (recompute) lds += (size_t)4 * 2 * ((FIELD == 2 ? 3 : 2) + 2 * ((16 * IT + 31) / 32)) * 1024;  // prefetch ring: 4 waves x 2 slots x (grad + input pieces) KiB
-    // ffmlp_bwd_tr = 1: the transposing LDS reads instead of the selection-matrix MFMAs (A/B switch; instantiated for the ngp field's shapes).
-    // MEASURED (round 4, profiles/r04_ffmlp_tr_ab.json): 64.8 / 49.7 us (colour / sigma backward) against 59.6 / 47.0 with the selection
-    // MFMAs -- 38 (54) MFMAs and ~180 VALU instructions fewer per 32-row step, and slower: one wave per SIMD has nobody to hide the LDS round
-    // trip behind, and the CU's LDS port already carries the weight fragments of four waves (software-pipelining the round trips a stage
-    // ahead of their consumers: 68.4 / 50.8).  The default stays the selection form.
-    const bool tr = ACT == (int)kRelu && IT == 2 && (NL == 2 || NL == 3) && knob(kKnobFfmlpBwdTr);
-    constexpr int kTrColsHost = H > 32 * ((16 * IT + 31) / 32) ? H : 32 * ((16 * IT + 31) / 32);
-    if (tr) lds += (size_t)4 * 32 * (kTrColsHost + 8) * sizeof(elem_t);  // the four waves' transposition patches
+    // MEASURED (round 4, profiles/r04_ffmlp_tr_ab.json): transposing LDS reads in place of the selection MFMAs are slower (64.8 / 49.7 us against
+    // 59.6 / 47.0; software-pipelined 68.4 / 50.8) -- one wave per SIMD has nobody to hide the LDS round trip behind.  That form is removed.
     int rc = lds_check(lds);
     if (rc != NERFTEX_OK) return rc;
     uint32_t n_parts = B / kRowsPerBlock;
@@ -1488,18 +1408,9 @@ int launch_fused(const void* grad, const void* inputs, const void* weights, cons
             set_error("field backward: the recomputing form only");
             return NERFTEX_ERR_INVALID;
         }
-        if (tr) rc = launch(ffmlp_backward_fused_kernel<H, NL, IT, true, ACT, FIELD, true>, FIELD == 1 ? "field_color_backward_kernel" : "field_sigma_backward_kernel");
-        else if (step_live)  // the steps the compositing backward flagged as carrying a gradient; the others are not touched
-            rc = launch(ffmlp_backward_fused_kernel<H, NL, IT, true, ACT, FIELD, false, true>, FIELD == 1 ? "field_color_backward_kernel" : "field_sigma_backward_kernel");
-        else rc = launch(ffmlp_backward_fused_kernel<H, NL, IT, true, ACT, FIELD, false>, FIELD == 1 ? "field_color_backward_kernel" : "field_sigma_backward_kernel");
-    } else if constexpr (ACT == (int)kRelu && IT == 2 && (NL == 2 || NL == 3)) {
-        if (recompute) {
-            if (tr) rc = launch(ffmlp_backward_fused_kernel<H, NL, IT, true, ACT, 0, true>, "ffmlp_backward_recompute_kernel");
-            else rc = launch(ffmlp_backward_fused_kernel<H, NL, IT, true, ACT, 0, false>, "ffmlp_backward_recompute_kernel");
-        } else {
-            if (tr) rc = launch(ffmlp_backward_fused_kernel<H, NL, IT, false, ACT, 0, true>, "ffmlp_backward_fused_kernel");
-            else rc = launch(ffmlp_backward_fused_kernel<H, NL, IT, false, ACT, 0, false>, "ffmlp_backward_fused_kernel");
-        }
+        if (step_live)  // the steps the compositing backward flagged as carrying a gradient; the others are not touched
+            rc = launch(ffmlp_backward_fused_kernel<H, NL, IT, true, ACT, FIELD, true>, FIELD == 1 ? "field_color_backward_kernel" : "field_sigma_backward_kernel");
+        else rc = launch(ffmlp_backward_fused_kernel<H, NL, IT, true, ACT, FIELD>, FIELD == 1 ? "field_color_backward_kernel" : "field_sigma_backward_kernel");
     } else if (recompute) {
         rc = launch(ffmlp_backward_fused_kernel<H, NL, IT, true, ACT>, "ffmlp_backward_recompute_kernel");
     } else {

@@ -51,7 +51,7 @@ __device__ __forceinline__ void lit_reads_row(const PlanarLightArgs& l, const ui
     }
     if constexpr (ROWS) {
         half4_t o[2];
-        bilinear_read<1, 8>(l.phi_map, H, W, u, v, 0u, o);
+        bilinear_read<8>(l.phi_map, H, W, u, v, o);
         half_t* n_lbc = static_cast<half_t*>(phi_out);
 #pragma unroll
         for (int lv = 0; lv < 4; lv++) {
@@ -60,7 +60,7 @@ __device__ __forceinline__ void lit_reads_row(const PlanarLightArgs& l, const ui
         }
     } else {
         float4_t o[2];
-        bilinear_read<1, 8, float4_t>(l.phi_map, H, W, u, v, 0u, o);
+        bilinear_read<8, float4_t>(l.phi_map, H, W, u, v, o);
         float4_t* dst = reinterpret_cast<float4_t*>(static_cast<float*>(phi_out) + (size_t)b * 8);
         dst[0] = o[0]; dst[1] = o[1];
         id_out[b] = id;  // (-1: a texel whose id is not in [0, P))

@@ -10,12 +10,8 @@
 //   lit      [V,20] fp32   {phi 0..7 | frame 0..8 | 0 0 0}        five 16-byte words (NERFTEX_PATCH_LIT_STRIDE; the lit lookups only)
 // A row gathers 8 x (2 + 4 [+ 5]) words.  The patch of a 128 x 128 export is 16 384 points: 0.5 + 1 + 1.25 MiB, L2-resident.
 //
-// Lane mapping (the knob `patch_lanes`; DESIGN.md 4.20):
-//   LANES = 1  one thread per row: the search, the weights, and all 8 x 4 (+ 8 x 5) gathers, each neighbour's words requested together.
-//   LANES = 4  four adjacent lanes per row: every lane runs the SAME search and the same weights (the four lanes' loads of the search fall on one
-//              address and cost one fetch), lane q gathers word q of each neighbour's features (the four lanes read a record's 64 contiguous
-//              bytes with one instruction) and, lit, words q and q + 4 of the lit record; lane 0 writes what a row has once.
-// Either way an output element is the same expression tree over the same operands: the same bits.
+// Lane mapping: one thread per row -- the search, the weights, and all 8 x 4 (+ 8 x 5) gathers, each neighbour's words requested together.  (Four
+// adjacent lanes per row measured twice as slow -- DESIGN.md 4.20 -- and was removed.)
 
 namespace nerftex {
 namespace {
@@ -37,22 +33,18 @@ struct PatchPlainOut {
 
 // ROWS: the rows contract of nerftex_curved_field_infer's kernels -- rows >= live untouched; a marked slot searches and gathers nothing and gets
 // mask 0, normal 0, features 0, z = 0 | ones.  phi_out: ROWS half, level-major [4,B,2] (what curved_light_mid_row reads as n_lbc); plain fp32 [B,8].
-template <bool ROWS, bool LIT, int LANES>
+template <bool ROWS, bool LIT>
 __global__ __launch_bounds__(256) void patch_lookup_kernel(const float* __restrict__ xyz, const float* __restrict__ dirs, const uint32_t B, const GridDesc g,
                                                            const uint32_t* __restrict__ cell_start, const P4* __restrict__ points, const PatchArgs a,
                                                            uint8_t* __restrict__ mask, float* __restrict__ normal_out, half_t* __restrict__ xin,
                                                            void* __restrict__ phi_out, float* __restrict__ tbn_out, const PatchPlainOut po,
                                                            const int32_t* __restrict__ units_dev, const uint32_t rows_per_unit) {
 #pragma clang fp contract(off)  // every framework op rounds on its own
-    static_assert(LANES == 1 || LANES == 4, "one thread or four lanes per row");
     constexpr int K = 8;
-    const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t b = tid / LANES, q = tid % LANES;
-    const bool first = q == 0;  // the lane that writes what a row has once
+    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= (ROWS ? live_rows(B, units_dev, rows_per_unit) : B)) return;
     half_t* row = xin + (size_t)b * 48;
     if (ROWS && slot_unused(dirs, b)) {  // no search, no gather
-        if (!first) return;
         mask[b] = 0;
 #pragma unroll
         for (int c = 0; c < 3; c++) normal_out[(size_t)b * 3 + c] = 0.0f;
@@ -92,7 +84,7 @@ __global__ __launch_bounds__(256) void patch_lookup_kernel(const float* __restri
         cr_min = fminf(cr_min, sqrtf((c0 * c0 + c1 * c1) + c2 * c2));
     }
     const bool above = 2.0f * cr_min < 1.0f;
-    if (!ROWS && first) {
+    if (!ROWS) {
 #pragma unroll
         for (int k = 0; k < K; k++) {
             po.idx[(size_t)b * K + k] = ids[k];
@@ -150,25 +142,23 @@ __global__ __launch_bounds__(256) void patch_lookup_kernel(const float* __restri
         w[k] = w[k] / (W + 1e-5f);
         sdf = sdf + s[k] * w[k];
     }
-    if (first) {
-        mask[b] = (fabsf(sdf) < a.h_threshold && dis[0] < a.h_threshold) ? 1 : 0;  // (dis ascending: dis[0] is the minimum, 1e5 where the test failed)
+    mask[b] = (fabsf(sdf) < a.h_threshold && dis[0] < a.h_threshold) ? 1 : 0;  // (dis ascending: dis[0] is the minimum, 1e5 where the test failed)
 #pragma unroll
-        for (int c = 0; c < 3; c++) normal_out[(size_t)b * 3 + c] = n[c];
-        if (!ROWS) {
-            po.sdf[b] = sdf;
+    for (int c = 0; c < 3; c++) normal_out[(size_t)b * 3 + c] = n[c];
+    if (!ROWS) {
+        po.sdf[b] = sdf;
 #pragma unroll
-            for (int k = 0; k < K; k++) po.weights[(size_t)b * K + k] = w[k];
-        }
+        for (int k = 0; k < K; k++) po.weights[(size_t)b * K + k] = w[k];
     }
 
     // ---- the gathers (:679-680, :688-691): sum_k w_k record_k, ascending k, every product and sum rounded on its own ----
-    constexpr int Q = 4 / LANES;  // 16-byte words of a feature record this lane gathers: all four, or word q
+    constexpr int Q = 4;  // 16-byte words of a feature record
     float4_t f[K][Q];
 #pragma unroll
     for (int k = 0; k < K; k++) {
         const float4_t* src = reinterpret_cast<const float4_t*>(a.features + (size_t)max(ids[k], 0) * 16);
 #pragma unroll
-        for (int j = 0; j < Q; j++) f[k][j] = src[LANES == 1 ? (uint32_t)j : q];
+        for (int j = 0; j < Q; j++) f[k][j] = src[j];
     }
     half4_t o[Q];
 #pragma unroll
@@ -180,24 +170,17 @@ __global__ __launch_bounds__(256) void patch_lookup_kernel(const float* __restri
             for (int k = 0; k < K; k++) acc = acc + w[k] * f[k][j][c];
             o[j][c] = narrow(acc);
         }
-    if constexpr (LANES == 1) {
-        half8_t o8[2];
+    half8_t o8[2];
 #pragma unroll
-        for (int c = 0; c < 16; c++) o8[c / 8][c % 8] = o[c / 4][c % 4];
-        reinterpret_cast<half8_t*>(row)[0] = o8[0];
-        reinterpret_cast<half8_t*>(row)[1] = o8[1];
-    } else {
-        reinterpret_cast<half4_t*>(row)[q] = o[0];
-    }
-    if (first) write_height_ladder(sdf, row);
+    for (int c = 0; c < 16; c++) o8[c / 8][c % 8] = o[c / 4][c % 4];
+    reinterpret_cast<half8_t*>(row)[0] = o8[0];
+    reinterpret_cast<half8_t*>(row)[1] = o8[1];
+    write_height_ladder(sdf, row);
 
     if constexpr (LIT) {
-        // words 0, 1 of a lit record: phi; words 2, 3, 4: the frame (9 floats, three zeros).  LANES = 4: lane q takes words q and (q = 0) 4.
-        constexpr int NW = LANES == 1 ? 5 : 2;
+        // words 0, 1 of a lit record: phi; words 2, 3, 4: the frame (9 floats, three zeros)
 #pragma unroll
-        for (int j = 0; j < NW; j++) {
-            const int word = LANES == 1 ? j : (j == 0 ? (int)q : 4);
-            if (LANES == 4 && j == 1 && !first) break;
+        for (int word = 0; word < 5; word++) {
             float4_t l[K];
 #pragma unroll
             for (int k = 0; k < K; k++) l[k] = reinterpret_cast<const float4_t*>(a.lit + (size_t)max(ids[k], 0) * 20)[word];
@@ -238,12 +221,8 @@ void launch_patch_lookup(hipStream_t st, const nerftex_knn* kn, const float* xyz
     const uint32_t* cs = static_cast<const uint32_t*>(kn->cell_start);
     const P4* pts = static_cast<const P4*>(kn->points);
     KernelTimer kt("patch_lookup_kernel", st);
-    if (knob(kKnobPatchLanes) == 4 && B < (1u << 30))  // (4 B thread indices stay 32-bit)
-        hipLaunchKernelGGL((patch_lookup_kernel<ROWS, LIT, 4>), dim3(div_up(4u * B, 256u)), dim3(256), 0, st, xyz, dirs, B, g, cs, pts, a, mask, normal, xin, phi, tbn,
-                           po, units_dev, rows_per_unit);
-    else
-        hipLaunchKernelGGL((patch_lookup_kernel<ROWS, LIT, 1>), dim3(div_up(B, 256u)), dim3(256), 0, st, xyz, dirs, B, g, cs, pts, a, mask, normal, xin, phi, tbn, po,
-                           units_dev, rows_per_unit);
+    hipLaunchKernelGGL((patch_lookup_kernel<ROWS, LIT>), dim3(div_up(B, 256u)), dim3(256), 0, st, xyz, dirs, B, g, cs, pts, a, mask, normal, xin, phi, tbn, po,
+                       units_dev, rows_per_unit);
 }
 
 inline bool aligned16_(const void* p) { return !(reinterpret_cast<uintptr_t>(p) & 15); }

@@ -15,29 +15,23 @@ struct PlanarArgs {
     float offset, h_threshold;
 };
 
-// LANES = 1: one thread per row -- the four corners' 64 bytes each as four 16-byte loads, 16 independent loads in flight, two 16-byte stores of features.
-// LANES = 4: four adjacent lanes per row -- lane q loads quarter q of each corner (the four lanes read one texel's 64 contiguous bytes with one
-// instruction) and stores its 8 bytes; lane 0 also writes the row's scalars and the ladder.  Which one runs: the knob `planar_lanes`; the measured
-// choice is DESIGN.md 4.15's.  The arithmetic is the same expression tree per element in both: the same bits.
+// One thread per row: the four corners' 64 bytes each as four 16-byte loads, 16 independent loads in flight, two 16-byte stores of features.  (Four
+// adjacent lanes per row, one quarter of each corner per lane, measured no faster -- DESIGN.md 4.15 -- and was removed.)
 // ROWS: the rows contract of nerftex_curved_field_infer's kernels (writes the raw normal (0, 0, 1) for the mid kernel); otherwise the plain form
 // (every row, writes p_uv and sdf).  Both write mask [B] and the sigma net's input row xin [B,48] = [half(features) | half(ladder) | ones].
-// One row of the lookup (lane q of its LANES): everything the two kernels below and the lit lookup (planar_light.inc) write alike -- one expression
-// tree, so the same bits wherever it is called.  -> false: this thread is done (past the live rows, or a marked slot whose zeros are written);
-// true: b, q, u, v are the row, the lane and the map coordinates of a row that reads its texels.
-template <bool ROWS, int LANES>
+// One row of the lookup: everything the two kernels below and the lit lookup (planar_light.inc) write alike -- one expression tree, so the same
+// bits wherever it is called.  -> false: this thread is done (past the live rows, or a marked slot whose zeros are written); true: b, u, v are
+// the row and the map coordinates of a row that reads its texels.
+template <bool ROWS>
 __device__ __forceinline__ bool planar_lookup_row(const float* __restrict__ xyz, const float* __restrict__ dirs, const uint32_t B, const PlanarArgs& a,
                                                   float* __restrict__ p_uv, float* __restrict__ sdf_out, uint8_t* __restrict__ mask, float* __restrict__ normal,
                                                   half_t* __restrict__ xin, const int32_t* __restrict__ units_dev, const uint32_t rows_per_unit, uint32_t& b,
-                                                  uint32_t& q, float& u, float& v) {
+                                                  float& u, float& v) {
 #pragma clang fp contract(off)  // every framework op rounds on its own
-    static_assert(LANES == 1 || LANES == 4, "one thread or four lanes per row");
-    const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x;
-    b = tid / LANES, q = tid % LANES;
-    const bool first = q == 0;  // the lane that writes what a row has once
+    b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= (ROWS ? live_rows(B, units_dev, rows_per_unit) : B)) return false;
     half_t* row = xin + (size_t)b * 48;
     if (ROWS && slot_unused(dirs, b)) {  // no texel is read
-        if (!first) return false;
         mask[b] = 0;
 #pragma unroll
         for (int c = 0; c < 3; c++) normal[(size_t)b * 3 + c] = 0.0f;
@@ -51,49 +45,36 @@ __device__ __forceinline__ bool planar_lookup_row(const float* __restrict__ xyz,
     u = a.divide ? x0 / a.plane0 : x0 * a.plane0;
     v = a.divide ? x1 / a.plane1 : x1 * a.plane1;
     const float sdf = (x2 * a.height0) * a.height1 - a.offset;
-    if (first) {
-        mask[b] = (fabsf(sdf) < a.h_threshold && u >= -1.0f && u <= 1.0f && v >= -1.0f && v <= 1.0f) ? 1 : 0;
-        if (ROWS) {
-            normal[(size_t)b * 3] = 0.0f; normal[(size_t)b * 3 + 1] = 0.0f; normal[(size_t)b * 3 + 2] = 1.0f;
-        } else {
-            p_uv[(size_t)b * 2] = u; p_uv[(size_t)b * 2 + 1] = v;
-            sdf_out[b] = sdf;
-        }
+    mask[b] = (fabsf(sdf) < a.h_threshold && u >= -1.0f && u <= 1.0f && v >= -1.0f && v <= 1.0f) ? 1 : 0;
+    if (ROWS) {
+        normal[(size_t)b * 3] = 0.0f; normal[(size_t)b * 3 + 1] = 0.0f; normal[(size_t)b * 3 + 2] = 1.0f;
+    } else {
+        p_uv[(size_t)b * 2] = u; p_uv[(size_t)b * 2 + 1] = v;
+        sdf_out[b] = sdf;
     }
     // grid_sample(bilinear, align_corners=True, padding zeros); u runs along the map's first axis (bilinear_read.hpp: the shape lookup's read, too)
-    constexpr int Q = 4 / LANES;  // 16-byte quarters of a texel this lane reads: all four, or quarter q
-    half4_t o[Q];
-    bilinear_read<LANES>(a.map, a.H, a.W, u, v, q, o);
-    if constexpr (LANES == 1) {
-        store_features(o, row);
-    } else {
-        reinterpret_cast<half4_t*>(row)[q] = o[0];
-    }
-    if (first) write_height_ladder(sdf, row);
+    half4_t o[4];
+    bilinear_read(a.map, a.H, a.W, u, v, o);
+    store_features(o, row);
+    write_height_ladder(sdf, row);
     return true;
 }
 
-template <bool ROWS, int LANES>
+template <bool ROWS>
 __global__ __launch_bounds__(256) void planar_lookup_rows_kernel(const float* __restrict__ xyz, const float* __restrict__ dirs, const uint32_t B, const PlanarArgs a,
                                                                  float* __restrict__ p_uv, float* __restrict__ sdf_out, uint8_t* __restrict__ mask,
                                                                  float* __restrict__ normal, half_t* __restrict__ xin, const int32_t* __restrict__ units_dev,
                                                                  const uint32_t rows_per_unit) {
-    uint32_t b, q;
+    uint32_t b;
     float u, v;
-    planar_lookup_row<ROWS, LANES>(xyz, dirs, B, a, p_uv, sdf_out, mask, normal, xin, units_dev, rows_per_unit, b, q, u, v);
+    planar_lookup_row<ROWS>(xyz, dirs, B, a, p_uv, sdf_out, mask, normal, xin, units_dev, rows_per_unit, b, u, v);
 }
 
-// one launch of the lookup in the lane mapping the knob `planar_lanes` names (4: four lanes per row; anything else: one thread per row)
 template <bool ROWS>
 void launch_planar_lookup(hipStream_t st, const float* xyz, const float* dirs, uint32_t B, const PlanarArgs& a, float* p_uv, float* sdf, uint8_t* mask,
                           float* normal, half_t* xin, const int32_t* units_dev, uint32_t rows_per_unit) {
     KernelTimer kt("planar_lookup_rows_kernel", st);
-    if (knob(kKnobPlanarLanes) == 4 && B < (1u << 30))  // (4 B thread indices stay 32-bit)
-        hipLaunchKernelGGL((planar_lookup_rows_kernel<ROWS, 4>), dim3(div_up(4u * B, 256u)), dim3(256), 0, st, xyz, dirs, B, a, p_uv, sdf, mask, normal, xin, units_dev,
-                           rows_per_unit);
-    else
-        hipLaunchKernelGGL((planar_lookup_rows_kernel<ROWS, 1>), dim3(div_up(B, 256u)), dim3(256), 0, st, xyz, dirs, B, a, p_uv, sdf, mask, normal, xin, units_dev,
-                           rows_per_unit);
+    hipLaunchKernelGGL(planar_lookup_rows_kernel<ROWS>, dim3(div_up(B, 256u)), dim3(256), 0, st, xyz, dirs, B, a, p_uv, sdf, mask, normal, xin, units_dev, rows_per_unit);
 }
 
 // (no message: each entry names what it refuses)

@@ -5,8 +5,7 @@
 // row function of the lookup is planar.inc's, the lit reads lit_reads.hpp's, the closing sequence (the mid kernel with its second frame, the BRDF net, the closing
 // kernel) curved_light.inc's curved_light_back_half.
 //
-// Lane mapping: one thread per row (planar.inc's LANES = 1; DESIGN.md 4.15 measured the four-lane mapping no faster for the feature read, and the
-// 6 + 3 + 3 sixteen-byte words a row reads here beside the features do not split over four lanes evenly).  DESIGN.md 4.17.
+// Lane mapping: one thread per row, as planar.inc's (DESIGN.md 4.15, 4.17).
 
 namespace nerftex {
 namespace {
@@ -22,9 +21,9 @@ __global__ __launch_bounds__(256) void planar_light_lookup_rows_kernel(const flo
                                                                        half_t* __restrict__ xin, void* __restrict__ phi_out, int32_t* __restrict__ id_out,
                                                                        float* __restrict__ local_tbn, float* __restrict__ sample_tbn,
                                                                        const int32_t* __restrict__ units_dev, const uint32_t rows_per_unit) {
-    uint32_t b, q;
+    uint32_t b;
     float u, v;
-    if (!planar_lookup_row<ROWS, 1>(xyz, dirs, B, a, p_uv, sdf_out, mask, normal, xin, units_dev, rows_per_unit, b, q, u, v)) return;
+    if (!planar_lookup_row<ROWS>(xyz, dirs, B, a, p_uv, sdf_out, mask, normal, xin, units_dev, rows_per_unit, b, u, v)) return;
     lit_reads_row<ROWS>(l, a.H, a.W, u, v, b, B, phi_out, id_out, local_tbn, sample_tbn);  // (lit_reads.hpp: the reads the lit shape lookup shares)
 }
 

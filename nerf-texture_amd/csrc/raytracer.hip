@@ -553,7 +553,7 @@ __global__ __launch_bounds__(64) void shape_lookup_kernel(const uint32_t N, cons
     const float v = ((uv0.y * b0 + uv1.y * b1) + uv2.y * b2) * a.uv_rate;
     if constexpr (LIT) lit_reads_row<ROWS>(t.l, a.H, a.W, u, v, i, N, t.phi, t.patch_id, t.local_tbn, t.sample_tbn);
     half4_t o[4];
-    bilinear_read<1>(a.map, a.H, a.W, u, v, 0u, o);
+    bilinear_read(a.map, a.H, a.W, u, v, o);
     store_features(o, row);
     mask[i] = (fabsf(sdf) < a.h_limit && best >= 0) ? 1 : 0;
     normal_out[3 * (size_t)i] = nrm.x; normal_out[3 * (size_t)i + 1] = nrm.y; normal_out[3 * (size_t)i + 2] = nrm.z;

@@ -618,7 +618,7 @@ class Renderer(nn.Module):
         on how fast the host enqueues (r4: 65 to 84 Mpix/s between a 16-core and a 128-core host for the same device work).  What made the
         iteration recordable: its launch sizes are the range's full size (N rays, F N sample slots) and n_step = clamp(F N / alive, F, 8 F) is
         derived by the kernels from the alive count on the device (NERFTEX_ROWS_AUTO) -- the host only learns, one block late, whether any ray is
-        left (a 4-byte copy per block into pinned memory).  Rays, accumulators and the iteration's buffers are persistent (the graphs bake
+        left (one word in pinned memory, see Round 6 below).  Rays, accumulators and the iteration's buffers are persistent (the graphs bake
         their addresses): the frame's rays are copied in.  The ranges replay side by side on their own streams; their graphs were recorded
         under scratch sets of their own (nerftex_workspace_capture_set).  Same image as the reference loop, bit for bit: a ray's samples and
         the order they are composited in do not depend on how they are cut into iterations (tests/test_gpu_round5.py).  No perturbation
@@ -639,7 +639,7 @@ class Renderer(nn.Module):
         # valid across training steps), else the fp32 parameters with their versions (a changed parameter means a new cached 16-bit copy)
         have_leaves = all(t is not None for t in leaves) and len(leaves) > 0
         stamp = (N, parts, int(slots_per_ray), int(block), float(dt_gamma), int(max_steps), self.density_bitfield.data_ptr(), self.aabb_infer.data_ptr(),
-                 float(self.density_scale), float(self.bound), int(self.cascade), int(self.grid_size), float(self.min_near), torch.get_autocast_dtype("cuda"), bool(_InferGraphPart.COUNT_MIRROR),
+                 float(self.density_scale), float(self.bound), int(self.cascade), int(self.grid_size), float(self.min_near), torch.get_autocast_dtype("cuda"),
                  torch.is_autocast_enabled(),
                  tuple(t.data_ptr() for t in leaves) if have_leaves else tuple((p.data_ptr(), p._version) for p in field.parameters()))
         if hasattr(field, "graph_stamp"):  # a field whose kernels read more than its parameters (CurvedField: the mesh, its search structures, scalars)
@@ -677,16 +677,14 @@ class Renderer(nn.Module):
                     job.graph_for(job.known).replay()
                     slot = rounds % job.ring
                     # the alive count at the START of the block's last iteration (an upper bound of what is left): read by the host one block late.
-                    # The compaction kernel itself writes it to pinned memory (job.mirror); the copy node is the A/B form (COUNT_MIRROR = False)
-                    if not job.mirror:
-                        job.host[slot:slot + 1].copy_(job.counters[1:2], non_blocking=True)
+                    # The compaction kernel itself writes it to pinned memory (job.host[1]); the event orders the host's read behind the block
                     job.events[slot].record()
                 job.pending.append(slot)
                 if len(job.pending) > 1:
                     s_ = job.pending.pop(0)
                     job.events[s_].synchronize()
-                    # (mirror: the word may already hold a LATER block's count -- a newer upper bound, alive rays never increase)
-                    job.known = min(job.known, int(job.host[1] if job.mirror else job.host[s_]))
+                    # (the word may already hold a LATER block's count -- a newer upper bound, alive rays never increase)
+                    job.known = min(job.known, int(job.host[1]))
                     if job.known <= 0:
                         active.remove(k)
             rounds += 1
@@ -727,8 +725,6 @@ class _InferGraphPart:
     (NERFTEX_ROWS_AUTO): compaction -> march -> hash-grid gather + field -> compositing, every launch sized for all N rays / F N slots and
     cut short by the kernels."""
 
-    COUNT_MIRROR = True  # the alive count reaches the host through a store of the compaction kernel (round 6) instead of a copy node per block (A/B)
-
     def __init__(self, renderer, rays_o, rays_d, dt_gamma, max_steps, F, block, set_id, stream):
         from nerftex_hip import rows_auto
 
@@ -748,8 +744,7 @@ class _InferGraphPart:
         self.M = (N * F + 127) // 128 * 128
         self.buf = torch.empty(self.M * 8, dtype=torch.float32, device=dev)
         self.ring = 4
-        self.host = torch.zeros(self.ring, dtype=torch.int32).pin_memory()
-        self.mirror = bool(self.COUNT_MIRROR)
+        self.host = torch.zeros(2, dtype=torch.int32).pin_memory()  # the compaction's copy of the alive count, one word per ping-pong half
         self.events = [torch.cuda.Event() for _ in range(self.ring)]
         self.g_init = self.g_block = None
         self.bounds = [N] + [b for b in (N // 2, N // 4, N // 8, N // 32, N // 128, N // 512) if b >= 256]
@@ -782,12 +777,9 @@ class _InferGraphPart:
         c, ra, rt = self.counters, self.rays_alive, self.rays_t
         # (the compaction also keeps the reference loop's condition `step < max_steps`, step += n_step: a ray still alive when the budget is used
         # up is not marched any further -- the kernels derive n_step >= F, up to 8 F, so counting F per iteration on the host would overshoot)
-        if self.mirror:  # ... and the kernel leaves a copy of the count in pinned host memory (word `cur`): no copy node behind the block
-            check(lib.nerftex_compact_rays_budget_mirror_dev(N, ptr(c[old:]), ptr(ra[cur]), ptr(ra[old]), ptr(rt[cur]), ptr(rt[old]), ptr(c[cur:]), ptr(self.steps_done),
-                                                             self.max_steps, self.auto, self.host.data_ptr() + 4 * cur, stream()))
-        else:
-            check(lib.nerftex_compact_rays_budget_dev(N, ptr(c[old:]), ptr(ra[cur]), ptr(ra[old]), ptr(rt[cur]), ptr(rt[old]), ptr(c[cur:]), ptr(self.steps_done),
-                                                      self.max_steps, self.auto, stream()))
+        # ... and the kernel leaves a copy of the count in pinned host memory (word `cur`): no copy node behind the block
+        check(lib.nerftex_compact_rays_budget_mirror_dev(N, ptr(c[old:]), ptr(ra[cur]), ptr(ra[old]), ptr(rt[cur]), ptr(rt[old]), ptr(c[cur:]), ptr(self.steps_done),
+                                                         self.max_steps, self.auto, self.host.data_ptr() + 4 * cur, stream()))
         buf = self.buf
         xyzs, dirs, deltas = buf[:3 * M].view(M, 3), buf[3 * M:6 * M].view(M, 3), buf[6 * M:8 * M].view(M, 2)
         check(lib.nerftex_march_rays_dev(N, ptr(c[cur:]), self.auto, ptr(ra[cur]), ptr(rt[cur]), ptr(self.rays_o), ptr(self.rays_d), float(r.bound), self.dt_gamma,

@@ -96,21 +96,6 @@ def test_the_threshold_and_the_plane_edges(dev):
     assert np.array_equal(xin_b[0, :16].float().cpu().numpy(), F[H - 1, W - 1].astype(np.float16).astype(np.float32))
 
 
-@pytest.mark.parametrize("rescale", [True, False], ids=["modeA", "modeB"])
-def test_the_four_lane_mapping_writes_the_same_bits(dev, knobs, rescale):
-    """The knob `planar_lanes` = 4 (four lanes per row, an A/B form of the lookup kernel): every output of the plain entry bit for bit, at batch
-    sizes around its 64-row workgroups."""
-    H, W = 5, 4
-    fmap = torch.from_numpy(pf.seeded_map(H, W)).to(dev)
-    cases = [(B, torch.from_numpy(pf.case_points(H, W, B, rescale, 1.7, 0.01)).to(dev)) for B in (1, 63, 64, 65, 384)]
-    scalars = _scalars(H, W, rescale, 1.7, 0.01)
-    want = [_lookup(x, fmap, scalars) for _, x in cases]
-    knobs(planar_lanes=4)
-    for (B, x), w in zip(cases, want):
-        got = _lookup(x, fmap, scalars)
-        assert all(torch.equal(g, v) for g, v in zip(got, w)), B
-
-
 # ---- 2. the chain against its pieces -------------------------------------------------------------------------------------------------------------------------
 
 def _half_weights(n, seed, scale, dev):

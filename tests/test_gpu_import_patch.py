@@ -130,19 +130,6 @@ def test_plain_lookups_against_float64_the_op_by_op_route_and_the_search(dev, li
     print(f"S={S}: decided rows (inside, outside) of the direct-above test, |sdf| < h, min dis < h: {sides.tolist()}")
 
 
-@pytest.mark.parametrize("lit", [False, True], ids=["static", "lit"])
-def test_the_four_lane_mapping_writes_the_same_bits(dev, lit_field, knobs, lit):
-    """The knob `patch_lanes` = 4 (four lanes per row): every output of the plain entry bit for bit, at batch sizes around its 64-row workgroups."""
-    field = lit_field
-    patch = _import(field, 12, True)
-    cases = [torch.from_numpy(pm.case_queries(patch, B, seed=3)).to(dev) for B in (1, 63, 64, 65, 384)]
-    want = [_lookup(field, x, lit) for x in cases]
-    knobs(patch_lanes=4)
-    for x, w in zip(cases, want):
-        got = _lookup(field, x, lit)
-        assert all(torch.equal(g.view(torch.uint8), v.view(torch.uint8)) for g, v in zip(got, w)), x.shape[0]
-
-
 # ---- 2. the chains against their pieces ------------------------------------------------------------------------------------------------------------------------
 
 def _half_weights(n, seed, scale, dev):
@@ -165,7 +152,7 @@ def _dirs(B, dev):
 
 
 @pytest.mark.parametrize("S,per_point", PATCHES)
-def test_static_chain_is_its_pieces_under_the_rows_contract(dev, static_field, knobs, S, per_point):
+def test_static_chain_is_its_pieces_under_the_rows_contract(dev, static_field, S, per_point):
     from nerftex_hip import CurvedPatchInferDesc, check, lib, ptr, stream
 
     field = static_field
@@ -188,24 +175,22 @@ def test_static_chain_is_its_pieces_under_the_rows_contract(dev, static_field, k
         assert int((mask == 0).sum()) > 0 and not want_sigma[mask == 0].any() and not want_rgb[mask == 0].any(), "outside the mask: sigma 0 and colour 0"
         marked, xm, dm = _marked(x, d)
         scratch = torch.empty(lib.nerftex_curved_patch_infer_scratch_bytes(B), dtype=torch.uint8, device=dev)
-        for lanes in (0, 4):
-            knobs(patch_lanes=lanes)
-            for units, rows_per_unit, live in ((0, 128, 0), (1, 128, 128), (None, 0, B), (B // 64, 64, B)):
-                units_dev = None if units is None else torch.tensor([units], dtype=torch.int32, device=dev)
-                sigma = torch.full((B,), SENTINEL, dtype=torch.float32, device=dev)
-                rgbs = torch.full((B, 3), SENTINEL, dtype=torch.float32, device=dev)
-                desc = CurvedPatchInferDesc(
-                    knn=field._patch_knn.value, xyz=ptr(xm), dirs=ptr(dm), B=B, n_points=S * S, geom=ptr(field.patch_geom), features=ptr(field.features_imported),
-                    n_features=16, h_threshold=pm.H_THRESHOLD, n_freqs=12, sigma_weights=ptr(ws), sigma_in=48, sigma_hidden=32, sigma_layers=2, sigma_out=16,
-                    color_weights=ptr(wc), color_in=32, color_hidden=64, color_layers=3, color_out=3, fc_weight=1.0, eval=3, sigma=ptr(sigma), rgbs=ptr(rgbs),
-                    units_dev=ptr(units_dev), rows_per_unit=rows_per_unit, scratch=ptr(scratch), scratch_bytes=scratch.numel())
-                check(lib.nerftex_curved_patch_infer(ctypes.byref(desc), stream()))
-                torch.cuda.synchronize()
-                rows = torch.arange(B, device=dev)
-                plain, unused, past = (rows < live) & ~marked, (rows < live) & marked, rows >= live
-                assert torch.equal(sigma[plain], want_sigma[plain]) and torch.equal(rgbs[plain], want_rgb[plain]), (B, units, lanes)
-                assert bool((sigma[unused] == 0).all()) and bool((rgbs[unused] == 0).all())
-                assert bool((sigma[past] == SENTINEL).all()) and bool((rgbs[past] == SENTINEL).all())
+        for units, rows_per_unit, live in ((0, 128, 0), (1, 128, 128), (None, 0, B), (B // 64, 64, B)):
+            units_dev = None if units is None else torch.tensor([units], dtype=torch.int32, device=dev)
+            sigma = torch.full((B,), SENTINEL, dtype=torch.float32, device=dev)
+            rgbs = torch.full((B, 3), SENTINEL, dtype=torch.float32, device=dev)
+            desc = CurvedPatchInferDesc(
+                knn=field._patch_knn.value, xyz=ptr(xm), dirs=ptr(dm), B=B, n_points=S * S, geom=ptr(field.patch_geom), features=ptr(field.features_imported),
+                n_features=16, h_threshold=pm.H_THRESHOLD, n_freqs=12, sigma_weights=ptr(ws), sigma_in=48, sigma_hidden=32, sigma_layers=2, sigma_out=16,
+                color_weights=ptr(wc), color_in=32, color_hidden=64, color_layers=3, color_out=3, fc_weight=1.0, eval=3, sigma=ptr(sigma), rgbs=ptr(rgbs),
+                units_dev=ptr(units_dev), rows_per_unit=rows_per_unit, scratch=ptr(scratch), scratch_bytes=scratch.numel())
+            check(lib.nerftex_curved_patch_infer(ctypes.byref(desc), stream()))
+            torch.cuda.synchronize()
+            rows = torch.arange(B, device=dev)
+            plain, unused, past = (rows < live) & ~marked, (rows < live) & marked, rows >= live
+            assert torch.equal(sigma[plain], want_sigma[plain]) and torch.equal(rgbs[plain], want_rgb[plain]), (B, units)
+            assert bool((sigma[unused] == 0).all()) and bool((rgbs[unused] == 0).all())
+            assert bool((sigma[past] == SENTINEL).all()) and bool((rgbs[past] == SENTINEL).all())
 
 
 def _call_lit(field, x, d, live=None):
@@ -230,12 +215,12 @@ def _call_lit(field, x, d, live=None):
 
 
 @pytest.mark.parametrize("S,per_point", PATCHES)
-def test_lit_chain_is_its_pieces_under_the_rows_contract(dev, lit_field, knobs, S, per_point):
+def test_lit_chain_is_its_pieces_under_the_rows_contract(dev, lit_field, S, per_point):
     """The lit chain has no plain entries for its back half; its pieces are the plain lit lookup and forward(): sigma and the mask are
     forward()'s bit for bit, the shading normal lies inside the float64 bound of tests/import_light_float64.py evaluated on the lookup's own
     outputs (ONE rotation: the second frame is the identity, which a half product leaves as it is), the colour within the 2e-2 the fixture
     tests apply to this back half; rows are independent (marked slots and rows past `live` as specified, every other row the unmarked call's
-    bits), under both lane mappings."""
+    bits)."""
     field = lit_field
     patch = _import(field, S, per_point)
     field.fc_weight, field.light_visual_mode = 0.7, "Full"
@@ -273,16 +258,14 @@ def test_lit_chain_is_its_pieces_under_the_rows_contract(dev, lit_field, knobs, 
             assert (err <= bound)[rows].all()
             assert float((full_c - f_color.float()).abs().max()) <= 2e-2
             marked, xm, dm = _marked(x, d)
-            for lanes in (0, 4):
-                knobs(patch_lanes=lanes)
-                for units, rows_per_unit, live in ((0, 128, 0), (1, 128, 128), (None, 0, B)):
-                    lv = None if units is None else (torch.tensor([units], dtype=torch.int32, device=dev), rows_per_unit)
-                    sigma, rgbs, normal = _call_lit(field, xm, dm, lv)
-                    r = torch.arange(B, device=dev)
-                    plain, unused, past = (r < live) & ~marked, (r < live) & marked, r >= live
-                    for got, want in ((sigma, full_s), (rgbs, full_c), (normal, full_n)):
-                        assert torch.equal(got[plain], want[plain]), (B, units, lanes)
-                        assert bool((got[unused] == 0).all()) and bool((got[past] == SENTINEL).all())
+            for units, rows_per_unit, live in ((0, 128, 0), (1, 128, 128), (None, 0, B)):
+                lv = None if units is None else (torch.tensor([units], dtype=torch.int32, device=dev), rows_per_unit)
+                sigma, rgbs, normal = _call_lit(field, xm, dm, lv)
+                r = torch.arange(B, device=dev)
+                plain, unused, past = (r < live) & ~marked, (r < live) & marked, r >= live
+                for got, want in ((sigma, full_s), (rgbs, full_c), (normal, full_n)):
+                    assert torch.equal(got[plain], want[plain]), (B, units)
+                    assert bool((got[unused] == 0).all()) and bool((got[past] == SENTINEL).all())
     finally:
         field.fc_weight = 1.0
 

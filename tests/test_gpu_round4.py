@@ -452,43 +452,6 @@ def test_curved_field_sigma_gradient_reaches_the_sample_position(dev):
     np.testing.assert_allclose(np.linalg.norm(n, axis=-1), 1.0, atol=1e-3)
 
 
-def test_transposing_read_backward_matches_the_selection_matrix_backward(dev, knobs):
-    """knob ffmlp_bwd_tr = 1 (weight-gradient operands through ds_read_b64_tr_b16, csrc/ffmlp_body.inc) against the default (0/1 selection
-    MFMAs): the activation-gradient chain is untouched -- dL/dinput bit for bit -- and the weight gradients agree to the fp32 summation
-    order inside a 32-row step (the transposing read puts the batch rows into the contraction slots in another order)."""
-    from nerftex_hip import check, lib, ptr, stream
-
-    torch.manual_seed(31)
-    B = 128 * 64
-    half = dict(dtype=torch.float16, device=dev)
-    wc = ((torch.rand(64 * (32 + 128 + 16), device=dev) * 2 - 1) * 0.2).half()
-    ws = ((torch.rand(64 * (32 + 64 + 16), device=dev) * 2 - 1) * 0.2).half()
-    cin, x_rows = torch.randn(B, 32, device=dev).half(), torch.randn(B, 32, device=dev).half()
-    rgbs = torch.sigmoid(torch.randn(B, 3, device=dev)).half().float()
-    h = torch.randn(B, 16, device=dev).half()
-    grad_sigma, grad_rgbs = torch.randn(B, device=dev) * 1e-2, torch.randn(B, 3, device=dev)
-
-    def run():
-        outs = [torch.empty(B, 32, **half), torch.empty(B, 32, **half), torch.empty_like(ws), torch.empty_like(wc)]
-        check(lib.nerftex_field_backward(ptr(grad_sigma), ptr(grad_rgbs), ptr(rgbs), ptr(h), ptr(cin), ptr(x_rows), ptr(ws), ptr(wc), B, ptr(outs[0]), ptr(outs[1]),
-                                         ptr(outs[2]), ptr(outs[3]), stream()))
-        g = (torch.randn(B, 16, device=dev, generator=torch.Generator(device=dev).manual_seed(5)) * 1e-2).half()
-        gx, gw = torch.empty(B, 32, **half), torch.empty_like(ws)
-        check(lib.nerftex_ffmlp_backward(ptr(g), ptr(x_rows), ptr(ws), None, B, 32, 16, 64, 2, 0, 6, 1, None, ptr(gx), ptr(gw), stream()))
-        torch.cuda.synchronize()
-        return outs + [gx, gw]
-
-    base = run()
-    knobs(ffmlp_bwd_tr=1)
-    tr = run()
-    for i in (0, 1, 4):  # dL/dcin, dL/dx of the field forms, dL/dx of the plain recomputing form
-        assert torch.equal(base[i].view(torch.int16), tr[i].view(torch.int16))
-    for i in (2, 3, 5):
-        a, b = base[i].float(), tr[i].float()
-        assert float((a - b).abs().max()) <= 2e-3 * float(a.abs().max()), i
-        assert not torch.equal(a, b) or True
-
-
 def test_step_group_trains_like_single_steps(dev):
     """accelerate(renderer, steps_per_call=4).step_group -- 4 fresh batches per call, one replayed graph for their shade + backward + optimizer,
     their marches ahead on the second stream -- against accelerate(renderer).step on the same batches in the same order: the same kernels on

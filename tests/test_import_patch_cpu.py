@@ -322,7 +322,7 @@ def test_the_descriptors_are_bound_field_for_field_with_the_compilers_layout(tmp
         assert int(out[n]) == getattr(cls, n).offset, n
 
 
-def test_the_symbols_the_constants_and_the_knob():
+def test_the_symbols_and_the_constants():
     import nerftex_hip
 
     header = open(HEADER).read()
@@ -331,10 +331,6 @@ def test_the_symbols_the_constants_and_the_knob():
         assert re.search(r"\b" + name + r"\s*\(", header) and hasattr(ctypes.CDLL(nerftex_hip.LIB_PATH), name) and name in nerftex_hip.EXPORTS, name
     assert (nerftex_hip.PATCH_GEOM_STRIDE, nerftex_hip.PATCH_LIT_STRIDE) == (8, 20)
     assert re.search(r"#define NERFTEX_PATCH_GEOM_STRIDE 8\b", header) and re.search(r"#define NERFTEX_PATCH_LIT_STRIDE 20\b", header)
-    assert nerftex_hip.lib.nerftex_tune_get(b"patch_lanes") == 0, "the default: one thread per row"
-    with nerftex_hip.tune(patch_lanes=4):
-        assert nerftex_hip.lib.nerftex_tune_get(b"patch_lanes") == 4
-    assert nerftex_hip.lib.nerftex_tune_get(b"patch_lanes") == 0
 
 
 def test_scratch_queries():

@@ -62,14 +62,8 @@ def main():
 
     import nerftex_hip
 
-    def four_lanes(fn):
-        def run():
-            with nerftex_hip.tune(planar_lanes=4):
-                return fn()
-        return run
-
-    forms = {"lookup_kernel": lookup_kernel, "lookup_kernel_four_lanes": four_lanes(lookup_kernel), "lookup_framework_baseline": lookup_framework,
-             "infer_fused": lambda: infer(True), "infer_fused_four_lanes": four_lanes(lambda: infer(True)), "infer_op_by_op": lambda: infer(False)}
+    forms = {"lookup_kernel": lookup_kernel, "lookup_framework_baseline": lookup_framework, "infer_fused": lambda: infer(True),
+             "infer_op_by_op": lambda: infer(False)}
     mask = lookup_kernel()[2]
     s_f, c_f = infer(True)
     s_o, c_o = infer(False)
@@ -94,27 +88,23 @@ def main():
             times[name].append(t0.elapsed_time(t1) * 1e3 / a.iters)
     out = {"what": f"CurvedField with an imported {a.map} x {a.map} x 16 fp32 map, {B} rows, fp16 autocast, eval; us per call between device events around "
                    f"{a.iters} eager calls (host launch time and the output allocations included for every form), {a.reps} alternating windows, median (min .. max). "
-                   "lookup_kernel = nerftex_planar_lookup, one thread per row (the default), _four_lanes: the knob planar_lanes = 4; lookup_framework_baseline = the reference's expressions as framework ops "
+                   "lookup_kernel = nerftex_planar_lookup, one thread per row; lookup_framework_baseline = the reference's expressions as framework ops "
                    "(a baseline, not a bar); infer_fused = nerftex_curved_import_infer; infer_op_by_op = forward() with fused_glue = False",
            "look": look,
            "median_us": {k: round(statistics.median(t), 1) for k, t in times.items()},
            "min_max_us": {k: [round(min(t), 1), round(max(t), 1)] for k, t in times.items()}}
-    # the device time of the chain's launches alone (the library's own event pairs around each kernel; no host time)
-    # the two lane mappings of the lookup (the knob `planar_lanes`), 3 alternating windows each
-    chain = {}
+    # the device time of the chain's launches alone (the library's own event pairs around each kernel; no host time), 3 windows
+    chain = []
     for _ in range(3):
-        for lanes in (1, 4):
-            with nerftex_hip.tune(planar_lanes=lanes):
-                nerftex_hip.kernel_profile(True, reset=True)
-                for _ in range(a.iters):
-                    infer(True)
-                torch.cuda.synchronize()
-                prof = nerftex_hip.kernel_profile()
-                nerftex_hip.kernel_profile(False)
-            chain.setdefault(lanes, []).append({k: v["avg_us"] for k, v in prof.items()})
-    out["chain_kernels_avg_us"] = {k: round(statistics.median(w[k] for w in chain[1]), 2) for k in chain[1][0]}
-    out["lookup_kernel_avg_us_by_lanes_per_row"] = {str(lanes): [round(w["planar_lookup_rows_kernel"], 2) for w in chain[lanes]] for lanes in (1, 4)}
-    assert torch.equal(four_lanes(lookup_kernel)()[3], lookup_kernel()[3]), "the two lane mappings write the same bits"
+        nerftex_hip.kernel_profile(True, reset=True)
+        for _ in range(a.iters):
+            infer(True)
+        torch.cuda.synchronize()
+        prof = nerftex_hip.kernel_profile()
+        nerftex_hip.kernel_profile(False)
+        chain.append({k: v["avg_us"] for k, v in prof.items()})
+    out["chain_kernels_avg_us"] = {k: round(statistics.median(w[k] for w in chain), 2) for k in chain[0]}
+    out["lookup_kernel_avg_us"] = [round(w["planar_lookup_rows_kernel"], 2) for w in chain]
     out["lookup_bytes_per_row"] = {"read": 12 + 4 * 64, "written_rows_form": 1 + 12 + 96}
     out["framework_over_kernel"] = round(out["median_us"]["lookup_framework_baseline"] / out["median_us"]["lookup_kernel"], 2)
     out["op_by_op_over_fused"] = round(out["median_us"]["infer_op_by_op"] / out["median_us"]["infer_fused"], 2)

@@ -1,10 +1,9 @@
 """What rendering an imported feature patch costs (CurvedField.import_patch): a 128 x 128 patch (what export_field produces by default), 262 144
 samples near it, fp16 autocast, eval.  Per figure: one warm-up call, then the median (min .. max) of five calls, each timed by an event pair
 around the call on the stream (device time of everything the call enqueues; the op-by-op route's includes the gaps between its ~60 launches):
-  * the fused chain, CurvedField.infer -> nerftex_curved_patch_infer (static) and nerftex_curved_light_patch_infer (SH-lit), in both lane
-    mappings of the lookup kernel (the knob `patch_lanes`);
+  * the fused chain, CurvedField.infer -> nerftex_curved_patch_infer (static) and nerftex_curved_light_patch_infer (SH-lit);
   * the op-by-op route, forward() over CurvedField._patch_embed_reference (the library's neighbour search, framework ops behind it);
-  * the plain lookups alone (nerftex_patch_lookup, nerftex_patch_light_lookup) in both lane mappings.
+  * the plain lookups alone (nerftex_patch_lookup, nerftex_patch_light_lookup).
 The parent commit has no path that renders a patch: there is nothing to compare these figures with.
     timeout 600 python tools/import_patch_timing.py > profiles/import_patch_timing.json"""
 import argparse
@@ -26,7 +25,6 @@ def main():
     import numpy as np
     import torch
 
-    import nerftex_hip
     from ngp_harness.curved import CurvedField, star_flower_mesh
 
     assert torch.cuda.is_available(), "a timing needs the GPU"
@@ -90,10 +88,8 @@ def main():
             assert field._infer_route(x, d)[0] == ("nerftex_curved_light_patch_infer" if lit else "nerftex_curved_patch_infer")
             mask = field._patch_lookup(x)[1]
         res = {"share_of_rows_inside_the_mask": round(float(mask.float().mean()), 4)}
-        for lanes in (1, 4):
-            with nerftex_hip.tune(patch_lanes=lanes):
-                res[f"fused_chain_lanes{lanes}"] = timed(infer)
-                res[f"plain_lookup_lanes{lanes}"] = timed(lambda: field._patch_lookup(x, lit=lit))
+        res["fused_chain"] = timed(infer)
+        res["plain_lookup"] = timed(lambda: field._patch_lookup(x, lit=lit))
         res["op_by_op_embed"] = timed(op_by_op)
         if not lit:
             res["op_by_op_forward"] = timed(forward_op_by_op)
