@@ -1488,6 +1488,41 @@ typedef struct nerftex_envmap_fit_desc { /* device pointers unless noted */
 int nerftex_envmap_fit(const nerftex_envmap_fit_desc* d, void* stream);
 size_t nerftex_envmap_fit_scratch_bytes(uint32_t H, uint32_t W);
 
+/* -------------------------------------------------------------------------
+ * Extension: the per-probe visibility lighting of an imported map -- load_envmap_with_visibility without a file (nerf/sh_light_model.py:653-665)
+ * around fit_product_of_SHs (:692-709).  For each probe p of K, from sh = env_shs[:9], `rounds` steps of torch.optim.Adam(lr) on
+ *   loss(sh) = mean over `batch` sphere points x of  sum_c ( Y(x) . sh[:, c] - (Y(x) . env_shs[:9, c]) (Y(x) . lobes[p]) )^2
+ * with Y the nine svox2 bases (the polynomials and signs of nerf/spherical_harmonics.py, degree 2) and fresh points every step.  AS THE REFERENCE
+ * EXECUTES IT: it never clears the gradient, so the gradient Adam sees at step t is the SUM of the gradients of steps 1..t.  The result is not
+ * converged; it is defined by this trajectory and by the points.
+ *   points     given ([K, rounds, batch, 3]): read.  NULL: point (p, r, i) comes from a counter hash keyed by (seed, p, r, i) -- two uniforms in
+ *              [0, 1) with 24 bits, phi = 2 pi u1, theta = acos(1 - 2 u2), (cos phi sin theta, sin phi sin theta, cos theta), the reference's
+ *              expression -- so the result does not depend on the launch shape.  THIS LIBRARY'S OWN STREAM, NOT torch.rand's: a run with its own
+ *              points agrees with the reference's only statistically.  points_out, if given, receives every point used.
+ *   a round    one workgroup of 256 threads per probe walks all rounds; thread t takes points t, t + 256, ...: per point the nine bases, the
+ *              three residuals 2 (pred - gt) / batch, 27 partial sums; the wave's sum on the DPP paths, the four waves in order through LDS;
+ *              added to the running gradient; torch's single-tensor Adam on fp32 state (betas 0.9 / 0.999, eps 1e-8, step size lr / (1 - 0.9^t)
+ *              and sqrt(1 - 0.999^t) from double, rounded to fp32):  m += 0.1 (g - m);  v = 0.999 v + (0.001 g) g;
+ *              sh += (-step_size m) / (sqrt(v) / bc2 + eps).  All fp32, every operation rounded on its own, the order of every sum fixed.
+ * One launch, nothing allocated, the host never waits: the call can be captured; the same bits on every run.
+ * NERFTEX_ERR_INVALID with a message, before anything is launched: a NULL descriptor, env_shs, lobes or tables, n_sh < 9, K == 0 or K > 256,
+ * rounds == 0 or batch == 0, lr not positive and finite.
+ * ------------------------------------------------------------------------- */
+typedef struct nerftex_envmap_vis_fit_desc { /* device pointers unless noted */
+    const float* env_shs;              /* [n_sh,3] fp32: the imported lighting; rows 0..8 are read                                */
+    uint32_t n_sh;                     /* rows of env_shs, >= 9                                                                   */
+    const float* lobes;                /* [K,9] fp32: the visibility lobe rotated onto each probe; one lobe for all three colours */
+    uint32_t K;                        /* 1 .. 256                                                                                */
+    uint32_t rounds;                   /* the reference: 800                                                                      */
+    uint32_t batch;                    /* points per round; the reference: 1024.  Any positive number                             */
+    double lr;                         /* host value; the reference: 1e-3                                                         */
+    uint64_t seed;                     /* host value; keys the points when `points` is NULL                                       */
+    const float* points;               /* [K,rounds,batch,3] fp32 or NULL                                                         */
+    float* points_out;                 /* [K,rounds,batch,3] fp32 or NULL                                                         */
+    float* tables;                     /* [K,9,3] fp32 out                                                                        */
+} nerftex_envmap_vis_fit_desc;
+int nerftex_envmap_vis_fit(const nerftex_envmap_vis_fit_desc* d, void* stream);
+
 /* grad_hc [B,16] fp16 = sigmoid backward of the fp16-narrowed grad_rgbs, columns 3..15 zero                      */
 int nerftex_field_out_backward(const float* grad_rgbs, const float* rgbs, uint32_t B, void* grad_hc, void* stream);
 

@@ -724,3 +724,6 @@ extern "C" int nerftex_field_out_backward(const float* grad_rgbs, const float* r
 
 // ---- fitting SH lighting to an imported environment map (nerftex_envmap_fit): svox2_basis9 comes from shlight.inc -----------------------------------------
 #include "envmap.inc"
+
+// ---- the per-probe visibility lighting of an imported map (nerftex_envmap_vis_fit): svox2_basis9 and AdamConsts come from the two above -------------------
+#include "envmap_vis.inc"

@@ -72,6 +72,7 @@ _SIGNATURES = {
     "nerftex_sh_light_backward": [_vp, _vp],
     "nerftex_sh_light_probe_forward": [_vp, _vp],
     "nerftex_envmap_fit": [_vp, _vp],
+    "nerftex_envmap_vis_fit": [_vp, _vp],
     "nerftex_field_mid_backward": [_vp, _vp, _vp, _u32, _vp, _vp],
     "nerftex_field_out_forward": [_vp, _u32, _vp, _vp],
     "nerftex_field_out_backward": [_vp, _vp, _u32, _vp, _vp],
@@ -364,6 +365,12 @@ class EnvmapFitDesc(C.Structure):
     """nerftex_envmap_fit_desc of include/nerftex_hip.h, field for field: SH lighting fitted to an environment map."""
     _fields_ = [("envmap", _vp), ("phi", _vp), ("theta", _vp), ("H", _u32), ("W", _u32), ("n_sh", _u32), ("max_steps", _u32), ("min_steps", _u32),
                 ("lr", _f64), ("min_loss", _f64), ("env_shs", _vp), ("steps_run", _vp), ("final_loss", _vp), ("scratch", _vp), ("scratch_bytes", _sz)]
+
+
+class EnvmapVisFitDesc(C.Structure):
+    """nerftex_envmap_vis_fit_desc of include/nerftex_hip.h, field for field: the per-probe visibility lighting of an imported map."""
+    _fields_ = [("env_shs", _vp), ("n_sh", _u32), ("lobes", _vp), ("K", _u32), ("rounds", _u32), ("batch", _u32), ("lr", _f64), ("seed", _u64),
+                ("points", _vp), ("points_out", _vp), ("tables", _vp)]
 
 
 # texture synthesis (nerftex_synth_*): status codes, modes, log layout and the arrays nerftex_synth_read copies

@@ -23,9 +23,14 @@ Relighting (the reference's load_envmap :625, switch_envmap_import :675, the eva
                     reference's loop op by op with torch.optim.Adam.
   load_envmap       takes such a map, or fitted coefficients (the reference's .npy), and optionally the reference's _vis.npz tables: one
                     lighting per probe direction, chosen per sample by its coarse normal (`shade_visibility`); fused: nerftex_sh_light_probe_forward.
+                    With visibility=True it computes those tables itself:
+  envmap_probe_tables   load_envmap_with_visibility without a file (:653-665): the 8 x 8 probe grid (probe_grid), the clamped-cosine lobe rotated onto
+                    every probe (visibility_lobes: rotate_coeff_by_normal, :228-282) and, per probe, fit_product_of_SHs (:692-709): 800 Adam steps on
+                    1024 fresh sphere points each, WITHOUT zero_grad, as the reference executes it.  On the GPU one call of nerftex_envmap_vis_fit
+                    (csrc/envmap_vis.inc: a workgroup per probe walks all rounds) with this library's own counter-based points; `fused = False` or a
+                    CPU tensor runs the reference's loop op by op (fit_product_of_shs) with torch.rand.
   lighting()        the coefficients in effect: the imported ones in eval once switched on, envSHs otherwise.  Training never sees the import.
-Out of scope: COMPUTING the probe tables (load_envmap_with_visibility's branch without a file: a stochastic Adam fit over
-rotate_coeff_by_normal's band rotations), reading image files, the SG and Envmap models.  The reference's `euler` lighting rotation lives in front
+Out of scope: reading image files, the SG and Envmap models.  The reference's `euler` lighting rotation lives in front
 of the head, on the field: CurvedField.set_light_rotation / forward(euler=) hand this module rotated vectors.
 """
 import math
@@ -185,6 +190,176 @@ def envmap_to_sh(envmap, sh_order=3, *, min_loss=1e-5, max_steps=5000, min_steps
     return env_shs, {"steps": int(steps.item()), "loss": float(loss.item())}
 
 
+_VIS_LOBE = (0.8754318, 0.0, 1.023545, 0.0, 0.0, 0.0, 0.449686, 0.0, 0.0)  # the clamped cosine about +z, bands 0..2 (:661)
+
+
+def probe_grid(H=8, W=8):
+    """The probe directions of load_envmap_with_visibility (:657-660), made as the reference makes them: [H W, 3] fp32 on the host.  As executed:
+    both linspaces include their ends, so the last column repeats the first and the last row (polar angle pi) is W copies of the pole (0, -1, 0)
+    up to sin(fp32 pi); the first row sits at pi / H, not on the other pole.  The probe head takes the lowest index among equal probes."""
+    phi, theta = torch.meshgrid([torch.linspace(math.pi / H, math.pi, H), torch.linspace(-0.5 * math.pi, 1.5 * math.pi, W)], indexing="ij")
+    return torch.stack([torch.cos(theta) * torch.sin(phi), torch.cos(phi), torch.sin(theta) * torch.sin(phi)], dim=-1).reshape([-1, 3])
+
+
+def _band2_rotation(r1):
+    """The band-2 SH rotation [B, 5, 5] from the band-1 rotation r1 [B, 3, 3] by the recursion of Ivanic and Ruedenberg as compute_band_rotation
+    (:194-219) runs it for l = 2, rows and columns by centred indices -2..2.  With l = 2 the coefficient w is zero for every (m, n), so only the U
+    and V terms exist."""
+    def e(i, j):
+        return r1[:, i + 1, j + 1]
+
+    def P(i, a, b):  # (:131-142) with l = 2: the previous band is band 1 itself
+        if b == 2:
+            return e(i, 1) * e(a, 1) - e(i, -1) * e(a, -1)
+        if b == -2:
+            return e(i, 1) * e(a, -1) + e(i, -1) * e(a, 1)
+        return e(i, 0) * e(a, b)
+
+    out = torch.zeros(r1.shape[0], 5, 5, dtype=r1.dtype, device=r1.device)
+    for m in range(-2, 3):
+        for n in range(-2, 3):
+            d = 1.0 if m == 0 else 0.0
+            denom = 12.0 if abs(n) == 2 else (2 + n) * (2 - n)
+            u = math.sqrt((2 + m) * (2 - m) / denom)
+            v = 0.5 * math.sqrt((1 + d) * (abs(m) + 1.0) * (abs(m) + 2) / denom) * (1 - 2 * d)
+            if u != 0.0:
+                u = u * P(0, m, n)
+            if m == 0:
+                v = v * (P(1, 1, n) + P(-1, -1, n))
+            elif m > 0:
+                v = v * (P(1, m - 1, n) * math.sqrt(2.0 if m == 1 else 1.0) - P(-1, -m + 1, n) * (0.0 if m == 1 else 1.0))
+            else:
+                v = v * (P(1, m + 1, n) * (0.0 if m == -1 else 1.0) + P(-1, -m - 1, n) * math.sqrt(2.0 if m == -1 else 1.0))
+            out[:, m + 2, n + 2] = u + v
+    return out
+
+
+def visibility_lobes(probes, lobe=None):
+    """rotate_coeff_by_normal(2, probes, lobe) (:228-282) op by op: the order-2 lobe about +z ([9], default the reference's clamped cosine) rotated
+    onto each of probes [K, 3] -> [K, 9].  The frame is x = normalize(n x z), y = n x x, columns (x, y, n); |n_z| > 0.999 takes the identity
+    (n_z > 0) or diag(-1, 1, -1) (n_z < 0) instead, where n x z degenerates.  The band-1 matrix is read off the frame, band 2 comes from
+    _band2_rotation.  Runs on the host: K x 9 numbers, computed once.  (The reference calls torch.cross without `dim`, which picks the FIRST
+    dimension of size 3: for exactly three normals that is the wrong one.  It only ever passes 64; here the cross product is always per row.)"""
+    n = torch.as_tensor(probes, dtype=torch.float32).detach().cpu()
+    if n.dim() != 2 or n.shape[1] != 3:
+        raise ValueError(f"visibility_lobes: probes is [K, 3], but got {tuple(n.shape)}")
+    coeff = torch.tensor(_VIS_LOBE, dtype=torch.float32) if lobe is None else torch.as_tensor(lobe, dtype=torch.float32).detach().cpu().reshape(9)
+    n = n / (n.norm(dim=1, keepdim=True) + 1e-9)
+    z = torch.zeros_like(n)
+    z[:, 2] = 1
+    x = torch.linalg.cross(n, z, dim=1)
+    x = x / (x.norm(dim=1, keepdim=True) + 1e-9)
+    y = torch.linalg.cross(n, x, dim=1)
+    R = torch.stack([x, y, n], dim=-1)
+    R[n[:, 2] > 0.999] = torch.tensor([[1.0, 0, 0], [0, 1, 0], [0, 0, 1]])
+    R[n[:, 2] < -0.999] = torch.tensor([[-1.0, 0, 0], [0, 1, 0], [0, 0, -1]])
+    r1 = torch.stack([R[:, 1, 1], -R[:, 1, 2], R[:, 1, 0], -R[:, 2, 1], R[:, 2, 2], -R[:, 2, 0], R[:, 0, 1], -R[:, 0, 2], R[:, 0, 0]], dim=-1).reshape(-1, 3, 3)
+    out = coeff[None, :].repeat(n.shape[0], 1)
+    out[:, 1:4] = torch.bmm(r1, coeff[None, 1:4, None].repeat(n.shape[0], 1, 1))[:, :, 0]
+    out[:, 4:9] = torch.bmm(_band2_rotation(r1), coeff[None, 4:9, None].repeat(n.shape[0], 1, 1))[:, :, 0]
+    return out
+
+
+def _eval_sh2(coeffs, dirs):
+    """evaluate_spherical_harmonics(2, coeffs, dirs) (nerf/spherical_harmonics.py:64-105), term by term in its order: coeffs [..., C, 9],
+    dirs [N, 3] -> [N, C].  The same polynomials and signs as svox2_basis9."""
+    x, y, z = dirs[..., 0:1], dirs[..., 1:2], dirs[..., 2:3]
+    result = _C0 * coeffs[..., 0]
+    result = result - _C1 * y * coeffs[..., 1] + _C1 * z * coeffs[..., 2] - _C1 * x * coeffs[..., 3]
+    xx, yy, zz = x * x, y * y, z * z
+    xy, yz, xz = x * y, y * z, x * z
+    return (result + _C2[0] * xy * coeffs[..., 4] + _C2[1] * yz * coeffs[..., 5] + _C2[2] * (2.0 * zz - xx - yy) * coeffs[..., 6]
+            + _C2[3] * xz * coeffs[..., 7] + _C2[4] * (xx - yy) * coeffs[..., 8])
+
+
+def sphere_points(u_phi, u_theta):
+    """The points fit_product_of_SHs draws (:701-703) from two uniforms in [0, 1): [...] -> [..., 3]."""
+    phi = 2 * math.pi * u_phi
+    theta = torch.arccos(1 - 2 * u_theta)
+    return torch.stack([torch.cos(phi) * torch.sin(theta), torch.sin(phi) * torch.sin(theta), torch.cos(theta)], dim=-1)
+
+
+def fit_product_of_shs(sh1, sh2, *, rounds=800, batch=1024, lr=1e-3, points=None, generator=None):
+    """fit_product_of_SHs (:692-709) op by op: sh1 [9, 3] (the lighting), sh2 [9] or [9, 3] (the lobe) -> [9, 3], the coefficients after `rounds`
+    steps of torch.optim.Adam(lr) from sh1 towards the product of the two on `batch` points per step.  AS EXECUTED: no zero_grad(), so the
+    gradient of step t is added to those of steps 1..t-1 and Adam sees the sum; the result is not converged and is defined by the trajectory.
+    points [rounds, batch, 3] are used if given; otherwise each step calls torch.rand twice, phi first, as the reference (with `generator`)."""
+    sh1 = sh1.detach()[None, :9]
+    sh2 = sh2.detach().to(sh1)
+    sh2 = (sh2[:, None].repeat(1, 3) if sh2.dim() == 1 else sh2)[None]
+    sh = nn.Parameter(sh1.clone())
+    optimizer = torch.optim.Adam([sh], lr=lr)
+    for r in range(rounds):
+        if points is None:
+            u_phi = torch.rand([batch], device=sh.device, generator=generator)
+            pts = sphere_points(u_phi, torch.rand([batch], device=sh.device, generator=generator)).to(sh.dtype)
+        else:
+            pts = points[r]
+        with torch.enable_grad():  # (a caller that relights holds no_grad)
+            gt = _eval_sh2(sh1.permute(0, 2, 1), pts) * _eval_sh2(sh2.permute(0, 2, 1), pts)
+            pred = _eval_sh2(sh.permute(0, 2, 1), pts)
+            loss = ((gt - pred) ** 2).sum(dim=-1).mean()
+            loss.backward()
+        optimizer.step()
+    return sh.detach()[0]
+
+
+def envmap_probe_tables(env_shs, probes=None, *, rounds=800, batch=1024, lr=1e-3, seed=0, points=None, points_out=False, fused=None):
+    """load_envmap_with_visibility without a file (:653-665): env_shs [N >= 9, 3] -> (tables [K, 9, 3], probes [K, 3]) on env_shs' device, with
+    probes = probe_grid() unless given (1 <= K <= 256); with points_out=True a third result, the points used [K, rounds, batch, 3].
+    A GPU tensor goes through nerftex_envmap_vis_fit: one launch, no wait; its points come from the library's own counter-based stream keyed by
+    (seed, probe, round, sample) -- not torch.rand's -- unless points [K, rounds, batch, 3] are given.  fused = False or a CPU tensor runs
+    fit_product_of_shs per probe, drawing from torch.Generator().manual_seed(seed).  The two agree bit for bit on given points only as far as
+    fp32 summation order allows (tests/test_gpu_probe_table.py), and on their own points statistically."""
+    env_shs = torch.as_tensor(env_shs).detach()
+    if env_shs.dim() != 2 or env_shs.shape[0] < 9 or env_shs.shape[1] != 3:
+        raise ValueError(f"envmap_probe_tables: env_shs is [N >= 9, 3], but got {tuple(env_shs.shape)}")
+    dev = env_shs.device
+    probes = probe_grid() if probes is None else torch.as_tensor(probes).detach()
+    K = probes.shape[0] if probes.dim() == 2 else 0
+    if tuple(probes.shape) != (K, 3) or not 1 <= K <= 256:
+        raise ValueError(f"envmap_probe_tables: probes is [K, 3] with 1 <= K <= 256, but got {tuple(probes.shape)}")
+    rounds, batch = int(rounds), int(batch)
+    if rounds < 1 or batch < 1 or not (lr > 0 and math.isfinite(lr)):
+        raise ValueError(f"envmap_probe_tables: rounds and batch are positive and lr is positive and finite, but got {rounds}, {batch}, {lr}")
+    if points is not None and tuple(points.shape) != (K, rounds, batch, 3):
+        raise ValueError(f"envmap_probe_tables: points is [K, rounds, batch, 3] = {(K, rounds, batch, 3)}, but got {tuple(points.shape)}")
+    lobes = visibility_lobes(probes)
+    probes = probes.to(device=dev, dtype=torch.float32).contiguous()
+    if fused is None:
+        fused = env_shs.is_cuda
+    if not fused:
+        env = env_shs if env_shs.dtype == torch.float64 else env_shs.float()
+        lobes = lobes.to(env)
+        gen = None if points is not None else torch.Generator(device=dev).manual_seed(int(seed))
+        used = torch.empty(K, rounds, batch, 3, dtype=env.dtype, device=dev) if points_out and points is None else points
+        tables = torch.empty(K, 9, 3, dtype=env.dtype, device=dev)
+        for i in range(K):
+            if points is None and points_out:
+                for r in range(rounds):
+                    u_phi = torch.rand([batch], device=dev, generator=gen)
+                    used[i, r] = sphere_points(u_phi, torch.rand([batch], device=dev, generator=gen))
+            tables[i] = fit_product_of_shs(env, lobes[i], rounds=rounds, batch=batch, lr=lr, points=None if used is None else used[i].to(env),
+                                           generator=gen)
+        return (tables, probes, used) if points_out else (tables, probes)
+    if not env_shs.is_cuda:
+        raise RuntimeError("envmap_probe_tables(fused=True) needs the lighting on the GPU: there is no fused CPU path")
+    import ctypes
+
+    from nerftex_hip import EnvmapVisFitDesc, check, lib, ptr, stream
+
+    env = env_shs.contiguous().float()
+    lobes = lobes.to(dev).contiguous()
+    if points is not None:
+        points = points.detach().to(device=dev, dtype=torch.float32).contiguous()
+    used = torch.empty(K, rounds, batch, 3, dtype=torch.float32, device=dev) if points_out else None
+    tables = torch.empty(K, 9, 3, dtype=torch.float32, device=dev)
+    desc = EnvmapVisFitDesc(env_shs=ptr(env), n_sh=env.shape[0], lobes=ptr(lobes), K=K, rounds=rounds, batch=batch, lr=float(lr),
+                            seed=int(seed) & 0xFFFFFFFFFFFFFFFF, points=ptr(points), points_out=ptr(used), tables=ptr(tables))
+    check(lib.nerftex_envmap_vis_fit(ctypes.byref(desc), stream()))
+    return (tables, probes, used) if points_out else (tables, probes)
+
+
 class _SHLight(torch.autograd.Function):
     """brdf [B, 5] half (rows of the BRDF MLP's 16-wide output), normals, dirs [B, 3] fp32, envSHs -> the four outputs [B, 3] fp32: one launch;
     the backward recomputes the forward from the inputs (nerftex_sh_light_backward) and sums the lighting gradient in a fixed order."""
@@ -282,11 +457,16 @@ class SHLightNet(nn.Module):
         for name in ("envSHs_import", "envSHs_import_vis", "probes"):
             self.register_buffer(name, None, persistent=False)
 
-    def load_envmap(self, envmap=None, *, env_shs=None, env_shs_vis=None, probes=None, force_white=True):
+    def load_envmap(self, envmap=None, *, env_shs=None, env_shs_vis=None, probes=None, force_white=True, visibility=False, seed=0, vis_fit=None):
         """load_envmap (:625-645) without the files: an [H, W, 3] array in [0, 1] that is tone-mapped (image_to_envmap) and fitted (envmap_to_sh),
         or fitted coefficients env_shs [N >= 9, 3] (the reference's .npy); optionally the contents of its _vis.npz, env_shs_vis [K, 9, 3] and
-        probes [K, 3], 1 <= K <= 256.  Switches the imported lighting on and returns True; ValueError for shapes that do not match."""
+        probes [K, 3], 1 <= K <= 256 -- or visibility=True, which computes the tables from the lighting just fitted or handed in, as the reference
+        does when it finds no _vis.npz (load_envmap_with_visibility(seed); vis_fit: keyword overrides for envmap_probe_tables, such as rounds and
+        batch).  visibility=False without tables leaves them None: forward() then raises under shade_visibility.  Switches the imported lighting
+        on and returns True; ValueError for shapes that do not match and for visibility=True together with given tables."""
         dev = self.envSHs.device
+        if visibility and (env_shs_vis is not None or probes is not None):
+            raise ValueError("SHLightNet.load_envmap: visibility=True computes the probe tables; it does not go together with env_shs_vis= / probes=")
         if (envmap is None) == (env_shs is None):
             raise ValueError("SHLightNet.load_envmap: give either an [H, W, 3] map or fitted coefficients env_shs [N, 3]")
         if (env_shs_vis is None) != (probes is None):
@@ -311,8 +491,26 @@ class SHLightNet(nn.Module):
         self.envSHs_import = env_shs.contiguous().clone()
         self.envSHs_import_vis = None if env_shs_vis is None else env_shs_vis.contiguous().clone()
         self.probes = None if probes is None else probes.contiguous().clone()
+        if visibility:
+            self.load_envmap_with_visibility(seed=seed, **(vis_fit or {}))
         self.import_envmap = True
         return True
+
+    def load_envmap_with_visibility(self, seed=0, **fit):
+        """load_envmap_with_visibility's branch without a file (:653-665): computes envSHs_import_vis [64, 9, 3] and probes [64, 3] for the lighting
+        already imported (envmap_probe_tables; `fit`: its keywords).  RuntimeError if none is imported.  Returns True."""
+        if self.envSHs_import is None:
+            raise RuntimeError("SHLightNet.load_envmap_with_visibility: no lighting is imported: call load_envmap first")
+        tables, probes = envmap_probe_tables(self.envSHs_import, seed=seed, **fit)[:2]
+        self.envSHs_import_vis, self.probes = tables.float().contiguous(), probes.contiguous()
+        return True
+
+    def probe_tables(self):
+        """{"envSHs": [K, 9, 3], "probes": [K, 3]} as numpy: exactly the content of the reference's _vis.npz (:666), for np.savez.  RuntimeError
+        without tables."""
+        if self.envSHs_import_vis is None or self.probes is None:
+            raise RuntimeError("SHLightNet.probe_tables: no probe tables are loaded or computed")
+        return {"envSHs": self.envSHs_import_vis.detach().cpu().numpy(), "probes": self.probes.detach().cpu().numpy()}
 
     def switch_envmap_import(self):
         """switch_envmap_import (:675-681): toggles the imported lighting and returns the new state; False while nothing is loaded."""
@@ -338,7 +536,7 @@ class SHLightNet(nn.Module):
         probe = self.probe_lighting(shade_visibility)
         if shade_visibility and self._imported() and not probe:
             raise RuntimeError("SHLightNet: shade_visibility asks for one imported lighting per visibility probe, but no probe tables are loaded: "
-                               "give them to load_envmap(env_shs_vis=, probes=), or set field.shade_visibility = False to light every sample "
+                               "give them to load_envmap(env_shs_vis=, probes=), compute them with load_envmap(visibility=True), or set field.shade_visibility = False to light every sample "
                                "with envSHs_import")
         if probe and normal_secondary is None:
             raise ValueError("SHLightNet: shade_visibility needs normal_secondary, the normal the probe is chosen by")
