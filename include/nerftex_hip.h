@@ -952,6 +952,85 @@ size_t nerftex_curved_shape_infer_scratch_bytes(uint32_t B);
 int nerftex_curved_shape_infer(const nerftex_curved_shape_infer_desc* d, void* stream);
 
 /* -------------------------------------------------------------------------
+ * Extension: the field BAKED ONTO THE VERTICES of a fine mesh -- the `imported_type == 'unhash'` branch of MeshFeatureField.forward
+ * (tools/map.py:708-714) over knn() with its defaults on the field's OWN mesh (:454-501: K neighbours, use_dir_vec, Shepard weights -- the normal
+ * nerftex_curved_project computes, the same expression tree) and barycentric_mapping on the FINE mesh (:503-528).  One launch behind the
+ * neighbour search (nerftex_knn_query over the field's own vertices).  Per sample x, all fp32; behind the normal every operation rounds on its own
+ * (no fused multiply-add but the tracer's own o + t d):
+ *   normal = nerftex_curved_project's coarse normal                          knn_idx: -1 is the last vertex, anything else is clamped
+ *   d1, d2 = the closest hits on the fine mesh along +normal and -normal (10 on a miss); inner = d1 < d2; the nearer hit's face (-1 when both miss)
+ *   sdf    = (inner ? -d1 : d2) / sdf_scale - sdf_offset                     (a true division; the caller clamps sdf_scale to >= 1e-5)
+ *   mask   = |sdf| < min(9.5, h_threshold) and face != -1
+ *   b      = (|p1 x p2|, |p2 x p0|, |p0 x p1|) / (their sum + 1e-5),  p_k = corner_k - p_sur        (face -1 reads face 0 under mask = 0)
+ *   feature_c = (b0 f0c + b1 f1c) + b2 f2c,  f_k = vertex_features[face_vertices[face][k]]
+ *   xin [N,48] fp16 = [half(features) | half(FreqEncoder(sdf)) | 1 x 7]
+ * The reference's query_tbn(x) of :711 is dead work (nothing reads the tuple it returns) and is not done.
+ * face_vertices [n_faces,3]: the corners' vertex ids by ORIGINAL face id, corner k being corner k of the triangle the raytracer was built from.  Every
+ * id must lie in [0, n_fine_verts): the kernel does not clamp them, the caller checks the table once when it is made.  The corners' positions are read
+ * from the raytracer's own triangle records, which hold fine_vertices[face_vertices[face]] as fp32: fine_vertices [n_fine_verts,3] is the array
+ * the raytracer was built from and is not dereferenced.
+ * nerftex_vertex_lookup is the plain form: any N, every row; bary [N,3].  NERFTEX_ERR_INVALID before anything is launched, in this order: a NULL
+ * pointer; K outside 1..16; n_verts, then n_fine_verts, outside 1..2^31-1; n_faces other than the raytracer's triangle count; n_freqs other than 12;
+ * vertex_features or xin not 16-byte aligned; sdf_scale or h_threshold not positive and finite; sdf_offset not finite.  (N == 0 returns NERFTEX_OK
+ * behind these; N above 2^31 - 1 -- two lanes per point -- is refused last.)
+ *
+ * nerftex_curved_unhash_infer: the whole no-grad forward as ONE call under the rows contract of nerftex_curved_field_infer --
+ *   neighbour search (K, the field's own grid) -> vertex lookup -> sigma net -> trunc_exp / reflected view direction / SH -> colour net -> sigmoid + mask,
+ * six launches (the last four are nerftex_curved_field_infer's own), nothing allocated, capturable.  The mid kernel normalises the coarse
+ * normal (eval bit 1).
+ *   rows >= live                      no work; sigma / rgbs keep what they held.
+ *   live rows the march marked unused no search, no traversal, no row read; sigma = 0, rgbs = 0.
+ *   every other live row              bit for bit what nerftex_knn_query, nerftex_vertex_lookup, nerftex_ffmlp_inference,
+ *                                     nerftex_curved_mid_forward, nerftex_ffmlp_inference and nerftex_curved_out_forward give one after
+ *                                     the other, widened to fp32.
+ * NERFTEX_ERR_INVALID before anything is launched, in this order: a NULL descriptor; B % 128 != 0; n_verts outside 1..2^31-1; K outside 1..16;
+ * n_features other than 16 or other network shapes than sigma net 48 / 32 / 2 / 16, colour net 32 / 64 / 3 / 3; a NULL raytracer or n_faces
+ * other than its triangle count; n_fine_verts, n_freqs, alignment, scale, threshold and offset as above; (B == 0 returns NERFTEX_OK here;) a NULL
+ * pointer, a scratch that is not 256-byte aligned or smaller than nerftex_curved_unhash_infer_scratch_bytes(B); a weight vector that is not
+ * 16-byte aligned.
+ * ------------------------------------------------------------------------- */
+int nerftex_vertex_lookup(const nerftex_raytracer* rt_fine, const float* xyz, const int32_t* knn_idx, const float* knn_dist, uint32_t N, uint32_t K,
+                          const float* mesh_vertices, const float* vertex_normals, uint32_t n_verts, float dir_vec_wdist, /* the field's OWN mesh */
+                          const float* fine_vertices, uint32_t n_fine_verts, const int32_t* face_vertices, uint32_t n_faces,
+                          const float* vertex_features,                                                                   /* [n_fine_verts,16] fp32 */
+                          float sdf_scale, float sdf_offset, float h_threshold, uint32_t n_freqs, float* sdf, uint8_t* mask, float* normal,
+                          int64_t* face_idx, float* bary, void* xin, void* stream);
+typedef struct nerftex_curved_unhash_infer_desc {
+    const nerftex_knn* knn;            /* the field's OWN mesh's neighbour grid                                                   */
+    const nerftex_raytracer* tracer;   /* the FINE mesh's BVH                                                                     */
+    const float* xyz;                  /* [B,3] sample positions                                                                  */
+    const float* dirs;                 /* [B,3] view directions; dirs[row][0] > 1e29 marks an unused slot                         */
+    uint32_t B;
+    uint32_t n_verts;
+    const float* mesh_vertices;        /* [n_verts,3], the field's own mesh                                                       */
+    const float* vertex_normals;       /* [n_verts,3]                                                                             */
+    uint32_t K;                        /* neighbours per point                                                                    */
+    float dir_vec_wdist;
+    const float* fine_vertices;        /* [n_fine_verts,3], what the raytracer was built from                                     */
+    uint32_t n_fine_verts;
+    const int32_t* face_vertices;      /* [n_faces,3]                                                                             */
+    uint32_t n_faces;
+    const float* vertex_features;      /* [n_fine_verts, n_features] fp32, 16-byte aligned                                        */
+    uint32_t n_features;
+    float sdf_scale, sdf_offset, h_threshold;
+    uint32_t n_freqs;                  /* FreqEncoder(height) bands (multires)                                                    */
+    const void* sigma_weights;         /* fp16, 16-byte aligned                                                                   */
+    uint32_t sigma_in, sigma_hidden, sigma_layers, sigma_out;
+    const void* color_weights;         /* fp16, 16-byte aligned                                                                   */
+    uint32_t color_in, color_hidden, color_layers, color_out;
+    float fc_weight;
+    int eval;                          /* the eval bits of nerftex_curved_mid_forward                                             */
+    float* sigma;                      /* [B] fp32                                                                                */
+    float* rgbs;                       /* [B,3] fp32                                                                              */
+    const int32_t* units_dev;
+    uint32_t rows_per_unit;
+    void* scratch;                     /* caller-owned, 256-byte aligned, >= nerftex_curved_unhash_infer_scratch_bytes(B) bytes   */
+    size_t scratch_bytes;
+} nerftex_curved_unhash_infer_desc;
+size_t nerftex_curved_unhash_infer_scratch_bytes(uint32_t B);
+int nerftex_curved_unhash_infer(const nerftex_curved_unhash_infer_desc* d, void* stream);
+
+/* -------------------------------------------------------------------------
  * Extension: the same ONE call for the curved field with the SH light model (CurvedField(light_model="SH")), under the same rows contract:
  *   neighbour search -> projector (+ the hit face's frame) -> hash-grid gather of the texture table -> gather of the normal net's table ->
  *   sigma net 48 -> 32 -> 16 -> light mid: exp / BRDF input / the factorized fine-normal net (two 16-wide LipMLPs, toCoor, the frame's

@@ -65,6 +65,26 @@ int curved_shape_light_rows(const nerftex_raytracer* rt, const float* xyz, const
                             uint32_t K, const float* mesh_vertices, const float* vertex_normals, uint32_t n_verts, const ShapeLookup& s, const ShapeLight& t,
                             uint8_t* mask, float* normal, const int32_t* units_dev, uint32_t rows_per_unit, hipStream_t st);
 
+// The vertex lookup (raytracer.hip: the field baked onto the vertices of a fine mesh) -- what nerftex_vertex_lookup and
+// nerftex_curved_unhash_infer hand it alike.
+struct VertexLookup {
+    const int32_t* face_vertices;  // [n_faces,3] corner vertex ids by original face id
+    const float* features;         // [n_fine_verts,16] fp32
+    uint32_t n_fine_verts;
+    float dir_vec_wdist, sdf_scale, sdf_offset, h_threshold;
+    uint32_t n_freqs;
+    void* xin;                     // [N,48] half
+};
+// NULL, or why the two entries refuse these values -- in the order include/nerftex_hip.h documents: the fine vertex count, n_freqs, alignment of the
+// features and of xin, scale and threshold, offset
+const char* vertex_lookup_refusal(const VertexLookup& s);
+// nerftex_vertex_lookup's rows for unmarked live rows: mask [N], the raw coarse normal [N,3], and the whole sigma-net input row xin [N,48] =
+// [half(features) | half(ladder) | ones].  A marked live row: mask = 0, normal = 0, features 0, z = 0 | ones; nothing is traced and no row read.
+// The caller has validated (front_batch_ok's K and n_verts, n_faces, vertex_lookup_refusal).
+int curved_vertex_rows(const nerftex_raytracer* rt_fine, const float* xyz, const float* dirs, const int32_t* knn_idx, const float* knn_dist, uint32_t N, uint32_t K,
+                       const float* mesh_vertices, const float* vertex_normals, uint32_t n_verts, const VertexLookup& s, uint8_t* mask, float* normal,
+                       const int32_t* units_dev, uint32_t rows_per_unit, hipStream_t st);
+
 // The patch lookup (knn.hip / patch_import.inc: an imported feature patch resampled from its 8 nearest points) -- what the two plain entries and
 // nerftex_curved_patch_infer / nerftex_curved_light_patch_infer (patch_chain.inc) hand it alike.
 struct PatchLookup {

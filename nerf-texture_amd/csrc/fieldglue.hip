@@ -707,6 +707,9 @@ extern "C" int nerftex_field_out_backward(const float* grad_rgbs, const float* r
 // ---- the planar lookup of an imported feature map and its chain (nerftex_planar_lookup, nerftex_curved_import_infer): in front of shlight.inc ------------
 #include "planar.inc"
 
+// ---- the field baked onto the vertices of a fine mesh (nerftex_curved_unhash_infer): the vertex lookup (raytracer.hip) in front of the static back half --
+#include "unhash.inc"
+
 // ---- the SH light head of the curved field (nerftex_sh_light_forward / _backward) ----------------------------------------------------------------------
 #include "shlight.inc"
 

@@ -247,20 +247,11 @@ __global__ __launch_bounds__(64) void raytrace_kernel(uint32_t N, const float* r
 //   tools/encoding.py:5-43).  The reference runs this as ~35 framework launches + two trace launches and materialises every
 //   intermediate ([N,K,3] gathers, two full hit records); the neighbour search itself (frnn, un-vendored) stays outside.
 constexpr int kMaxK = 16;
-// One point of the projector, run by the TWO lanes of a pair (side 0: the trace along +normal, which also writes; side 1: along -normal) -- both
-// lanes must arrive here together: the traces meet in an __shfl_xor.
-// INFER (nerftex_curved_field_infer): no height, face or frame output, and FreqEncoder(height) leaves as the 16-bit values the sigma net reads --
-// z_embed is then the point's row of that net's [N,48] half input, columns 16..40 = half(z), 41..47 = the padding ones.
-template <bool INFER>
-__device__ __forceinline__ void curved_project_point(const uint32_t i, const uint32_t side, const float* __restrict__ xyz, const int32_t* __restrict__ knn_idx,
-                                                     const float* __restrict__ knn_dist, uint32_t K, const float* __restrict__ verts,
-                                                     const float* __restrict__ vnormals, int n_verts, float dir_vec_wdist, float h_limit,
-                                                     const Node* __restrict__ nodes, const Tri* __restrict__ tris, const float* __restrict__ tbn,
-                                                     uint32_t n_freqs, float* __restrict__ p_sur, float* __restrict__ sdf_out, uint8_t* __restrict__ h_mask,
-                                                     float* __restrict__ normal_out, int64_t* __restrict__ face_idx, float* __restrict__ tbn_out,
-                                                     void* __restrict__ z_embed) {
-    const V3 x = load3(xyz + 3 * (size_t)i);
-    // ---- knn(): weighted normal (both lanes of a pair: the same loads, served once)
+// knn() of tools/map.py:454-501 with its defaults (use_dir_vec=True, Shepard weights): the coarse normal of the point x from its K nearest mesh
+// vertices -- their normals and the mean direction to them, inverse-distance weighted.  The one normal of the projector (curved_project_point) and
+// of the vertex lookup (vertex_lookup_kernel), whose branch calls the same knn() over the field's own mesh: one expression tree, the same bits.
+__device__ __forceinline__ V3 shepard_normal(const V3& x, const uint32_t i, const int32_t* __restrict__ knn_idx, const float* __restrict__ knn_dist, const uint32_t K,
+                                             const float* __restrict__ verts, const float* __restrict__ vnormals, const int n_verts, const float dir_vec_wdist) {
     V3 mean_dir{0, 0, 0}, nsum{0, 0, 0}, acc{0, 0, 0};
     float wsum = 0;
     for (uint32_t k = 0; k < K; k++) {
@@ -290,10 +281,25 @@ __device__ __forceinline__ void curved_project_point(const uint32_t i, const uin
         wsum += w;
     }
     V3 nrm{acc.x / wsum, acc.y / wsum, acc.z / wsum};
-    {
-        const float l = sqrtf(dot(nrm, nrm)) + 1e-5f;
-        nrm = {nrm.x / l, nrm.y / l, nrm.z / l};
-    }
+    const float l = sqrtf(dot(nrm, nrm)) + 1e-5f;
+    return {nrm.x / l, nrm.y / l, nrm.z / l};
+}
+
+// One point of the projector, run by the TWO lanes of a pair (side 0: the trace along +normal, which also writes; side 1: along -normal) -- both
+// lanes must arrive here together: the traces meet in an __shfl_xor.
+// INFER (nerftex_curved_field_infer): no height, face or frame output, and FreqEncoder(height) leaves as the 16-bit values the sigma net reads --
+// z_embed is then the point's row of that net's [N,48] half input, columns 16..40 = half(z), 41..47 = the padding ones.
+template <bool INFER>
+__device__ __forceinline__ void curved_project_point(const uint32_t i, const uint32_t side, const float* __restrict__ xyz, const int32_t* __restrict__ knn_idx,
+                                                     const float* __restrict__ knn_dist, uint32_t K, const float* __restrict__ verts,
+                                                     const float* __restrict__ vnormals, int n_verts, float dir_vec_wdist, float h_limit,
+                                                     const Node* __restrict__ nodes, const Tri* __restrict__ tris, const float* __restrict__ tbn,
+                                                     uint32_t n_freqs, float* __restrict__ p_sur, float* __restrict__ sdf_out, uint8_t* __restrict__ h_mask,
+                                                     float* __restrict__ normal_out, int64_t* __restrict__ face_idx, float* __restrict__ tbn_out,
+                                                     void* __restrict__ z_embed) {
+    const V3 x = load3(xyz + 3 * (size_t)i);
+    // ---- knn(): weighted normal (both lanes of a pair: the same loads, served once)
+    const V3 nrm = shepard_normal(x, i, knn_idx, knn_dist, K, verts, vnormals, n_verts, dir_vec_wdist);
     // ---- project(): two closest hits, the nearer wins
     const V3 neg{-nrm.x, -nrm.y, -nrm.z};
     int b_mine;
@@ -561,6 +567,101 @@ __global__ __launch_bounds__(64) void shape_lookup_kernel(const uint32_t N, cons
         p_uv[2 * (size_t)i] = u; p_uv[2 * (size_t)i + 1] = v;
         sdf_out[i] = sdf;
         face_idx[i] = face;
+    }
+}
+
+// ---------------------------------------------------------------- vertex lookup: the field baked onto the vertices of a fine mesh
+// The `imported_type == 'unhash'` branch of MeshFeatureField.forward (tools/map.py:708-714) for one sample point per PAIR of lanes, in one kernel
+// behind the neighbour search over the field's OWN mesh: knn() with its defaults (:454-501, shepard_normal above: the projector's normal) ->
+// barycentric_mapping over the FINE mesh (:503-528: the two traces, the scaled and offset height, the mask that also wants a hit, the hit's
+// barycentric coordinates, :85-93) -> the three corners' feature rows interpolated -> FreqEncoder(height).  The reference's query_tbn(x) of :711 is
+// dead work there (nothing reads its tuple) and is not done.
+// Behind the normal every operation rounds on its own, as the shape lookup's do: plain products and sums, no fused multiply-add -- except the
+// surface point, which is the tracer's own o + t d.
+// Lane mapping: the shape lookup's.  Lanes 2 i and 2 i + 1 compute the normal alike, trace along +normal and -normal and meet in an __shfl_xor; every
+// exit in front of it is decided by the point.  Behind it lane 0 does the barycentrics, the three 64-byte row reads (twelve independent 16-byte
+// loads, issued as soon as the hit's face is known, in front of the barycentric arithmetic) and every per-point store, lane 1 the height ladder.
+// The corners come from the tracer's own triangle record (the fp32 values of fine_vertices[face_vertices[face]], which it was built from): one
+// 48-byte read the face id needs anyway, where three more dependent gathers into a [V',3] array would stand.
+struct VertexArgs {
+    const int32_t* face_vertices;  // [F,3]: the three corners' vertex ids by ORIGINAL face id, each in [0, V') (the caller's promise)
+    const float* features;         // [V',16] fp32, 16-byte aligned
+    float dir_vec_wdist, sdf_scale, sdf_offset, h_limit;
+    uint32_t face0;                // nerftex_raytracer::face0
+};
+
+// ROWS: the rows contract of nerftex_curved_field_infer's kernels (no sdf, face or barycentric output); otherwise the plain form (every row).
+template <bool ROWS>
+__global__ __launch_bounds__(64) void vertex_lookup_kernel(const uint32_t N, const float* __restrict__ xyz, const float* __restrict__ dirs,
+                                                           const int32_t* __restrict__ knn_idx, const float* __restrict__ knn_dist, const uint32_t K,
+                                                           const float* __restrict__ verts, const float* __restrict__ vnormals, const int n_verts,
+                                                           const Node* __restrict__ nodes, const Tri* __restrict__ tris, const VertexArgs a,
+                                                           float* __restrict__ sdf_out, uint8_t* __restrict__ mask, float* __restrict__ normal_out,
+                                                           int64_t* __restrict__ face_idx, float* __restrict__ bary_out, half_t* __restrict__ xin,
+                                                           const int32_t* __restrict__ units_dev, const uint32_t rows_per_unit) {
+    const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t i = tid >> 1, side = tid & 1u;
+    if (i >= (ROWS ? live_rows(N, units_dev, rows_per_unit) : N)) return;
+    half_t* row = xin + (size_t)i * 48;
+    if (ROWS && slot_unused(dirs, i)) {  // no neighbour list to read, no tree to walk, no row: the constants that make the rest of the chain answer zeros
+        if (side) return;
+        mask[i] = 0;
+#pragma unroll
+        for (int c = 0; c < 3; c++) normal_out[3 * (size_t)i + c] = 0.0f;
+        const half8_t zero = {0, 0, 0, 0, 0, 0, 0, 0};
+        reinterpret_cast<half8_t*>(row)[0] = zero;
+        reinterpret_cast<half8_t*>(row)[1] = zero;
+        write_unused_ladder(row);
+        return;
+    }
+    const V3 x = load3(xyz + 3 * (size_t)i);
+    const V3 nrm = shepard_normal(x, i, knn_idx, knn_dist, K, verts, vnormals, n_verts, a.dir_vec_wdist);
+    // ---- barycentric_mapping(): two closest hits on the fine mesh, the nearer wins
+    const V3 neg{-nrm.x, -nrm.y, -nrm.z};
+    int b_mine;
+    const float d_mine = closest_hit(x, side ? neg : nrm, nodes, tris, b_mine);
+    const float d_other = __shfl_xor(d_mine, 1, kWave);
+    const int b_other = __shfl_xor(b_mine, 1, kWave);
+    const float d1 = side ? d_other : d_mine, d2 = side ? d_mine : d_other;
+    const bool inner = d1 < d2;
+    const float sdf = (inner ? -d1 : d2) / a.sdf_scale - a.sdf_offset;  // (a true division)
+    if (side) {  // lane 1: the ladder, columns 16..47
+        write_height_ladder(sdf, row);
+        return;
+    }
+    const int best = inner ? b_mine : b_other;
+    const Tri tr = tris[best >= 0 ? (uint32_t)best : a.face0];  // face -1 reads face 0, as the reference does; the mask covers it
+    const int64_t face = best >= 0 ? tr.id : (int64_t)-1;
+    const int32_t* fv = a.face_vertices + 3 * (size_t)(best >= 0 ? tr.id : (int64_t)0);
+    const float4_t* r0 = reinterpret_cast<const float4_t*>(a.features + 16 * (size_t)fv[0]);
+    const float4_t* r1 = reinterpret_cast<const float4_t*>(a.features + 16 * (size_t)fv[1]);
+    const float4_t* r2 = reinterpret_cast<const float4_t*>(a.features + 16 * (size_t)fv[2]);
+    float4_t f0[4], f1[4], f2[4];
+#pragma unroll
+    for (int q = 0; q < 4; q++) { f0[q] = r0[q]; f1[q] = r1[q]; f2[q] = r2[q]; }
+    const float d = inner ? d1 : d2;
+    const V3 dir = inner ? nrm : neg;
+    const V3 p_sur{fmaf(d, dir.x, x.x), fmaf(d, dir.y, x.y), fmaf(d, dir.z, x.z)};
+    // points_to_barycentric (tools/map.py:85-93)
+    const V3 p0 = sub(load3(tr.a), p_sur), p1 = sub(load3(tr.b), p_sur), p2 = sub(load3(tr.c), p_sur);
+    const float s0 = norm_plain(cross_plain(p1, p2)), s1 = norm_plain(cross_plain(p2, p0)), s2 = norm_plain(cross_plain(p0, p1));
+    const float den = ((s0 + s1) + s2) + 1e-5f;
+    const float b0 = s0 / den, b1 = s1 / den, b2 = s2 / den;
+    auto narrow = [](float v) {  // (the value rounded to fp32 first, then to half: the conversion is not folded into the sum that produces it)
+        asm volatile("" : "+v"(v));
+        return (half_t)v;
+    };
+    half8_t o[2];
+#pragma unroll
+    for (int c = 0; c < 16; c++) o[c / 8][c % 8] = narrow((f0[c / 4][c % 4] * b0 + f1[c / 4][c % 4] * b1) + f2[c / 4][c % 4] * b2);
+    reinterpret_cast<half8_t*>(row)[0] = o[0];
+    reinterpret_cast<half8_t*>(row)[1] = o[1];
+    mask[i] = (fabsf(sdf) < a.h_limit && best >= 0) ? 1 : 0;
+    normal_out[3 * (size_t)i] = nrm.x; normal_out[3 * (size_t)i + 1] = nrm.y; normal_out[3 * (size_t)i + 2] = nrm.z;
+    if constexpr (!ROWS) {
+        sdf_out[i] = sdf;
+        face_idx[i] = face;
+        bary_out[3 * (size_t)i] = b0; bary_out[3 * (size_t)i + 1] = b1; bary_out[3 * (size_t)i + 2] = b2;
     }
 }
 
@@ -840,6 +941,85 @@ extern "C" int nerftex_shape_lookup(const nerftex_raytracer* rt, const float* xy
     launch_shape_lookup<false>(as_stream(stream), rt, xyz, nullptr, knn_idx, knn_dist, N, K, mesh_vertices, vertex_normals, n_verts, s, p_uv, sdf, mask, normal, face_idx,
                                static_cast<half_t*>(xin), nullptr, 0u);
     return check_launch("shape_lookup");
+}
+
+// ---- the vertex lookup's launches (nerftex_vertex_lookup below; nerftex_curved_unhash_infer, unhash.inc, through curved_vertex_rows)
+namespace nerftex {
+namespace {
+
+template <bool ROWS>
+void launch_vertex_lookup(hipStream_t st, const nerftex_raytracer* rt, const float* xyz, const float* dirs, const int32_t* knn_idx, const float* knn_dist, uint32_t N,
+                          uint32_t K, const float* verts, const float* vnormals, uint32_t n_verts, const VertexLookup& s, float* sdf, uint8_t* mask, float* normal,
+                          int64_t* face_idx, float* bary, const int32_t* units_dev, uint32_t rows_per_unit) {
+    const VertexArgs a{s.face_vertices, s.features, s.dir_vec_wdist, s.sdf_scale, s.sdf_offset, fminf(9.5f, s.h_threshold), rt->face0};  // depth_threshold of tools/map.py:407
+    KernelTimer kt("vertex_lookup_kernel", st);
+    hipLaunchKernelGGL(vertex_lookup_kernel<ROWS>, dim3(div_up(2 * N, 64u)), dim3(64), 0, st, N, xyz, dirs, knn_idx, knn_dist, K, verts, vnormals, (int)n_verts,
+                       static_cast<const Node*>(rt->nodes), static_cast<const Tri*>(rt->triangles), a, sdf, mask, normal, face_idx, bary, static_cast<half_t*>(s.xin),
+                       units_dev, rows_per_unit);
+}
+
+}  // namespace
+}  // namespace nerftex
+
+const char* nerftex::vertex_lookup_refusal(const VertexLookup& s) {
+    auto pos = [](float v) { return v > 0.0f && std::isfinite(v); };
+    if (s.n_fine_verts == 0 || s.n_fine_verts > 0x7fffffffu) return "the fine mesh needs between 1 and 2^31 - 1 vertices";
+    if (s.n_freqs != kInferFreqs) return "the kernel writes the curved field's 12 height bands";
+    if ((reinterpret_cast<uintptr_t>(s.features) & 15) || (reinterpret_cast<uintptr_t>(s.xin) & 15)) return "vertex_features and xin must be 16-byte aligned";
+    if (!pos(s.sdf_scale) || !pos(s.h_threshold)) return "sdf_scale and h_threshold must be positive and finite";
+    if (!std::isfinite(s.sdf_offset)) return "sdf_offset must be finite";
+    return nullptr;
+}
+
+int nerftex::curved_vertex_rows(const nerftex_raytracer* rt_fine, const float* xyz, const float* dirs, const int32_t* knn_idx, const float* knn_dist, uint32_t N,
+                                uint32_t K, const float* mesh_vertices, const float* vertex_normals, uint32_t n_verts, const VertexLookup& s, uint8_t* mask,
+                                float* normal, const int32_t* units_dev, uint32_t rows_per_unit, hipStream_t st) {
+    if (N == 0) return NERFTEX_OK;
+    launch_vertex_lookup<true>(st, rt_fine, xyz, dirs, knn_idx, knn_dist, N, K, mesh_vertices, vertex_normals, n_verts, s, nullptr, mask, normal, nullptr, nullptr,
+                               units_dev, rows_per_unit);
+    return check_launch("curved_unhash_infer(lookup)");
+}
+
+extern "C" int nerftex_vertex_lookup(const nerftex_raytracer* rt_fine, const float* xyz, const int32_t* knn_idx, const float* knn_dist, uint32_t N, uint32_t K,
+                                     const float* mesh_vertices, const float* vertex_normals, uint32_t n_verts, float dir_vec_wdist, const float* fine_vertices,
+                                     uint32_t n_fine_verts, const int32_t* face_vertices, uint32_t n_faces, const float* vertex_features, float sdf_scale,
+                                     float sdf_offset, float h_threshold, uint32_t n_freqs, float* sdf, uint8_t* mask, float* normal, int64_t* face_idx, float* bary,
+                                     void* xin, void* stream) {
+    clear_error();
+    if (!rt_fine || !xyz || !knn_idx || !knn_dist || !mesh_vertices || !vertex_normals || !fine_vertices || !face_vertices || !vertex_features || !sdf || !mask ||
+        !normal || !face_idx || !bary || !xin) {
+        set_error("vertex_lookup: the raytracer, inputs, both meshes' arrays, face_vertices, vertex_features and outputs must not be NULL");
+        return NERFTEX_ERR_INVALID;
+    }
+    if (K == 0 || K > (uint32_t)kMaxK) {
+        set_error("vertex_lookup: 1 <= K <= %d neighbours per point, but got K = %u", kMaxK, K);
+        return NERFTEX_ERR_INVALID;
+    }
+    if (n_verts == 0 || n_verts > 0x7fffffffu) {
+        set_error("vertex_lookup: the field's mesh needs between 1 and 2^31 - 1 vertices, but got %u", n_verts);
+        return NERFTEX_ERR_INVALID;
+    }
+    const VertexLookup s{face_vertices, vertex_features, n_fine_verts, dir_vec_wdist, sdf_scale, sdf_offset, h_threshold, n_freqs, xin};
+    if (n_fine_verts == 0 || n_fine_verts > 0x7fffffffu) {
+        set_error("vertex_lookup: %s, but got %u", vertex_lookup_refusal(s), n_fine_verts);
+        return NERFTEX_ERR_INVALID;
+    }
+    if (n_faces != rt_fine->n_triangles) {
+        set_error("vertex_lookup: face_vertices holds %u faces, but the raytracer was built over %u", n_faces, rt_fine->n_triangles);
+        return NERFTEX_ERR_INVALID;
+    }
+    if (const char* why = vertex_lookup_refusal(s)) {
+        set_error("vertex_lookup: %s", why);
+        return NERFTEX_ERR_INVALID;
+    }
+    if (N == 0) return NERFTEX_OK;
+    if (N > 0x7fffffffu) {
+        set_error("vertex_lookup: at most 2^31 - 1 points per call (two lanes each), but got %u", N);
+        return NERFTEX_ERR_INVALID;
+    }
+    launch_vertex_lookup<false>(as_stream(stream), rt_fine, xyz, nullptr, knn_idx, knn_dist, N, K, mesh_vertices, vertex_normals, n_verts, s, sdf, mask, normal, face_idx,
+                                bary, nullptr, 0u);
+    return check_launch("vertex_lookup");
 }
 
 #include "patch_export.inc"

@@ -56,6 +56,9 @@ _SIGNATURES = {
     "nerftex_shape_lookup": [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _u32, _vp, _u32, _vp, _u32, _u32, _f32, _f32, _f32, _f32, _u32, _vp, _vp, _vp, _vp, _vp,
                              _vp, _vp],
     "nerftex_curved_shape_infer": [_vp, _vp],
+    "nerftex_vertex_lookup": [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _u32, _f32, _vp, _u32, _vp, _u32, _vp, _f32, _f32, _f32, _u32, _vp, _vp, _vp, _vp, _vp,
+                              _vp, _vp],
+    "nerftex_curved_unhash_infer": [_vp, _vp],
     "nerftex_shape_light_lookup": [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _u32, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _f32, _f32, _f32,
                                    _f32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "nerftex_curved_light_shape_infer": [_vp, _vp],
@@ -262,6 +265,17 @@ class CurvedShapeInferDesc(C.Structure):
                 ("rows_per_unit", _u32), ("scratch", _vp), ("scratch_bytes", _sz)]
 
 
+class CurvedUnhashInferDesc(C.Structure):
+    """nerftex_curved_unhash_infer_desc of include/nerftex_hip.h, field for field: the curved field's no-grad forward over features baked onto the vertices of
+    a fine mesh."""
+    _fields_ = [("knn", _vp), ("tracer", _vp), ("xyz", _vp), ("dirs", _vp), ("B", _u32), ("n_verts", _u32), ("mesh_vertices", _vp), ("vertex_normals", _vp),
+                ("K", _u32), ("dir_vec_wdist", _f32), ("fine_vertices", _vp), ("n_fine_verts", _u32), ("face_vertices", _vp), ("n_faces", _u32),
+                ("vertex_features", _vp), ("n_features", _u32), ("sdf_scale", _f32), ("sdf_offset", _f32), ("h_threshold", _f32), ("n_freqs", _u32),
+                ("sigma_weights", _vp), ("sigma_in", _u32), ("sigma_hidden", _u32), ("sigma_layers", _u32), ("sigma_out", _u32), ("color_weights", _vp),
+                ("color_in", _u32), ("color_hidden", _u32), ("color_layers", _u32), ("color_out", _u32), ("fc_weight", _f32), ("eval", _i), ("sigma", _vp),
+                ("rgbs", _vp), ("units_dev", _vp), ("rows_per_unit", _u32), ("scratch", _vp), ("scratch_bytes", _sz)]
+
+
 LIGHT_VISUAL = {"Full": 0, "Specular": 1, "Diffuse": 2, "Albedo": 3}  # NERFTEX_LIGHT_VISUAL_*
 NORMAL_NET_WEIGHTS, NORMAL_NET_BIASES = 1312, 66  # NERFTEX_NORMAL_NET_*
 
@@ -396,7 +410,7 @@ class SynthView(C.Structure):
 EXPORTS = ["nerftex_last_error", "nerftex_version", "nerftex_tune_get", "nerftex_workspace_slots_touched", "nerftex_curved_field_infer_scratch_bytes",
            "nerftex_curved_light_infer_scratch_bytes", "nerftex_curved_import_infer_scratch_bytes", "nerftex_curved_shape_infer_scratch_bytes",
            "nerftex_curved_light_import_infer_scratch_bytes", "nerftex_curved_light_shape_infer_scratch_bytes", "nerftex_curved_patch_infer_scratch_bytes",
-           "nerftex_curved_light_patch_infer_scratch_bytes", "nerftex_sh_light_scratch_bytes", "nerftex_envmap_fit_scratch_bytes"] + list(_SIGNATURES)
+           "nerftex_curved_light_patch_infer_scratch_bytes", "nerftex_curved_unhash_infer_scratch_bytes", "nerftex_sh_light_scratch_bytes", "nerftex_envmap_fit_scratch_bytes"] + list(_SIGNATURES)
 
 
 def _load():
@@ -428,6 +442,8 @@ def _load():
     lib.nerftex_curved_patch_infer_scratch_bytes.restype = _sz
     lib.nerftex_curved_light_patch_infer_scratch_bytes.argtypes = [_u32]
     lib.nerftex_curved_light_patch_infer_scratch_bytes.restype = _sz
+    lib.nerftex_curved_unhash_infer_scratch_bytes.argtypes = [_u32]
+    lib.nerftex_curved_unhash_infer_scratch_bytes.restype = _sz
     lib.nerftex_sh_light_scratch_bytes.argtypes = [_u32]
     lib.nerftex_sh_light_scratch_bytes.restype = _sz
     lib.nerftex_envmap_fit_scratch_bytes.argtypes = [_u32, _u32]

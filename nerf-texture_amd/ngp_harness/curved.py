@@ -16,6 +16,8 @@ xatlas, open3d, trimesh).
                      factorized normal net.  import_field / import_shape: an imported planar feature map rendered on its own plane or
                      on a new UV-mapped mesh (the 'field' and 'shape' branches of MeshFeatureField.forward, tools/map.py:646-700); with the
                      normal net or the light model, the planar map comes with its phi_embed, local_tbn and sample_tbn maps (:670-675);
+                     unhash / import_unhash_vertices: the field's own table baked onto the vertices of a finely subdivided mesh and
+                     interpolated at the hit (the 'unhash' branch, :708-714; the static light model only);
   CurvedFieldLookup  round 1's minimal chain (analytic normals -> traces -> hash lookup), kept for its test.
 """
 from typing import NamedTuple, Optional
@@ -25,8 +27,10 @@ import torch
 
 from gridencoder import GridEncoder_clustering
 from nerftex_hip import (LIGHT_VISUAL, SH_LIGHT_SPECULAR, CurvedImportInferDesc, CurvedInferDesc, CurvedLightImportInferDesc, CurvedLightInferDesc,
-                         CurvedLightPatchInferDesc, CurvedLightShapeInferDesc, CurvedPatchInferDesc, CurvedShapeInferDesc, RelightDesc, ptr)
+                         CurvedLightPatchInferDesc, CurvedLightShapeInferDesc, CurvedPatchInferDesc, CurvedShapeInferDesc, CurvedUnhashInferDesc, RelightDesc, ptr)
 from RayTracer import RayTracer
+
+from .subdivide import subdivide_midpoint, subdivide_until  # noqa: F401  (subdivide_midpoint: for the callers who bake a mesh of their own)
 
 
 def star_flower_mesh(n_lat=72, n_lon=144, lobes=5, amp=0.18, radius=0.7):
@@ -635,6 +639,8 @@ class CurvedField(torch.nn.Module):
         self.patch_id = 0
         self.patch_points = self.patch_normals = self.patch_phi_embed = self.patch_local_tbn = None
         self.patch_geom = self.patch_lit = self._patch_knn = None
+        # ... and of the 'unhash' branch (:842-873): no fine mesh, no per-vertex rows
+        self.unhash_tracer = self.unhash_vertices = self.unhash_faces = self.unhash_face_vertices = None
 
     def _lit(self):
         """A field whose forward reads a fine normal: the normal net, or a light model (which shades with it)."""
@@ -792,7 +798,7 @@ class CurvedField(torch.nn.Module):
     # what the lookup kernels write per sample, by name: (trailing shape, dtype)
     _LOOKUP_BUFFERS = {"p_uv": ((2,), torch.float32), "sdf": ((), torch.float32), "mask": ((), torch.uint8), "normal": ((3,), torch.float32),
                        "face": ((), torch.int64), "xin": ((48,), torch.float16), "phi": ((8,), torch.float32), "ids": ((), torch.int32),
-                       "frame": ((9,), torch.float32), "idx": ((8,), torch.int32), "dis": ((8,), torch.float32), "weights": ((8,), torch.float32)}
+                       "frame": ((9,), torch.float32), "idx": ((8,), torch.int32), "dis": ((8,), torch.float32), "weights": ((8,), torch.float32), "bary": ((3,), torch.float32)}
 
     @classmethod
     def _lookup_buffers(cls, x, *names):
@@ -1062,6 +1068,143 @@ class CurvedField(torch.nn.Module):
             more += (phi, local_tbn)
         return out + more if details else out
 
+    # ---- the field baked onto the vertices of a fine mesh (MeshFeatureField.unhash / import_unhash_vertices, tools/map.py:842-873; the 'unhash' branch, :708-714) ----
+
+    def _unhash_refuse_lit(self, who):
+        if self._lit():
+            raise NotImplementedError(f"CurvedField.{who}: the reference's unhash branch does not run on a field with the fine-normal net or a light model "
+                                      "(its query_tbn returns a tuple the rotation of tools/map.py:725 cannot take); only the static light model without a "
+                                      "normal net takes this import")
+
+    def _unhash_mesh(self, who, vertices, faces):
+        """The fine mesh of an unhash import, checked: -> (vertices [V',3] fp32, faces [F',3] int64) as numpy arrays.  A field with the fine-normal net
+        or a light model is refused here, before any work."""
+        self._unhash_refuse_lit(who)
+        v = np.asarray(vertices.detach().cpu() if torch.is_tensor(vertices) else vertices)
+        f = np.asarray(faces.detach().cpu() if torch.is_tensor(faces) else faces)
+        if v.ndim != 2 or v.shape[1] != 3 or v.shape[0] < 1 or f.ndim != 2 or f.shape[1] != 3 or f.shape[0] < 1:
+            raise ValueError(f"CurvedField.{who}: vertices are [V', 3] and faces [F', 3], but got {tuple(v.shape)} and {tuple(f.shape)}")
+        if not np.issubdtype(f.dtype, np.integer) or f.min() < 0 or f.max() >= v.shape[0]:
+            raise ValueError(f"CurvedField.{who}: every face indexes into the {v.shape[0]} fine vertices with whole numbers")
+        if not np.issubdtype(v.dtype, np.number) or not np.isfinite(v.astype(np.float64)).all():
+            raise ValueError(f"CurvedField.{who}: every fine vertex must be finite")
+        return np.ascontiguousarray(v, dtype=np.float32), f.astype(np.int64)
+
+    def _unhash_state(self, who, vertices, faces, features, sdf_factor):
+        """The checked state of an unhash import, brought to the device -- everything that can fail, before anything of the field changes: fine
+        vertices [V',3] fp32, faces [F',3], features [V',16] fp32 (a device tensor is kept as it is), the fine mesh's tracer (the tracer ALONE: the
+        neighbour grid of a full MeshProjector over 5e5 points would never be read) and the [F',3] int32 table of corner vertex ids by original
+        face id, padded where the tracer pads a mesh of <= 8 faces (`shape_face_uv` is padded so)."""
+        v, f = self._unhash_mesh(who, vertices, faces)
+        dev = self.sigma_net.weights.device
+        feats = features.detach() if torch.is_tensor(features) else torch.as_tensor(np.asarray(features))
+        if tuple(feats.shape) != (v.shape[0], self.encoder.output_dim):
+            raise ValueError(f"CurvedField.{who}: features are [V', {self.encoder.output_dim}] = {(v.shape[0], self.encoder.output_dim)}, but got {tuple(feats.shape)}")
+        feats = feats.to(device=dev, dtype=torch.float32).contiguous()
+        if not bool(torch.isfinite(feats).all()):
+            raise ValueError(f"CurvedField.{who}: every feature must be finite")
+        factor = float(sdf_factor)
+        if not np.isfinite(factor):
+            raise ValueError(f"CurvedField.{who}: sdf_factor must be finite, but got {sdf_factor!r}")
+        table = f.astype(np.int32)
+        if len(table) <= 8:  # (RayTracer pads so small a mesh with 8 far-away faces: the table follows the tracer's face count, the rows are never hit)
+            table = np.concatenate([table, np.zeros((8, 3), np.int32)], 0)
+        with torch.cuda.device(dev):
+            tracer = RayTracer(v, f)
+        return (tracer, torch.from_numpy(v).to(dev), torch.from_numpy(f.astype(np.int64)).to(dev), torch.from_numpy(table).to(dev).contiguous(), feats, factor)
+
+    def _set_unhash(self, state):
+        self.unhash_tracer, self.unhash_vertices, self.unhash_faces, self.unhash_face_vertices, self.features_imported, self.sdf_scale_factor = state
+        self.imported, self.imported_type = True, "unhash"
+        self._import_version += 1
+
+    @torch.no_grad()
+    def unhash(self, min_vnum=5e5, *, mesh=None):
+        """MeshFeatureField.unhash (tools/map.py:842-860), the GUI's "unhash" button: the field's own mesh subdivided at its edge midpoints until it
+        has at least min_vnum vertices (`subdivide.subdivide_until`; mesh=(vertices, faces): a fine mesh taken as given instead), the field's own hash
+        table looked up at every fine vertex -- `encoder(vertices, bound)` in fp32, outside autocast --, and from here on embed() / density() /
+        forward() / infer() interpolate these per-vertex rows at the hit on the FINE mesh along the normal of the field's OWN mesh, until
+        switch_import() or the next import.  sdf_scale_factor stays what it is.  -> dict(vertices=, faces=, features=, sdf_factor=): numpy arrays,
+        what `import_unhash_vertices` takes.  The caller re-estimates the occupancy grid (Renderer.initialize_states).  A refused call changes
+        nothing of the field's state."""
+        if mesh is None:
+            self._unhash_refuse_lit("unhash")  # (before the subdivision)
+            mesh = subdivide_until(self.projector.mesh_vertices.detach().cpu().numpy(), self.mesh_faces, min_vnum)
+        v, f = self._unhash_mesh("unhash", *mesh)
+        dev = self.sigma_net.weights.device
+        with torch.autocast("cuda", enabled=False):
+            feats = self.encoder(torch.from_numpy(v).to(dev), bound=self.bound).float()
+        state = self._unhash_state("unhash", v, f, feats, self.sdf_scale_factor)
+        self._set_unhash(state)
+        return dict(vertices=v, faces=state[2].cpu().numpy(), features=feats.cpu().numpy(), sdf_factor=float(self.sdf_scale_factor))
+
+    def import_unhash_vertices(self, vertices, faces, features, sdf_factor=1.0):
+        """MeshFeatureField.import_unhash_vertices (tools/map.py:862-873) from arrays (the reference unpickles a mesh from an .npz, which is not read
+        here): fine vertices [V',3], faces [F',3] indexing into them, features [V',16], everything finite; sdf_scale_factor = sdf_factor.  The state
+        `unhash()` sets, from what it returned or from a synthesis on the curved surface.  A refused call changes nothing of the field's state."""
+        self._set_unhash(self._unhash_state("import_unhash_vertices", vertices, faces, features, sdf_factor))
+
+    def _unhash_active(self):
+        return bool(getattr(self, "imported", False)) and getattr(self, "imported_type", None) == "unhash"
+
+    def _unhash_scalars(self):
+        """(K, sdf_scale, sdf_offset, h_threshold) of nerftex_vertex_lookup for the state as it is: K is knn()'s default 8 (tools/map.py:709 passes
+        none) clamped to the field's own vertex count; the scale is the reference's max(1e-5, sdf_scale_factor) in Python double, rounded to fp32."""
+        scale = float(np.float32(max(1e-5, float(self.sdf_scale_factor))))
+        return max(1, min(8, int(self.projector.mesh_vertices.shape[0]))), scale, float(self.sdf_offset), float(self.h_threshold)
+
+    def _unhash_fused(self, x):
+        """Whether the vertex lookup kernel serves this call: the default shapes under fp16 autocast without the probabilistic table, unless
+        `fused_glue` is off, everything on the device of x."""
+        return (self._unhash_active() and self._sigma_fused(x) and getattr(self, "fused_glue", True)
+                and self._on_device_of(x, self.features_imported, self.unhash_vertices, self.unhash_face_vertices, self.projector.mesh_vertices))
+
+    @torch.no_grad()
+    def _unhash_lookup(self, x, neighbours=None):
+        """nerftex_knn_query (the field's own grid) + nerftex_vertex_lookup: -> sdf [N], h_mask [N] bool, normal [N,3] (raw), face [N], bary [N,3],
+        xin [N,48] half."""
+        from nerftex_hip import check, lib, stream
+
+        x, p = x.detach().float().contiguous(), self.projector
+        K, scale, off, h = self._unhash_scalars()
+        idx, dis = p.knn(x, K) if neighbours is None else neighbours
+        idx, dis = idx.int().contiguous(), dis.float().contiguous()
+        fv, table, f = self.unhash_vertices, self.unhash_face_vertices, self.features_imported
+        sdf, mask, normal, face, bary, xin = out = self._lookup_buffers(x, "sdf", "mask", "normal", "face", "bary", "xin")
+        check(lib.nerftex_vertex_lookup(self.unhash_tracer._handle, ptr(x), ptr(idx), ptr(dis), x.shape[0], idx.shape[1], ptr(p.mesh_vertices), ptr(p.vertex_normals),
+                                        p.mesh_vertices.shape[0], 0.05, ptr(fv), fv.shape[0], ptr(table), table.shape[0], ptr(f), scale, off, h, int(self.multires),
+                                        *map(ptr, out), stream()))
+        return sdf, mask.bool(), normal, face, bary, xin
+
+    def _unhash_embed_reference(self, x, neighbours=None, details=False):
+        """The 'unhash' branch op by op, the reference's expressions (tools/map.py:708-714 over knn(), :454-501, barycentric_mapping, :503-528, and
+        :85-93) over RayTracer.trace: -> embed [N,41] fp32, normal_coarse, h_mask (details: + sdf, the raw normal, face, bary).  The divisor is a
+        0-d tensor, as in `_shape_embed_reference`.  neighbours: a neighbour list from elsewhere (default: the library's search over the field's
+        own mesh)."""
+        x = x.float()
+        p = self.projector
+        K, scale, off, h = self._unhash_scalars()
+        idx, dis = p.knn(x, K) if neighbours is None else neighbours
+        normal = p.knn_normal(x, idx, dis)
+        p1, _, d1, f1 = self.unhash_tracer.trace(x, normal)
+        p2, _, d2, f2 = self.unhash_tracer.trace(x, -normal)
+        cond = d1 < d2
+        sdf = torch.where(cond, -d1, d2).unsqueeze(-1) / torch.tensor(scale, dtype=torch.float32, device=x.device) - off
+        p_sur = torch.where(cond.unsqueeze(-1), p1, p2)
+        face = torch.where(cond, f1, f2)
+        h_mask = (sdf.abs() < min(9.5, h)).squeeze(-1)
+        face_mask = face == -1
+        h_mask = torch.logical_and(h_mask, torch.logical_not(face_mask))
+        face0 = torch.where(face_mask, torch.zeros_like(face), face)
+        vertex_idx = self.unhash_faces[face0]
+        bary = points_to_barycentric(self.unhash_vertices[vertex_idx], p_sur)
+        x_embed = (self.features_imported[vertex_idx] * bary.unsqueeze(-1)).sum(-2)
+        embed = torch.cat([x_embed, freq_encode(sdf, self.multires)], dim=-1)
+        normal_coarse = normal / (normal.norm(dim=-1, keepdim=True) + 1e-5)
+        if details:
+            return embed, normal_coarse, h_mask, sdf[..., 0], normal, face, bary
+        return embed, normal_coarse, h_mask
+
     # ---- the trained field exported as texture patches (NeRFNetwork.export_field -> MeshFeatureField.sample_patches, tools/map.py:951-1128) ----
 
     def export_field(self, sample_points, sample_normals, *, scan_points=None, first_component=None, grid_gap=None, pattern_rate=1 / 50, patch_size=128,
@@ -1143,6 +1286,9 @@ class CurvedField(torch.nn.Module):
             kn = self._patch_knn
             return (("import-patch", f.data_ptr(), tuple(f.shape), None if kn is None else kn.value, self.patch_geom.data_ptr(),
                      None if self.patch_lit is None else self.patch_lit.data_ptr(), float(self.h_threshold), self._import_version))
+        if self._unhash_active():  # the per-vertex rows, the fine mesh's arrays and its tracer, the scalars
+            return (("import-unhash", f.data_ptr(), tuple(f.shape), self.unhash_vertices.data_ptr(), self.unhash_face_vertices.data_ptr(),
+                     self.unhash_tracer._handle.value) + self._unhash_scalars()[1:] + (self._import_version,))
         if self._shape_active():
             p = self.shape_projector
             stamp = (("import-shape", f.data_ptr(), tuple(f.shape), p._knn.value, p.tracer._handle.value, p.mesh_vertices.data_ptr(), p.vertex_normals.data_ptr(),
@@ -1228,6 +1374,8 @@ class CurvedField(torch.nn.Module):
         """Whether the lookup kernels serve the ACTIVE imported source for this call (lit: with the reads the fine normal needs)."""
         if self._patch_active():
             return self._patch_fused(x)
+        if self._unhash_active():
+            return not lit and self._unhash_fused(x)
         lit_reads = self._shape_light_fused(x) if self._shape_active() else self._import_light_fused(x)
         return lit_reads or (not lit and self._import_fused(x))  # (the lit field without a fine normal: none of the lit reads is needed)
 
@@ -1238,6 +1386,9 @@ class CurvedField(torch.nn.Module):
         if self._patch_active():
             out = self._patch_lookup(x, lit=lit)
             return _SourceLookup(out[1], out[2], out[3], *((out[7], out[8:]) if lit else ()))
+        if self._unhash_active():
+            out = self._unhash_lookup(x)
+            return _SourceLookup(out[1], out[2], out[5])
         if self._shape_active():
             out = self._shape_light_lookup(x) if lit else self._shape_lookup(x)
             return _SourceLookup(out[2], out[3], out[5], *((out[6], out[8:]) if lit else ()))
@@ -1296,6 +1447,10 @@ class CurvedField(torch.nn.Module):
                 if requires_grad_xyz or (with_fine_normal and self.patch_lit is None):
                     raise NotImplementedError("CurvedField.embed: an imported patch is rendered without gradients to the sample position, and without a fine "
                                               "normal unless it came with local_tbn and phi_embed")
+            elif self._unhash_active():
+                if requires_grad_xyz or with_fine_normal:
+                    raise NotImplementedError("CurvedField.embed: the features baked onto a fine mesh are rendered without gradients to the sample position "
+                                              "and without a fine normal")
             else:
                 lit_maps = self._lit() and self.phi_embed_imported is not None and (not self._shape_active() or self.shape_face_tbn is not None)
                 if requires_grad_xyz or (with_fine_normal and not lit_maps):
@@ -1310,6 +1465,8 @@ class CurvedField(torch.nn.Module):
                 return s.xin[:, :self.in_dim], coarse, s.h_mask, self._rotate_fine(local, *s.frames)
             if self._patch_active():  # ... and op by op where the kernels do not serve the call
                 return self._patch_embed_reference(x, with_fine_normal=with_fine_normal)
+            if self._unhash_active():
+                return self._unhash_embed_reference(x)
             if self._shape_active():
                 return self._shape_light_embed_reference(x) if with_fine_normal else self._shape_embed_reference(x)
             return self._import_light_embed_reference(x) if with_fine_normal else self._import_embed_reference(x)
@@ -1576,7 +1733,7 @@ class CurvedField(torch.nn.Module):
         return (env.data_ptr(), tuple(env.shape), bool(net.import_envmap), bool(getattr(self, "shade_visibility", True)),
                 0 if net.envSHs_import_vis is None else net.envSHs_import_vis.data_ptr(), 0 if net.probes is None else net.probes.data_ptr())
 
-    # ---- the eight fused inference chains: what each asks of a call (the entries refuse everything else) ----
+    # ---- the nine fused inference chains: what each asks of a call (the entries refuse everything else) ----
     _SIGMA_NET, _COLOR_NET, _BRDF_NET = (48, 32, 2, 16), (32, 64, 3, 3), (16, 64, 3, 5)  # (in, hidden, layers, out) the entries' kernels are built for
 
     @staticmethod
@@ -1700,6 +1857,15 @@ class CurvedField(torch.nn.Module):
         _, phi, frame, rows = maps = self._lit_maps()
         return dict(phi_map=ptr(phi), frame_map=ptr(frame), sample_tbn_inv=ptr(rows), n_phi=phi.shape[2], n_patches=rows.shape[0]), maps
 
+    def _infer_unhash(self):
+        """The features baked onto the fine mesh: the field's OWN neighbour grid and vertex arrays, the FINE mesh's tracer, arrays and rows,
+        `_unhash_scalars`."""
+        p, fv, table, f = self.projector, self.unhash_vertices, self.unhash_face_vertices, self.features_imported
+        K, scale, off, h = self._unhash_scalars()
+        return dict(knn=p._knn.value, tracer=self.unhash_tracer._handle.value, n_verts=p.mesh_vertices.shape[0], mesh_vertices=ptr(p.mesh_vertices),
+                    vertex_normals=ptr(p.vertex_normals), K=K, dir_vec_wdist=0.05, fine_vertices=ptr(fv), n_fine_verts=fv.shape[0], face_vertices=ptr(table),
+                    n_faces=table.shape[0], vertex_features=ptr(f), n_features=f.shape[1], sdf_scale=scale, sdf_offset=off, **self._infer_ladder(h))
+
     def _infer_lit_patch(self):
         """The lit records the lit patch chain reads beside the patch's own, and everything of the patch the call points into."""
         lit = self.patch_lit
@@ -1789,6 +1955,15 @@ class CurvedField(torch.nn.Module):
         _infer_light_import_fused()'s conditions over it."""
         return (self._infer_light_back_fused(x) and self._patch_fused(x) and self.patch_lit is not None and self._infer_rows_ok(x, d)
                 and self._on_device_of(x, self.patch_lit))
+
+    def _infer_unhash_fused(self, x, d):
+        """Whether nerftex_curved_unhash_infer serves this call: features baked onto a fine mesh, and _infer_import_fused()'s conditions over them."""
+        return self._unhash_fused(x) and self._infer_static_back_ok(x) and self._infer_rows_ok(x, d)
+
+    def _infer_unhash_desc(self, x, d, live, sigma, rgbs, scratch):
+        """The nerftex_curved_unhash_infer_desc of one call (and the tensors it points into, to be kept until the call is enqueued)."""
+        back, weights = self._infer_static_back(x, d, live, sigma, rgbs, scratch)
+        return CurvedUnhashInferDesc(**self._infer_unhash(), **back), (self.features_imported, self.unhash_vertices, self.unhash_face_vertices, self.unhash_tracer) + weights
 
     def _infer_patch_desc(self, x, d, live, sigma, rgbs, scratch):
         """The nerftex_curved_patch_infer_desc of one call (and the tensors it points into, to be kept until the call is enqueued)."""
@@ -1897,11 +2072,12 @@ class CurvedField(torch.nn.Module):
         `_infer_light_shape_fused`, which the caller has checked)."""
         return self._infer_call("nerftex_curved_light_shape_infer", self._infer_light_shape_desc, x, d, live, shading_normal)
 
-    # The one priority table of the eight chains: (the sources a row serves, its predicate, the library entry, the builder of its descriptor, lit).
+    # The one priority table of the nine chains: (the sources a row serves, its predicate, the library entry, the builder of its descriptor, lit).
     # The first row of the ACTIVE source whose predicate holds serves the call.  A source sees its own rows only: an imported patch never takes a
     # map's chain (the maps of an earlier import_field are not this import's), an import never the mesh field's.  Patch: DESIGN.md 4.20; the maps:
     # 4.18, 4.17, 4.16, 4.15 (the lit planar row serves either map source: its predicate refuses the imported mesh); the mesh field: lit (4.14, opt-in:
-    # `fused_light_infer`), static.  The predicates are looked up by name: the tests substitute them.
+    # `fused_light_infer`), static; the features baked onto a fine mesh (static light only): 4.25.  The predicates are looked up by name: the tests
+    # substitute them.
     _INFER_ROUTES = (
         (("mesh",), "_infer_light_fused", "nerftex_curved_light_infer", "_infer_light_desc", True),
         (("mesh",), "_infer_fused", "nerftex_curved_field_infer", "_infer_desc", False),
@@ -1911,6 +2087,7 @@ class CurvedField(torch.nn.Module):
         (("field", "shape"), "_infer_light_import_fused", "nerftex_curved_light_import_infer", "_infer_light_import_desc", True),
         (("shape",), "_infer_import_fused", "nerftex_curved_shape_infer", "_infer_shape_desc", False),
         (("field",), "_infer_import_fused", "nerftex_curved_import_infer", "_infer_import_desc", False),
+        (("unhash",), "_infer_unhash_fused", "nerftex_curved_unhash_infer", "_infer_unhash_desc", False),
     )
 
     def _infer_row(self, x, d):
@@ -1960,7 +2137,8 @@ class CurvedField(torch.nn.Module):
         lighting in eval) is forward()'s, and so is a lighting rotation (set_light_rotation) -- unless `fused_relight_infer` is
         set (default False): then the chain's _relit entry shades with the probe tables and the rotation.
         An imported patch (import_patch): nerftex_curved_patch_infer, and for the SH-lit field with the switch set
-        nerftex_curved_light_patch_infer, under the same contract."""
+        nerftex_curved_light_patch_infer, under the same contract.  The field baked onto a fine mesh (unhash,
+        import_unhash_vertices): nerftex_curved_unhash_infer."""
         row = self._infer_row(x, d)
         if row is None:
             sigma, rgbs, _ = self.forward(x, d)

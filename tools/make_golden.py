@@ -520,6 +520,9 @@ def main():
     if "--synthesis-only" in sys.argv:
         synthesis_goldens()
         return
+    if "--unhash-only" in sys.argv:
+        unhash_goldens()
+        return
     if "--sh-light-only" in sys.argv:
         sh_light_goldens()
         sh_field_goldens()
@@ -1866,6 +1869,131 @@ SYNTHESIS_CASES = {
     "A": dict(P=40, S=12, match_dim=16, phi_dim=8, max_patch_res=4, mirrors=False, output=30, patch_length=1.0, seed=2),
     "B": dict(P=24, S=13, match_dim=16, phi_dim=8, max_patch_res=4, mirrors=True, output=30, patch_length=7.5, seed=10),
 }
+
+
+def unhash_goldens():
+    """ref_python_unhash.npz: the `imported_type == 'unhash'` branch of MeshFeatureField.forward (tools/map.py:708-714, :719-720) executed on the
+    CPU -- knn() with its defaults over the field's own mesh, query_tbn (dead work there, but it runs), barycentric_mapping over the fine mesh
+    (:503-528), the three-row interpolation and FreqEncoder(height).  The coarse mesh is `_small_star_flower`, the fine one ONE round of
+    ngp_harness/subdivide.py's subdivide_midpoint of it (loaded by path: the drop-in packages are not importable here), rounded to fp32; both
+    MeshProjectors are made past their trimesh / open3d constructors from the arrays; frnn -> exact brute force (its neighbour lists are kept), tracer -> the oracle.
+    Per-vertex features: a seeded table of multiples of 2^-10.  512 points at h_threshold 0.0625: most within +-0.055 of the surface, 8 % between 0.07 and 0.12 from it
+    (outside the mask), 3 % thirty away (both traces miss).  Three cases: U0 the state unhash() leaves (:853-857), U1 sdf_scale_factor 2.5 and
+    sdf_offset 0.01, U2 the real import_unhash_vertices (:862-873) on a file written to a temporary directory (another table, sdf_factor 0.8; its
+    BvhMeshProjector(...) call is answered by the fine projector).  Values only."""
+    import importlib.util
+    import tempfile
+    import time
+
+    import torch
+
+    started = time.time()
+    _install_map_imports()
+    for name, cls in (("sg_light_model", "SG_EnvmapMaterialNet"), ("sh_light_model", "SH_EnvmapMaterialNet"), ("envmap_light_model", "Envmap_EnvmapMaterialNet")):
+        if "nerf." + name not in sys.modules:
+            _stub("nerf." + name, **{cls: None})
+    import tools.map as ref_map
+    from RayTracer import RayTracer as RefRayTracer
+    from tools.encoding import get_encoder
+
+    spec = importlib.util.spec_from_file_location("_subdivide", os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "nerf-texture_amd", "ngp_harness",
+                                                                            "subdivide.py"))
+    subdivide = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(subdivide)
+
+    h_threshold = 0.0625
+    v, f, vn, tbn = _small_star_flower()
+    faces = f.astype(np.int64)
+    fine_v64, fine_faces = subdivide.subdivide_midpoint(v, faces)
+    fine_v = fine_v64.astype(np.float32)
+    assert len(fine_v) > len(v) and len(fine_faces) == 4 * len(faces)
+
+    def area_normals(vertices, tris):
+        v8 = vertices.astype(np.float64)
+        fn = np.cross(v8[tris[:, 1]] - v8[tris[:, 0]], v8[tris[:, 2]] - v8[tris[:, 0]])
+        out = np.zeros_like(v8)
+        for k in range(3):
+            np.add.at(out, tris[:, k], fn)
+        return (out / (np.linalg.norm(out, axis=-1, keepdims=True) + 1e-12)).astype(np.float32)
+
+    def projector(vertices, tris, normals, frames=None):  # (the members knn(), query_tbn() and barycentric_mapping() read)
+        mp = object.__new__(ref_map.MeshProjector)
+        mp.mesh_vertices, mp.vertex_normals = torch.from_numpy(vertices), torch.from_numpy(normals)
+        mp.tbn = None if frames is None else torch.from_numpy(frames)
+        mp.grid, mp.radius, mp.max_K, mp.depth_threshold = None, 100.0, vertices.shape[0], 9.5
+        mp.raytracer = RefRayTracer(vertices, tris.astype(np.uint32))
+        mp.faces = torch.from_numpy(tris).long()
+        return mp
+
+    coarse, fine = projector(v, faces, vn, tbn), projector(fine_v, fine_faces, area_normals(fine_v, fine_faces))
+
+    rng = np.random.default_rng(181)
+    # (multiples of 2^-10: ten bits a value, so that the compressed fixture stays a third of the size raw fp32 noise would have)
+    features = (np.round(rng.uniform(-0.5, 0.5, (len(fine_v), 16)) * 1024) / 1024).astype(np.float32)
+    features_u2 = (np.round(rng.uniform(-0.5, 0.5, (len(fine_v), 16)) * 1024) / 1024).astype(np.float32)
+    N = 512
+    pick, bary = rng.integers(0, len(faces), N), rng.dirichlet([1, 1, 1], N)
+    on = (v[faces[pick]].astype(np.float64) * bary[..., None]).sum(1)
+    nn = (vn[faces[pick]].astype(np.float64) * bary[..., None]).sum(1)
+    nn /= np.linalg.norm(nn, axis=-1, keepdims=True)
+    offset = rng.uniform(-0.055, 0.055, N)
+    rows = rng.permutation(N)
+    beyond, away = rows[:41], rows[41:56]
+    offset[beyond] = rng.uniform(0.07, 0.12, len(beyond)) * rng.choice([-1.0, 1.0], len(beyond))
+    pts = on + nn * offset[:, None]
+    far = rng.normal(size=(len(away), 3))
+    pts[away] = far / np.linalg.norm(far, axis=-1, keepdims=True) * 30.0
+    pts = pts.astype(np.float32)
+
+    mff = object.__new__(ref_map.MeshFeatureField)
+    torch.nn.Module.__init__(mff)
+    mff.device, mff.h_threshold, mff.K, mff.bound, mff.hash, mff.prob_model, mff.pred_normal, mff.clustering = "cpu", h_threshold, 8, 1, True, False, False, True
+    mff.imported, mff.imported_type, mff.normal_net, mff.rescale = False, None, None, False
+    mff.sdf_scale_factor, mff.sdf_offset, mff.uv_utilize_rate, mff.K_for_uv = 1.0, 0.0, 1.0, 5
+    mff.encoder_f_out_dim = 16
+    mff.encoder_z, mff.encoder_z_outdim = get_encoder("frequency", input_dim=1, multires=12)
+    mff.meshprojector, mff.meshprojector_imported = coarse, None
+
+    x = torch.from_numpy(pts)
+    out = dict(vertices=v, faces=faces.astype(np.int32), vertex_normals=vn, fine_vertices=fine_v, fine_faces=fine_faces.astype(np.int32), xyz=pts,
+               h_threshold=h_threshold, features=features, U2_features=features_u2)
+
+    def record(key):
+        with torch.no_grad(), emulated_autocast():
+            embed, nc, nf, hm = mff(x)
+            normal, _, indices, dis = coarse.knn(x)
+            _, b, sdf, hm_b = fine.barycentric_mapping(x, normal=normal, h_threshold=h_threshold, sdf_scale=mff.sdf_scale_factor, sdf_offset=mff.sdf_offset)
+            _, _, d1, f1 = fine.raytracer.trace(x, normal)
+            _, _, d2, f2 = fine.raytracer.trace(x, -normal)
+        face = torch.where(d1 < d2, f1, f2)  # (barycentric_mapping overwrites its -1 with 0: kept here as the tracer gives it)
+        assert nf is None and torch.equal(hm, hm_b) and torch.equal(embed[:, 16], sdf[:, 0]) and embed.dtype == torch.float32
+        out.update({key + "_sdf_factor": float(mff.sdf_scale_factor), key + "_offset": float(mff.sdf_offset), key + "_embed": embed.numpy(), key + "_normal": nc.numpy(),
+                    key + "_normal_raw": normal.numpy(), key + "_h_mask": hm.numpy(), key + "_sdf": sdf[:, 0].numpy(), key + "_face": face.numpy().astype(np.int32),
+                    key + "_bary": b.numpy()})
+        # the neighbours knn() found, the same for every case (the pole vertices are duplicated: which copies a search returns is its own business)
+        out.update(knn_idx=indices.numpy().astype(np.int32), knn_dis=dis[:, :8].numpy())
+        print("ref_python_unhash.npz:", key, "inside the mask", float(hm.float().mean()), "both traces miss", float((face < 0).float().mean()))
+
+    # U0, U1: the state unhash() leaves (:853-857) behind its subdivision and its encoder call
+    mff.meshprojector_imported = fine
+    mff.features_imported = torch.nn.Parameter(torch.from_numpy(features))
+    mff.imported, mff.imported_type = True, "unhash"
+    record("U0")
+    mff.sdf_scale_factor, mff.sdf_offset = 2.5, 0.01
+    record("U1")
+    # U2: import_unhash_vertices itself
+    mff.sdf_offset, mff.meshprojector_imported, mff.features_imported, mff.imported_type = 0.0, None, None, None
+    _stub("tools.map_bvh", BvhMeshProjector=lambda **kw: fine)
+    with tempfile.TemporaryDirectory() as tmp:
+        path = os.path.join(tmp, "unhash.npz")
+        np.savez(path, mesh=np.array(types.SimpleNamespace(vertices=fine_v, faces=fine_faces), dtype=object), features=features_u2, sdf_factor=0.8)
+        mff.import_unhash_vertices(path)
+    sys.modules.pop("tools.map_bvh", None)
+    assert mff.imported_type == "unhash" and mff.sdf_scale_factor == 0.8 and mff.meshprojector_imported is fine
+    record("U2")
+    np.savez_compressed(os.path.join(OUT, "ref_python_unhash.npz"), **out)
+    new = [os.path.join(r, n) for r, _, names in os.walk(REF) for n in names if os.lstat(os.path.join(r, n)).st_mtime >= started]
+    assert not new, "files appeared under the reference tree:\n" + "\n".join(new[:20])
 
 
 def synthesis_inputs(case):
